@@ -11,7 +11,11 @@ synthetic envs (obs 64, act 8) + value pre-pass + GAE + the advantage-normalisat
 clip + Adam).  Inputs are device resident; env shards are one per GPU (weak scaling).  Rank 0 prints ONE JSON line
 (exactly one line on stdout: libraries' C-level stdout is redirected to stderr).
 
-Besides the throughput the line carries
+A plain run sets up, warms up, times the K steps and prints the line: the throughput (`value`, `ms_per_step`), the configuration
+and the last step's logged objectives.  `--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy
+(dump_outputs).  Everything below is measured only with `--full`.
+
+With `--full` the line also carries
   roofline      dominant kernel of the timed region (the PPO minibatch kernel: ppo_step_s3_kernel, bf16 matrix pipe with
                 fp32-equivalent split arithmetic, or ppo_step_w4_kernel on the fp32 MFMA).  `avg_launch_us` is the kernel's
                 own span on the device clock (first workgroup in -> last workgroup out), measured on every launch of the
@@ -350,6 +354,32 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_BUDGET_BYTES = 60 << 20      # --dump-outputs writes at most 64 MB in all
+
+
+def dump_outputs(out_dir: str, arrays: dict):
+    """--dump-outputs: what the timed path computed in its last step, one DIR/<name>.npy per array, float32 (float64 stays float64).
+    Arrays of two or more axes lead with (horizon, envs); when they would not fit the budget, every one of them keeps the same fixed,
+    seeded sample of (step, env) rows, so two runs with the same arguments write the same elements.  Smaller arrays are written whole."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    size = lambda t: t.numel() * (8 if t.dtype == th.float64 else 4)     # noqa: E731
+    whole = sum(size(t) for t in arrays.values() if t.dim() < 2)
+    rows = sum(size(t) for t in arrays.values() if t.dim() >= 2)
+    frac = min(1.0, (DUMP_BUDGET_BYTES - whole) / rows) if rows else 1.0
+    picks = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if frac < 1.0 and t.dim() >= 2:
+            n = t.shape[0] * t.shape[1]
+            if n not in picks:
+                pick = np.sort(np.random.default_rng(0).choice(n, max(1, int(n * frac)), replace=False))
+                picks[n] = th.from_numpy(pick).to(t.device)
+            t = t.reshape(n, *t.shape[2:])[picks[n]]
+        a = t.cpu().numpy().astype(np.float64 if t.dtype == th.float64 else np.float32)
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def usable_cores() -> int:
     """cores this process may actually run on: affinity mask, capped by the cgroup CPU quota (os.cpu_count() reports
     the whole host and oversubscribing OpenMP threads onto a small quota makes torch-CPU orders of magnitude slower)."""
@@ -435,24 +465,47 @@ def bench_sac(opt):
                     th.rand((max_size // 2 + 7, N), device=dev, generator=g) < 0.995))
     assert buf.if_full and buf.cur_size == max_size
     t_k9 = EventTimer()
-    buf.sample = t_k9.wrap(buf.sample)        # (the class's sample: the interleaved ring's row kernel since round 6)
+    if opt.full:
+        buf.sample = t_k9.wrap(buf.sample)        # (the class's sample: the interleaved ring's row kernel since round 6)
+    last = {}
 
     def step():
-        buf.update(agent.explore_env(env, H))
+        last["items"] = agent.explore_env(env, H)
+        buf.update(last["items"])
         return agent.update_net(buf)
 
     from elegantrl_amd import _hip
     for _ in range(opt.warmup):
         step()
     quiet_gc()
-    t_k9.enabled = True
-    _hip.kernel_span_enable(True)      # the critic's training pass and the sample kernel leave their own device-clock spans (no brackets)
+    if opt.full:
+        t_k9.enabled = True
+        _hip.kernel_span_enable(True)      # the critic's training pass and the sample kernel leave their own device-clock spans (no brackets)
     th.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(opt.steps):
         objs = step()
     th.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if opt.dump_outputs:
+        names = ("states", "actions", "rewards", "undones", "unmasks")
+        dump_outputs(opt.dump_outputs, {**dict(zip(names, last["items"])), "objectives": th.tensor(objs, dtype=th.float64),
+                                        "actor_params": agent._actor_flat, "critic_params": agent._critic_flat, "alpha_log": agent.alpha_log})
+    line = {
+        "metric": "sac_updates_per_sec_replay1M_batch256", "value": round(UPD * opt.steps / elapsed, 1), "unit": "updates/s",
+        "n_gpus": 1, "steps": opt.steps, "warmup": opt.warmup, "ms_per_step": round(elapsed / opt.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "BASELINE configs[2]: AgentSAC, Hopper-v3-shaped synthetic VecEnv obs_dim=11 act_dim=3, 64 envs, full "
+                               "ReplayBuffer of 1e6 transitions, per step 64x64 env steps + 64 x [sample(256) + SAC update], "
+                               "net [256,256], 4 critics, fp32", "name": "c3", "envs_per_gpu": N, "horizon": H, "batch": B,
+                   "update_times": UPD, "parallelism": "single"},
+        "env_steps_per_sec": round(N * H * opt.steps / elapsed, 1),
+        "us_per_update": round(elapsed / opt.steps / UPD * 1e6, 1),
+        "objectives_last": [round(float(x), 6) for x in objs],
+    }
+    if not opt.full:
+        emit(line)
+        return
     t_k9.enabled = False
     crit_us, crit_n = _hip.kernel_span_read(_hip.SPAN_SAC_CRITIC_TRAIN)
     k9_loop_us, k9_loop_n = _hip.kernel_span_read(_hip.SPAN_REPLAY_SAMPLE)
@@ -514,16 +567,7 @@ def bench_sac(opt):
     th.cuda.synchronize()
     big_s = e0.elapsed_time(e1) * 1e-4
     big_bytes = (2 * (2 * S + A + 3) * 4 + 8) * (1 << 20)
-    line = {
-        "metric": "sac_updates_per_sec_replay1M_batch256", "value": round(UPD * opt.steps / elapsed, 1), "unit": "updates/s",
-        "n_gpus": 1, "steps": opt.steps, "warmup": opt.warmup, "ms_per_step": round(elapsed / opt.steps * 1e3, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "BASELINE configs[2]: AgentSAC, Hopper-v3-shaped synthetic VecEnv obs_dim=11 act_dim=3, 64 envs, full "
-                               "ReplayBuffer of 1e6 transitions, per step 64x64 env steps + 64 x [sample(256) + SAC update], "
-                               "net [256,256], 4 critics, fp32", "name": "c3", "envs_per_gpu": N, "horizon": H, "batch": B,
-                   "update_times": UPD, "parallelism": "single"},
-        "env_steps_per_sec": round(N * H * opt.steps / elapsed, 1),
-        "us_per_update": round(elapsed / opt.steps / UPD * 1e6, 1),
+    line.update({
         "roofline": ({"kernel": "critic_tile_kernel<1> (the critic ensemble's training pass: dominant in-loop kernel of the fused SAC step)",
                       "bound": "mfma", "achieved": round(crit_flops / (crit_us * 1e-6) / 1e12, 3), "peak": MFMA_F32_PEAK_TFLOPS, "unit": "TFLOP/s",
                       "frac": round(crit_flops / (crit_us * 1e-6) / 1e12 / MFMA_F32_PEAK_TFLOPS, 4), "traffic": crit_tr, "traffic_source": crit_src,
@@ -542,8 +586,7 @@ def bench_sac(opt):
                      "at_batch_2^20": {"bytes_per_launch": big_bytes, "us": round(big_s * 1e6, 1),
                                        "achieved": round(big_bytes / big_s / 1e9, 1), "frac": round(big_bytes / big_s / 1e9 / HBM_PEAK_GBPS, 4)},
                      "kernel_span_by_size": k9_sizes, "traffic_by_size_file": K9_PMC_FILE},
-        "objectives_last": [round(float(x), 6) for x in objs],
-    }
+    })
     if not opt.no_cpu_baseline:
         log(f"cpu baseline ({usable_cores()} usable cores of {os.cpu_count()})")
         line["cpu_baseline"] = cpu_baseline_subprocess(max(2, opt.cpu_iters // 2), "c3")
@@ -553,8 +596,13 @@ def bench_sac(opt):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="measure everything besides the headline figure: CPU baseline, GAE size sweep, per-kernel "
+                                                        "rooflines and breakdown, repeated regions, the fp32 minibatch kernel, the all-reduce, "
+                                                        "the rocm-smi / amd-smi snapshot (the --no-* options below switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, "
+                                                          "at most 64 MB in all: a fixed, seeded sample of larger rollouts)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-gae-sweep", action="store_true")
     ap.add_argument("--gc-after-warmup", action="store_true", help="gc.collect() + gc.freeze() and the null-bracket measurement between the warm-up and "
@@ -577,6 +625,8 @@ def main():
                          "c3 = SAC on a 1e6-transition ring, c5 = Ant-shaped 8192 envs, cw = the reference demo's (256,128) network, "
                          "cd = the reference's default horizon / batch shape (2048 x 4096 rollout, 128 minibatches of 128)")
     opt = ap.parse_args()
+    if opt.steps < 1:
+        ap.error("--steps must be at least 1")
     if opt.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(opt.gpus)
     claim_stdout()
@@ -619,20 +669,22 @@ def main():
 
     from elegantrl_amd import _hip
     t_gae = EventTimer()
-    ops.gae_scan = t_gae.wrap(ops.gae_scan)
-
-    # one event bracket per call around the two drop-in entry points (2 per iteration: ~6 us of a 2.4 ms step): the parts of a step
+    # --full: one event bracket per call around the two drop-in entry points (2 per iteration: ~6 us of a 2.4 ms step): the parts of a step
     t_explore, t_update = EventTimer(), EventTimer()
-    explore_env, update_net = t_explore.wrap(agent.explore_env), t_update.wrap(agent.update_net)
+    explore_env, update_net = agent.explore_env, agent.update_net
+    if opt.full:
+        ops.gae_scan = t_gae.wrap(ops.gae_scan)
+        explore_env, update_net = t_explore.wrap(agent.explore_env), t_update.wrap(agent.update_net)
 
     # the loop of elegantrl_amd.train.run.train_agent_single_process: an update's three logged objectives are read ONE ROLLOUT LATE
     # (update_net(lazy=True) -> PendingLogs), i.e. after the next rollout has been enqueued -- the GPU runs it while the interpreter
     # blocks on the finished update instead of idling behind update_net's host sync (--eager-logs: read them at once)
     lazy = bool(getattr(agent, "supports_lazy_logs", False)) and not opt.eager_logs
     pend = []
+    last = {}
 
     def step():
-        items = explore_env(env, HORIZON)
+        items = last["items"] = explore_env(env, HORIZON)
         out = pend.pop().result() if pend else None
         r = update_net(list(items), lazy=True) if lazy else update_net(list(items))
         if hasattr(r, "result"):
@@ -643,13 +695,13 @@ def main():
     def flush():
         return pend.pop().result() if pend else None
 
-    # The GAE size sweep (part of the line: `roofline_gae.sweep`) runs BEFORE the warm-up since round 6 (`--gae-sweep-after` restores the old
+    # With --full, the GAE size sweep (part of the line: `roofline_gae.sweep`) runs BEFORE the warm-up since round 6 (`--gae-sweep-after` restores the old
     # order): it is ~0.2 s of HBM-bound GPU work, and a process that starts its timed region 11 ms after its first launch measures the
     # clocks' ramp, not the loop -- round 5's driver lines read 2.25 ms per step in the primary region next to 2.09-2.10 in the five regions
     # that followed it in the same process (`extra.repeated_regions_ms_per_step`; update_net fell from 2.15 to 1.90 ms ACROSS the region).
     # The timed region itself is unchanged: W warm-up steps, barrier + synchronize, exactly K steps, barrier + synchronize.
     sweep_early = None
-    if not opt.no_gae_sweep and opt.config == "c4" and not opt.gae_sweep_after:
+    if opt.full and not opt.no_gae_sweep and opt.config == "c4" and not opt.gae_sweep_after:
         log("GAE size sweep (before the warm-up)")
         sweep_early = gae_sweep(ops, dev)
         th.cuda.synchronize()
@@ -661,9 +713,11 @@ def main():
     # then the W warm-up steps, then -- with the collector switched off for the region, as timeit does -- barrier + synchronize and the K
     # timed steps.  `--gc-after-warmup` restores the old order.
     import gc
+    null_bracket_us = None
     if not opt.gc_after_warmup:
         quiet_gc()
-        null_bracket_us = _hip.k6_null_bracket_us(200)   # what an event bracket adds to its content on this box (empty launch)
+        if opt.full:
+            null_bracket_us = _hip.k6_null_bracket_us(200)   # what an event bracket adds to its content on this box (empty launch)
     log(f"rank {rank}/{world}: agent + env ready, warm-up x{opt.warmup}")
     for _ in range(opt.warmup):
         step()
@@ -671,14 +725,16 @@ def main():
     th.cuda.synchronize()
     if opt.gc_after_warmup:
         quiet_gc()
-        null_bracket_us = _hip.k6_null_bracket_us(200)
+        if opt.full:
+            null_bracket_us = _hip.k6_null_bracket_us(200)
     else:
         gc.disable()
     log("timed region")
-    t_gae.enabled = t_explore.enabled = t_update.enabled = True
-    # every n-th K6 launch is timed twice: a HIP-event bracket on its stream and the kernel's own span on the device clock
-    _hip.k6_timing_enable(opt.k6_sample)
-    _hip.kernel_span_enable(8)             # every 8th launch of the loop's other kernels leaves its own device-clock span (no brackets): GAE scan, slab reduction, clip + Adam
+    if opt.full:
+        t_gae.enabled = t_explore.enabled = t_update.enabled = True
+        # every n-th K6 launch is timed twice: a HIP-event bracket on its stream and the kernel's own span on the device clock
+        _hip.k6_timing_enable(opt.k6_sample)
+        _hip.kernel_span_enable(8)             # every 8th launch of the loop's other kernels leaves its own device-clock span (no brackets): GAE scan, slab reduction, clip + Adam
     parallel.barrier()
     th.cuda.synchronize()
     t0 = time.perf_counter()
@@ -690,6 +746,33 @@ def main():
     gc.enable()
     parallel.barrier()
     elapsed = parallel.all_reduce_max_float(time.perf_counter() - t0, device=dev)
+    if opt.dump_outputs and rank == 0:
+        names = ("states", "actions", "logprobs", "rewards", "undones", "unmasks")
+        dump_outputs(opt.dump_outputs, {**dict(zip(names, last["items"])), "objectives": th.tensor(objs, dtype=th.float64),
+                                        "params": agent._flat})
+    k6_arith = ops.ppo_arith_in_use(STATE_DIM, NET_DIMS[0], NET_DIMS[1], ACTION_DIM) if len(NET_DIMS) == 2 else "f32"
+    line = {
+        "metric": cfg["metric"], "value": round(world * N_ENVS * HORIZON * opt.steps / elapsed, 1), "unit": "env-steps/s",
+        "n_gpus": world, "steps": opt.steps, "warmup": opt.warmup, "ms_per_step": round(elapsed / opt.steps * 1e3, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": cfg["workload"], "name": opt.config,
+                   "envs_per_gpu": N_ENVS, "horizon": HORIZON, "batch": BATCH, "update_times": UPDATE_TIMES,
+                   "parallelism": f"dp{world}" if world > 1 else "single",
+                   "last_state": "private copy (reference behaviour)" if agent.snapshot_last_state else "aliases the env's live state buffer",
+                   "interpreter": ("gc.collect() + gc.freeze() after the warm-up (as elegantrl_amd.train.run does)" if opt.gc_after_warmup else
+                                   "gc.collect() + gc.freeze() before the warm-up, collector off for the timed region (nothing slow between warm-up and region)"),
+                   "logs": ("update_net's three logged objectives are read one rollout late (update_net(lazy=True), as elegantrl_amd.train.run does): "
+                            "no host sync between an update and the next rollout's launch; every kernel of the K steps and the last read are inside the timed region"
+                            if lazy else "read at once (one host sync per iteration)"),
+                   "k6_arith": ("split: fp32 operands as three bf16 parts on the bf16 matrix pipe, fp32 accumulate (as close to fp64 as the "
+                                "fp32 MFMA: tests/test_kernels_gpu.py::test_ppo_step_split_arith)" if k6_arith == "split" else "f32 MFMA")},
+        "objectives_last": [round(float(x), 6) for x in objs],
+    }
+    if not opt.full:
+        log("done")
+        if rank == 0:
+            emit(line)
+        return
     rank_ms_max = parallel.all_reduce_max_float(own_elapsed, device=dev) / opt.steps * 1e3
     rank_ms_min = -parallel.all_reduce_max_float(-own_elapsed, device=dev) / opt.steps * 1e3
     t_gae.enabled = t_explore.enabled = t_update.enabled = False
@@ -725,7 +808,6 @@ def main():
         repeats.append(parallel.all_reduce_max_float(time.perf_counter() - t1, device=dev) / opt.steps * 1e3)
     # the same region on the fp32-MFMA minibatch kernel (when the default is the split-arithmetic one), for the record
     f32_region = None
-    k6_arith = ops.ppo_arith_in_use(STATE_DIM, NET_DIMS[0], NET_DIMS[1], ACTION_DIM) if len(NET_DIMS) == 2 else "f32"
     wide = bool(getattr(agent, "_wide", False))             # net_dims (256, h2): one kernel, split arithmetic only
     if k6_arith == "split" and opt.repeats and not wide:
         prev_arith, agent.ppo_arith = agent.ppo_arith, "f32"      # (the agent applies its ppo_arith at every update_net)
@@ -771,7 +853,6 @@ def main():
                      "stats_exchange": "same route (fp64, 8 sums per iteration)" if comm is not None else "torch.distributed"}
     if rank != 0:
         return
-    env_steps = world * N_ENVS * HORIZON * opt.steps
     flops = ppo_flops_per_sample(STATE_DIM, *NET_DIMS, ACTION_DIM) * BATCH
     n_k6 = k6_launches
     k6_event_s = k6_event_seconds / n_k6 if n_k6 else float("nan")
@@ -860,21 +941,7 @@ def main():
     if wg_info.get("us_map0") and wg_info.get("us_map2") and wg_info["us_map0"] > 1.15 * wg_info["us_map2"]:
         log(f"NOTE: this box's instruction caches miss slowly (minibatch kernel back to back: {wg_info['us_map0']} us with both networks' code paths behind "
             f"every instruction cache, {wg_info['us_map2']} us with one): the library chose workgroup map {wg_info['map']} and the code touch (DESIGN.md section 4, 'Instruction fetch and the workgroup map')")
-    line = {
-        "metric": cfg["metric"], "value": round(env_steps / elapsed, 1), "unit": "env-steps/s",
-        "n_gpus": world, "steps": opt.steps, "warmup": opt.warmup, "ms_per_step": round(elapsed / opt.steps * 1e3, 3),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": cfg["workload"], "name": opt.config,
-                   "envs_per_gpu": N_ENVS, "horizon": HORIZON, "batch": BATCH, "update_times": UPDATE_TIMES,
-                   "parallelism": f"dp{world}" if world > 1 else "single",
-                   "last_state": "private copy (reference behaviour)" if agent.snapshot_last_state else "aliases the env's live state buffer",
-                   "interpreter": ("gc.collect() + gc.freeze() after the warm-up (as elegantrl_amd.train.run does)" if opt.gc_after_warmup else
-                                   "gc.collect() + gc.freeze() before the warm-up, collector off for the timed region (nothing slow between warm-up and region)"),
-                   "logs": ("update_net's three logged objectives are read one rollout late (update_net(lazy=True), as elegantrl_amd.train.run does): "
-                            "no host sync between an update and the next rollout's launch; every kernel of the K steps and the last read are inside the timed region"
-                            if lazy else "read at once (one host sync per iteration)"),
-                   "k6_arith": ("split: fp32 operands as three bf16 parts on the bf16 matrix pipe, fp32 accumulate (as close to fp64 as the "
-                                "fp32 MFMA: tests/test_kernels_gpu.py::test_ppo_step_split_arith)" if k6_arith == "split" else "f32 MFMA")},
+    line.update({
         "roofline": {"kernel": k6_kernel, "bound": "mfma", "achieved": round(flops / k6_chains / ppo_s / 1e12, 2),
                      "peak": round(k6_peak / k6_chains, 1), "unit": "TFLOP/s", "frac": round(flops / ppo_s / 1e12 / k6_peak, 4),
                      "launch_form": ("one launch per minibatch over both networks (the whole chip)" if k6_chains == 1 else
@@ -939,8 +1006,7 @@ def main():
                                     "epilogue (csrc/rollout_fused.hip; ERL_FUSED_GAE=0 restores the scan launches); the scan kernel's HBM figures: `sweep`",
                           "bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": None, "traffic": None,
                           "bytes_per_launch": 18 * HORIZON * N_ENVS, "avg_launch_us": None}),
-        "objectives_last": [round(float(x), 6) for x in objs],
-    }
+    })
     if opt.config == "cd":
         # at this shape the rollout (2048 steps x 4096 envs in ONE launch) is the dominant kernel: it becomes `roofline`, the minibatch
         # kernel (2 workgroups per launch at B = 128: latency, not throughput) moves to `roofline_k6`

@@ -673,6 +673,43 @@ def make_per_update():
     print("wrote", path, {k: v.shape for k, v in g.items() if "tree_after_td" in k})
 
 
+def make_per_reference_failures():
+    """Why the sampling half of the reference's prioritised replay has no parity fixture (tests/test_per.py): SumTree.important_sampling
+    (elegantrl/train/replay_buffer.py:284-299) asserts on every tree -- its walk from the root (:272-282) takes `depth - 2` steps and ends
+    on a node above the leaves, a negative index (at power-of-two lengths the root, which update_ids' `depth - 2` propagation steps never
+    reach (:254), is also 0: every value is 0 and every walk goes left); and the PER branch of ReplayBuffer.update raises on a wrapping
+    append (th.arange(self.p, p) with p already reduced, :92 / :109).  Stored: the tree after update_ids, the node each of 16 values' walk
+    ends on, the exception each call raised."""
+    sys.path.insert(0, REF)
+    from elegantrl.train.replay_buffer import ReplayBuffer, SumTree
+
+    th.manual_seed(52)
+    g = {"buf_lens": np.array([8, 1000, 1024], dtype=np.int64)}
+    for buf_len in g["buf_lens"].tolist():
+        tree = SumTree(buf_len=buf_len)
+        tree.update_ids(th.arange(buf_len), prob=th.rand(buf_len) + 0.1)
+        values = (th.arange(16) + th.rand(16)) * (tree.tree[0] / 16)            # important_sampling's own draw (:286)
+        g[f"n{buf_len}_tree"] = np32(tree.tree)
+        g[f"n{buf_len}_walk_ends"] = np.array([tree.get_leaf_id_and_value(v)[0] for v in values], dtype=np.int64)
+        try:
+            tree.important_sampling(batch_size=16, beg=-buf_len, end=-1, per_beta=0.4)
+            g[f"n{buf_len}_sampling_raised"] = np.array("")
+        except Exception as e:
+            g[f"n{buf_len}_sampling_raised"] = np.array(type(e).__name__)
+    buf = ReplayBuffer(max_size=8, state_dim=3, action_dim=2, gpu_id=-1, num_seqs=2, if_use_per=True)
+    mk = lambda add: (th.randn(add, 2, 3), th.randn(add, 2, 2), th.randn(add, 2), th.rand(add, 2) > 0.1, th.rand(add, 2) > 0.1)   # noqa: E731
+    buf.update(mk(6))
+    g["wrap_p_before"] = np.array(buf.p, dtype=np.int64)
+    try:
+        buf.update(mk(5))
+        g["wrap_append_raised"] = np.array("")
+    except Exception as e:
+        g["wrap_append_raised"] = np.array(type(e).__name__)
+    path = os.path.join(OUT, "per_reference_failures.npz")
+    np.savez_compressed(path, **g)
+    print("wrote", path, {k: v.tolist() for k, v in g.items() if v.ndim == 0})
+
+
 def make_evaluator():
     """the reference's Evaluator (elegantrl/train/evaluator.py:12-155) driven with a toy single env and a toy vectorised env
     (tests/helpers.py) through a fixed schedule of evaluate_and_save calls: the files it leaves in cwd and recorder.npy."""
@@ -738,3 +775,4 @@ if __name__ == "__main__":
     make_sac_mod("small", N=4, S=11, A=3, rows=40, net_dims=(64, 32), batch_size=64, n_updates=4, seed=23)
     make_state_norm()
     make_per_update()
+    make_per_reference_failures()

@@ -50,3 +50,30 @@ def test_a_failing_rank_fails_the_launcher(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert e.value.code == 3
+
+
+def test_dump_outputs_keeps_to_its_budget_with_one_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 files; past the budget every (horizon, envs) array keeps the SAME seeded rows, run after run"""
+    import numpy as np
+    import torch as th
+    bench = _bench()
+    H, N = 16, 4096
+    row = th.arange(H * N, dtype=th.float32).reshape(H, N)
+    arrays = {"states": th.stack([row, -row], dim=2), "rewards": row, "undones": row.remainder(2) == 0,
+              "objectives": th.tensor([0.5, -1.25, 3.0], dtype=th.float64), "params": th.linspace(-1, 1, 1000)}
+    bench.dump_outputs(str(tmp_path / "whole"), arrays)                # 0.9 MB: under the budget, written whole
+    whole = {f[:-4]: np.load(tmp_path / "whole" / f) for f in os.listdir(tmp_path / "whole")}
+    assert set(whole) == set(arrays) and whole["states"].shape == (H, N, 2) and whole["undones"].dtype == np.float32
+    np.testing.assert_array_equal(whole["rewards"], row.numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 200_000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sum(x.nbytes for x in a.values()) <= 200_000 and a["objectives"].dtype == np.float64 and a["params"].shape == (1000,)
+    k = a["rewards"].shape[0]
+    assert 0 < k < H * N and a["states"].shape == (k, 2) and a["undones"].shape == (k,)
+    np.testing.assert_array_equal(a["states"][:, 0], a["rewards"])    # the same (step, env) rows in every array
+    np.testing.assert_array_equal(a["undones"], (a["rewards"] % 2 == 0).astype(np.float32))
+    assert len(np.unique(a["rewards"])) == k
+    for name, x in a.items():
+        np.testing.assert_array_equal(x, np.load(tmp_path / "b" / f"{name}.npy"))

@@ -1,16 +1,23 @@
-"""bench.py itself: the contract line at N = 1 (every configuration) and the N > 1 code path (two ranks sharing the GPU over
-gloo: the barrier / max-over-ranks timing, the gradient exchange in the loop and the all-reduce micro-benchmark run for real)."""
+"""bench.py itself: the plain line and --dump-outputs, the --full contract line at N = 1 (every configuration) and the N > 1 code path
+(two ranks sharing the GPU over gloo: the barrier / max-over-ranks timing, the gradient exchange in the loop and the all-reduce
+micro-benchmark run for real)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
-KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
-        "data", "config", "roofline"}
+PLAIN_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+              "data", "config", "objectives_last"}
+KEYS = PLAIN_KEYS | {"roofline"}
+# torch.distributed.run as the driver starts it, but its agent process never opens the GPU: the agent asks torch.cuda.is_available() only
+# to choose a default NUMA binding, which applies when every rank has a GPU of its own (never here), and eight ranks with their eight
+# peer-to-peer probe children are already sixteen processes with the GPU open
+TORCHRUN = [sys.executable, "-c", "import sys, torch; torch.cuda.is_available = lambda: False; from torch.distributed.run import main; main()"]
 
 
 def run(cmd, env=None):
@@ -22,9 +29,25 @@ def run(cmd, env=None):
     return json.loads(lines[0])
 
 
+@pytest.mark.parametrize("config", ["c4", "c3"])
+def test_bench_plain_line_and_dump_outputs(config, tmp_path):
+    """a plain run: the headline line without the --full measurements, exactly --steps timed steps, and --dump-outputs writes the last
+    step's arrays (float32 / float64, at most 64 MB)"""
+    line = run([sys.executable, "bench.py", "--config", config, "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert PLAIN_KEYS <= set(line) and line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert not {"roofline", "roofline_gae", "roofline_sample", "breakdown", "clocks", "extra", "cpu_baseline", "allreduce"} & set(line)
+    out = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert {"states", "actions", "rewards", "undones", "unmasks", "objectives"} <= set(out)
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 << 20
+    np.testing.assert_allclose(out["objectives"], line["objectives_last"], rtol=0, atol=1e-6)
+    if config == "c4":                 # the whole rollout fits the budget: nothing sampled
+        assert out["states"].shape == (32, 4096, 64) and out["actions"].shape == (32, 4096, 8) and out["rewards"].shape == (32, 4096)
+    assert all(np.isfinite(a).all() for a in out.values())
+
+
 @pytest.mark.parametrize("config", ["c4", "c5", "c2", "c3"])
 def test_bench_line_contract(config):
-    line = run([sys.executable, "bench.py", "--config", config, "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-gae-sweep"])
+    line = run([sys.executable, "bench.py", "--full", "--config", config, "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-gae-sweep"])
     assert KEYS <= set(line) and line["n_gpus"] == 1 and line["steps"] == 2 and line["value"] > 0
     assert line["config"]["name"] == config and "workload" in line["config"] and line["vs_baseline"] is None
     r = line["roofline"]
@@ -46,7 +69,7 @@ def test_bench_line_contract(config):
 
 def test_bench_two_ranks_on_one_gpu_over_gloo():
     line = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                "--master-port", "29561", "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-gae-sweep"],
+                "--master-port", "29561", "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-gae-sweep"],
                env={"ERL_DIST_BACKEND": "gloo"})
     assert line["n_gpus"] == 2 and line["config"]["parallelism"] == "dp2" and line["scaling"] == "weak"
     a = line["allreduce"]
@@ -58,8 +81,8 @@ def test_bench_two_ranks_on_one_gpu_over_gloo():
 
 
 def _torchrun(n, port, extra, env):
-    return run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
-                "--master-port", str(port), "bench.py", "--gpus", str(n), "--steps", "2", "--warmup", "1", "--no-gae-sweep", "--no-smi", *extra], env=env)
+    return run([*TORCHRUN, "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py",
+                "--gpus", str(n), "--steps", "2", "--warmup", "1", "--full", "--no-gae-sweep", "--no-smi", *extra], env=env)
 
 
 def test_bench_eight_ranks_on_one_gpu_rehearsal():
@@ -93,7 +116,8 @@ def test_bench_gpus_2_starts_its_own_ranks():
     """plain `python bench.py --gpus 2` -- no torchrun around it, no WORLD_SIZE in the environment: bench.py starts the two ranks itself
     (`self_launch`), rank 0's single line comes through with n_gpus = 2, the exchange route it chose, what RCCL saw, every rank's own time"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--config", "cr", "--steps", "2", "--warmup", "1", "--no-gae-sweep", "--no-smi"],
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--config", "cr", "--steps", "2", "--warmup", "1", "--full", "--no-gae-sweep",
+                          "--no-smi"],
                          cwd=ROOT, capture_output=True, text=True, timeout=600, env=dict(env, ERL_DIST_BACKEND="gloo"))
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -10,43 +10,31 @@ import torch as th
 from oracle.per_numpy import PerTrees
 
 
-def test_reference_sumtree_asserts_which_is_why_parity_is_unpinned():
-    """documents the claim in oracle/per_numpy.py: run the reference's SumTree when it is mounted (authoring container only)."""
+def _reference_failures():
+    """tests/golden/per_reference_failures.npz: what the reference's PER code did when it ran (oracle/make_golden.py::make_per_reference_failures)"""
     import os
-    import sys
-    ref = os.environ.get("ERL_REFERENCE", "/root/reference")
-    if not os.path.isdir(ref):
-        pytest.skip("reference not mounted")
-    sys.path.insert(0, ref)
-    try:
-        from elegantrl.train.replay_buffer import SumTree
-    finally:
-        sys.path.remove(ref)
-    for buf_len in (8, 1000, 1024):
-        tree = SumTree(buf_len=buf_len)
-        tree.update_ids(th.arange(buf_len), prob=th.rand(buf_len) + 0.1)
-        with pytest.raises(AssertionError):
-            tree.important_sampling(batch_size=16, beg=-buf_len, end=-1, per_beta=0.4)
+    return np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "per_reference_failures.npz"))
+
+
+def test_reference_sumtree_asserts_which_is_why_parity_is_unpinned():
+    """documents the claim in oracle/per_numpy.py from the reference's own SumTree, recorded: important_sampling asserted on every tree,
+    because its walk from the root stops on a node above the leaves (a negative index: `assert 0 <= indices.min()`)."""
+    g = _reference_failures()
+    for buf_len in g["buf_lens"].tolist():
+        assert str(g[f"n{buf_len}_sampling_raised"]) == "AssertionError"
+        tree, ends = g[f"n{buf_len}_tree"], g[f"n{buf_len}_walk_ends"]
+        assert tree.shape == (2 * buf_len - 1,) and (tree[buf_len - 1:] > 0).all()
+        assert len(ends) == 16 and (ends - (buf_len - 1)).max() < 0
+        if buf_len & (buf_len - 1) == 0:                   # power of two: update_ids never reaches the root, so every walk goes left
+            assert tree[0] == 0 and len(set(ends.tolist())) == 1
 
 
 def test_reference_per_append_raises_on_wrap():
     """why tests/golden/per_update.npz has no wrapping append: the reference's PER branch of ReplayBuffer.update builds
-    th.arange(self.p, p) AFTER p was reduced modulo max_size (replay_buffer.py:92,109) and raises (authoring container only)."""
-    import os
-    import sys
-    ref = os.environ.get("ERL_REFERENCE", "/root/reference")
-    if not os.path.isdir(ref):
-        pytest.skip("reference not mounted")
-    sys.path.insert(0, ref)
-    try:
-        from elegantrl.train.replay_buffer import ReplayBuffer
-    finally:
-        sys.path.remove(ref)
-    buf = ReplayBuffer(max_size=8, state_dim=3, action_dim=2, gpu_id=-1, num_seqs=2, if_use_per=True)
-    mk = lambda add: (th.randn(add, 2, 3), th.randn(add, 2, 2), th.randn(add, 2), th.rand(add, 2) > 0.1, th.rand(add, 2) > 0.1)   # noqa: E731
-    buf.update(mk(6))
-    with pytest.raises(RuntimeError):
-        buf.update(mk(5))
+    th.arange(self.p, p) AFTER p was reduced modulo max_size (replay_buffer.py:92,109) and raised, recorded: 6 rows of a
+    ring of 8, then 5 more."""
+    g = _reference_failures()
+    assert int(g["wrap_p_before"]) == 6 and str(g["wrap_append_raised"]) == "RuntimeError"
 
 
 def _golden_per_steps():

@@ -15,7 +15,7 @@ from bench import KERNEL_SOURCES, kernel_source_sha16  # noqa: E402
 
 def main():
     out_path, csv_path = sys.argv[1], sys.argv[2]
-    cmd = sys.argv[3] if len(sys.argv) > 3 else "python bench.py --gpus 1 --steps 20 --warmup 5"
+    cmd = sys.argv[3] if len(sys.argv) > 3 else "python bench.py --full --gpus 1 --steps 20 --warmup 5"
     res = {}
     for row in csv.DictReader(open(csv_path, newline="")):
         m = re.search(r"(\w+_kernel)", row["Name"])

@@ -8,8 +8,8 @@ export ERL_QUIET=1
 tools/bin/clock_probe > $O/clock_probe.json 2> $O/clock_probe.err
 for rep in 0 1; do
   for t in 0 1 auto; do
-    if [ $t = auto ]; then python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 --k6-sample 3 > $O/c4_touch${t}_$rep.json 2> /dev/null
-    else ERL_K6_CODE_TOUCH=$t python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 --k6-sample 3 > $O/c4_touch${t}_$rep.json 2> /dev/null; fi
+    if [ $t = auto ]; then python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 --k6-sample 3 > $O/c4_touch${t}_$rep.json 2> /dev/null
+    else ERL_K6_CODE_TOUCH=$t python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 --k6-sample 3 > $O/c4_touch${t}_$rep.json 2> /dev/null; fi
   done
 done
 if [ -z "$2" ]; then

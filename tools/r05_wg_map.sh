@@ -8,9 +8,9 @@ export ERL_QUIET=1
 tools/bin/clock_probe > $O/clock_probe.json 2> $O/clock_probe.err
 python tools/k6_wg_map_ab.py 4 > $O/ab.jsonl 2> $O/ab.err
 for rep in 0 1; do
-  python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/c4_auto_$rep.json 2> $O/c4_auto_$rep.err
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/c4_auto_$rep.json 2> $O/c4_auto_$rep.err
   for m in 0 1 2; do
-    ERL_K6_WG_MAP=$m python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/c4_map${m}_$rep.json 2> /dev/null
+    ERL_K6_WG_MAP=$m python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/c4_map${m}_$rep.json 2> /dev/null
   done
 done
 if [ -z "$2" ]; then

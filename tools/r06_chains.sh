@@ -6,7 +6,7 @@ export ERL_QUIET=1
 timeout 300 python tools/chains_check.py 40 > $O/chains_check.txt 2>&1; cat $O/chains_check.txt | tail -14
 for rep in 0 1; do
   for c in 1 2; do
-    ERL_PPO_CHAINS=$c timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/c${c}_$rep.json 2> $O/c${c}_$rep.err
+    ERL_PPO_CHAINS=$c timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/c${c}_$rep.json 2> $O/c${c}_$rep.err
   done
 done
 python - <<PY

@@ -8,7 +8,7 @@ tail -5 $O/pytest_gpu.log
 for cfg in c4 c2 c5 cd; do
   for rep in 0 1; do
     for c in 1 2; do
-      ERL_PPO_CHAINS=$c timeout 300 python bench.py --config $cfg --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/${cfg}_c${c}_$rep.json 2> $O/${cfg}_c${c}_$rep.err
+      ERL_PPO_CHAINS=$c timeout 300 python bench.py --full --config $cfg --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/${cfg}_c${c}_$rep.json 2> $O/${cfg}_c${c}_$rep.err
     done
   done
 done

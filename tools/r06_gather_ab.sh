@@ -10,7 +10,7 @@ timeout 900 python -m pytest tests/test_kernels_gpu.py tests/test_agent_gpu.py -
 for rep in 0 1 2; do
   for a in g0 main; do
     lib=$L/liberl_hip.so; [ $a != main ] && lib=$L/liberl_hip_$a.so
-    ERL_HIP_LIB=$lib timeout 300 python bench.py --config c4 --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/c4_${a}_$rep.json 2> $O/c4_${a}_$rep.err
+    ERL_HIP_LIB=$lib timeout 300 python bench.py --full --config c4 --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/c4_${a}_$rep.json 2> $O/c4_${a}_$rep.err
   done
 done
 ERL_HIP_PROF_LIB=$L/liberl_hip_prof.so K6_LOOP=1 python tools/ppo_phase_profile.py > $O/k6_phase_c4.txt 2>&1

@@ -10,7 +10,7 @@ for rep in 0 1; do
   for v in main nodot; do
     lib=$L/liberl_hip.so; [ $v != main ] && lib=$L/liberl_hip_$v.so
     [ -f $lib ] || continue
-    ERL_HIP_LIB=$lib python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/${v}_$rep.json 2> $O/${v}_$rep.err
+    ERL_HIP_LIB=$lib python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/${v}_$rep.json 2> $O/${v}_$rep.err
   done
 done
 python - <<PY

@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 export ERL_QUIET=1
 for rep in 0 1 2; do
   for c in 1 2; do
-    ERL_PPO_CHAINS=$c timeout 300 python bench.py --config c4 --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/c4_ch${c}_$rep.json 2> $O/c4_ch${c}_$rep.err
+    ERL_PPO_CHAINS=$c timeout 300 python bench.py --full --config c4 --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/c4_ch${c}_$rep.json 2> $O/c4_ch${c}_$rep.err
   done
 done
 python tools/box_record.py > $O/box.json 2>/dev/null

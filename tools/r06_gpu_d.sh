@@ -6,8 +6,8 @@ export ERL_QUIET=1
 timeout 900 python -m pytest tests/test_sac.py tests/test_per.py -m gpu -q -x > $O/pytest_sac.log 2>&1; echo "pytest rc=$?" >> $O/pytest_sac.log
 tail -5 $O/pytest_sac.log
 for rep in 0 1; do
-  python bench.py --config c3 --no-cpu-baseline > $O/bench_c3_split_$rep.json 2> $O/bench_c3_split_$rep.err
-  ERL_SAC_TRAIN_SPLIT=0 python bench.py --config c3 --no-cpu-baseline > $O/bench_c3_unsplit_$rep.json 2> $O/bench_c3_unsplit_$rep.err
+  python bench.py --full --config c3 --no-cpu-baseline > $O/bench_c3_split_$rep.json 2> $O/bench_c3_split_$rep.err
+  ERL_SAC_TRAIN_SPLIT=0 python bench.py --full --config c3 --no-cpu-baseline > $O/bench_c3_unsplit_$rep.json 2> $O/bench_c3_unsplit_$rep.err
 done
 python - <<PY
 import json, glob

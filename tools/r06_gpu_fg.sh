@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 export ERL_QUIET=1
 for rep in 0 1 2; do
   for f in 1 0; do
-    ERL_FUSED_GAE=$f timeout 300 python bench.py --config c2 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/c2_fg${f}_$rep.json 2> $O/c2_fg${f}_$rep.err
+    ERL_FUSED_GAE=$f timeout 300 python bench.py --full --config c2 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/c2_fg${f}_$rep.json 2> $O/c2_fg${f}_$rep.err
   done
 done
 python - <<PY

@@ -8,7 +8,7 @@ tail -6 $O/pytest_rollout.log
 for cfg in c4 c2 cd; do
   for rep in 0 1; do
     for r in 0 1; do
-      ERL_RF_ROLE_SPLIT=$r timeout 300 python bench.py --config $cfg --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/${cfg}_rs${r}_$rep.json 2> $O/${cfg}_rs${r}_$rep.err
+      ERL_RF_ROLE_SPLIT=$r timeout 300 python bench.py --full --config $cfg --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/${cfg}_rs${r}_$rep.json 2> $O/${cfg}_rs${r}_$rep.err
     done
   done
 done

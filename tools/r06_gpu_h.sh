@@ -8,7 +8,7 @@ tail -4 $O/pytest.log
 for cfg in c4 c2 c5; do
   for rep in 0 1; do
     for a in 0 1; do
-      ERL_K6_AUX=$a timeout 300 python bench.py --config $cfg --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/${cfg}_aux${a}_$rep.json 2> $O/${cfg}_aux${a}_$rep.err
+      ERL_K6_AUX=$a timeout 300 python bench.py --full --config $cfg --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/${cfg}_aux${a}_$rep.json 2> $O/${cfg}_aux${a}_$rep.err
     done
   done
 done

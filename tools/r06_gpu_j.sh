@@ -13,7 +13,7 @@ for cfg in c4 c2; do
   for rep in 0 1 2; do
     for a in rd0 main dwo2; do
       lib=$L/liberl_hip.so; [ $a != main ] && lib=$L/liberl_hip_$a.so
-      ERL_HIP_LIB=$lib timeout 300 python bench.py --config $cfg --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/${cfg}_${a}_$rep.json 2> $O/${cfg}_${a}_$rep.err
+      ERL_HIP_LIB=$lib timeout 300 python bench.py --full --config $cfg --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/${cfg}_${a}_$rep.json 2> $O/${cfg}_${a}_$rep.err
     done
   done
 done

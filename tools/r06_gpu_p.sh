@@ -7,7 +7,7 @@ L=$GRAFT_REPO_ROOT/elegantrl_amd/lib
 for rep in 0 1; do
   for a in main nost; do
     lib=$L/liberl_hip.so; [ $a != main ] && lib=$L/liberl_hip_$a.so
-    ERL_HIP_LIB=$lib timeout 300 python bench.py --config c4 --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/c4_${a}_$rep.json 2> $O/c4_${a}_$rep.err
+    ERL_HIP_LIB=$lib timeout 300 python bench.py --full --config c4 --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-gae-sweep --no-smi --repeats 3 > $O/c4_${a}_$rep.json 2> $O/c4_${a}_$rep.err
   done
 done
 python - <<PY

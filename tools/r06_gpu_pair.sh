@@ -9,7 +9,7 @@ for p in 1 0; do
 done
 for rep in 0 1 2; do
   for p in 0 1; do
-    ERL_SAC_PAIR=$p timeout 300 python bench.py --config c3 --no-cpu-baseline > $O/c3_pair${p}_$rep.json 2> $O/c3_pair${p}_$rep.err
+    ERL_SAC_PAIR=$p timeout 300 python bench.py --full --config c3 --no-cpu-baseline > $O/c3_pair${p}_$rep.json 2> $O/c3_pair${p}_$rep.err
   done
 done
 python - <<PY

@@ -5,9 +5,9 @@ O=$GRAFT_REPO_ROOT/gpurun_out/r06_sac_batch; mkdir -p $O
 cd $GRAFT_REPO_ROOT
 export ERL_QUIET=1
 python -m pytest tests/test_sac.py -m gpu -x -q 2>&1 | tail -2
-for rep in 0 1 2; do python bench.py --config c3 --no-cpu-baseline > $O/c3_$rep.json 2> $O/c3_$rep.err; done
+for rep in 0 1 2; do python bench.py --full --config c3 --no-cpu-baseline > $O/c3_$rep.json 2> $O/c3_$rep.err; done
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o c3 -- python bench.py --config c3 --steps 10 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o c3 -- python bench.py --full --config c3 --steps 10 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
 cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/c3_kernel_stats.csv; rm -rf $O/prof
 python - <<PY
 import json, glob, os

@@ -7,11 +7,11 @@ cd $GRAFT_REPO_ROOT
 export ERL_QUIET=1
 for y in 1 0; do ERL_SAC_YX=$y python -m pytest tests/test_sac.py -m gpu -x -q 2>&1 | tail -1; done
 for rep in 0 1 2; do for y in 0 1; do
-  ERL_SAC_YX=$y python bench.py --config c3 --no-cpu-baseline > $O/c3_yx${y}_$rep.json 2> $O/c3_yx${y}_$rep.err
+  ERL_SAC_YX=$y python bench.py --full --config c3 --no-cpu-baseline > $O/c3_yx${y}_$rep.json 2> $O/c3_yx${y}_$rep.err
 done; done
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 for y in 0 1; do
-  ERL_SAC_YX=$y rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$y -o c3 -- python bench.py --config c3 --steps 10 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
+  ERL_SAC_YX=$y rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$y -o c3 -- python bench.py --full --config c3 --steps 10 --warmup 2 --no-cpu-baseline > /dev/null 2>&1
   cp $(find $O/prof_$y -name "*kernel_stats.csv" | head -1) $O/c3_yx${y}_kernel_stats.csv; rm -rf $O/prof_$y
 done
 python - <<PY

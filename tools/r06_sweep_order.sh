@@ -5,8 +5,8 @@ O=$GRAFT_REPO_ROOT/gpurun_out/r06_order; mkdir -p $O
 cd $GRAFT_REPO_ROOT
 export ERL_QUIET=1
 for rep in 0 1 2; do
-  python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-smi > $O/before_$rep.json 2> /dev/null
-  python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-smi --gc-after-warmup --gae-sweep-after > $O/after_$rep.json 2> /dev/null
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-smi > $O/before_$rep.json 2> /dev/null
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-smi --gc-after-warmup --gae-sweep-after > $O/after_$rep.json 2> /dev/null
 done
 python - <<PY
 import json, glob

@@ -9,8 +9,8 @@ python tools/rollout_arith_ab.py --compare old new | tee -a $O/arith.txt
 rm -f gpurun_out/rollout_ab_old.npz gpurun_out/rollout_ab_new.npz
 for round in 1 2; do
   for c in c4 c2; do
-    ERL_HIP_LIB=$OLD python bench.py --config $c --repeats 2 2>/dev/null > $O/${c}_old_$round.json
-    python bench.py --config $c --repeats 2 2>/dev/null > $O/${c}_new_$round.json
+    ERL_HIP_LIB=$OLD python bench.py --full --config $c --repeats 2 2>/dev/null > $O/${c}_old_$round.json
+    python bench.py --full --config $c --repeats 2 2>/dev/null > $O/${c}_new_$round.json
   done
 done
 python - <<'PY' | tee $O/summary.txt
