@@ -23,18 +23,22 @@
 //
 // Round 4 -- a tile workgroup streams a whole cold 256 x 256 layer through ONE CU (~9 us a layer: the weights were just written by Adam,
 // every kernel starts with cold L2s), and wherever the math allows it four workgroups share a tile, each owning 64 of a layer's 256 features
-// (`split`, ERL_SAC_SPLIT=0 turns it off):
+// (`split`):
 //   critic_fwd / critic_pg   linear in a slice of the decoder's hidden features (q is a sum over them; the policy-gradient pass's loss gradient is
 //                            a constant): `split` partial q / d q/d(action) per decoder, added in slice order by their consumers; no exchange
 //   actor_bwd                its heavy layer dH0 = W2^T dZ2 is output-split; no exchange
-//   actor_fwd (next state)   the head needs the full second layer: the LAST of a tile's four workgroups to arrive adds the four shares of the
-//                            head output in slice order and samples (an arrival counter per tile; nobody waits)
-//   critic_train             not split: its backward needs the full q of its own forward, i.e. a wait inside the launch
-// The clip + Adam launches sum fp64 squared-norm pieces that dw_table leaves (clip_adam_parts_kernel, optim.hip: no grid-wide wait), and
-// ReplayBuffer.sample rides in actor_fwd's prologue when the caller hands over the ring (erl_sac_update_ring_f32): 9 launches on the critical
-// path, 142 us per update at config 3 (235 in round 3).  The same tile code, looped over H steps with the actor's weights kept in registers /
+//   actor_fwd (next state)   the head needs the full second layer: the tile's last-dispatched workgroup polls the other three's shares of the
+//                            head output, adds the four in slice order and samples (ActorFwdArgs::yx)
+//   critic_train             its backward needs the full q of its own forward: the four workgroups exchange their shares of q inside the
+//                            launch, the last of them to arrive adds the shares of dEnc (CriticArgs::qx)
+// The two exchanges keep their granules and counters in a library-owned slot per (device, stream) (SacSlot).  The clip + Adam launches sum
+// fp64 squared-norm pieces that dw_table leaves (clip_adam_parts_kernel, optim.hip: no grid-wide wait), and ReplayBuffer.sample rides in
+// actor_fwd's prologue when the caller hands over the ring (erl_sac_update_ring_f32).  Every launch goes to the caller's stream: nine at
+// config 3, where the policy-gradient sample's forward rides in launch (1) (actor_fwd_pair_kernel).  The same tile code, looped over H steps with the actor's weights kept in registers /
 // LDS, is the persistent off-policy rollout (sac_rollout_synenv_kernel).
 #include "mlpn_common.h"
+
+#include <mutex>
 
 namespace {
 
@@ -384,19 +388,14 @@ struct ActorFwdArgs {
     FusedDims d;
     const float *X;                // (B, S) sampled state rows
     float *Xcopy;                  // not NULL: the rows are also written here (the off-policy rollout's states[t] = state)
-    // Feature split of the second layer (a call that keeps nothing for a backward pass): grid.y = split, workgroup (tile, s) owns hidden
-    // features [s d.h1, (s + 1) d.h1) -- d.h1 is the slice's width, h1_full the layer's: 64 KB of W2 instead of 256 KB through one CU -- and
-    // leaves its share of the head's output (a sum over the slice: bias from slice 0) in Ypart[s][b][2 A].  The workgroups of a tile count
-    // their arrivals in arrive[tile]; the LAST one adds the shares in slice order, samples, and re-arms the counter: nobody waits.
+    // Feature split of the second layer: grid.y = split, workgroup (tile, s) owns hidden features [s d.h1, (s + 1) d.h1) -- d.h1 is the
+    // slice's width, h1_full the layer's: 64 KB of W2 instead of 256 KB through one CU.  The slices meet by OWNER: each publishes its share
+    // of the head's output (a sum over the slice: bias from slice 0) as 8-byte {share, nonce} granules in yx[split][B][2 A] (library-owned,
+    // never cleared: the per-launch nonce invalidates older contents) and LEAVES -- no wait for the stores' acknowledgement, no arrival
+    // counter; the tile's LAST slice in dispatch order (by = split - 1: its partners were dispatched before it and wait for nothing, so it
+    // cannot wait for a workgroup that is not running or finished) polls the others' granules, adds the shares in slice order and samples.
+    // Bounded spin; a share that never arrives poisons the tile's actions with NaN and is counted in the host-visible fault word.
     int split, h1_full;
-    float *Ypart;
-    unsigned *arrive;
-    // OWNER form of the meeting (round 6, last session; yx != NULL): every slice publishes its share as 8-byte {share, nonce} granules in
-    // yx[split][B][2 A] (library-owned, never cleared: the per-launch nonce invalidates older contents) and LEAVES -- no wait for the stores'
-    // acknowledgement, no arrival counter; the tile's LAST slice in dispatch order (by = split - 1: its partners were dispatched before it
-    // and wait for nothing, so it cannot wait for a workgroup that is not running or finished) polls the others' granules, adds the
-    // shares in slice order and samples.  One round trip after the slowest slice instead of three (acknowledge, count, fetch).  Bounded
-    // spin; a share that never arrives poisons the tile's actions with NaN and is counted in the host-visible fault word.
     unsigned long long *yx;
     uint32_t nonce, spin_limit;
     uint32_t *fault;
@@ -406,7 +405,7 @@ struct ActorFwdArgs {
     // this kernel waits for anyway
     ErlRingSample rg;
     int rg_self;                   // 1: X = the ring's STATE rows of the drawn transitions themselves (not their next states), nothing copied out:
-                                   // the policy-gradient sample's forward pass, which then does not depend on launch (1)'s staging (round 6)
+                                   // the policy-gradient sample's forward pass in the same launch as launch (1), which is still staging them
     float *o_state, *o_action, *o_reward, *o_undone, *o_unmask, *o_next;
     const float *noise;            // (B, A) or NULL: Philox keyed by (seed, counter, row, a)
     uint64_t seed, counter;
@@ -508,87 +507,50 @@ __device__ __forceinline__ void actor_fwd_body(const ActorFwdArgs &g, TileLds &l
     layer_small_mma<false, true>(wh, fo == 0 ? g.P + d.abh : nullptr, d.h1, 2 * d.A, lds.T0, lds.part, lds.Yl, L);
     FPROF(0, 7);
     if (g.split > 1) {
-        // this slice's share of the head output goes to memory past the (per-XCD) L2; the last of the tile's workgroups to arrive adds the
-        // shares in slice order -- the sum every order of arrival gives -- into Yl and carries on as the unsplit kernel does
-        __shared__ int s_last;
+        // the slices' shares of the head output meet in their owner (ActorFwdArgs::yx), which adds them in slice order -- the sum every order
+        // of arrival gives -- into Yl and carries on as the unsplit kernel does
+        static_assert(kQxSplit == 4, "four shares are polled at once");
         const int A2 = 2 * d.A;
-        if (g.yx) {
-            static_assert(kQxSplit == 4, "four shares are polled at once");
-            const int s_ = L.tid >> 4, f = L.tid & 15;
-            const bool mine = L.tid < TS * 16 && f < A2 && row0 + s_ < d.B;
-            const int owner = g.split - 1;
-            if (by != owner) {
-                if (mine)
-                    __hip_atomic_store(g.yx + ((size_t)by * d.B + row0 + s_) * A2 + f,
-                                       (unsigned long long)__float_as_uint(lds.Yl[s_ * 16 + f]) | ((unsigned long long)g.nonce << 32), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_AGENT);
-                return;
-            }
-            if (L.tid < TS * 16) {
-                float y = 0.f;
-                if (mine) {
-                    unsigned long long gr4[kQxSplit];
-#pragma unroll
-                    for (int k = 0; k < kQxSplit; ++k)
-                        gr4[k] = __hip_atomic_load(g.yx + ((size_t)min(k, max(owner - 1, 0)) * d.B + row0 + s_) * A2 + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                    for (int k = 0; k < kQxSplit; ++k) {
-                        if (k >= g.split) continue;
-                        float sh;
-                        if (k == owner) {
-                            sh = lds.Yl[s_ * 16 + f];                   // (my own share: the bits the granule would carry)
-                        } else {
-                            const unsigned long long *src = g.yx + ((size_t)k * d.B + row0 + s_) * A2 + f;
-                            unsigned long long gr = gr4[k];
-                            for (uint32_t spins = 0; (uint32_t)(gr >> 32) != g.nonce && spins < g.spin_limit; ++spins) {
-                                __builtin_amdgcn_s_sleep(1);
-                                gr = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            }
-                            const bool ready = (uint32_t)(gr >> 32) == g.nonce;
-                            if (!ready && g.fault) __hip_atomic_fetch_add(g.fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                            sh = ready ? __uint_as_float((uint32_t)gr) : __uint_as_float(0x7FC00000u);
-                        }
-                        y = k == 0 ? sh : y + sh;                        // slice order: ((s0 + s1) + s2) + s3
-                    }
-                }
-                lds.Yl[s_ * 16 + f] = y;
-            }
-            lds_barrier();
-        } else {
-        if (L.tid < TS * 16) {
-            const int s_ = L.tid >> 4, f = L.tid & 15;
-            if (f < A2 && row0 + s_ < d.B)
-                __hip_atomic_store(g.Ypart + ((size_t)by * d.B + row0 + s_) * A2 + f, lds.Yl[s_ * 16 + f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int s_ = L.tid >> 4, f = L.tid & 15;
+        const bool mine = L.tid < TS * 16 && f < A2 && row0 + s_ < d.B;
+        const int owner = g.split - 1;
+        if (by != owner) {
+            if (mine)
+                __hip_atomic_store(g.yx + ((size_t)by * d.B + row0 + s_) * A2 + f,
+                                   (unsigned long long)__float_as_uint(lds.Yl[s_ * 16 + f]) | ((unsigned long long)g.nonce << 32), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+            return;
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (L.tid == 0) {
-            const unsigned old = __hip_atomic_fetch_add(g.arrive + bx, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_last = old == (unsigned)g.split - 1u;
-            if (s_last) __hip_atomic_store(g.arrive + bx, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // re-armed for the next launch
-        }
-        __syncthreads();
-        if (!s_last) return;
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         if (L.tid < TS * 16) {
-            const int s_ = L.tid >> 4, f = L.tid & 15;
             float y = 0.f;
-            if (f < A2 && row0 + s_ < d.B) {
-                // (all shares requested together -- one round trip instead of one per slice -- and added in slice order: the same bits)
-                static_assert(kQxSplit == 4, "four shares are fetched at once (kCritSplit below is the same 4)");
-                float yk[kQxSplit];
+            if (mine) {
+                unsigned long long gr4[kQxSplit];
 #pragma unroll
                 for (int k = 0; k < kQxSplit; ++k)
-                    yk[k] = __hip_atomic_load(g.Ypart + ((size_t)min(k, g.split - 1) * d.B + row0 + s_) * A2 + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                y = yk[0];
+                    gr4[k] = __hip_atomic_load(g.yx + ((size_t)min(k, max(owner - 1, 0)) * d.B + row0 + s_) * A2 + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
-                for (int k = 1; k < kQxSplit; ++k)
-                    if (k < g.split) y += yk[k];
+                for (int k = 0; k < kQxSplit; ++k) {
+                    if (k >= g.split) continue;
+                    float sh;
+                    if (k == owner) {
+                        sh = lds.Yl[s_ * 16 + f];                   // (my own share: the bits the granule would carry)
+                    } else {
+                        const unsigned long long *src = g.yx + ((size_t)k * d.B + row0 + s_) * A2 + f;
+                        unsigned long long gr = gr4[k];
+                        for (uint32_t spins = 0; (uint32_t)(gr >> 32) != g.nonce && spins < g.spin_limit; ++spins) {
+                            __builtin_amdgcn_s_sleep(1);
+                            gr = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        }
+                        const bool ready = (uint32_t)(gr >> 32) == g.nonce;
+                        if (!ready && g.fault) __hip_atomic_fetch_add(g.fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                        sh = ready ? __uint_as_float((uint32_t)gr) : __uint_as_float(0x7FC00000u);
+                    }
+                    y = k == 0 ? sh : y + sh;                        // slice order: ((s0 + s1) + s2) + s3
+                }
             }
             lds.Yl[s_ * 16 + f] = y;
         }
         lds_barrier();
-        }   // (last-arriver form)
     }
     if (L.tid < TS) {
         const int64_t b = row0 + L.tid;
@@ -619,16 +581,14 @@ __global__ __launch_bounds__(FT) void actor_fwd_kernel(ActorFwdArgs g)
     actor_fwd_body<C0, C1>(g, lds, (int)blockIdx.x, (int)blockIdx.y);
 }
 
-// Launch (1) -- the actor on the next state, its second layer split over `ay` workgroups per tile -- and the policy-gradient sample's forward
-// (unsplit: its activations are kept for the backward pass) as ONE launch: rows y < ay of the grid run the first, row ay the second.  The
-// two share nothing (the sample's forward reads its state rows from the ring itself), so this replaces the side stream that carried the
-// second one next to launches (1)-(2): one queue instead of two for most of the step (round 6; ERL_SAC_PAIR=0 keeps the side stream).
-template <int C0, int C1A, int C1B>
+// Launch (1) -- the actor on the next state -- and the policy-gradient sample's forward as ONE launch, the [256, 256] actor's second layer
+// split over `ay` workgroups per tile in both: rows y < ay of the grid run the first, the rest the second.  The two share nothing (the
+// sample's forward reads its state rows from the ring itself: ActorFwdArgs::rg_self).
 __global__ __launch_bounds__(FT) void actor_fwd_pair_kernel(ActorFwdArgs ga, ActorFwdArgs gb, int ay)
 {
     __shared__ TileLds lds;
-    if ((int)blockIdx.y < ay) actor_fwd_body<C0, C1A>(ga, lds, (int)blockIdx.x, (int)blockIdx.y);
-    else actor_fwd_body<C0, C1B>(gb, lds, (int)blockIdx.x, (int)blockIdx.y - ay);
+    if ((int)blockIdx.y < ay) actor_fwd_body<2, 0>(ga, lds, (int)blockIdx.x, (int)blockIdx.y);
+    else actor_fwd_body<2, 0>(gb, lds, (int)blockIdx.x, (int)blockIdx.y - ay);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -674,16 +634,10 @@ struct CriticArgs {
     uint32_t *fault;
 };
 
-// (ERL_SAC_TRAIN_WPE=4 compiles the training pass on decoder SLICES -- MODE 1, C1 = 0 -- for two workgroups per CU: 128 registers, 52 bytes
-// of scratch.  That was needed while the policy-gradient sample's kernels ran next to it -- its 256 workgroups wait for each other's
-// shares of q and the late ones kept their partners spinning: 33-35 us a launch; since that sample is forked before launch (1) the pass
-// has the chip to itself and the uncapped build -- 149 registers, one workgroup per CU, no scratch -- is the faster one: 20.7 against
-// 22.0 us, 139.7 against 142.5 us per update, profiles/r06_sac_train_split_ab.txt)
+// (the training pass on decoder SLICES -- MODE 1, C1 = 0 -- capped at two workgroups per CU, 128 registers and 52 bytes of scratch, measured
+// slower than this build, one workgroup per CU without scratch: 22.0 against 20.7 us, profiles/r06_sac_train_split_ab.txt)
 template <int MODE, int C0, int C1>
-#ifndef ERL_SAC_TRAIN_WPE
-#define ERL_SAC_TRAIN_WPE 2
-#endif
-__global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu((MODE == 1 && C1 == 0) ? ERL_SAC_TRAIN_WPE : 2))) void critic_tile_kernel(CriticArgs g)
+__global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(2))) void critic_tile_kernel(CriticArgs g)
 {
     __shared__ TileLds lds;
     __shared__ float dql[TS];
@@ -1110,13 +1064,11 @@ struct DwArgs {
     double *norm_parts;         // not NULL: [workgroups] the fp64 sum of squares of what each workgroup stores (its dW tile, its db rows): the
                                 // squared gradient norm in pieces, so that clip + Adam needs no pass over the gradient and no grid-wide wait
     // not NULL (al_lp): workgroup 0 first takes the temperature's Adam step (alpha_step_block: obj_alpha, AgentSAC.py:76-79) -- the critic's
-    // table carries it in the one-stream form of the step (round 6): nothing between launch (1) and the actor's backward reads alpha_log
+    // table carries it: nothing between launch (1) and the actor's backward reads alpha_log
     const float *al_lp;
     int64_t al_n;
     float *al_alpha_log, *al_m1, *al_m2;
     float al_target_entropy, al_beta1, al_beta2, al_eps, al_max_norm, al_step_size, al_bc2_sqrt;
-    int xcd_tiles;              // not 0: the launch's tile count, and workgroups take their tiles in the XCD-contiguous order (dw_table_kernel)
-    int alpha_wg;               // the workgroup that carries the temperature's duties: 0 (with its tile), or the extra one behind the last tile
 };
 constexpr int kDwMaxParts = 1024;      // workgroups of one dw_table launch at the widest supported network (8 decoders of 256 x 256: 592)
 
@@ -1149,24 +1101,13 @@ __global__ __launch_bounds__(256) void dw_table_kernel(DwArgs g)
     __shared__ float bsum[4][32];
     __shared__ double nscratch[16];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, hi = lane >> 5;
-    // the temperature's duties: workgroup 0's first duty (default), or a workgroup of their own behind the last tile (ERL_SAC_DW=2: the serial
-    // prefix -- a sum over the batch, then a dependent Adam round trip -- leaves workgroup 0; measured even, the launch is not held by it)
-    const int wg_alpha = g.alpha_wg;                              // 0, or the extra workgroup's index
-    // which tile: blockIdx.x itself, or (g.xcd_tiles: the launch's tile count) the XCD-contiguous order -- consecutive workgroups go to
-    // consecutive XCDs, so workgroup b takes tile (b % 8) * (tiles / 8) + b / 8 (remainders spread over the first XCDs): the tiles one
-    // XCD's L2 serves are then neighbours in (problem, tm, tn) order and share their dZ row blocks and X column blocks, instead of every XCD
-    // fetching every block of every problem over the fabric.  Everything below (the squared-norm piece too) is indexed by the TILE: same bits.
-    int bid = blockIdx.x;
-    if (g.xcd_tiles && bid < g.xcd_tiles) {
-        const int x = bid & 7, i = bid >> 3, fl = g.xcd_tiles >> 3, rem = g.xcd_tiles & 7;
-        bid = x * fl + min(x, rem) + i;
-    }
-    if (g.clamp_alpha_log && bid == wg_alpha && tid == 0)        // after alpha was read (AgentSAC.py:80-81): the actor's backward has run
+    const int bid = blockIdx.x;                                  // the tile
+    // the temperature's duties come first in workgroup 0 (a workgroup of their own behind the last tile measured even)
+    if (g.clamp_alpha_log && bid == 0 && tid == 0)               // after alpha was read (AgentSAC.py:80-81): the actor's backward has run
         g.clamp_alpha_log[0] = fminf(fmaxf(g.clamp_alpha_log[0], -16.f), 2.f);
-    if (g.al_lp && bid == wg_alpha)                              // (workgroup-uniform: every thread of that workgroup takes part in the sum)
+    if (g.al_lp && bid == 0)                                     // (workgroup-uniform: every thread of that workgroup takes part in the sum)
         alpha_step_block(g.al_lp, g.al_n, g.al_target_entropy, g.al_alpha_log, g.al_m1, g.al_m2, g.al_beta1, g.al_beta2, g.al_eps, g.al_max_norm,
                          g.al_step_size, g.al_bc2_sqrt);
-    if (wg_alpha && bid == wg_alpha) return;                     // (the extra workgroup owns no tile and no squared-norm piece)
     int pi = 0;
     for (int k = 1; k < g.np; ++k)
         if (bid >= g.p[k].tile0) pi = k;
@@ -1184,7 +1125,7 @@ __global__ __launch_bounds__(256) void dw_table_kernel(DwArgs g)
     // U row pairs per round trip; the nZ - 1 further matrices of a summed A operand (the encoder's gradient: one dEnc per decoder) are
     // requested KC at a time in the same round trip (round 6, last session: one more round trip per further matrix made the encoder's
     // tiles -- six round trips at four decoders against two -- the launch's stragglers).  Same loads, same order of every sum and of the
-    // MFMAs in every instantiation: the same bits.
+    // MFMAs for any U and KC: the same bits.
     for (int64_t b = b0; b < b1; b += 2 * U) {       // (uniform trip count; loads clamped + selected: 2 U .. (2 + KC) U in flight per lane)
         float a[U], x[U];
 #pragma unroll
@@ -1265,111 +1206,65 @@ int dw_launch(const DwArgs &a, hipStream_t s)
     const DwProb &last = a.p[a.np - 1];
     ERL_REQUIRE(!a.norm_parts || last.tile0 + last.ntiles <= kDwMaxParts, "erl_sac_update_f32(fused): %d weight-gradient tiles, table of %d",
                 last.tile0 + last.ntiles, kDwMaxParts);
-    // ERL_SAC_DW (read at every launch: the forms are compared inside one process by the tests; all leave the same bits):
-    //   0 (default) a summed operand's matrices requested in ONE round trip, three at a time (dw_table_kernel<16, 3>): config 3 118.7 -> 117.1 us
-    //     per update, the launch 9.45 -> 8.66 us on average (profiles/r06_sac_dw_ab.txt)
-    //   1 round 6's earlier form: one round trip per further matrix (<16, 1>)
-    //   2 as 0, and the temperature's duties in a workgroup of their own behind the last tile instead of in front of workgroup 0's tile: measured even
-    //   3 as 1 with that workgroup
-    //   5 as 0 with the tiles handed out in XCD-contiguous order; 6 as 1 with it
-    //   4 as 0 with a wave's whole quarter of a 256-sample batch in one round trip (<32, 3>: 325 registers, one wave per SIMD): measured slower
-    const char *form_env = getenv("ERL_SAC_DW");
-    const int form = form_env ? atoi(form_env) : 0;
-    DwArgs b = a;
-    const int ntiles = last.tile0 + last.ntiles;
-    const bool own_wg = (form == 2 || form == 3) && (b.al_lp || b.clamp_alpha_log);
-    b.alpha_wg = own_wg ? ntiles : 0;
-    b.xcd_tiles = (form == 5 || form == 6) ? ntiles : 0;
-    const dim3 grid(ntiles + (own_wg ? 1 : 0));
-    if (form == 1 || form == 3 || form == 6) hipLaunchKernelGGL((dw_table_kernel<16, 1>), grid, dim3(256), 0, s, b);
-    else if (form == 4) hipLaunchKernelGGL((dw_table_kernel<32, 3>), grid, dim3(256), 0, s, b);
-    else hipLaunchKernelGGL((dw_table_kernel<16, 3>), grid, dim3(256), 0, s, b);
+    // a summed operand's matrices requested in ONE round trip, three at a time: config 3 118.7 -> 117.1 us per update, the launch 9.45 -> 8.66 us
+    // on average against one round trip per further matrix (<16, 1>); a wave's whole quarter of a 256-sample batch in one round trip (<32, 3>:
+    // one wave per SIMD) measured slower, an XCD-contiguous tile order even (profiles/r06_sac_dw_ab.txt)
+    hipLaunchKernelGGL((dw_table_kernel<16, 3>), dim3(last.tile0 + last.ntiles), dim3(256), 0, s, a);
     return erl_hip_status(hipGetLastError(), "erl_sac_update_f32(fused: dw_table)");
-}
-
-__global__ __launch_bounds__(256) void alpha_step_fused_kernel(const float *__restrict__ lp, int64_t n, float target_entropy, float *__restrict__ alpha_log,
-                                                               float *__restrict__ m1, float *__restrict__ m2, float beta1, float beta2, float eps,
-                                                               float max_norm, float step_size, float bc2_sqrt)
-{
-    alpha_step_block(lp, n, target_entropy, alpha_log, m1, m2, beta1, beta2, eps, max_norm, step_size, bc2_sqrt);
 }
 
 int wclass(int width) { return width <= 64 ? 0 : (width <= 128 ? 1 : 2); }
 
-// a library-owned second stream per device (non-blocking) + the events that fork it from / join it into the caller's stream: the
-// policy-gradient sample (actor forward on `state`) and the temperature step depend on nothing the critic update produces, so they
-// run NEXT TO it (ERL_SAC_STREAMS=1 keeps everything on the caller's stream)
-struct SacSide {
+// The library-owned state of the in-launch exchanges, one slot per (device, caller stream): two agents on different streams of one device
+// never share granules or counters.  One allocation, zeroed on the caller's stream behind whatever it already holds (nothing synchronises
+// the host).  Without a slot -- the allocation failed, or all are taken -- the step runs the unsplit forms of the actor's forward and of the
+// critic's training pass.
+struct SacSlot {
     int device = -1;
-    hipStream_t owner = nullptr;          // the caller's stream this side stream serves
-    hipStream_t stream = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr, mid = nullptr;
-    unsigned *arrive = nullptr;           // [256] arrival counters of the split actor forward (zero between launches), owned by this slot
-    unsigned *arrive1 = nullptr;          // [256] ... of the split critic training pass (its dEnc shares)
-    unsigned long long *qx = nullptr;     // [FMAXE * kQxSplit * 4096] granules {share of q, nonce}: the split critic training pass's q exchange
-    uint32_t nonce = 0;
+    hipStream_t owner = nullptr;
+    unsigned long long *qx = nullptr;     // [FMAXE * kQxSplit * 4096] granules {share of q, nonce} (CriticArgs::qx)
     unsigned long long *yx = nullptr;     // [2 passes][kQxSplit][4096][16] granules {share of the actor's head output, nonce} (ActorFwdArgs::yx)
-    uint32_t nonce_y = 0;
+    unsigned *arrive = nullptr;           // [256] arrival counters of the training pass's dEnc shares (zero between launches)
+    uint32_t nonce = 0, nonce_y = 0;      // of the last step's q / head-share granules
 };
+constexpr size_t kQxGranules = (size_t)FMAXE * kQxSplit * 4096;
 constexpr size_t kYxPass = (size_t)kQxSplit * 4096 * 16;      // granules of one pass
-SacSide g_sac_side[16];
+constexpr size_t kSlotBytes = (kQxGranules + 2 * kYxPass) * sizeof(unsigned long long) + 256 * sizeof(unsigned);
+SacSlot g_sac_slot[16];
+std::mutex g_sac_slot_mutex;          // slot lookup / creation / nonce hand-out (agents on several devices or streams step from their own threads)
 
-// one side stream + event pair per (device, caller stream): two agents on different streams of one device never record each
-// other's events
-SacSide *sac_side_stream(hipStream_t owner)
+// the slot of (the current device, `owner`), created on first use, and this step's two nonces; nullptr: no slot
+SacSlot *sac_slot(hipStream_t owner, uint32_t &nonce, uint32_t &nonce_y)
 {
-    static const bool off = [] { const char *e = getenv("ERL_SAC_STREAMS"); return e && atoi(e) == 1; }();
     int dev = -1;
-    if (off || hipGetDevice(&dev) != hipSuccess || dev < 0) return nullptr;
-    for (auto &q : g_sac_side)
-        if (q.stream && q.device == dev && q.owner == owner) return &q;
-    for (auto &q : g_sac_side) {
-        if (q.stream) continue;
-        if (hipStreamCreateWithFlags(&q.stream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&q.fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&q.join, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&q.mid, hipEventDisableTiming) != hipSuccess) {
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0) return nullptr;
+    std::lock_guard<std::mutex> lock(g_sac_slot_mutex);
+    SacSlot *q = nullptr, *free_slot = nullptr;
+    for (auto &t : g_sac_slot) {
+        if (t.qx && t.device == dev && t.owner == owner) q = &t;
+        if (!t.qx && !free_slot) free_slot = &t;
+    }
+    if (!q) {
+        void *p = nullptr;
+        if (!free_slot) return nullptr;
+        if (hipMalloc(&p, kSlotBytes) != hipSuccess || hipMemsetAsync(p, 0, kSlotBytes, owner) != hipSuccess) {
+            if (p) (void)hipFree(p);
             (void)hipGetLastError();
-            q.stream = nullptr;
             return nullptr;
         }
-        void *cnt = nullptr;
-        if (hipMalloc(&cnt, 512 * sizeof(unsigned)) == hipSuccess && hipMemset(cnt, 0, 512 * sizeof(unsigned)) == hipSuccess) {
-            q.arrive = (unsigned *)cnt;
-            q.arrive1 = q.arrive + 256;
-        } else {
-            (void)hipGetLastError();          // (no counters: the actor's forward and the critic's training pass stay unsplit)
-        }
-        void *qx = nullptr;
-        const size_t qx_bytes = (size_t)FMAXE * kQxSplit * 4096 * sizeof(unsigned long long);
-        if (hipMalloc(&qx, qx_bytes) == hipSuccess && hipMemset(qx, 0, qx_bytes) == hipSuccess) q.qx = (unsigned long long *)qx;
-        else (void)hipGetLastError();
-        void *yx = nullptr;
-        if (hipMalloc(&yx, 2 * kYxPass * sizeof(unsigned long long)) == hipSuccess && hipMemset(yx, 0, 2 * kYxPass * sizeof(unsigned long long)) == hipSuccess)
-            q.yx = (unsigned long long *)yx;
-        else (void)hipGetLastError();
-        (void)hipDeviceSynchronize();             // (once per slot: the caller's stream may be non-blocking, i.e. not ordered behind those memsets)
-        q.device = dev;
-        q.owner = owner;
-        return &q;
+        q = free_slot;
+        q->qx = (unsigned long long *)p;
+        q->yx = q->qx + kQxGranules;
+        q->arrive = (unsigned *)(q->yx + 2 * kYxPass);
+        q->device = dev;
+        q->owner = owner;
     }
-    return nullptr;                          // every slot taken: run on the caller's stream
+    if (++q->nonce == 0) q->nonce = 1;        // (0 is what the cleared granules carry)
+    if (++q->nonce_y == 0) q->nonce_y = 1;
+    nonce = q->nonce;
+    nonce_y = q->nonce_y;
+    return q;
 }
-
-// after the fork every exit path must bring the side stream's work back under the caller's stream (an early error return would
-// otherwise leave kernels running on the shared workspace while the caller moves on)
-struct SacJoin {
-    SacSide *side;
-    hipStream_t s;
-    bool armed = false;
-    ~SacJoin()
-    {
-        if (armed && side) {
-            (void)hipEventRecord(side->join, side->stream);
-            (void)hipStreamWaitEvent(s, side->join, 0);
-        }
-    }
-};
 
 // ---------------------------------------------------------------------------------------------------------
 // Persistent off-policy rollout for the device-resident SynVecEnv: ONE launch per AgentSAC.explore_env.
@@ -1657,7 +1552,6 @@ int64_t erl_sac_fused_ws_floats(int S, int A, int h0, int h1, int E, int64_t B, 
     f += r((int64_t)kCritSplit * E * B * A) + r(B * h1) + r(B * h0);     // dAct | dZ2, dZ1 (actor)
     f += r(Pa) + r(Pc) + r((int64_t)kCritSplit * E * tiles) + r(tiles) + 64;   // gradients, partial sums, alpha0
     f += 2 * 2 * kDwMaxParts;                                           // the squared-norm pieces of the two dw_table launches (doubles)
-    f += 2 * r((int64_t)kCritSplit * B * 2 * A);                        // the slices' shares of the actor's head output (launch (1): both passes)
     return f;
 }
 
@@ -1713,14 +1607,21 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
     float *Y = take(B * 2 * A), *dY = take(B * 2 * A), *H0 = take(B * h0), *G0 = take(B * h0), *H1 = take(B * h1), *G1 = take(B * h1);
     float *dAct = take((int64_t)kCritSplit * E * B * A), *dZ2 = take(B * h1), *dZ1 = take(B * h0);
     float *g_actor = take(Pa), *g_critic = take(Pc), *qpart = take((int64_t)kCritSplit * E * tiles), *tdpart = take(tiles), *alpha0 = take(64);
-    float *act_pg = take(B * A);                        // (its own buffer: the policy-gradient sample runs next to the critic update)
+    float *act_pg = take(B * A);                        // (its own buffer: launch (1)'s action is read by launch (2))
     double *nparts_c = reinterpret_cast<double *>(take(2 * kDwMaxParts)), *nparts_a = reinterpret_cast<double *>(take(2 * kDwMaxParts));
-    float *ypart = take((int64_t)kCritSplit * B * 2 * A);      // the slices' shares of the actor's head output (launch (1))
-    float *ypart2 = take((int64_t)kCritSplit * B * 2 * A);     // ... of the policy-gradient sample's forward when it is split too
     float *dEncP = take((int64_t)kCritSplit * E * B * h0);     // the slices' shares of dEnc (launch (3))
     float *q_pg = qt;                                   // reused once its first contents are consumed
     const dim3 tgrid(tiles), cgrid(tiles, E), blk(FT);
     int rc;
+    // every launch goes to the caller's stream; the split forms' in-launch exchanges wait at most ERL_SAC_QX_SPIN polls per granule
+    static const uint32_t spin = [] { const char *e = getenv("ERL_SAC_QX_SPIN"); return e && atoi(e) > 0 ? (uint32_t)atoi(e) : 1u << 22; }();
+    uint32_t nonce = 0, nonce_y = 0;
+    SacSlot *slot = sac_slot(s, nonce, nonce_y);
+    auto actor_fwd = [&](const ActorFwdArgs &g, const dim3 &grid) {
+#define LAUNCH_ACTOR_FWD(K0, K1) hipLaunchKernelGGL((actor_fwd_kernel<K0, K1>), grid, blk, 0, s, g)
+        FUSED_KT_DISPATCH_D(g.d, LAUNCH_ACTOR_FWD)
+#undef LAUNCH_ACTOR_FWD
+    };
 
     // ---- (1) next action / log-prob (actor on next_state)                                                      (:50-51)
     ActorFwdArgs af{};
@@ -1732,112 +1633,42 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
         af.o_state = const_cast<float *>(state); af.o_action = const_cast<float *>(action); af.o_reward = const_cast<float *>(reward);
         af.o_undone = const_cast<float *>(undone); af.o_unmask = const_cast<float *>(unmask); af.o_next = const_cast<float *>(next_state);
     }
-    hipStream_t sa = s;                                 // the stream the actor-forward launches go to
-#define LAUNCH_ACTOR_FWD(K0, K1) hipLaunchKernelGGL((actor_fwd_kernel<K0, K1>), tgrid, blk, 0, sa, af)
-    SacSide *side = sac_side_stream(s);
-    // The policy-gradient sample (6) runs on a side stream.  Round 6 forks it BEFORE launch (1) -- it reads the actor and the drawn
-    // transitions' state rows (from the ring itself when the sample rides in launch (1): ActorFwdArgs::rg_self), nothing launch (1)
-    // writes -- so that it overlaps launches (1) and (2) and is gone by the time the critic's training pass (3) starts: that pass's 256
-    // workgroups wait for each other (CriticArgs::qx) and need the chip to themselves.  Only the temperature step behind it waits for
-    // launch (1), which parks the old temperature (event `mid`).  ERL_SAC_FORK=2: fork after launch (1) as in rounds 4-5; 0: no fork.
-    const char *fk_env = getenv("ERL_SAC_FORK");
-    const bool do_fork = side && !(fk_env && atoi(fk_env) == 0);
-    static const bool split_on = [] { const char *e = getenv("ERL_SAC_SPLIT"); return !(e && atoi(e) == 0); }();
-    static const bool asplit_on = [] { const char *e = getenv("ERL_SAC_SPLIT"); return !(e && atoi(e) == 2); }();      // (2: the critic passes only)
-    const bool a_split = split_on && asplit_on && side && side->arrive && h1 == 64 * kCritSplit && tiles * kCritSplit <= 256;
-    // round 6: launch (1) and the policy-gradient sample's forward as ONE launch (actor_fwd_pair_kernel; the [256, 256] actor with launch (1)
-    // split); only the temperature step is left for the side stream, forked behind that launch
-    const char *pr_env = getenv("ERL_SAC_PAIR");
-    const bool pair = do_fork && a_split && !(pr_env && atoi(pr_env) == 0) && wclass(h0) == 2 && wclass(h1) == 2 && wclass(h1 / kCritSplit) == 0 &&
-                      (int64_t)tiles * (kCritSplit + 1) <= 65535;
-    const bool fork_early = do_fork && !pair && !(fk_env && atoi(fk_env) == 2);
-    // ERL_SAC_PAIR: 4 (default) as 3 with the sample's forward split over kCritSplit workgroups per tile like launch (1); 3: the temperature step rides the critic's weight-gradient launch (4) -- no side stream at all, nine launches on one
-    // queue: the events that forked / joined the side stream cost ~20 us of gaps per step (profiles/r06_sac_pair_ab.txt); 2: a launch of its own on
-    // the caller's stream; 1: on the side stream; 0: rounds 4-6's side stream for the sample's forward too
-    const int pair_mode = !pair ? 0 : (pr_env ? atoi(pr_env) : 4);
-    const bool side_on = do_fork && !(pair && pair_mode >= 2);
-    const bool alpha_in_dw = pair && pair_mode >= 3;
-    SacJoin joiner{side, s};
-    if (fork_early) {
-        if ((rc = erl_hip_status(hipEventRecord(side->fork, s), "hipEventRecord(fork)"))) return rc;
-        if ((rc = erl_hip_status(hipStreamWaitEvent(side->stream, side->fork, 0), "hipStreamWaitEvent(fork)"))) return rc;
-        joiner.armed = true;
-    }
-    auto pg_args = [&](bool from_ring) {                 // the policy-gradient sample's forward: the actor on `state`, everything kept for the backward pass
-        ActorFwdArgs af2 = af;
-        af2.X = state; af2.noise = eps_cur; af2.counter = 2 * counter + 1; af2.act_t = act_pg; af2.lp = lp_cur; af2.eps_out = eps_used; af2.Y = Y;
-        af2.H0 = H0; af2.G0 = G0; af2.H1 = H1; af2.G1 = G1; af2.alpha0 = nullptr;
-        af2.rg = ErlRingSample{};                        // (`state`: the caller's batch, or staged by launch (1), which a late fork waits for)
-        if (from_ring && ring) {                         // launch (1) is still staging `state`: read the same rows from the ring
-            af2.rg = *ring;
-            af2.rg.out_ids0 = af2.rg.out_ids1 = nullptr;
-            af2.rg_self = 1;
-        }
-        return af2;
-    };
+    // ---- (6) policy-gradient sample (actor on state, everything kept for the backward pass)                       (:72-75)
+    // It reads the actor and `state` only, so it joins launch (1): where the [256, 256] actor's second layer splits, the two are ONE launch
+    // (actor_fwd_pair_kernel), the sample reading its state rows from the ring itself; elsewhere it is the launch right behind (1), reading
+    // the rows (1) staged.  The temperature's step (:76-79) rides the critic's weight-gradient launch (4).
+    ActorFwdArgs pg = af;
+    pg.X = state; pg.noise = eps_cur; pg.counter = 2 * counter + 1; pg.act_t = act_pg; pg.lp = lp_cur; pg.eps_out = eps_used; pg.Y = Y;
+    pg.H0 = H0; pg.G0 = G0; pg.H1 = H1; pg.G1 = G1; pg.alpha0 = nullptr; pg.rg = ErlRingSample{};
+    // (nothing of launch (1) is kept for a backward pass: a 256-wide second layer is split over kCritSplit workgroups per tile -- ActorFwdArgs::split)
+    const bool a_split = slot && h1 == 64 * kCritSplit && tiles * kCritSplit <= 256;
+    const bool pair = a_split && wclass(h0) == 2;
     if (a_split) {
-        // (nothing of this pass is kept for a backward pass: a 256-wide second layer is split over kCritSplit workgroups per tile, the last
-        // of them to arrive finishes the head -- ActorFwdArgs::split)
         ActorFwdArgs sp = af;
-        sp.split = kCritSplit; sp.h1_full = h1; sp.d.h1 = h1 / kCritSplit; sp.Ypart = ypart; sp.arrive = side->arrive;
-        // ERL_SAC_YX=0 keeps the last-arriver meeting of the head's shares (read at every call: the tests compare the two forms in one process)
-        const char *yx_env = getenv("ERL_SAC_YX");
-        const bool yx_on = side->yx && !(yx_env && atoi(yx_env) == 0) && B <= 4096 && 2 * A <= 16;
-        if (yx_on) {
-            static const uint32_t ylim = [] { const char *e = getenv("ERL_SAC_QX_SPIN"); return e && atoi(e) > 0 ? (uint32_t)atoi(e) : 1u << 22; }();
-            if (++side->nonce_y == 0) side->nonce_y = 1;
-            sp.yx = side->yx; sp.nonce = side->nonce_y; sp.spin_limit = ylim; sp.fault = erl_fault_word(ERL_FAULT_SAC_Q_EXCHANGE);
-        }
-        const dim3 sgrid(tiles, kCritSplit);
-#define LAUNCH_ACTOR_SPLIT(K0, K1) hipLaunchKernelGGL((actor_fwd_kernel<K0, K1>), sgrid, blk, 0, sa, sp)
-        if (pair && pair_mode >= 4) {                    // the sample's forward split over kCritSplit workgroups per tile like launch (1): its own counters and shares
-            ActorFwdArgs sp2 = pg_args(true);
-            sp2.split = kCritSplit; sp2.h1_full = h1; sp2.d.h1 = h1 / kCritSplit; sp2.Ypart = ypart2; sp2.arrive = side->arrive + 128;
-            if (yx_on) { sp2.yx = side->yx + kYxPass; sp2.nonce = sp.nonce; sp2.spin_limit = sp.spin_limit; sp2.fault = sp.fault; }
-            hipLaunchKernelGGL((actor_fwd_pair_kernel<2, 0, 0>), dim3(tiles, 2 * kCritSplit), blk, 0, sa, sp, sp2, (int)kCritSplit);
-        } else if (pair) {
-            const ActorFwdArgs af2 = pg_args(true);
-            hipLaunchKernelGGL((actor_fwd_pair_kernel<2, 0, 2>), dim3(tiles, kCritSplit + 1), blk, 0, sa, sp, af2, (int)kCritSplit);
+        sp.split = kCritSplit; sp.h1_full = h1; sp.d.h1 = h1 / kCritSplit;
+        sp.yx = slot->yx; sp.nonce = nonce_y; sp.spin_limit = spin; sp.fault = erl_fault_word(ERL_FAULT_SAC_Q_EXCHANGE);
+        if (pair) {                                      // the sample's forward split the same way, with shares of its own
+            ActorFwdArgs sp2 = pg;
+            if (ring) {
+                sp2.rg = *ring;
+                sp2.rg.out_ids0 = sp2.rg.out_ids1 = nullptr;
+                sp2.rg_self = 1;
+            }
+            sp2.split = kCritSplit; sp2.h1_full = h1; sp2.d.h1 = h1 / kCritSplit;
+            sp2.yx = slot->yx + kYxPass; sp2.nonce = nonce_y; sp2.spin_limit = spin; sp2.fault = sp.fault;
+            hipLaunchKernelGGL(actor_fwd_pair_kernel, dim3(tiles, 2 * kCritSplit), blk, 0, s, sp, sp2, (int)kCritSplit);
         } else {
-            FUSED_KT_DISPATCH_D(sp.d, LAUNCH_ACTOR_SPLIT)
+            actor_fwd(sp, dim3(tiles, kCritSplit));
         }
-#undef LAUNCH_ACTOR_SPLIT
     } else {
-        FUSED_KT_DISPATCH(LAUNCH_ACTOR_FWD)
+        actor_fwd(af, tgrid);
     }
-    // ---- (6) policy-gradient sample (actor on state, kept for the backward pass) and temperature step              (:72-79)
-    // FORKED here onto the side stream: they read the actor, `state` and alpha_log only -- the temperature BEFORE its update
-    // is already parked in alpha0 by launch (1) -- and run next to the critic update (2)-(5); joined before (7).
-    if (fork_early) {
-        if ((rc = erl_hip_status(hipEventRecord(side->mid, s), "hipEventRecord(mid)"))) return rc;     // launch (1) is enqueued
-        sa = side->stream;
-    } else if (side_on) {
-        if ((rc = erl_hip_status(hipEventRecord(side->fork, s), "hipEventRecord(fork)"))) return rc;
-        if ((rc = erl_hip_status(hipStreamWaitEvent(side->stream, side->fork, 0), "hipStreamWaitEvent(fork)"))) return rc;
-        sa = side->stream;
-        joiner.armed = true;
-    }
-    {
-        if (!pair) {
-            const ActorFwdArgs af2 = pg_args(fork_early);
-            ActorFwdArgs keep = af;
-            af = af2;
-            FUSED_KT_DISPATCH(LAUNCH_ACTOR_FWD)
-            af = keep;
-        }
-        if (fork_early && (rc = erl_hip_status(hipStreamWaitEvent(sa, side->mid, 0), "hipStreamWaitEvent(mid)"))) return rc;   // alpha0 is parked
-        const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-        if (!alpha_in_dw)
-            hipLaunchKernelGGL(alpha_step_fused_kernel, dim3(1), dim3(256), 0, sa, lp_cur, B, target_entropy, alpha_log, alpha_m, alpha_v, beta1, beta2,
-                               eps_adam, max_norm, (float)((double)lr / bc1), (float)sqrt(bc2));
-        if (side_on && (rc = erl_hip_status(hipEventRecord(side->join, sa), "hipEventRecord(join)"))) return rc;
-        sa = s;
-    }
+    if (!pair) actor_fwd(pg, tgrid);
     // ---- (2) target ensemble on (next_state, next_action)                                                     (:52)
     // (the passes whose backward does not need q -- (2) and (7) -- split every 256-wide decoder over kCritSplit workgroups while the
     // launch stays within the chip: 16 tiles x 4 decoders x 4 slices = 256 workgroups at B = 256, each streaming 64 KB of W1 instead of
-    // 256 KB through one CU's ~30 GB/s; ERL_SAC_SPLIT=0 turns it off)
-    const int split = (split_on && h1 == 64 * kCritSplit && (int64_t)tiles * E * kCritSplit <= 256) ? kCritSplit : 1;
+    // 256 KB through one CU's ~30 GB/s)
+    const int split = (h1 == 64 * kCritSplit && (int64_t)tiles * E * kCritSplit <= 256) ? kCritSplit : 1;
     FusedDims dsl = d;
     dsl.h1 = h1 / split;
     dim3 cg(tiles, E * split);
@@ -1849,20 +1680,14 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
 #define LAUNCH_CRITIC2(K0, K1) LAUNCH_CRITIC(2, K0, K1)
     FUSED_KT_DISPATCH_D(dsl, LAUNCH_CRITIC0)
     // ---- (3) critic training pass: labels, loss gradient, backward to the encoder output                      (:53-62)
-    // (round 6: split like (2) and (7); its workgroups exchange q inside the launch -- CriticArgs::qx; ERL_SAC_TRAIN_SPLIT=1 selects it)
-    // OFF by default: measured at config 3 (B = 256, 4 critics, profiles/r06_sac_train_split_ab.txt) the split launch is 33.2 us against the
-    // unsplit 28.9 -- workgroup (0, 0) itself runs 28.7k cycles instead of 40.8k (tools/sac_fused_profile.py: the decoder's forward 6.7k
-    // instead of 18.2k, its backward 2.6k instead of 7.4k) but pays 3.4k for the q exchange and 7.1k for the dEnc shares, and 256 mutually
-    // waiting workgroups start later and finish more raggedly than 64 independent ones.  ERL_SAC_TRAIN_SPLIT=1 turns it on (read per call).
-    const char *ts_env = getenv("ERL_SAC_TRAIN_SPLIT");
-    const bool tsplit_on = ts_env ? atoi(ts_env) == 1 : (fork_early || pair);
-    const int tsplit = (split > 1 && tsplit_on && side && side->arrive1 && side->qx && B <= 4096 && kCritSplit == kQxSplit) ? split : 1;
+    // (split like (2) whenever there is a slot: its workgroups exchange q inside the launch -- CriticArgs::qx; at config 3 22 us a launch
+    // against 28 unsplit, profiles/r06_sac_train_split_ab.txt)
+    static_assert(kCritSplit == kQxSplit, "the training pass exchanges kQxSplit shares");
+    const int tsplit = slot ? split : 1;
     cg = tsplit > 1 ? dim3(tiles, E * tsplit) : cgrid;
     ca.d = tsplit > 1 ? dsl : d; ca.split = tsplit; ca.qt_split = split; ca.h1_full = h1;
     if (tsplit > 1) {
-        if (++side->nonce == 0) side->nonce = 1;
-        static const uint32_t lim = [] { const char *e = getenv("ERL_SAC_QX_SPIN"); return e && atoi(e) > 0 ? (uint32_t)atoi(e) : 1u << 22; }();
-        ca.qx = side->qx; ca.nonce = side->nonce; ca.spin_limit = lim; ca.dEncP = dEncP; ca.arrive = side->arrive1;
+        ca.qx = slot->qx; ca.nonce = nonce; ca.spin_limit = spin; ca.dEncP = dEncP; ca.arrive = slot->arrive;
         ca.fault = erl_fault_word(ERL_FAULT_SAC_Q_EXCHANGE);
     }
     ca.P = critic_params; ca.Xs = state; ca.Xa = action; ca.q = qc;
@@ -1871,7 +1696,7 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
     ca.span = erl_span_slot(ERL_SPAN_SAC_CRITIC_TRAIN, (int64_t)cg.x * cg.y);
     FUSED_KT_DISPATCH_D(ca.d, LAUNCH_CRITIC1)
     ca.span = nullptr; ca.h1_full = 0;
-    // ---- (4) every critic weight / bias gradient in one launch
+    // ---- (4) every critic weight / bias gradient in one launch, and the temperature's step (workgroup 0)
     {
         DwArgs dw{};
         dw.B = B;
@@ -1882,12 +1707,10 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
             dw_add(dw, dq + (size_t)e * B, 0, 1, 1, H1e + (size_t)e * B * h1, h1, G + d.dWo, G + d.dbo);
         }
         dw.norm_parts = nparts_c;
-        if (alpha_in_dw) {
-            const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-            dw.al_lp = lp_cur; dw.al_n = B; dw.al_target_entropy = target_entropy; dw.al_alpha_log = alpha_log; dw.al_m1 = alpha_m; dw.al_m2 = alpha_v;
-            dw.al_beta1 = beta1; dw.al_beta2 = beta2; dw.al_eps = eps_adam; dw.al_max_norm = max_norm; dw.al_step_size = (float)((double)lr / bc1);
-            dw.al_bc2_sqrt = (float)sqrt(bc2);
-        }
+        const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+        dw.al_lp = lp_cur; dw.al_n = B; dw.al_target_entropy = target_entropy; dw.al_alpha_log = alpha_log; dw.al_m1 = alpha_m; dw.al_m2 = alpha_v;
+        dw.al_beta1 = beta1; dw.al_beta2 = beta2; dw.al_eps = eps_adam; dw.al_max_norm = max_norm; dw.al_step_size = (float)((double)lr / bc1);
+        dw.al_bc2_sqrt = (float)sqrt(bc2);
         if ((rc = dw_launch(dw, s))) return rc;
         // ---- (5) clip + Adam on the critic from the launch's squared-norm pieces, soft target update in the same launch  (:69-70)
         if ((rc = erl_clip_adam_parts_soft_f32(critic_params, g_critic, critic_m, critic_v, Pc, nparts_c, dw.p[dw.np - 1].tile0 + dw.p[dw.np - 1].ntiles,
@@ -1895,8 +1718,6 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
             return rc;
     }
     // ---- (7) TARGET ensemble on (state, action_pg): q and d(mean q)/d(action); finishes the critic objective    (:82-83)
-    if (side_on && (rc = erl_hip_status(hipStreamWaitEvent(s, side->join, 0), "hipStreamWaitEvent(join)"))) return rc;
-    joiner.armed = false;
     cg = dim3(tiles, E * split);
     ca.d = dsl; ca.split = split; ca.qt_split = 1;
     ca.P = target_params; ca.Xs = state; ca.Xa = act_pg; ca.q = q_pg;
@@ -1909,8 +1730,7 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
         ab.G1 = G1; ab.lp_cur = lp_cur; ab.dY = dY; ab.dZ2 = dZ2; ab.dZ1 = dZ1; ab.tdpart = tdpart; ab.qpart = qpart; ab.ntiles = tiles; ab.nsplit = split;
         ab.objs_out = objs_out;
         // (the one heavy layer of this pass, dH0 = W2^T dZ2, is output-split over kCritSplit workgroups per tile like the critic passes above)
-        static const bool bsplit_on = [] { const char *e = getenv("ERL_SAC_SPLIT"); return !(e && (atoi(e) == 2 || atoi(e) == 3)); }();   // (3: all but this one)
-        const int bsplit = (split_on && bsplit_on && h0 == 64 * kCritSplit && tiles * kCritSplit <= 256) ? kCritSplit : 1;
+        const int bsplit = (h0 == 64 * kCritSplit && tiles * kCritSplit <= 256) ? kCritSplit : 1;
         ab.split = bsplit; ab.h0_full = h0; ab.d.h0 = h0 / bsplit;
         const dim3 bgrid(tiles, bsplit);
 #define LAUNCH_ACTOR_BWD(K0, K1) hipLaunchKernelGGL((actor_bwd_kernel<K0, K1>), bgrid, blk, 0, s, ab)

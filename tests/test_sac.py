@@ -378,7 +378,7 @@ def test_train_agent_sac_pendulum_learns(tmp_path):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("S,A,hidden,E,B", [(5, 1, (32,), 1, 37), (11, 3, (256, 256), 4, 256), (17, 6, (64, 48, 32), 2, 130),
-                                           (3, 1, (128, 64), 4, 64)])
+                                           (3, 1, (128, 64), 4, 64), (11, 3, (256, 256), 8, 64)])
 def test_sac_update_matches_torch_restatement_on_other_shapes(S, A, hidden, E, B):
     """erl_sac_update_f32 vs oracle/sac_torch.py (itself pinned to the reference golden) on random batches for network
     shapes the golden does not cover: 1..3 hidden layers, 1..4 ensembles, scalar actions, the demos' [256, 256]."""
@@ -424,57 +424,14 @@ def test_sac_update_matches_torch_restatement_on_other_shapes(S, A, hidden, E, B
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("B,E", [(256, 4), (100, 2), (64, 8)])
-def test_sac_split_training_pass_agrees_with_the_unsplit_one(B, E, monkeypatch):
-    """round 6: the critic's training pass splits every 256-wide decoder over four workgroups that exchange their shares of q INSIDE the
-    launch (CriticArgs::qx) and add their shares of dEnc by last-arriver (ERL_SAC_TRAIN_SPLIT=0: one workgroup per tile and decoder, as
-    before).  Same inputs, three steps each: objectives, critic / target / actor weights and the returned td errors agree to summation
-    order (the shares of q and dEnc are added in slice order instead of feature order), repeated launches of the split form are
-    bit-identical to each other (fixed orders everywhere), no exchange wait timed out."""
-    from elegantrl_amd import _hip, ops
-    dev = th.device("cuda:0")
-    S, A, hidden = 11, 3, (256, 256)
-    spec = ops.SacSpec(S, A, hidden, E)
-    g = th.Generator(device=dev).manual_seed(B + E)
-    init = [0.05 * th.randn(n, device=dev, generator=g) for n in (spec.actor_count, spec.critic_count, spec.critic_count)]
-    batches = [((th.randn((B, S), device=dev, generator=g), th.randn((B, A), device=dev, generator=g).tanh(), th.randn(B, device=dev, generator=g),
-                 (th.rand(B, device=dev, generator=g) > 0.1).float(), (th.rand(B, device=dev, generator=g) > 0.1).float(),
-                 th.randn((B, S), device=dev, generator=g)), th.randn((B, A), device=dev, generator=g), th.randn((B, A), device=dev, generator=g))
-               for _ in range(3)]
-
-    def run(train_split):
-        monkeypatch.setenv("ERL_SAC_TRAIN_SPLIT", "1" if train_split else "0")
-        pa, pc, pt = [x.clone() for x in init]
-        alpha = th.full((1,), -1.0, device=dev)
-        mom = [th.zeros_like(pa), th.zeros_like(pa), th.zeros_like(pc), th.zeros_like(pc), th.zeros(1, device=dev), th.zeros(1, device=dev)]
-        objs, td, out = th.zeros(2, device=dev), th.zeros(B, device=dev), []
-        for step, (batch, e_next, e_cur) in enumerate(batches, 1):
-            ops.sac_update(spec, pa, pc, pt, alpha, mom, list(batch), step, gamma=0.97, target_entropy=-float(A), tau=5e-3, lr=1e-3, max_norm=3.0,
-                           objs_out=objs, noises=(e_next, e_cur), td_error_out=td)
-            out.append((objs.clone(), td.clone()))
-        th.cuda.synchronize()
-        _hip.check_async_faults()
-        return pa, pc, pt, out
-
-    a, b, a2 = run(True), run(False), run(True)
-    for x, y in zip(a[:3], a2[:3]):
-        assert th.equal(x, y)                                   # the split form is deterministic
-    for (oa, ta), (ob, tb) in zip(a[3], b[3]):
-        np.testing.assert_allclose(oa.cpu().numpy(), ob.cpu().numpy(), rtol=2e-5, atol=1e-6)
-        np.testing.assert_allclose(ta.cpu().numpy(), tb.cpu().numpy(), rtol=2e-4, atol=1e-6)
-    for x, y in zip(a[:3], b[:3]):
-        d = (x - y).abs().cpu().numpy()
-        assert (d <= 2e-5).mean() >= 0.995 and d.max() <= 6.6e-3      # (Adam's step for a gradient at the fp32 noise floor: see above)
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("B,E,hidden", [(256, 4, (256, 256)), (100, 2, (256, 256)), (64, 8, (256, 256)), (130, 5, (64, 48))])
-def test_sac_weight_gradient_table_forms_are_bit_identical(B, E, hidden, monkeypatch):
-    """dw_table_kernel (csrc/sac_fused.hip), ERL_SAC_DW: 0 (default) requests a summed operand's matrices (the encoder's gradient: one dEnc
-    per decoder) in one round trip; 1 is the earlier form (one round trip per further matrix); 2 / 3 the same two with the temperature's
-    Adam step / clamp in a workgroup of their own behind the last tile; 4 a deeper instantiation; 5 / 6 = 0 / 1 with the tiles handed out in
-    XCD-contiguous order.  Same loads, same order of every sum:
-    weights, moments, temperature and objectives must be the SAME BITS after three steps."""
+@pytest.mark.parametrize("B,E,hidden,alpha0", [(256, 4, (256, 256), 1.9), (100, 2, (256, 256), -1.0), (64, 8, (256, 256), -1.0),
+                                               (4096, 2, (256, 256), -1.0), (37, 1, (256, 256), -1.0), (130, 5, (64, 48), -1.0)])
+def test_sac_fused_step_is_bit_identical_when_repeated(B, E, hidden, alpha0):
+    """The fused step's in-launch exchanges (csrc/sac_fused.hip: the split training pass's shares of q and dEnc, the split actor forward's
+    head shares) add every share in slice order, and the weight-gradient table carries the temperature's step in workgroup 0: three steps run
+    twice from the same inputs give the SAME BITS -- weights, moments, temperature, objectives, td errors -- and a third time too (the nonce
+    moves on: older granules are never mistaken for new ones).  No exchange wait timed out.  alpha_log = 1.9 starts close to the clamp's
+    upper edge, so that the clamp has work to do."""
     from elegantrl_amd import _hip, ops
     dev = th.device("cuda:0")
     S, A = 11, 3
@@ -486,63 +443,23 @@ def test_sac_weight_gradient_table_forms_are_bit_identical(B, E, hidden, monkeyp
                  th.randn((B, S), device=dev, generator=g)), th.randn((B, A), device=dev, generator=g), th.randn((B, A), device=dev, generator=g))
                for _ in range(3)]
 
-    def run(form):
-        monkeypatch.setenv("ERL_SAC_DW", form)
+    def run():
         pa, pc, pt = [x.clone() for x in init]
-        alpha = th.full((1,), 1.9, device=dev)                   # (close to the clamp's upper edge: the clamp has work to do)
+        alpha = th.full((1,), alpha0, device=dev)
         mom = [th.zeros_like(pa), th.zeros_like(pa), th.zeros_like(pc), th.zeros_like(pc), th.zeros(1, device=dev), th.zeros(1, device=dev)]
-        objs, out = th.zeros(2, device=dev), []
+        objs, td, out = th.zeros(2, device=dev), th.zeros(B, device=dev), []
         for step, (batch, e_next, e_cur) in enumerate(batches, 1):
             ops.sac_update(spec, pa, pc, pt, alpha, mom, list(batch), step, gamma=0.97, target_entropy=-float(A), tau=5e-3, lr=1e-3, max_norm=3.0,
-                           objs_out=objs, noises=(e_next, e_cur))
-            out.append(objs.clone())
+                           objs_out=objs, noises=(e_next, e_cur), td_error_out=td)
+            out += [objs.clone(), td.clone()]
         th.cuda.synchronize()
         _hip.check_async_faults()
         return [pa, pc, pt, alpha] + mom + out
 
-    ref = run("1")
-    for form in ("0", "2", "3", "4", "5", "6"):
-        for x, y in zip(ref, run(form)):
-            assert th.equal(x, y), f"ERL_SAC_DW={form}"
-
-
-@pytest.mark.gpu
-@pytest.mark.parametrize("B,E", [(256, 4), (100, 2), (4096, 2), (37, 1)])
-def test_sac_head_share_meeting_forms_are_bit_identical(B, E, monkeypatch):
-    """The split actor forward's slices meet either by last arriver (shares to memory, acknowledged, an arrival counter, the last one fetches:
-    ERL_SAC_YX=0) or by owner (round 6: {share, nonce} granules, the tile's last-dispatched slice polls and adds in slice order: the default).
-    Same sums in the same order: actions, log-probs and everything downstream -- weights, moments, temperature, objectives -- are the SAME BITS
-    after three steps; no wait timed out (B = 4096: 2048 workgroups, far more than are resident at once)."""
-    from elegantrl_amd import _hip, ops
-    dev = th.device("cuda:0")
-    S, A, hidden = 11, 3, (256, 256)
-    spec = ops.SacSpec(S, A, hidden, E)
-    g = th.Generator(device=dev).manual_seed(11 * B + E)
-    init = [0.05 * th.randn(n, device=dev, generator=g) for n in (spec.actor_count, spec.critic_count, spec.critic_count)]
-    batches = [((th.randn((B, S), device=dev, generator=g), th.randn((B, A), device=dev, generator=g).tanh(), th.randn(B, device=dev, generator=g),
-                 (th.rand(B, device=dev, generator=g) > 0.1).float(), (th.rand(B, device=dev, generator=g) > 0.1).float(),
-                 th.randn((B, S), device=dev, generator=g)), th.randn((B, A), device=dev, generator=g), th.randn((B, A), device=dev, generator=g))
-               for _ in range(3)]
-
-    def run(form):
-        monkeypatch.setenv("ERL_SAC_YX", form)
-        pa, pc, pt = [x.clone() for x in init]
-        alpha = th.full((1,), -1.0, device=dev)
-        mom = [th.zeros_like(pa), th.zeros_like(pa), th.zeros_like(pc), th.zeros_like(pc), th.zeros(1, device=dev), th.zeros(1, device=dev)]
-        objs, out = th.zeros(2, device=dev), []
-        for step, (batch, e_next, e_cur) in enumerate(batches, 1):
-            ops.sac_update(spec, pa, pc, pt, alpha, mom, list(batch), step, gamma=0.97, target_entropy=-float(A), tau=5e-3, lr=1e-3, max_norm=3.0,
-                           objs_out=objs, noises=(e_next, e_cur))
-            out.append(objs.clone())
-        th.cuda.synchronize()
-        _hip.check_async_faults()
-        return [pa, pc, pt, alpha] + mom + out
-
-    ref = run("0")
-    for x, y in zip(ref, run("1")):
-        assert th.equal(x, y)
-    for x, y in zip(ref, run("1")):                               # (twice: the nonce moves on, older granules are never mistaken for new ones)
-        assert th.equal(x, y)
+    ref = run()
+    for again in range(2):
+        for x, y in zip(ref, run()):
+            assert th.equal(x, y), f"run {again + 2}"
 
 
 @pytest.mark.gpu
