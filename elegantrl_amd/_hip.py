@@ -22,7 +22,7 @@ GAE_VTRACE, GAE_MUTATE, GAE_STATS = 0x1, 0x2, 0x4
 GAE_ALGO_AUTO, GAE_ALGO_EXACT, GAE_ALGO_CHUNKED, GAE_ALGO_LOOKBACK = 0x00, 0x10, 0x20, 0x30
 MAX_STATE_DIM, MAX_HIDDEN, MAX_ACTION_DIM = 128, 128, 16
 MAX_LAYERS, MAXN_WIDTH = 6, 4096
-ABI_VERSION = 19
+ABI_VERSION = 20
 PPO_OBJ_REFERENCE, PPO_OBJ_CANONICAL, PPO_OBJ_A2C = 0, 1, 2      # include/erl_hip.h ERL_PPO_OBJ_*
 SAC_ACTOR_SAC, SAC_ACTOR_FIX = 0, 1                               # include/erl_hip.h ERL_SAC_ACTOR_*
 COMM_ID_BYTES = 128
@@ -146,6 +146,13 @@ _SIGNATURES = {
                                            c_uint64, c_uint64, c_float, _P, _P, _P, _P, _P, _P, _P]),
     "erl_sac_rollout_pendulum_f32": (c_int, [_P, POINTER(c_int), c_int, _P, _P, _P, _P, c_int, c_uint64, c_int64, c_int64, _P, c_uint64, c_uint64,
                                              c_float, _P, _P, _P, _P, _P, _P, _P]),
+    "erl_eval_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "erl_eval_synenv_f32": (c_int, [_P] * 3 + [c_int] * 4 + [_P] * 5 + [c_int, c_uint64, c_int64, c_int64, _P, c_int64, _P]),
+    "erl_eval_pendulum_f32": (c_int, [_P] * 3 + [c_int] * 2 + [_P] * 4 + [c_int, c_uint64, c_int64, c_int64, _P, c_int64, _P]),
+    "erl_sac_eval_synenv_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, _P, _P, _P, _P, c_int, c_uint64, c_int64, c_int64, _P,
+                                        c_int64, _P]),
+    "erl_sac_eval_pendulum_f32": (c_int, [_P, POINTER(c_int), c_int, _P, _P, _P, _P, c_int, c_uint64, c_int64, c_int64, _P, c_int64, _P]),
+    "erl_eval_episodes_compact_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, c_int64, _P, _P]),
     "erl_k6_timing_enable": (None, [c_int]),
     "erl_k6_timing_read": (c_int, [POINTER(ctypes.c_double), POINTER(c_int)]),
     "erl_k6_timing_read2": (c_int, [POINTER(ctypes.c_double), POINTER(ctypes.c_double), POINTER(c_int)]),

@@ -131,6 +131,33 @@ class AgentBase:
         self.rng_seed = (int(seed) if seed is not None else max(0, gpu_id)) * 1000003 + 7919 * self.rank
         self.rng_counter = 0
 
+    # ---- evaluation on the device (csrc/rollout_eval.hip) ---------------------------------------------
+    def evaluate_env(self, env) -> Optional[TEN]:
+        """(n_episodes, 2) float32 CPU tensor of (return, length) of every episode `env` finishes within `env.max_step` steps of the
+        deterministic policy `act(state)`, from two launches -- or None where this agent / env pair has no fused evaluation (the
+        Evaluator then runs its loop).  AgentPPO and AgentSAC implement it."""
+        return None
+
+    def _evaluate_env_fused(self, env, launch) -> TEN:
+        """env.reset(), `launch(workspace)` = the persistent evaluation launch, the compaction launch, and two device-to-host copies:
+        the episode count, then the rows.  Touches nothing the training loop reads: the buffers here are the evaluation's own."""
+        from ..envs.vec_envs import compact_episodes
+        N, H, dev = int(env.num_envs), int(env.max_step), self.device
+        nbytes = int(_hip.lib().erl_eval_workspace_bytes(N, H))
+        if nbytes <= 0:
+            raise _hip.HipExtensionError(f"evaluate_env: erl_eval_workspace_bytes({N}, {H}) = {nbytes}")
+        bufs = getattr(self, "_eval_bufs", None)
+        if bufs is None or bufs[0] != (N, H, dev):
+            bufs = ((N, H, dev), th.empty(nbytes, dtype=th.uint8, device=dev), th.empty((N * H, 2), dtype=th.float32, device=dev),
+                    th.empty(1, dtype=th.int32, device=dev))
+            self._eval_bufs = bufs
+        _, workspace, rows, count = bufs
+        env.reset()
+        launch(workspace)
+        compact_episodes(workspace, N, H, rows, count)
+        n = int(count.item())
+        return rows[:n].cpu()
+
     # `act` is settable (run.py:404-407 replaces it with the learner's copy); subclasses re-bind kernels
     @property
     def act(self):

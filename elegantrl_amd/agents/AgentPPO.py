@@ -462,6 +462,38 @@ class AgentPPO(AgentBase):
         unmasks = th.logical_not(truncates)
         return states, actions, logprobs, rewards, undones, unmasks
 
+    # ---- evaluation: the deterministic policy on a device-resident env, two launches ----------------
+    def _fused_eval_reason(self, env) -> Optional[str]:
+        """None when `evaluate_env(env)` runs the fused evaluation, else why not"""
+        if self.device.type != "cuda":
+            return "no GPU"
+        if not self._fused:
+            return "the agent is not on the fused path (" + self.kernel_path.split(":")[0] + ")"
+        if not self.fused_rollout:           # (the conditions of the training twin, _explore_vec_env)
+            return "args.fused_rollout is off (the persistent rollout and its evaluation form go together)"
+        if not hasattr(env, "fused_evaluate"):
+            return f"{type(env).__name__} has no fused_evaluate"
+        if getattr(env, "device", None) != self.device:
+            return f"the env lives on {getattr(env, 'device', None)}, the agent on {self.device}"
+        if getattr(env, "num_envs", None) != self.num_envs:
+            return f"the env has {getattr(env, 'num_envs', None)} envs, the agent {self.num_envs}"
+        S, A = self.state_dim, self.action_dim
+        if getattr(env, "state_dim", None) != S or getattr(env, "action_dim", None) != A:
+            return "the env's state / action dims are not the agent's"
+        if not _hip.lib().erl_rollout_fused_supported(S, self.net_dims[0], self.net_dims[1], A):
+            return f"S={S} net_dims={list(self.net_dims)} A={A} outside the persistent rollout's shapes"
+        return None
+
+    @_hip.on_device
+    def evaluate_env(self, env) -> Optional[TEN]:
+        """AgentBase.evaluate_env on the persistent rollout's evaluation form (erl_eval_synenv_f32 / erl_eval_pendulum_f32): env.reset(),
+        env.max_step steps of tanh(mean) in one launch, the episode table from a second; None outside the fused rollout's shapes.
+        Leaves rng_counter, last_state, the rollout cache, the weights and the optimiser state alone."""
+        if self._fused_eval_reason(env) is not None:
+            return None
+        self._sync_modules()
+        return self._evaluate_env_fused(env, lambda ws: env.fused_evaluate(self, int(env.max_step), ws))
+
     @_hip.on_device
     def _explore_one_env(self, env, horizon_len: int, if_random: bool = False):
         """single (numpy, non-vectorised) env: AgentPPO.py:34-85; the policy still runs on the GPU."""

@@ -262,6 +262,37 @@ class AgentSAC(AgentBase):
         self._last_state_token = (last_out, last_out._version, env, getattr(env, "state_epoch", None), (id(env.state), env.state._version))
         return states, actions, rewards, undones, unmasks
 
+    def _fused_eval_reason(self, env) -> Optional[str]:
+        """None when `evaluate_env(env)` runs the fused evaluation, else why not"""
+        # (the conditions of the training twin, _explore_vec_env: support is exactly that of the persistent rollout)
+        if self.device.type != "cuda":
+            return "no GPU"
+        if self._actor_variant:
+            return "ActorFixSAC (AgentModSAC) has no persistent rollout"
+        if not self.fused_rollout:
+            return "args.fused_rollout is off (the persistent rollout and its evaluation form go together)"
+        if not hasattr(env, "fused_evaluate_offpolicy"):
+            return f"{type(env).__name__} has no fused_evaluate_offpolicy"
+        if getattr(env, "device", None) != self.device:
+            return f"the env lives on {getattr(env, 'device', None)}, the agent on {self.device}"
+        if getattr(env, "num_envs", None) != self.num_envs:
+            return f"the env has {getattr(env, 'num_envs', None)} envs, the agent {self.num_envs}"
+        if getattr(env, "state_dim", None) != self.state_dim or getattr(env, "action_dim", None) != self.action_dim:
+            return "the env's state / action dims are not the agent's"
+        sp = self._spec
+        if not _hip.lib().erl_sac_rollout_synenv_supported(sp.S, sp.A, sp._c, len(sp.hidden), self.num_envs):
+            return f"S={sp.S} A={sp.A} net_dims={list(self.net_dims)} N={self.num_envs} outside the persistent off-policy rollout's shapes"
+        return None
+
+    @_hip.on_device
+    def evaluate_env(self, env) -> Optional[TEN]:
+        """AgentBase.evaluate_env on the persistent off-policy rollout's evaluation form (erl_sac_eval_synenv_f32 / erl_sac_eval_pendulum_f32):
+        env.reset(), env.max_step steps of ActorSAC.forward in one launch, the episode table from a second; None outside its shapes."""
+        if self._fused_eval_reason(env) is not None:
+            return None
+        self._sync_modules()
+        return self._evaluate_env_fused(env, lambda ws: env.fused_evaluate_offpolicy(self, int(env.max_step), ws))
+
     @_hip.on_device
     def explore_action(self, state: TEN, noise: Optional[TEN] = None, out: Optional[TEN] = None, out_state: Optional[TEN] = None) -> TEN:
         """`out` (n, action_dim), contiguous: the kernel writes the action there (the rollout passes its buffer row: no copy);

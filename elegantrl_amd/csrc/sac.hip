@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "mlpn_common.h"
+#include "eval_ws.h"
 
 extern "C" int erl_clip_adam_f32(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, const int64_t *group_off,
                                  const int64_t *group_len, int n_groups, const int32_t *step_base, int32_t step_offset, float lr,
@@ -713,6 +714,44 @@ extern "C" int erl_sac_rollout_pendulum_f32(const float *actor_params, const int
     return erl_sac_rollout_fused(actor_params, 3, 1, hidden[0], hidden[1], aoff, obs, nullptr, nullptr, phys, step_count, episode, max_step, env_seed,
                                  N, H, noise, seed, counter0, reward_scale, out_states, out_actions, out_rewards, out_undones, out_unmasks,
                                  out_last_state, (hipStream_t)stream);
+}
+
+// The evaluation form of the two launches above (sac_fused.hip sac_rollout_synenv_kernel<.., EV>): H steps of the deterministic policy
+// ActorSAC.forward, per-episode (return, length) records and per-env episode counts into `workspace` (erl_eval_workspace_bytes(N, H));
+// erl_eval_episodes_compact_f32 (rollout_eval.hip) turns them into the evaluator's table.  Support is that of the training twin.
+static int sac_eval_impl(const char *what, const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state,
+                         const float *Ws, const float *Wa, float *phys, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
+                         int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    ERL_REQUIRE(hidden && n_hidden >= 1 && erl_sac_rollout_synenv_supported(S, A, hidden, n_hidden, N), "%s: unsupported dims S=%d A=%d N=%lld (two "
+                "hidden layers <= 256 wide in steps of 16, S + A <= 64, A <= 8, N <= 4096; ERL_SAC_FUSED=0 turns it off)", what, S, A, (long long)N);
+    ERL_REQUIRE(H >= 1 && H < (1LL << 30) && max_step >= 1 && erl_eval_ws_bytes(N, H) > 0, "%s: bad H=%lld max_step=%d", what, (long long)H, max_step);
+    ERL_REQUIRE(workspace_bytes >= erl_eval_ws_bytes(N, H), "%s: workspace of %lld bytes, erl_eval_workspace_bytes(N, H) = %lld", what,
+                (long long)workspace_bytes, (long long)erl_eval_ws_bytes(N, H));
+    SacDims d;
+    ERL_REQUIRE(make_sac_dims(S, A, hidden, n_hidden, 1, &d), "%s: unsupported dims", what);
+    const int64_t aoff[6] = {d.actor.oW[0], d.actor.ob[0], d.actor.oW[1], d.actor.ob[1], d.actor.oW[2], d.actor.ob[2]};
+    const ErlEvalWs w = erl_eval_ws_layout(workspace, N, H);
+    return erl_sac_rollout_fused(actor_params, S, A, hidden[0], hidden[1], aoff, env_state, Ws, Wa, phys, step_count, episode, max_step, env_seed,
+                                 N, H, nullptr, 0, 0, 1.0f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, w.rec, w.cnt);
+}
+
+extern "C" int erl_sac_eval_synenv_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state, const float *Ws,
+                                       const float *Wa, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
+                                       void *workspace, int64_t workspace_bytes, void *stream)
+{
+    ERL_REQUIRE(actor_params && env_state && Ws && Wa && step_count && episode && workspace, "erl_sac_eval_synenv_f32: NULL tensor");
+    return sac_eval_impl("erl_sac_eval_synenv_f32", actor_params, S, A, hidden, n_hidden, env_state, Ws, Wa, nullptr, step_count, episode, max_step,
+                         env_seed, N, H, workspace, workspace_bytes, stream);
+}
+
+extern "C" int erl_sac_eval_pendulum_f32(const float *actor_params, const int *hidden, int n_hidden, float *phys, float *obs, int32_t *step_count,
+                                         int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H, void *workspace,
+                                         int64_t workspace_bytes, void *stream)
+{
+    ERL_REQUIRE(actor_params && phys && obs && step_count && episode && workspace, "erl_sac_eval_pendulum_f32: NULL tensor");
+    return sac_eval_impl("erl_sac_eval_pendulum_f32", actor_params, 3, 1, hidden, n_hidden, obs, nullptr, nullptr, phys, step_count, episode, max_step,
+                         env_seed, N, H, workspace, workspace_bytes, stream);
 }
 
 // ActorSAC.get_action for the off-policy rollout (AgentSAC.py:179-185): action = tanh(mean + std * eps); state_out (may be NULL):

@@ -1295,6 +1295,10 @@ struct SacRolloutArgs {
     int32_t *step_count, *episode;
     int max_step;
     uint64_t env_seed;
+    // evaluation form (EV): (H, N) records (return, length) of the episode that ended at (t, env) -- length 0: none -- and the number
+    // of episodes each env finished (eval_ws.h)
+    float2 *ev_rec;
+    int32_t *ev_cnt;
 };
 
 constexpr int SR_XLD = 68, SR_WLD = 68;
@@ -1304,7 +1308,12 @@ constexpr int SR_O_RED = SR_O_ACT + 16 * 16, SR_O_W1L = SR_O_RED + 8 * 16 * 2, S
 
 enum { SR_ENV_SYN = 0, SR_ENV_PENDULUM = 1 };
 
-template <int C0, int C1, int ENV>
+// EV (the evaluation form, behind erl_sac_eval_*_f32): the deterministic policy -- the action is tanh of the first A head outputs,
+// ActorSAC.forward -- without the draws, the states / actions / rewards / flags rows and the reward scale.  The layers and the env
+// step are the statements of the training form (which under an all-zero injected noise computes tanh(mean + std * 0)), so rewards,
+// flags, final state and counters are its own, bit for bit; the thread that owns an env's reward keeps a running return (fp32 rewards
+// summed in fp64, in time order) and length instead, and leaves a record where an episode ends (rollout_eval.hip compacts them).
+template <int C0, int C1, int ENV, bool EV = false>
 __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g)
 {
     __shared__ TileLds lds;
@@ -1355,6 +1364,15 @@ __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g
     float th = 0.f, thdot = 0.f;
     int psc = 0, pep = 0;
     if (ENV == SR_ENV_PENDULUM) { th = g.phys[2 * prow]; thdot = g.phys[2 * prow + 1]; psc = g.step_count[prow]; pep = g.episode[prow]; }
+    // (evaluation form) the open episode of the env whose reward this thread computes, and the episodes it has finished
+    double ev_ret = 0.0;
+    int ev_len = 0, ev_n = 0;
+    auto ev_account = [&](int t, int64_t e, float rew, bool done) {
+        ev_ret += (double)rew;
+        ev_len += 1;
+        g.ev_rec[(size_t)t * N + e] = done ? make_float2((float)ev_ret, (float)ev_len) : make_float2(0.f, 0.f);
+        if (done) { ev_n += 1; ev_ret = 0.0; ev_len = 0; }
+    };
     lds_barrier();
 
     for (int t = 0; t < H; ++t) {
@@ -1370,7 +1388,7 @@ __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g
             const int s_ = e / (16 * ns), c = e - s_ * (16 * ns);
             const float v = XS[s_ * SR_XLD + c];
             lds.T0[s_ * LDT + c] = v;
-            if (c < S && row0 + s_ < N) g.o_states[((size_t)t * N + row0 + s_) * S + c] = v;
+            if (!EV && c < S && row0 + s_ < N) g.o_states[((size_t)t * N + row0 + s_) * S + c] = v;
         }
         lds_barrier();
         f32x4 z[2], gk[2];
@@ -1383,7 +1401,11 @@ __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g
         layer_small_mma<false, true>(wh, BIA + 2 * FMAXW, d.h1, 2 * d.A, lds.T0, lds.part, lds.Yl, L);
         if (L.tid < TS) {                                  // actor_fwd_kernel's tail: action = tanh(mean + std * eps)
             const int64_t b = row0 + L.tid, bc = min(b, N - 1);
-            for (int a = 0; a < A; ++a) {
+            if constexpr (EV) {                            // ActorSAC.forward (AgentSAC.py:47-48): tanh of the first A head outputs
+#pragma unroll 1
+                for (int a = 0; a < A; ++a) ACT[L.tid * 16 + a] = tanhf(lds.Yl[L.tid * 16 + a]);
+            }
+            for (int a = 0; !EV && a < A; ++a) {
                 const float mean = lds.Yl[L.tid * 16 + a], ls = lds.Yl[L.tid * 16 + A + a];
                 const float lsc = fminf(fmaxf(ls, -16.f), 2.f);
                 const float sd = expf(lsc);
@@ -1420,7 +1442,19 @@ __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g
                 XS[L.tid * SR_XLD + 0] = cosf(nth);
                 XS[L.tid * SR_XLD + 1] = sinf(nth);
                 XS[L.tid * SR_XLD + 2] = nthdot;
-                if (b < N) {
+                if constexpr (EV) {
+                    // the env's account waits in LDS between steps -- its thread's own row of ACT, columns 8..11 (A = 1 uses column 0; zeroed
+                    // with the tile before the loop): held in registers across the layers it cost four more than the training form has
+                    double *acc = reinterpret_cast<double *>(ACT + L.tid * 16 + 8);
+                    int *cnt = reinterpret_cast<int *>(ACT + L.tid * 16 + 10);      // [length of the open episode, episodes finished]
+                    const double ret = *acc + (double)(-0.5f * cost);
+                    const int len = cnt[0] + 1;
+                    if (b < N) g.ev_rec[(size_t)t * N + b] = trunc ? make_float2((float)ret, (float)len) : make_float2(0.f, 0.f);
+                    *acc = trunc ? 0.0 : ret;
+                    cnt[0] = trunc ? 0 : len;
+                    if (trunc) cnt[1] += 1;
+                }
+                if (!EV && b < N) {
                     const float rew = -0.5f * cost;
                     g.o_rewards[(size_t)t * N + b] = g.reward_scale == 1.0f ? rew : rew * g.reward_scale;
                     g.o_undones[(size_t)t * N + b] = 1;
@@ -1485,7 +1519,8 @@ __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g
                 for (int r = 0; r < 4; ++r) if (j0 + r >= S) out[r] = 0.f;
                 *reinterpret_cast<float4 *>(XS + L.l15 * SR_XLD + j0) = make_float4(out[0], out[1], out[2], out[3]);
             }
-            if (L.wave == 0 && L.q == 0 && valid) {
+            if constexpr (EV) { if (L.wave == 0 && L.q == 0 && valid) ev_account(t, row, -(sq / (float)S) - 0.01f * (a2 / (float)A), done); }
+            if (!EV && L.wave == 0 && L.q == 0 && valid) {
                 const float rew = -(sq / (float)S) - 0.01f * (a2 / (float)A);
                 g.o_rewards[(size_t)t * N + row] = g.reward_scale == 1.0f ? rew : rew * g.reward_scale;      // rewards *= reward_scale
                 g.o_undones[(size_t)t * N + row] = term ? 0 : 1;                                               // logical_not
@@ -1509,8 +1544,10 @@ __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g
         if (L.wave == 0 && L.q == 0 && valid) {
             g.step_count[row] = sc;
             g.episode[row] = ep;
+            if constexpr (EV) g.ev_cnt[row] = ev_n;
         }
     } else if (L.tid < TS && row0 + L.tid < N) {
+        if constexpr (EV) g.ev_cnt[prow] = reinterpret_cast<const int *>(ACT + L.tid * 16 + 10)[1];
         g.step_count[prow] = psc;
         g.episode[prow] = pep;
         g.phys[2 * prow] = th;
@@ -1760,7 +1797,8 @@ extern "C" int erl_sac_rollout_synenv_supported(int S, int A, const int *hidden,
 int erl_sac_rollout_fused(const float *actor_params, int S, int A, int h0, int h1, const int64_t *aoff, float *env_state, const float *Ws,
                           const float *Wa, float *phys, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
                           const float *noise, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states, float *out_actions,
-                          float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, hipStream_t stream)
+                          float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, hipStream_t stream,
+                          float2 *ev_rec, int32_t *ev_cnt)
 {
     FusedDims d{};
     d.S = S; d.A = A; d.E = 1; d.h0 = h0; d.h1 = h1; d.B = N;
@@ -1770,24 +1808,33 @@ int erl_sac_rollout_fused(const float *actor_params, int S, int A, int h0, int h
     g.o_states = out_states; g.o_actions = out_actions; g.o_rewards = out_rewards; g.o_undones = out_undones; g.o_unmasks = out_unmasks;
     g.o_last_state = out_last_state; g.env_state = env_state; g.Ws = Ws; g.Wa = Wa; g.phys = phys; g.step_count = step_count; g.episode = episode;
     g.max_step = max_step; g.env_seed = env_seed;
+    g.ev_rec = ev_rec; g.ev_cnt = ev_cnt;
     const dim3 grid((unsigned)((N + TS - 1) / TS)), blk(FT);
     const size_t lds_bytes = (size_t)SR_FLOATS * sizeof(float);
-    static bool attr[2][9] = {};                         // (the dynamic part alone is beyond 64 KB)
-#define LAUNCH_SAC_ROLLOUT_E(K0, K1, EV)                                                                                        \
+    static bool attr[2][2][9] = {};                      // (the dynamic part alone is beyond 64 KB)
+#define LAUNCH_SAC_ROLLOUT_E(K0, K1, ENV_, EVAL_)                                                                               \
     do {                                                                                                                        \
-        if (!attr[EV][K0 * 3 + K1]) {                                                                                           \
-            int rc = erl_hip_status(hipFuncSetAttribute((const void *)sac_rollout_synenv_kernel<K0, K1, EV>,                    \
+        if (!attr[EVAL_][ENV_][K0 * 3 + K1]) {                                                                                  \
+            int rc = erl_hip_status(hipFuncSetAttribute((const void *)sac_rollout_synenv_kernel<K0, K1, ENV_, EVAL_>,           \
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes),            \
                                     "hipFuncSetAttribute(sac_rollout_synenv_kernel)");                                          \
             if (rc) return rc;                                                                                                  \
-            attr[EV][K0 * 3 + K1] = true;                                                                                       \
+            attr[EVAL_][ENV_][K0 * 3 + K1] = true;                                                                              \
         }                                                                                                                       \
-        hipLaunchKernelGGL((sac_rollout_synenv_kernel<K0, K1, EV>), grid, blk, lds_bytes, stream, g);                           \
+        hipLaunchKernelGGL((sac_rollout_synenv_kernel<K0, K1, ENV_, EVAL_>), grid, blk, lds_bytes, stream, g);                  \
     } while (0)
-#define LAUNCH_SAC_ROLLOUT_SYN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_SYN)
-#define LAUNCH_SAC_ROLLOUT_PEN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_PENDULUM)
-    if (phys) { FUSED_KT_DISPATCH(LAUNCH_SAC_ROLLOUT_PEN) }
+#define LAUNCH_SAC_ROLLOUT_SYN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_SYN, false)
+#define LAUNCH_SAC_ROLLOUT_PEN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_PENDULUM, false)
+#define LAUNCH_SAC_EVAL_SYN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_SYN, true)
+#define LAUNCH_SAC_EVAL_PEN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_PENDULUM, true)
+    if (ev_rec) {                                        // the evaluation form (erl_sac_eval_*_f32)
+        if (phys) { FUSED_KT_DISPATCH(LAUNCH_SAC_EVAL_PEN) }
+        else { FUSED_KT_DISPATCH(LAUNCH_SAC_EVAL_SYN) }
+    }
+    else if (phys) { FUSED_KT_DISPATCH(LAUNCH_SAC_ROLLOUT_PEN) }
     else { FUSED_KT_DISPATCH(LAUNCH_SAC_ROLLOUT_SYN) }
+#undef LAUNCH_SAC_EVAL_SYN
+#undef LAUNCH_SAC_EVAL_PEN
 #undef LAUNCH_SAC_ROLLOUT_SYN
 #undef LAUNCH_SAC_ROLLOUT_PEN
 #undef LAUNCH_SAC_ROLLOUT_E

@@ -60,6 +60,14 @@ class _GpuVecEnv:
         pass
 
 
+def compact_episodes(workspace: TEN, num_envs: int, horizon_len: int, rows: TEN, count: TEN) -> None:
+    """records + counts a `fused_evaluate*` launch left in `workspace` -> `rows` (capacity, 2) f32: (return, length) of every finished
+    episode, env-major, time order inside an env; `count` (1,) int32: how many (erl_eval_episodes_compact_f32, one launch)"""
+    _hip.check(_hip.lib().erl_eval_episodes_compact_f32(
+        _hip.ptr(workspace, th.uint8), workspace.numel(), num_envs, horizon_len, _hip.ptr(rows, th.float32), rows.shape[0],
+        _hip.ptr(count, th.int32), _hip.stream_ptr()), "erl_eval_episodes_compact_f32")
+
+
 class SynVecEnv(_GpuVecEnv):
     """Synthetic continuous-control workload of SURVEY.md 8d: s' = s Ws + a Wa with Ws = 0.9 I + 0.05 G1,
     Wa = 0.1 G2 (G ~ N(0,1), torch.Generator().manual_seed(0)); reward = -mean(s'^2) - 0.01 mean(a^2);
@@ -143,6 +151,33 @@ class SynVecEnv(_GpuVecEnv):
             p(last_state_out, f32) if last_state_out is not None else None, _hip.stream_ptr()), "erl_sac_rollout_synenv_f32")
 
 
+    def fused_evaluate(self, agent, horizon_len: int, workspace) -> None:
+        """`horizon_len` steps of the deterministic policy tanh(mean) of a fused-path AgentPPO in ONE launch (erl_eval_synenv_f32: the
+        evaluation form of `fused_rollout`); the per-episode records and per-env counts go to `workspace` (uint8, erl_eval_workspace_bytes);
+        the env's state / counters advance."""
+        from .. import _hip
+        self.state_epoch += 1
+        p, f32 = _hip.ptr, th.float32
+        a = agent._act
+        h1, h2 = agent.net_dims
+        _hip.check(_hip.lib().erl_eval_synenv_f32(
+            p(agent._flat_a.flat, f32), p(a.state_avg.data, f32), p(a.state_std.data, f32), self.state_dim, h1, h2, self.action_dim,
+            p(self.state, f32), p(self.Ws, f32), p(self.Wa, f32), p(self.step_count, th.int32), p(self.episode, th.int32), self.max_step,
+            self.seed & (2 ** 64 - 1), self.num_envs, horizon_len, p(workspace, th.uint8), workspace.numel(), _hip.stream_ptr()),
+            "erl_eval_synenv_f32")
+
+    def fused_evaluate_offpolicy(self, agent, horizon_len: int, workspace) -> None:
+        """... of the deterministic policy of a fused-path AgentSAC (erl_sac_eval_synenv_f32: the evaluation form of `fused_rollout_offpolicy`)"""
+        from .. import _hip
+        self.state_epoch += 1
+        p, f32 = _hip.ptr, th.float32
+        spec = agent._spec
+        _hip.check(_hip.lib().erl_sac_eval_synenv_f32(
+            p(agent._actor_flat, f32), spec.S, spec.A, spec._c, len(spec.hidden), p(self.state, f32), p(self.Ws, f32), p(self.Wa, f32),
+            p(self.step_count, th.int32), p(self.episode, th.int32), self.max_step, self.seed & (2 ** 64 - 1), self.num_envs, horizon_len,
+            p(workspace, th.uint8), workspace.numel(), _hip.stream_ptr()), "erl_sac_eval_synenv_f32")
+
+
 class PendulumVecEnv(_GpuVecEnv):
     """Pendulum-v1 (g=10, m=l=1, dt=0.05, 200-step truncation) behind the reference wrapper's scaling
     (elegantrl/envs/CustomGymEnv.py:42-44: torque = 2*action, reward = 0.5*gym reward)."""
@@ -216,6 +251,30 @@ class PendulumVecEnv(_GpuVecEnv):
             float(agent.reward_scale), p(states, f32), p(actions, f32), p(logprobs, f32), p(rewards, f32),
             _hip.flag_ptr(undones), _hip.flag_ptr(unmasks), p(values, f32), p(next_value, f32), *_epilogue_args(epilogue),
             _hip.stream_ptr()), "erl_rollout_pendulum_f32")
+
+
+    def fused_evaluate(self, agent, horizon_len: int, workspace) -> None:
+        """`horizon_len` steps of the deterministic policy in ONE launch (erl_eval_pendulum_f32); arguments as SynVecEnv.fused_evaluate."""
+        from .. import _hip
+        self.state_epoch += 1
+        p, f32 = _hip.ptr, th.float32
+        a = agent._act
+        h1, h2 = agent.net_dims
+        _hip.check(_hip.lib().erl_eval_pendulum_f32(
+            p(agent._flat_a.flat, f32), p(a.state_avg.data, f32), p(a.state_std.data, f32), h1, h2, p(self.phys, f32), p(self.state, f32),
+            p(self.step_count, th.int32), p(self.episode, th.int32), self.max_step, self.seed & (2 ** 64 - 1), self.num_envs, horizon_len,
+            p(workspace, th.uint8), workspace.numel(), _hip.stream_ptr()), "erl_eval_pendulum_f32")
+
+    def fused_evaluate_offpolicy(self, agent, horizon_len: int, workspace) -> None:
+        """... of a fused-path AgentSAC (erl_sac_eval_pendulum_f32); arguments as SynVecEnv.fused_evaluate_offpolicy."""
+        from .. import _hip
+        self.state_epoch += 1
+        p, f32 = _hip.ptr, th.float32
+        spec = agent._spec
+        _hip.check(_hip.lib().erl_sac_eval_pendulum_f32(
+            p(agent._actor_flat, f32), spec._c, len(spec.hidden), p(self.phys, f32), p(self.state, f32), p(self.step_count, th.int32),
+            p(self.episode, th.int32), self.max_step, self.seed & (2 ** 64 - 1), self.num_envs, horizon_len, p(workspace, th.uint8),
+            workspace.numel(), _hip.stream_ptr()), "erl_sac_eval_pendulum_f32")
 
 
 class CartPoleVecEnv:

@@ -24,6 +24,7 @@ _COMMON_DEFAULTS: Dict[str, Any] = dict(
     cwd=None, if_remove=True, break_step=np.inf, break_score=np.inf, if_keep_save=True, if_over_write=False,
     if_save_buffer=False, save_gap=8, eval_times=3, eval_per_step=int(2e4), eval_env_class=None, eval_env_args=None,
     eval_record_step=0,
+    fused_eval=True,      # Evaluator(agent=...): episodes from agent.evaluate_env (two launches) where the agent / env pair has it
 )
 _OFF_POLICY_DEFAULTS: Dict[str, Any] = dict(
     batch_size=64, horizon_len=512, buffer_size=int(1e6), repeat_times=1.0, if_use_per=False, lambda_fit_cum_r=0.0,

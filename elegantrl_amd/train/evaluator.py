@@ -16,8 +16,13 @@ TEN = th.Tensor
 
 
 class Evaluator:
-    def __init__(self, cwd: str, env, args: Config, if_tensorboard: bool = False):
+    def __init__(self, cwd: str, env, args: Config, if_tensorboard: bool = False, agent=None):
         self.cwd, self.env = cwd, env
+        # with an `agent`, vectorised evaluations go through `agent.evaluate_env(env)` (two launches, csrc/rollout_eval.hip) while
+        # `args.fused_eval` is on, the actor handed in is the agent's own and the agent / env pair has a fused evaluation
+        self.agent = agent
+        self.fused_eval = bool(getattr(args, "fused_eval", True))
+        self.eval_path = None                # said once, at the first evaluation
         self.agent_id = args.gpu_id
         self.total_step = 0
         self.start_time = time.time()
@@ -74,7 +79,40 @@ class Evaluator:
             out = [get_rewards_and_steps(self.env, actor) for _ in range(self.eval_times)]
             return th.tensor(out, dtype=th.float32)
         rounds = max(1, self.eval_times // self.env.num_envs)                       # evaluator.py:150-155
+        why = self._loop_reason(actor)
+        if why is None:
+            out = []
+            for _ in range(rounds):
+                rs = self.agent.evaluate_env(self.env)
+                if rs is None:
+                    why = "agent.evaluate_env returned None"
+                    break
+                out.append(rs)
+            if why is None:
+                self._say_path("fused evaluation (agent.evaluate_env: env.reset(), one persistent launch of env.max_step steps of the "
+                               "deterministic policy, one compaction launch)")
+                return th.cat(out, dim=0)
+        self._say_path(f"loop evaluation (actor(state) + env.step per step, episodes cut on the host): {why}")
         return th.cat([get_cumulative_rewards_and_step_from_vec_env(self.env, actor) for _ in range(rounds)], dim=0)
+
+    def _loop_reason(self, actor):
+        """None when this evaluation goes through `agent.evaluate_env`, else why the step loop runs"""
+        agent = self.agent
+        if agent is None:
+            return "no agent was given to the Evaluator"
+        if not self.fused_eval:
+            return "args.fused_eval is off"
+        if actor is not getattr(agent, "act", None):
+            return "the actor to evaluate is not agent.act"
+        reason = getattr(agent, "_fused_eval_reason", None)
+        if reason is None:
+            return f"{type(agent).__name__} has no fused evaluation"
+        return reason(self.env)
+
+    def _say_path(self, text: str):
+        if self.eval_path is None:
+            print(f"| Evaluator: {text}", flush=True)
+        self.eval_path = text
 
     def save_or_load_recoder(self, if_save: bool):
         if if_save:

@@ -85,7 +85,7 @@ def train_agent_single_process(args: Config):
     if rank == 0:
         eval_env_class = args.eval_env_class if args.eval_env_class else args.env_class
         eval_env_args = args.eval_env_args if args.eval_env_args else args.env_args
-        evaluator = Evaluator(cwd=args.cwd, env=build_env(eval_env_class, eval_env_args, args.gpu_id), args=args)
+        evaluator = Evaluator(cwd=args.cwd, env=build_env(eval_env_class, eval_env_args, args.gpu_id), args=args, agent=agent)
 
     cwd, break_step, horizon_len = args.cwd, args.break_step, args.horizon_len
     if_off_policy, if_save_buffer = args.if_off_policy, args.if_save_buffer

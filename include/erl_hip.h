@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ERL_ABI_VERSION 19
+#define ERL_ABI_VERSION 20
 #define ERL_API __attribute__((visibility("default")))
 #define ERL_OK 0
 #define ERL_EINVAL (-1)
@@ -281,6 +281,48 @@ ERL_API int erl_rollout_pendulum_f32(const float *actor_params, const float *cri
                              float *out_last_state, float *out_advantages, float *out_reward_sums, double *gae_stats,
                              double *gae_workspace, int64_t gae_workspace_bytes, float gamma, float lambda_gae,
                              int use_v_trace, void *stream);
+
+/* Policy evaluation on the device (ABI 20): the Evaluator's episodes (elegantrl/train/evaluator.py:201-238) in two launches.
+ *
+ * erl_eval_synenv_f32 / erl_eval_pendulum_f32 are the EVALUATION FORM of the two persistent rollouts above: ONE launch plays H
+ * steps of the deterministic policy on the env -- the action sent to it is tanh(mean), ActorPPO.forward (AgentPPO.py:44-45).  The
+ * policy mean and the env step are the training rollout's own statements, so the rewards, the done flags, the final env state,
+ * step_count and episode are bit-identical to what erl_rollout_*_f32 leaves under an all-zero `noise` and reward_scale = 1.  Left
+ * out: the critic, the draws, the log-prob, every rollout buffer, reward_scale (evaluated returns are unscaled) and the epilogue.
+ * Instead the kernel keeps, per env, a running return (the fp32 rewards summed in fp64, in time order) and length, both zero at
+ * entry; where a step is done (terminal | truncate) it records (float(return), length) and clears them.  An episode still open
+ * after step H - 1 is dropped, as the reference does.  The env's live state / counters are read at entry and written back at exit:
+ * the env afterwards is where H calls of its step would have left it.  H is free (the Evaluator passes env.max_step).
+ * `workspace` (erl_eval_workspace_bytes(N, H) bytes, device memory, the caller's; need not be cleared -- the launch writes every
+ * element): [(H, N) x (float return, float length): the episode that ended at (t, env), length 0 = none] [(N) int32: episodes
+ * finished per env].  Support is exactly erl_rollout_fused_supported(S, h1, h2, A); anything else is ERL_EINVAL before any launch.
+ *
+ * erl_sac_eval_synenv_f32 / erl_sac_eval_pendulum_f32 are the same for erl_sac_rollout_*_f32: the action is tanh of the first A
+ * head outputs (ActorSAC.forward, AgentSAC.py:47-48); same workspace; support is erl_sac_rollout_synenv_supported(...).
+ *
+ * erl_eval_episodes_compact_f32 turns a workspace into the evaluator's table: out_rows (out_capacity, 2) f32 receives one row
+ * (return, length) per finished episode, env-major and in time order inside an env (the reference's order, evaluator.py:225-237);
+ * *out_count (device int32) receives the number of episodes.  Rows beyond out_capacity are counted, not written (N * H rows always
+ * suffice).  One launch: every 256-env workgroup sums the counts of the envs before it, scans its own, and each thread walks its
+ * env's column of records.  N * H < 2^31.  Sized for the env counts the persistent rollouts run at (up to some 10^5): workgroup b
+ * reads 256 b counts for its offset, 2 N^2 / 256 bytes over the launch (N = 4096: 128 KB; N = 65536: 32 MB, all of it from L2);
+ * beyond that a two-level prefix would be the form to write.
+ * No call allocates, synchronises the host or reads the environment; all work is enqueued on `stream`. */
+ERL_API int64_t erl_eval_workspace_bytes(int64_t N, int64_t H);       /* host only; -1 for a bad shape */
+ERL_API int erl_eval_synenv_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2, int A,
+                        float *env_state, const float *Ws, const float *Wa, int32_t *step_count, int32_t *episode, int max_step,
+                        uint64_t env_seed, int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_eval_pendulum_f32(const float *actor_params, const float *act_avg, const float *act_std, int h1, int h2, float *phys,
+                          float *obs, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
+                          void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_sac_eval_synenv_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state,
+                            const float *Ws, const float *Wa, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
+                            int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_sac_eval_pendulum_f32(const float *actor_params, const int *hidden, int n_hidden, float *phys, float *obs,
+                              int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
+                              void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_eval_episodes_compact_f32(const void *workspace, int64_t workspace_bytes, int64_t N, int64_t H, float *out_rows,
+                                  int64_t out_capacity, int32_t *out_count, void *stream);
 
 /* K6  one PPO minibatch: gather (K5 indices) + critic fwd/bwd + actor fwd/bwd, both networks in one
  * launch.  Replaces AgentPPO.update_objectives up to (not including) the two optimizer steps
