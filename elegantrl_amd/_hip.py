@@ -22,7 +22,7 @@ GAE_VTRACE, GAE_MUTATE, GAE_STATS = 0x1, 0x2, 0x4
 GAE_ALGO_AUTO, GAE_ALGO_EXACT, GAE_ALGO_CHUNKED, GAE_ALGO_LOOKBACK = 0x00, 0x10, 0x20, 0x30
 MAX_STATE_DIM, MAX_HIDDEN, MAX_ACTION_DIM = 128, 128, 16
 MAX_LAYERS, MAXN_WIDTH = 6, 4096
-ABI_VERSION = 20
+ABI_VERSION = 21
 PPO_OBJ_REFERENCE, PPO_OBJ_CANONICAL, PPO_OBJ_A2C = 0, 1, 2      # include/erl_hip.h ERL_PPO_OBJ_*
 SAC_ACTOR_SAC, SAC_ACTOR_FIX = 0, 1                               # include/erl_hip.h ERL_SAC_ACTOR_*
 COMM_ID_BYTES = 128
@@ -61,6 +61,8 @@ _SIGNATURES = {
     "erl_per_add_rows_f32": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int64, c_float, _P]),
     "erl_per_update_f32": (c_int, [_P, _P, c_int64, c_int64, _P, _P, _P, c_int64, c_float, _P]),
     "erl_per_sample_f32": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, c_float, _P, _P, _P]),
+    "erl_per_sample_rows_f32": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, c_int64, c_int64, c_float, _P, c_int, c_int, c_int64] + [_P] * 11),
+    "erl_per_update_index_f32": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, c_float, _P]),
     "erl_mlp_param_count": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "erl_value_forward_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, c_int64, _P, _P]),
     "erl_rollout_step_f32": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_int64, _P, c_uint64, c_uint64,
@@ -137,6 +139,8 @@ _SIGNATURES = {
                                         c_uint64] + [c_float] * 8 + [c_int32, _P, _P, c_int64, _P]),
     "erl_sac_update_ring_loop_f32": (c_int, [_P] * 10 + [c_int, c_int, POINTER(c_int), c_int, c_int, _P, _P, c_int64] + [_P] * 6 + [c_int64, c_uint64,
                                              c_uint64] + [c_float] * 8 + [c_int32, _P, _P, c_int64, _P]),
+    "erl_sac_update_per_loop_f32": (c_int, [_P] * 10 + [c_int, c_int, POINTER(c_int), c_int, c_int, _P, _P, c_int64] + [_P] * 6 + [c_int64, c_uint64,
+                                            c_uint64] + [c_float] * 8 + [c_int32, _P, _P, c_int64, _P]),
     "erl_sac_explore_action_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, c_int64, _P, c_uint64, c_uint64, _P, _P, _P,
                                            c_int64, _P]),
     "erl_sac_explore_action_opt_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, c_int64, _P, c_uint64, c_uint64, _P, _P, _P,

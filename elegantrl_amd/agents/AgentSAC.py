@@ -161,6 +161,11 @@ class AgentSAC(AgentBase):
         # round 6: with the sample inside the step, update_net's whole loop is ONE C call (erl_sac_update_ring_loop_f32): bit-identical to the
         # per-step calls; `args.update_loop_in_c = False` / ERL_SAC_LOOP_IN_C=0 keeps one call per step
         self.update_loop_in_c = bool(getattr(args, "update_loop_in_c", os.environ.get("ERL_SAC_LOOP_IN_C", "1") != "0"))
+        # prioritised replay: update_net's whole loop is ONE C call as well (erl_sac_update_per_loop_f32: draw + gather, step, tree update per
+        # step, bit-identical to the per-step calls on the same uniforms); `args.per_loop_in_c = False` / ERL_SAC_PER_LOOP_IN_C=0 keeps
+        # _per_step's six host-driven calls per step
+        self.per_loop_in_c = bool(getattr(args, "per_loop_in_c", os.environ.get("ERL_SAC_PER_LOOP_IN_C", "1") != "0"))
+        self.per_path = None                       # which route the last prioritised update_net took (None: none yet / not prioritised)
         self._last_state_token = None
         self._spec = ops.SacSpec(state_dim, action_dim, net_dims, self.num_ensembles, actor_variant=self._actor_variant)
         dev, f32 = self.device, th.float32
@@ -181,6 +186,7 @@ class AgentSAC(AgentBase):
         self.target_entropy = math.log(action_dim)               # np.log(action_dim), as the reference (:31)
         self._step = 0
         self._objs = th.zeros(2, dtype=f32, device=dev)
+        self.objs_all = None                       # (update_times, 2) device tensor: the last update_net's (obj_critic, obj_actor) per step
         self._td_error = None                      # per-sample td errors of a prioritised step (csrc/sac.hip critic_loss_kernel)
         self.save_attr_names = self.save_attr_names | {"alpha_log", "alpha_optim"}
         import ctypes as _ct
@@ -353,24 +359,40 @@ class AgentSAC(AgentBase):
         _hip.check_async_faults()          # the stream is drained: a skipped optimiser step (grid-wait timeout) raises here
         return oc, oa
 
-    def _per_step(self, buffer, objs_out: TEN, noises=None, update_t: int = 0):
+    def _per_step(self, buffer, objs_out: TEN, noises=None, update_t: int = 0, uniform: Optional[TEN] = None):
         """one step on a prioritised sample: importance weights into the critic objective, td errors back into the trees"""
-        *batch, is_weight, is_index = buffer.sample_for_per(self.batch_size)
+        *batch, is_weight, is_index = buffer.sample_for_per(self.batch_size) if uniform is None else buffer.sample_for_per(self.batch_size, uniform)
         if self._td_error is None or self._td_error.numel() != is_weight.numel():
             self._td_error = th.empty_like(is_weight)
         self._update_on_batch(batch, objs_out, noises, is_weight=is_weight, td_error_out=self._td_error, buffer=buffer, update_t=update_t)
         buffer.td_error_update_for_per(is_index, self._td_error)
 
     @_hip.on_device
-    def update_net(self, buffer) -> Tuple[float, float]:
-        """AgentBase.update_net (:172-189) with ONE host sync: the per-step objectives stay on the device until the end."""
+    def _per_loop_reason(self, buffer) -> Optional[str]:
+        """None when a prioritised update_net runs as one C call, else why it takes one _per_step per step"""
+        if not self.per_loop_in_c:
+            return "args.per_loop_in_c is off"
+        if not self.update_loop_in_c:
+            return "args.update_loop_in_c is off"
+        if self.lambda_fit_cum_r:
+            return "lambda_fit_cum_r needs ids0 / ids1 on the host side of every step"
+        if self._actor_variant:
+            return "ActorFixSAC / two-time-scale options (AgentModSAC) are decided per step by the host"
+        if not getattr(buffer, "per_for_fused_loop", None):
+            return f"{type(buffer).__name__} has no per_for_fused_loop"
+        return None
+
+    @_hip.on_device
+    def update_net(self, buffer, per_uniform: Optional[TEN] = None) -> Tuple[float, float]:
+        """AgentBase.update_net (:172-189) with ONE host sync: the per-step objectives stay on the device until the end.
+        `per_uniform` (update_times, num_seqs, batch_size // num_seqs) in [0, 1) injects the prioritised sampler's random numbers (tests)."""
         if self.lambda_fit_cum_r:                     # AgentBase.py:176-177 (bootstraps with the current actor: see get_cumulative_rewards)
             buffer.update_cum_rewards(get_cumulative_rewards=self.get_cumulative_rewards)
         self._sync_modules()
         update_times = int(buffer.cur_size * self.repeat_times / self.batch_size)
         if update_times < 1:
             return 0.0, 0.0
-        objs = th.zeros((update_times, 2), dtype=th.float32, device=self.device)
+        objs = self.objs_all = th.zeros((update_times, 2), dtype=th.float32, device=self.device)
         id_rows = None
         if not self.if_use_per and self.sample_ids_ahead:
             # the sample ids of ALL the steps in one th.randint (the reference draws batch_size of them per step, replay_buffer.py:121-122:
@@ -396,9 +418,37 @@ class AgentSAC(AgentBase):
             buffer.ids0, buffer.ids1 = stage.ids
             self.act_optimizer.step_count = self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
             update_times = 0                              # (nothing left for the Python loop)
+        if self.if_use_per:
+            why = self._per_loop_reason(buffer)
+            per = None if why else buffer.per_for_fused_loop(self.batch_size)
+            if per:
+                # the prioritised loop from ONE C call (erl_sac_update_per_loop_f32): step t = what _per_step enqueues on uniforms[t].  The
+                # uniforms of ALL the steps in one th.rand (sample_for_per draws (num_seqs, batch_size // num_seqs) per step: same
+                # distribution, same generator; the trees change inside the loop, the uniforms do not depend on them)
+                from .. import ops
+                p_ring, trees, cur_size, cursor, per_alpha, per_beta, stage, per_stage = per
+                if per_uniform is None:
+                    per_uniform = th.rand((update_times, buffer.num_seqs, self.batch_size // buffer.num_seqs), dtype=th.float32, device=self.device)
+                assert per_uniform.shape == (update_times, buffer.num_seqs, self.batch_size // buffer.num_seqs)
+                ops.sac_update_per_loop(self._spec, self._actor_flat, self._critic_flat, self._target_flat, self.alpha_log,
+                                        (self.act_optimizer.exp_avg, self.act_optimizer.exp_avg_sq, self.cri_optimizer.exp_avg,
+                                         self.cri_optimizer.exp_avg_sq, self.alpha_optim.exp_avg, self.alpha_optim.exp_avg_sq),
+                                        p_ring, trees, per_uniform.contiguous(), cur_size, cursor, per_alpha, per_beta, stage, per_stage, self._step + 1,
+                                        gamma=float(self.gamma), target_entropy=float(self.target_entropy), tau=float(self.soft_update_tau),
+                                        lr=float(self.learning_rate), max_norm=float(self.clip_grad_norm), objs_all=objs, seed=self.rng_seed + 1,
+                                        counter0=self._step + 1)
+                self._step += update_times
+                buffer.ids0, buffer.ids1 = stage.ids
+                self._td_error = per_stage.td_error
+                self.act_optimizer.step_count = self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
+                self.per_path = "prioritised update loop in one C call (erl_sac_update_per_loop_f32: draw + gather, step, tree update per step)"
+                update_times = 0
+            else:
+                self.per_path = "prioritised update loop per step (_per_step: six host-driven calls): " + (
+                    why or "the buffer is not an interleaved continuous-action ring of >= 2 rows, or batch_size is no multiple of num_seqs")
         for t in range(update_times):
             if self.if_use_per:
-                self._per_step(buffer, objs[t], update_t=t)
+                self._per_step(buffer, objs[t], update_t=t, uniform=None if per_uniform is None else per_uniform[t])
             elif ring:
                 self._update_from_ring(buffer, ring, id_rows[t], objs[t])
             else:       # (the batch is consumed before the next draw)

@@ -19,20 +19,44 @@ struct PerItems {
     const int64_t *ids0, *ids1;
     const float *td;
     float alpha;
+    // or the same list as the sampler left it: is_index = ids1 * cur_size + ids0, decoded here (the reference's fmod / div, :155-156)
+    const int64_t *is_index;
+    int64_t cur_size;
     // or a row range of every sequence (ReplayBuffer.update): rows (start + i / Q) mod max_size, priority `prob`
     int64_t start, max_size;
     float prob;
     int64_t n;
     int Q;
+    __host__ __device__ bool is_list() const { return ids0 || is_index; }
 };
 
 // returns false for an explicit item whose (row, sequence) lies outside the trees: it is skipped (the ids are device data the
 // host cannot validate without a sync)
 __device__ __forceinline__ bool per_item(const PerItems &it, int64_t i, int64_t &row, int &q, float &p)
 {
-    if (it.ids0) {
-        row = it.ids0[i];
-        const int64_t q64 = it.ids1[i];
+    if (it.is_list()) {
+        int64_t q64;
+        if (it.is_index) {
+            // a non-negative index decodes as th.fmod / th.div(floor) do; one outside [0, Q * cur_size) (negative ones included) names
+            // no leaf.  An index below 2^32 takes the 32-bit division: this runs once per item and tree level.
+            const uint64_t id = (uint64_t)it.is_index[i];
+            if (id >= (uint64_t)it.Q * (uint64_t)it.cur_size) {
+                row = 0; q = 0; p = 0.f;
+                return false;
+            }
+            if (id >> 32) {
+                q64 = (int64_t)(id / (uint64_t)it.cur_size);
+                row = (int64_t)id - q64 * it.cur_size;
+            } else {                                                    // (cur_size <= max_size <= 2^30)
+                const uint32_t id32 = (uint32_t)id, c32 = (uint32_t)it.cur_size;
+                const uint32_t q32 = id32 / c32;
+                q64 = q32;
+                row = id32 - q32 * c32;
+            }
+        } else {
+            row = it.ids0[i];
+            q64 = it.ids1[i];
+        }
         q = (int)q64;
         const float t = fminf(fmaxf(it.td[i], 1e-8f), 10.f);            // td_error.clamp(1e-8, 10).pow(per_alpha)   (:168)
         p = it.alpha == 1.f ? t : powf(t, it.alpha);                    // (alpha = 1: the priorities as given, exactly)
@@ -55,7 +79,7 @@ __global__ __launch_bounds__(PER_T) void per_update_kernel(float *__restrict__ s
 {
     const int64_t twoL = 2 * L;
     unsigned win = 0xffffffffu;                            // bit k: this thread's k-th item writes its leaf (n <= 8 * PER_T here)
-    if (it.ids0) {
+    if (it.is_list()) {
         for (int64_t i = threadIdx.x; i < it.n; i += PER_T) {
             int64_t row; int q; float p;
             if (per_item(it, i, row, q, p)) reinterpret_cast<int *>(mn)[(int64_t)q * twoL + L + row] = -1;
@@ -134,16 +158,13 @@ __global__ __launch_bounds__(256) void per_init_kernel(float *__restrict__ sum, 
     }
 }
 
-// proportional prioritisation with stratified draws (:285-298), full-depth descent; one thread per sample
-__global__ __launch_bounds__(256) void per_sample_kernel(const float *__restrict__ sum, const float *__restrict__ mn, int64_t L, int Q,
-                                                         const float *__restrict__ uniform, int64_t n, int64_t cur_size, int64_t newest,
-                                                         float beta, int64_t *__restrict__ out_index, float *__restrict__ out_weight)
+// one stratified draw of sequence q (stratum j of n, `u` its uniform): proportional prioritisation (:285-298) by a full-depth descent,
+// then the two row moves; returns the time row and its importance weight.  Shared by both sampling kernels: one arithmetic.
+__device__ __forceinline__ int64_t per_draw(const float *__restrict__ sum, const float *__restrict__ mn, int64_t L, int64_t base, int64_t n,
+                                            int64_t j, float u, int64_t cur_size, int64_t newest, float beta, float &weight)
 {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)Q * n) return;
-    const int64_t q = i / n, j = i - q * n, base = q * 2 * L;
     const float total = sum[base + 1];
-    float v = ((float)j + uniform[i]) * (total / (float)n);             // (arange(n) + rand(n)) * (tree[0] / n)   (:287)
+    float v = ((float)j + u) * (total / (float)n);                      // (arange(n) + rand(n)) * (tree[0] / n)   (:287)
     int64_t node = 1;
     while (node < L) {
         const float left = sum[base + 2 * node];
@@ -156,8 +177,85 @@ __global__ __launch_bounds__(256) void per_sample_kernel(const float *__restrict
     int64_t row = node - L;
     if (row > cur_size - 2) row = cur_size - 2;                        // the last filled position has no successor row (oracle D4)
     if (row == newest) row = newest >= 1 ? newest - 1 : 1;             // full ring: the newest row's successor slot holds the OLDEST data (D6)
+    weight = powf(sum[base + L + row] / mn[base + 1], -beta);           // (prob / min prob)^(-beta)   (:296-297)
+    return row;
+}
+
+// one thread per sample
+__global__ __launch_bounds__(256) void per_sample_kernel(const float *__restrict__ sum, const float *__restrict__ mn, int64_t L, int Q,
+                                                         const float *__restrict__ uniform, int64_t n, int64_t cur_size, int64_t newest,
+                                                         float beta, int64_t *__restrict__ out_index, float *__restrict__ out_weight)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)Q * n) return;
+    const int64_t q = i / n, j = i - q * n;
+    float w;
+    const int64_t row = per_draw(sum, mn, L, q * 2 * L, n, j, uniform[i], cur_size, newest, beta, w);
     out_index[i] = q * cur_size + row;                                  // decodes by the reference's fmod / div (:155-156)
-    out_weight[i] = powf(sum[base + L + row] / mn[base + 1], -beta);    // (prob / min prob)^(-beta)   (:296-297)
+    out_weight[i] = w;
+}
+
+// sample_for_per from ONE launch: the draw above, then that transition's row of the interleaved ring (gather.hip: ring[Q][max_size][RW],
+// row = [state | action | reward | undone | unmask | pad], the next state = the head of the following row) into the staging block.
+// A WAVE owns `dpw` draws per trip: lanes [0, dpw) walk the trees (a dependent chain of log2 L loads each), then all 64 lanes move the
+// dpw x CW 16-byte chunks, as replay_sample_rows_kernel does.  The lanes that gather take a draw's ring row from the lane that drew it by a
+// cross-lane read (ds_bpermute): producer and consumers are one wave, so there is no LDS array, no barrier, and a wave whose walks are
+// short does not wait for the workgroup's longest.  The gather loop's trip count is wave-uniform: every lane is active at each shuffle.
+__global__ __launch_bounds__(256) void per_sample_rows_kernel(const float *__restrict__ sum, const float *__restrict__ mn, int64_t L, int Q,
+                                                              const float *__restrict__ uniform, int64_t n, int64_t cur_size, int64_t newest,
+                                                              float beta, const float *__restrict__ ring, int64_t max_size, int S, int A,
+                                                              int RW, int64_t *__restrict__ out_index, float *__restrict__ out_weight,
+                                                              float *__restrict__ o_state, float *__restrict__ o_action,
+                                                              float *__restrict__ o_reward, float *__restrict__ o_undone,
+                                                              float *__restrict__ o_unmask, float *__restrict__ o_next,
+                                                              int64_t *__restrict__ o_ids0, int64_t *__restrict__ o_ids1, int dpw)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t B = (int64_t)Q * n;
+    const int C0 = RW >> 2, C1 = (S + 3) >> 2, CW = C0 + C1;
+    const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), stride = (int64_t)gridDim.x * 4 * dpw;
+    for (int64_t b0 = wave * dpw; b0 < B; b0 += stride) {
+        const int nb = (int)min((int64_t)dpw, B - b0);
+        int64_t mine = 0;                                               // this lane's draw as a row of the block: q * max_size + time row
+        if (lane < nb) {
+            const int64_t i = b0 + lane, q = i / n, j = i - q * n;
+            float w;
+            const int64_t row = per_draw(sum, mn, L, q * 2 * L, n, j, uniform[i], cur_size, newest, beta, w);
+            out_index[i] = q * cur_size + row;
+            out_weight[i] = w;
+            if (o_ids0) o_ids0[i] = row;                                // ids0 = fmod(is_index, cur_size), ids1 = div  (:155-156)
+            if (o_ids1) o_ids1[i] = q;
+            mine = q * max_size + row;
+        }
+        const int total = nb * CW;
+        for (int e0 = 0; e0 < total; e0 += 64) {
+            const int e = e0 + lane, bl = e / CW, c = e - bl * CW;
+            const int64_t row = __shfl(mine, bl < nb ? bl : nb - 1, 64);
+            if (e >= total) continue;
+            const int64_t b = b0 + bl;
+            if (c < C0) {
+                const float4 v4 = *reinterpret_cast<const float4 *>(ring + row * RW + 4 * c);
+                const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int col = 4 * c + k;
+                    if (col < S) o_state[b * S + col] = v[k];
+                    else if (col < S + A) o_action[b * A + (col - S)] = v[k];
+                    else if (col == S + A) o_reward[b] = v[k];
+                    else if (col == S + A + 1) o_undone[b] = v[k];
+                    else if (col == S + A + 2) o_unmask[b] = v[k];
+                }
+            } else {
+                // states[ids0 + 1, ids1] (:133): the draw's moves leave time row <= cur_size - 2 <= max_size - 2, so the next row exists
+                const int cc = c - C0;
+                const float4 v4 = *reinterpret_cast<const float4 *>(ring + (row + 1) * RW + 4 * cc);
+                const float v[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (4 * cc + k < S) o_next[b * S + 4 * cc + k] = v[k];
+            }
+        }
+    }
 }
 
 int64_t per_leaves(int64_t max_size)
@@ -175,7 +273,7 @@ int per_update_impl(const char *what, float *sum, float *mn, int64_t max_size, i
         hipLaunchKernelGGL(per_update_kernel, dim3(1), dim3(PER_T), 0, s, sum, mn, L, it);
     } else {
         const dim3 grid((unsigned)erl_cdiv(it.n, 256));
-        if (it.ids0)
+        if (it.is_list())
             for (int phase = 0; phase < 4; ++phase) hipLaunchKernelGGL(per_leaves_kernel, grid, dim3(256), 0, s, sum, mn, L, it, phase);
         else
             hipLaunchKernelGGL(per_leaves_kernel, grid, dim3(256), 0, s, sum, mn, L, it, -1);
@@ -231,6 +329,22 @@ extern "C" int erl_per_update_f32(float *sum_tree, float *min_tree, int64_t max_
     return per_update_impl("erl_per_update_f32", sum_tree, min_tree, max_size, (int)num_seqs, it, (hipStream_t)stream);
 }
 
+extern "C" int erl_per_update_index_f32(float *sum_tree, float *min_tree, int64_t max_size, int64_t num_seqs, const int64_t *is_index,
+                                        int64_t cur_size, const float *td_error, int64_t n, float per_alpha, void *stream)
+{
+    ERL_REQUIRE(sum_tree && min_tree && is_index && td_error, "erl_per_update_index_f32: NULL tensor");
+    ERL_REQUIRE(max_size >= 2 && max_size <= (1LL << 30) && num_seqs >= 1 && num_seqs < (1 << 30) && cur_size >= 2 && cur_size <= max_size &&
+                    n >= 0 && n < (1LL << 31),
+                "erl_per_update_index_f32: bad argument (cur_size=%lld max_size=%lld num_seqs=%lld n=%lld)", (long long)cur_size,
+                (long long)max_size, (long long)num_seqs, (long long)n);
+    PerItems it{};
+    it.is_index = is_index; it.cur_size = cur_size; it.td = td_error; it.alpha = per_alpha;
+    it.max_size = max_size;
+    it.n = n;
+    it.Q = (int)num_seqs;
+    return per_update_impl("erl_per_update_index_f32", sum_tree, min_tree, max_size, (int)num_seqs, it, (hipStream_t)stream);
+}
+
 extern "C" int erl_per_sample_f32(const float *sum_tree, const float *min_tree, int64_t max_size, int64_t num_seqs,
                                   const float *uniform, int64_t n_per_seq, int64_t cur_size, int64_t cursor, float per_beta,
                                   int64_t *out_index, float *out_weight, void *stream)
@@ -246,4 +360,36 @@ extern "C" int erl_per_sample_f32(const float *sum_tree, const float *min_tree, 
     hipLaunchKernelGGL(per_sample_kernel, dim3((unsigned)erl_cdiv(num_seqs * n_per_seq, 256)), dim3(256), 0, (hipStream_t)stream, sum_tree,
                        min_tree, L, (int)num_seqs, uniform, n_per_seq, cur_size, newest, per_beta, out_index, out_weight);
     ERL_LAUNCH_CHECK("erl_per_sample_f32");
+}
+
+extern "C" int erl_per_sample_rows_f32(const float *sum_tree, const float *min_tree, int64_t max_size, int64_t num_seqs, const float *uniform,
+                                       int64_t n_per_seq, int64_t cur_size, int64_t cursor, float per_beta, const float *ring, int S, int A,
+                                       int64_t row_floats, int64_t *out_index, float *out_weight, float *out_state, float *out_action,
+                                       float *out_reward, float *out_undone, float *out_unmask, float *out_next_state, int64_t *out_ids0,
+                                       int64_t *out_ids1, void *stream)
+{
+    ERL_REQUIRE(sum_tree && min_tree && uniform && ring && out_index && out_weight, "erl_per_sample_rows_f32: NULL tensor");
+    ERL_REQUIRE(out_state && out_action && out_reward && out_undone && out_unmask && out_next_state, "erl_per_sample_rows_f32: NULL output");
+    ERL_REQUIRE(row_floats > 0 && row_floats == erl_replay_row_floats(S, A),
+                "erl_per_sample_rows_f32: row_floats=%lld is not erl_replay_row_floats(%d, %d) (interleaved rings only)", (long long)row_floats, S, A);
+    ERL_REQUIRE((reinterpret_cast<uintptr_t>(ring) & 15) == 0, "erl_per_sample_rows_f32: the ring must be 16-byte aligned");
+    ERL_REQUIRE(max_size >= 2 && max_size <= (1LL << 30) && num_seqs >= 1 && num_seqs < (1 << 30) && n_per_seq >= 1 &&
+                    n_per_seq < (1LL << 31) / num_seqs && cur_size >= 2 && cur_size <= max_size && cursor <= max_size,
+                "erl_per_sample_rows_f32: bad argument (cur_size=%lld max_size=%lld cursor=%lld num_seqs=%lld n_per_seq=%lld)", (long long)cur_size,
+                (long long)max_size, (long long)cursor, (long long)num_seqs, (long long)n_per_seq);
+    const int64_t L = per_leaves(max_size), B = num_seqs * n_per_seq;
+    const int64_t newest = (cursor >= 0 && cur_size == max_size && max_size >= 3) ? (cursor + max_size - 1) % max_size : -1;   // (erl_per_sample_f32)
+    // draws per wave and trip: what fills the wave's 64 lanes with one 16-byte chunk each, so that a small batch (the SAC step's 256 rows)
+    // is one round trip after its walks; more for large batches, up to one draw per lane
+    const int RW = (int)row_floats, CW = RW / 4 + (S + 3) / 4;
+    int64_t dpw = B / 4096;
+    if (dpw < 64 / CW) dpw = 64 / CW;
+    if (dpw < 1) dpw = 1;
+    if (dpw > 64) dpw = 64;
+    int64_t g = erl_cdiv(erl_cdiv(B, dpw), 4);
+    if (g > 256 * 8) g = 256 * 8;
+    hipLaunchKernelGGL(per_sample_rows_kernel, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, sum_tree, min_tree, L, (int)num_seqs, uniform,
+                       n_per_seq, cur_size, newest, per_beta, ring, max_size, S, A, RW, out_index, out_weight, out_state, out_action, out_reward,
+                       out_undone, out_unmask, out_next_state, out_ids0, out_ids1, (int)dpw);
+    ERL_LAUNCH_CHECK("erl_per_sample_rows_f32");
 }

@@ -507,6 +507,60 @@ extern "C" int erl_sac_update_ring_loop_f32(float *actor_params, float *critic_p
     return ERL_OK;
 }
 
+// The same loop with prioritised replay (AgentSAC.py:45-47, :58-62; include/erl_hip.h): per step the draw + gather (per.hip), the step
+// with the importance weights in and the td errors out, the tree update from the sampler's own indices -- what AgentSAC._per_step issues
+// as six host-driven calls.  Stream order alone makes step t + 1 draw from the trees step t wrote.  Everything the three entry points
+// would refuse is refused here, before the first launch.
+extern "C" int erl_sac_update_per_loop_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
+                                           float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
+                                           const int *hidden, int n_hidden, int E, const ErlRingSample *ring, const ErlPerSample *per,
+                                           int64_t n_steps, float *state, float *action, float *reward, float *undone, float *unmask,
+                                           float *next_state, int64_t B, uint64_t seed, uint64_t counter0, float gamma, float target_entropy,
+                                           float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step0,
+                                           float *objs_all, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    ERL_REQUIRE(ring && per && objs_all, "erl_sac_update_per_loop_f32: NULL argument");
+    ERL_REQUIRE(per->sum_tree && per->min_tree, "erl_sac_update_per_loop_f32: NULL trees");
+    ERL_REQUIRE(ring->buf_states && per->uniform_all && per->is_index && per->is_weight && per->td_error,
+                "erl_sac_update_per_loop_f32: NULL ring / sampler tensor");
+    ERL_REQUIRE(actor_params && critic_params && target_params && alpha_log && actor_m && actor_v && critic_m && critic_v && alpha_m && alpha_v &&
+                    state && action && reward && undone && unmask && next_state && workspace,
+                "erl_sac_update_per_loop_f32: NULL tensor");
+    ERL_REQUIRE(n_steps >= 1 && n_steps < (1LL << 31) - step0 && step0 >= 1, "erl_sac_update_per_loop_f32: n_steps=%lld step0=%d",
+                (long long)n_steps, (int)step0);
+    SacDims d;
+    ERL_REQUIRE(make_sac_dims(S, A, hidden, n_hidden, E, &d), "erl_sac_update_per_loop_f32: unsupported dims");
+    ERL_REQUIRE(ring->row_floats > 0 && ring->row_floats == erl_replay_row_floats(S, A) && (reinterpret_cast<uintptr_t>(ring->buf_states) & 15) == 0,
+                "erl_sac_update_per_loop_f32: row_floats=%lld: the interleaved ring only (erl_replay_row_floats = %lld, 16-byte aligned)",
+                (long long)ring->row_floats, (long long)erl_replay_row_floats(S, A));
+    ERL_REQUIRE(per->max_size >= 2 && per->max_size <= (1LL << 30) && per->num_seqs >= 1 && per->num_seqs < (1 << 30) &&
+                    ring->max_size == per->max_size && ring->num_seqs == per->num_seqs,
+                "erl_sac_update_per_loop_f32: ring (max_size=%lld num_seqs=%lld) and trees (max_size=%lld num_seqs=%lld) do not match",
+                (long long)ring->max_size, (long long)ring->num_seqs, (long long)per->max_size, (long long)per->num_seqs);
+    ERL_REQUIRE(per->cur_size >= 2 && per->cur_size <= per->max_size && per->cursor <= per->max_size,
+                "erl_sac_update_per_loop_f32: cur_size=%lld cursor=%lld max_size=%lld", (long long)per->cur_size, (long long)per->cursor,
+                (long long)per->max_size);
+    ERL_REQUIRE(B >= 1 && B < (1LL << 24) && B % per->num_seqs == 0,
+                "erl_sac_update_per_loop_f32: batch %lld must be num_seqs=%lld x n_per_seq, n_per_seq >= 1", (long long)B, (long long)per->num_seqs);
+    ERL_REQUIRE(workspace_bytes >= erl_sac_workspace_bytes(S, A, hidden, n_hidden, E, B), "erl_sac_update_per_loop_f32: workspace too small");
+    const int64_t n_per_seq = B / per->num_seqs;
+    for (int64_t t = 0; t < n_steps; ++t) {
+        int rc = erl_per_sample_rows_f32(per->sum_tree, per->min_tree, per->max_size, per->num_seqs, per->uniform_all + t * B, n_per_seq,
+                                         per->cur_size, per->cursor, per->per_beta, ring->buf_states, S, A, ring->row_floats, per->is_index,
+                                         per->is_weight, state, action, reward, undone, unmask, next_state, ring->out_ids0, ring->out_ids1, stream);
+        if (rc) return rc;
+        rc = erl_sac_update_f32(actor_params, critic_params, target_params, alpha_log, actor_m, actor_v, critic_m, critic_v, alpha_m, alpha_v, S, A,
+                                hidden, n_hidden, E, state, action, reward, undone, unmask, next_state, per->is_weight, per->td_error, nullptr, 0.f,
+                                B, nullptr, nullptr, seed, counter0 + (uint64_t)t, gamma, target_entropy, tau, lr, beta1, beta2, eps_adam, max_norm,
+                                step0 + (int32_t)t, objs_all + 2 * t, workspace, workspace_bytes, stream);
+        if (rc) return rc;
+        rc = erl_per_update_index_f32(per->sum_tree, per->min_tree, per->max_size, per->num_seqs, per->is_index, per->cur_size, per->td_error, B,
+                                      per->per_alpha, stream);
+        if (rc) return rc;
+    }
+    return ERL_OK;
+}
+
 static int sac_update_impl(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
                            float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
                            const int *hidden, int n_hidden, int E, const float *state, const float *action,

@@ -275,6 +275,40 @@ class PerTrees:
         return idx, w
 
 
+class PerStage:
+    """the three scratch vectors of a prioritised step for one batch size: is_index (B,) int64, is_weight and td_error (B,) float32"""
+
+    def __init__(self, B: int, device):
+        self.B = int(B)
+        self.is_index = th.empty(self.B, dtype=th.int64, device=device)
+        self.is_weight = th.empty(self.B, dtype=th.float32, device=device)
+        self.td_error = th.empty(self.B, dtype=th.float32, device=device)
+
+
+def per_sample_rows(trees: PerTrees, ring: ReplayRing, uniform: TEN, cur_size: int, per_beta: float, cursor: int = -1,
+                    stage: Optional[ReplayStage] = None, per_stage: Optional[PerStage] = None):
+    """ReplayBuffer.sample_for_per on the interleaved ring from ONE launch (erl_per_sample_rows_f32): PerTrees.sample(uniform, ...) and
+    ReplayRing.sample(is_index, cur_size) together.  Returns ((state, action, reward, undone, unmask, next_state), (ids0, ids1), is_index,
+    is_weight)."""
+    assert uniform.shape[0] == trees.num_seqs == ring.num_seqs and trees.max_size == ring.max_size and uniform.dtype == th.float32
+    n = uniform.shape[1]
+    B = trees.num_seqs * n
+    st = stage if stage is not None else ReplayStage(B, ring.S, ring.A, False, ring.block.device)
+    ps = per_stage if per_stage is not None else PerStage(B, ring.block.device)
+    assert st.B == B and ps.B == B and not st.discrete
+    check(lib().erl_per_sample_rows_f32(ptr(trees.sum), ptr(trees.min), trees.max_size, trees.num_seqs, ptr(uniform.contiguous(), th.float32), n,
+                                        int(cur_size), int(cursor), float(per_beta), ptr(ring.block, th.float32), ring.S, ring.A, ring.row_floats,
+                                        ptr(ps.is_index), ptr(ps.is_weight), st.p_state, st.p_action, st.p_reward, st.p_undone, st.p_unmask,
+                                        st.p_next, st.p_ids0, st.p_ids1, stream_ptr()), "erl_per_sample_rows_f32")
+    return st.out, st.ids, ps.is_index, ps.is_weight
+
+
+def per_update_index(trees: PerTrees, is_index: TEN, cur_size: int, td_error: TEN, per_alpha: float) -> None:
+    """ReplayBuffer.td_error_update_for_per from ONE launch (erl_per_update_index_f32): the kernel decodes is_index = ids1 * cur_size + ids0"""
+    check(lib().erl_per_update_index_f32(ptr(trees.sum), ptr(trees.min), trees.max_size, trees.num_seqs, ptr(is_index, th.int64), int(cur_size),
+                                         ptr(td_error, th.float32), is_index.numel(), float(per_alpha), stream_ptr()), "erl_per_update_index_f32")
+
+
 # ------------------------------------------------------------------------------------------------
 # MLP kernels (K1, K2, K6, K7)
 # ------------------------------------------------------------------------------------------------
@@ -765,6 +799,39 @@ def sac_update_ring_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, al
                                              seed & (2 ** 64 - 1), counter0 & (2 ** 64 - 1), gamma, target_entropy, tau, lr, betas[0], betas[1], eps,
                                              max_norm, int(step0), ptr(objs_all, f32), ptr(ws), ws.numel(), stream_ptr()),
           "erl_sac_update_ring_loop_f32")
+
+
+class _PerSample(ctypes.Structure):         # include/erl_hip.h ErlPerSample
+    _fields_ = [("sum_tree", ctypes.c_void_p), ("min_tree", ctypes.c_void_p), ("max_size", ctypes.c_int64), ("num_seqs", ctypes.c_int64),
+                ("cur_size", ctypes.c_int64), ("cursor", ctypes.c_int64), ("per_alpha", ctypes.c_float), ("per_beta", ctypes.c_float),
+                ("uniform_all", ctypes.c_void_p), ("is_index", ctypes.c_void_p), ("is_weight", ctypes.c_void_p), ("td_error", ctypes.c_void_p)]
+
+
+def sac_update_per_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring: ReplayRing,
+                        trees: PerTrees, uniform_all: TEN, cur_size: int, cursor: int, per_alpha: float, per_beta: float, stage: ReplayStage,
+                        per_stage: PerStage, step0: int, *, gamma: float, target_entropy: float, tau: float, lr: float, max_norm: float,
+                        objs_all: TEN, seed: int = 0, counter0: int = 0, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+    """`uniform_all.shape[0]` prioritised steps from ONE C call (erl_sac_update_per_loop_f32): step t = per_sample_rows(uniform_all[t]), the
+    step sac_update runs with is_weight / td_error_out, per_update_index; optimiser step step0 + t, noise counter counter0 + t,
+    objs_all[t].  `stage` / `per_stage` end up holding the last step's batch, ids0 / ids1, indices, weights and td errors."""
+    T, Q, n = uniform_all.shape
+    B = Q * n
+    f32 = th.float32
+    assert isinstance(ring, ReplayRing) and (ring.S, ring.A) == (spec.S, spec.A) and Q == trees.num_seqs == ring.num_seqs
+    assert uniform_all.is_contiguous() and objs_all.shape == (T, 2) and objs_all.is_contiguous()
+    assert stage.B == B and per_stage.B == B and not stage.discrete
+    rs = _RingSample(ptr(ring.block, f32), None, None, None, None, ring.max_size, ring.num_seqs, None, 0, stage.p_ids0, stage.p_ids1,
+                     ring.row_floats)
+    pr = _PerSample(ptr(trees.sum, f32), ptr(trees.min, f32), trees.max_size, trees.num_seqs, int(cur_size), int(cursor), float(per_alpha),
+                    float(per_beta), ptr(uniform_all, f32), ptr(per_stage.is_index, th.int64), ptr(per_stage.is_weight, f32),
+                    ptr(per_stage.td_error, f32))
+    ws = _workspace(ring.block.device, spec.workspace_bytes(B))
+    check(lib().erl_sac_update_per_loop_f32(ptr(actor, f32), ptr(critic, f32), ptr(target, f32), ptr(alpha_log, f32), *[ptr(m, f32) for m in moments],
+                                            spec.S, spec.A, spec._c, len(spec.hidden), spec.E, ctypes.addressof(rs), ctypes.addressof(pr), T,
+                                            stage.p_state, stage.p_action, stage.p_reward, stage.p_undone, stage.p_unmask, stage.p_next, B,
+                                            seed & (2 ** 64 - 1), counter0 & (2 ** 64 - 1), gamma, target_entropy, tau, lr, betas[0], betas[1], eps,
+                                            max_norm, int(step0), ptr(objs_all, f32), ptr(ws), ws.numel(), stream_ptr()),
+          "erl_sac_update_per_loop_f32")
 
 
 def sac_explore_action(spec: SacSpec, actor: TEN, state: TEN, *, noise: Optional[TEN] = None, seed: int = 0, counter: int = 0,

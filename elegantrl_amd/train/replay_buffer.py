@@ -36,6 +36,7 @@ class ReplayBuffer:
         f32 = dict(dtype=th.float32, device=self.device)
         self.if_discrete = bool(if_discrete)
         self._stage = None
+        self._per_stage = None
         # Continuous-action buffers on a HIP device keep ONE interleaved block (ops.ReplayRing, round 6): a row is [state | action |
         # reward | undone | unmask], sequence-major, so a sampled transition and its next state are consecutive bytes; the reference's
         # five attributes (replay_buffer.py:40-58) are strided views of it -- same shapes, dtypes, indexing and assignment behaviour, not
@@ -130,6 +131,22 @@ class ReplayBuffer:
             self._stage = ops.ReplayStage(batch_size, self.states.shape[2], self.actions.shape[2], False, self.device)
         arrays = self._ring if self._ring is not None else (self.states, self.actions, self.rewards, self.undones, self.unmasks)
         return arrays, self.cur_size - 1, self._stage
+
+    def per_for_fused_loop(self, batch_size: int):
+        """the PER twin of ring_for_fused_sample: (ring, trees, cur_size, cursor, per_alpha, per_beta, stage, per_stage) for a consumer that
+        runs `sample_for_per` / `td_error_update_for_per` itself (ops.sac_update_per_loop: the whole prioritised update loop from one C
+        call), or None where that does not apply (no PER, a discrete or planar ring, fewer than two rows, a batch that is no multiple of
+        num_seqs).  `stage` is the block `sample(..., reuse=True)` writes to, `per_stage` the indices / weights / td errors."""
+        from .. import ops
+        if (not self.if_use_per or self.if_discrete or self._ring is None or self.cur_size < 2 or batch_size < self.num_seqs
+                or batch_size % self.num_seqs != 0):
+            return None
+        if self._stage is None or self._stage.B != batch_size:
+            self._stage = ops.ReplayStage(batch_size, self.states.shape[2], self.actions.shape[2], False, self.device)
+        if self._per_stage is None or self._per_stage.B != batch_size:
+            self._per_stage = ops.PerStage(batch_size, self.device)
+        return (self._ring, self.sum_trees, self.cur_size, self.p if self.if_full else -1, self.per_alpha, self.per_beta, self._stage,
+                self._per_stage)
 
     @_hip.on_device
     def sample_for_per(self, batch_size: int, uniform: Optional[TEN] = None):

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ERL_ABI_VERSION 20
+#define ERL_ABI_VERSION 21
 #define ERL_API __attribute__((visibility("default")))
 #define ERL_OK 0
 #define ERL_EINVAL (-1)
@@ -207,6 +207,22 @@ ERL_API int erl_per_update_f32(float *sum_tree, float *min_tree, int64_t max_siz
 ERL_API int erl_per_sample_f32(const float *sum_tree, const float *min_tree, int64_t max_size, int64_t num_seqs,
                        const float *uniform, int64_t n_per_seq, int64_t cur_size, int64_t cursor, float per_beta, int64_t *out_index,
                        float *out_weight, void *stream);
+/* The two halves of a prioritised step's replay traffic as ONE launch each, on the caller's stream, without host arithmetic (ABI 21):
+ *   erl_per_sample_rows_f32   sample_for_per whole (:136-165) on the INTERLEAVED ring (`ring` = the block, row_floats =
+ *                             erl_replay_row_floats(S, A); planar rings keep erl_per_sample_f32 + erl_replay_sample_f32): the draws of
+ *                             erl_per_sample_f32 -- same arithmetic, same out_index / out_weight (num_seqs * n_per_seq each) -- and, from the
+ *                             same launch, what erl_replay_sample_rows_f32(ids = out_index, sample_len = cur_size) would stage: the six
+ *                             (B, .) batch tensors and out_ids0 / out_ids1 (B,) int64 (may be NULL), bit for bit
+ *   erl_per_update_index_f32  erl_per_update_f32 on the sampler's own indices: is_index[i] = ids1 * cur_size + ids0 is decoded in the kernel
+ *                             (the reference's fmod / div, :155-156); duplicates and indices outside [0, num_seqs * cur_size) as
+ *                             erl_per_update_f32 treats duplicate / outside pairs (highest list index wins; skipped) */
+ERL_API int erl_per_sample_rows_f32(const float *sum_tree, const float *min_tree, int64_t max_size, int64_t num_seqs,
+                            const float *uniform, int64_t n_per_seq, int64_t cur_size, int64_t cursor, float per_beta,
+                            const float *ring, int S, int A, int64_t row_floats, int64_t *out_index, float *out_weight,
+                            float *out_state, float *out_action, float *out_reward, float *out_undone, float *out_unmask,
+                            float *out_next_state, int64_t *out_ids0, int64_t *out_ids1, void *stream);
+ERL_API int erl_per_update_index_f32(float *sum_tree, float *min_tree, int64_t max_size, int64_t num_seqs, const int64_t *is_index,
+                             int64_t cur_size, const float *td_error, int64_t n, float per_alpha, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * MLP parameter block used by K1/K2/K6/K7: one flat fp32 buffer per network, laid out as
@@ -625,6 +641,18 @@ typedef struct ErlRingSample {
     int64_t row_floats;     /* ABI 18: 0 = the five planar arrays above; > 0 = the interleaved ring (erl_replay_row_floats): buf_states is
                              * the block's base, the other four pointers are ignored */
 } ErlRingSample;
+/* Prioritised replay's side of a step (sample_for_per / td_error_update_for_per, :136-179) handed to erl_sac_update_per_loop_f32 next to
+ * the ring (ABI 21): the trees (erl_per_tree_floats floats each) with their shape, the ring's fill state (cur_size; cursor = its write
+ * position when full, < 0 otherwise), the two exponents, the uniforms of every step (n_steps, num_seqs, n_per_seq) in [0, 1), and
+ * three caller-owned scratch vectors of B = num_seqs * n_per_seq elements that end up holding the last step's values. */
+typedef struct ErlPerSample {
+    float *sum_tree, *min_tree;
+    int64_t max_size, num_seqs, cur_size, cursor;
+    float per_alpha, per_beta;
+    const float *uniform_all;
+    int64_t *is_index;
+    float *is_weight, *td_error;
+} ErlPerSample;
 
 /* AgentModSAC (elegantrl/agents/AgentSAC.py:89-165) on the same step: ErlSacOptions names what differs from AgentSAC (ABI 17).
  *   actor_variant        ERL_SAC_ACTOR_SAC = ActorSAC (:167-199); ERL_SAC_ACTOR_FIX = ActorFixSAC (:201-243): encoder build_mlp([S, *hidden])
@@ -705,6 +733,19 @@ ERL_API int erl_sac_update_ring_loop_f32(float *actor_params, float *critic_para
                                  float *unmask, float *next_state, int64_t B, uint64_t seed, uint64_t counter0, float gamma,
                                  float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm,
                                  int32_t step0, float *objs_all, void *workspace, int64_t workspace_bytes, void *stream);
+/* AgentBase.update_net's loop with prioritised replay (AgentSAC.py:45-47, :58-62) from one call (ABI 21): n_steps (>= 1) x
+ * [erl_per_sample_rows_f32 with per->uniform_all[t], the step erl_sac_update_f32 runs for this shape with is_weight = per->is_weight and
+ * td_error_out = per->td_error, erl_per_update_index_f32], all on the caller's stream, so step t + 1 draws from the trees step t
+ * updated.  `ring`: the interleaved block in buf_states with max_size / num_seqs / row_floats (> 0) and out_ids0 / out_ids1; its ids and
+ * sample_len are not used.  B must be a multiple of num_seqs.  Step numbering, noise counters, objs_all and the staging block as
+ * erl_sac_update_ring_loop_f32.  Every argument is validated before the first launch. */
+ERL_API int erl_sac_update_per_loop_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log,
+                                float *actor_m, float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v,
+                                int S, int A, const int *hidden, int n_hidden, int E, const ErlRingSample *ring,
+                                const ErlPerSample *per, int64_t n_steps, float *state, float *action, float *reward, float *undone,
+                                float *unmask, float *next_state, int64_t B, uint64_t seed, uint64_t counter0, float gamma,
+                                float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm,
+                                int32_t step0, float *objs_all, void *workspace, int64_t workspace_bytes, void *stream);
 ERL_API int erl_sac_explore_action_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden,
                                const float *state, int64_t N, const float *noise, uint64_t seed, uint64_t counter,
                                float *action_out, float *state_out, void *workspace, int64_t workspace_bytes, void *stream);
