@@ -22,7 +22,7 @@ GAE_VTRACE, GAE_MUTATE, GAE_STATS = 0x1, 0x2, 0x4
 GAE_ALGO_AUTO, GAE_ALGO_EXACT, GAE_ALGO_CHUNKED, GAE_ALGO_LOOKBACK = 0x00, 0x10, 0x20, 0x30
 MAX_STATE_DIM, MAX_HIDDEN, MAX_ACTION_DIM = 128, 128, 16
 MAX_LAYERS, MAXN_WIDTH = 6, 4096
-ABI_VERSION = 21
+ABI_VERSION = 22
 PPO_OBJ_REFERENCE, PPO_OBJ_CANONICAL, PPO_OBJ_A2C = 0, 1, 2      # include/erl_hip.h ERL_PPO_OBJ_*
 SAC_ACTOR_SAC, SAC_ACTOR_FIX = 0, 1                               # include/erl_hip.h ERL_SAC_ACTOR_*
 COMM_ID_BYTES = 128
@@ -168,6 +168,11 @@ _SIGNATURES = {
                                      POINTER(ctypes.c_double), c_int, POINTER(c_int), POINTER(c_int)]),
     "erl_synenv_step_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, c_int, c_uint64, _P]),
     "erl_pendulum_step_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_uint64, _P]),
+    "erl_rollout_discrete_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "erl_cartpole_step_f32": (c_int, [_P] * 7 + [c_int64, c_int, c_uint64, _P]),
+    "erl_rollout_discrete_cartpole_f32": (c_int, [_P] * 3 + [c_int] * 4 + [_P] * 3 + [c_int, c_uint64, c_int64, c_int64, _P, c_uint64, c_uint64,
+                                                  c_float] + [_P] * 9),
+    "erl_eval_discrete_cartpole_f32": (c_int, [_P] * 3 + [c_int] * 4 + [_P] * 3 + [c_int, c_uint64, c_int64, c_int64, _P, c_int64, _P]),
     "erl_selftest_mfma": (c_int, [POINTER(c_float)]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -146,6 +146,7 @@ class PendingLogs:
 class AgentPPO(AgentBase):
     """PPO + GAE, reference-form objective, HIP kernels."""
     _discrete = False            # AgentDiscretePPO: categorical head on the layered path
+    _fused_rollout_default = "1"       # what args.fused_rollout / ERL_FUSED_ROLLOUT default to
     _actor_class = ActorPPO
     supports_lazy_logs = True          # update_net(..., lazy=True) -> PendingLogs (train_agent reads it after the next rollout is enqueued)
 
@@ -239,7 +240,7 @@ class AgentPPO(AgentBase):
         # also leaves the critic's values of the visited states for update_net; ERL_FUSED_ROLLOUT=0 / args.fused_rollout=False
         # keep the per-step launches (A/B runs, parity tests)
         import os
-        self.fused_rollout = bool(getattr(args, "fused_rollout", os.environ.get("ERL_FUSED_ROLLOUT", "1") != "0"))
+        self.fused_rollout = bool(getattr(args, "fused_rollout", os.environ.get("ERL_FUSED_ROLLOUT", self._fused_rollout_default) != "0"))
         self._rollout_cache = None
         self._norm_version = 0
         self.kernel_path = self._describe_kernel_path()
@@ -781,15 +782,71 @@ class AgentDiscretePPO(AgentPPO):
     """PPO with a categorical policy (elegantrl/agents/AgentPPO.py:305-320, ActorDiscretePPO :393-422) on the layered
     path: logits from the layered path's MFMA GEMMs, inverse-CDF sampling / log-prob and the clipped-scale objective
     with its state-dependent entropy in hand-written kernels (erl_mlpn_rollout_step_discrete_f32,
-    erl_mlpn_ppo_step_discrete_f32).  Rollout dtypes as the reference: actions (H, N) int32, env receives int64."""
+    erl_mlpn_ppo_step_discrete_f32).  Rollout dtypes as the reference: actions (H, N) int32, env receives int64.
+    On an env that offers `fused_rollout_discrete` / `fused_evaluate_discrete` (CartPoleGpuVecEnv) the whole rollout and the whole
+    evaluation are one launch each (csrc/rollout_discrete.hip) for two hidden layers of 32..128 in steps of 32."""
     _discrete = True
     _actor_class = ActorDiscretePPO
+    # the one-launch discrete rollout / evaluation has NOT been timed against the per-step loop yet (tools/discrete_rollout_ab.py has no
+    # record in profiles/): until it has, the route is opt-in -- args.fused_rollout = True or ERL_FUSED_ROLLOUT=1 (DESIGN.md section 9)
+    _fused_rollout_default = "0"
 
     def __init__(self, net_dims: List[int], state_dim: int, action_dim: int, gpu_id: int = 0, args: Config = None):
         args = Config() if args is None else args
         super().__init__(net_dims, state_dim, action_dim, gpu_id, args)
         self.lambda_entropy_value = float(getattr(args, "lambda_entropy", 0.01))          # AgentPPO.py:318
         self.lambda_entropy = th.tensor(self.lambda_entropy_value, dtype=th.float32, device=self.device)
+        self.rollout_path = None                  # which route the last _explore_vec_env took: "one-launch" | "loop"
+
+    def _one_launch_shape(self) -> bool:
+        """the policy shapes of the one-launch discrete rollout / evaluation: the library's own answer (erl_rollout_discrete_supported)"""
+        dims = list(self.net_dims)
+        return len(dims) == 2 and bool(_hip.lib().erl_rollout_discrete_supported(self.state_dim, dims[0], dims[1], self.action_dim))
+
+    def _describe_kernel_path(self) -> str:
+        text = super()._describe_kernel_path()
+        dims, S, A = list(self.net_dims), self.state_dim, self.action_dim
+        ok = self._one_launch_shape()
+        if ok and self.fused_rollout:
+            route = "one-launch rollout and evaluation on envs that offer fused_rollout_discrete (CartPoleGpuVecEnv)"
+        elif ok:
+            route = "per-step rollout loop (args.fused_rollout is off, the default for discrete agents while the one-launch route is unmeasured; the shape has it)"
+        else:
+            route = (f"per-step rollout loop (the one-launch discrete rollout needs two hidden layers of 32..128 in steps of 32, "
+                     f"state_dim <= 64, 2 <= action_dim <= 8; here net_dims {dims}, S={S}, A={A})")
+        return text + "; rollout: " + route
+
+    def _one_launch_reason(self, env, what: str) -> Optional[str]:
+        """None when `env` and this agent take the one-launch route through the env's method `what`, else why not"""
+        if self.device.type != "cuda":
+            return "no GPU"
+        if not self.fused_rollout:
+            return "args.fused_rollout is off (the one-launch rollout and its evaluation form go together)"
+        if not self._one_launch_shape():
+            return f"S={self.state_dim} net_dims={list(self.net_dims)} A={self.action_dim} outside the one-launch discrete rollout's shapes"
+        if not hasattr(env, what):
+            return f"{type(env).__name__} has no {what}"
+        if getattr(env, "device", None) != self.device:
+            return f"the env lives on {getattr(env, 'device', None)}, the agent on {self.device}"
+        if getattr(env, "num_envs", None) != self.num_envs:
+            return f"the env has {getattr(env, 'num_envs', None)} envs, the agent {self.num_envs}"
+        if getattr(env, "state_dim", None) != self.state_dim or getattr(env, "action_dim", None) != self.action_dim:
+            return "the env's state / action dims are not the agent's"
+        return None
+
+    def _fused_eval_reason(self, env) -> Optional[str]:
+        """None when `evaluate_env(env)` runs the one-launch evaluation, else why not"""
+        return self._one_launch_reason(env, "fused_evaluate_discrete")
+
+    @_hip.on_device
+    def evaluate_env(self, env) -> Optional[TEN]:
+        """AgentBase.evaluate_env on the evaluation form of the one-launch discrete rollout (erl_eval_discrete_cartpole_f32): env.reset(),
+        env.max_step steps of argmax(logits) in one launch, the episode table from a second; None where `_fused_eval_reason` says why.
+        Leaves rng_counter, last_state, the weights and the optimiser state alone."""
+        if self._fused_eval_reason(env) is not None:
+            return None
+        self._sync_modules()
+        return self._evaluate_env_fused(env, lambda ws: env.fused_evaluate_discrete(self, int(env.max_step), ws))
 
     @_hip.on_device
     def explore_action(self, state: TEN, uniform: Optional[TEN] = None) -> Tuple[TEN, TEN]:
@@ -825,6 +882,28 @@ class AgentDiscretePPO(AgentPPO):
         state = self.last_state
         assert state.shape == (N, S), f"last_state {tuple(state.shape)} != {(N, S)}"
         state = state.to(dev, th.float32).contiguous()
+        if self._one_launch_reason(env, "fused_rollout_discrete") is None:
+            # one launch for all H steps: policy, draw, log-prob, env, buffer rows, reward scaling and flag inversion
+            # (csrc/rollout_discrete.hip); the env owns the live state buffer, the agent gets a copy of the final state
+            if state.data_ptr() != env.state.data_ptr():
+                tok = self._last_state_token
+                # `state` is the copy of the final state the last one-launch rollout of THIS env wrote, untouched, and the env has
+                # not moved since: the live buffer already holds it (no copy-back launch)
+                same = (tok is not None and tok[0] is self.last_state and tok[1] == self.last_state._version and tok[2] is env
+                        and tok[3] == getattr(env, "state_epoch", None) and tok[4] == (id(env.state), env.state._version))
+                if not same:
+                    env.state.copy_(state)
+                    env.state_epoch += 1
+            last_out = th.empty((N, S), dtype=th.float32, device=dev)
+            env.fused_rollout_discrete(self, H, None if noise is None else noise.contiguous(),
+                                       (states, actions, logprobs, rewards, terminals, truncates), last_out)
+            self.rng_counter += H
+            self.last_state = last_out
+            self._last_state_token = (last_out, last_out._version, env, getattr(env, "state_epoch", None), (id(env.state), env.state._version))
+            self.rollout_path = "one-launch"
+            return states, actions, logprobs, rewards, terminals, truncates          # (the kernel wrote the inverted flags)
+        self._last_state_token = None
+        self.rollout_path = "loop"
         for t in range(H):
             ops.mlpn_rollout_step_discrete(self._flat_a.flat, self._spec_a, self._act.state_avg.data, self._act.state_std.data, state,
                                            uniform=None if noise is None else noise[t].contiguous(), seed=self.rng_seed,

@@ -2,6 +2,7 @@
 // erl_sac_* (sac.hip).
 #pragma once
 
+#include "categorical.h"
 #include "gemm_tiles.h"
 #include "ppo_objective.h"
 
@@ -207,22 +208,7 @@ __global__ __launch_bounds__(256) void objective_kernel(float *__restrict__ Y, f
     }
 }
 
-// ---- discrete policy (ActorDiscretePPO, elegantrl/agents/AgentPPO.py:393-422) ------------------------------------
-// torch.distributions.Categorical(probs = softmax(z)) works on logits = log(clamp(p, eps, 1 - eps)) with
-// eps = float32 machine epsilon: log_prob(a) = logits[a], entropy = -sum p logits; the clamp has zero gradient outside.
-constexpr int kMaxDiscrete = 64;             // action_dim of the discrete path
-constexpr float kCatEps = 1.1920928955078125e-07f;
-
-__device__ __forceinline__ void softmax_row(const float *__restrict__ z, int A, float *p)
-{
-    float mx = z[0];
-    for (int a = 1; a < A; ++a) mx = fmaxf(mx, z[a]);
-    float sum = 0.f;
-    for (int a = 0; a < A; ++a) { p[a] = expf(z[a] - mx); sum += p[a]; }
-    const float inv = 1.f / sum;
-    for (int a = 0; a < A; ++a) p[a] *= inv;
-}
-
+// ---- discrete policy (ActorDiscretePPO, elegantrl/agents/AgentPPO.py:393-422): softmax_row / categorical_draw in categorical.h ----
 // rollout sampling: inverse-CDF draw from softmax(logits) with u in [0, 1) (injected or Philox), log-prob of the draw
 __global__ __launch_bounds__(256) void sample_categorical_kernel(const float *__restrict__ Y, int A, int64_t N,
                                                                  const float *__restrict__ uniform, uint64_t seed, uint64_t counter,
@@ -232,17 +218,13 @@ __global__ __launch_bounds__(256) void sample_categorical_kernel(const float *__
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
     float p[kMaxDiscrete];
-    softmax_row(Y + n * A, A, p);
     const float u = uniform ? uniform[n] : philox_uniform(seed, counter, (uint32_t)n);
-    int act = A - 1;
-    float c = 0.f;
-    for (int a = 0; a < A; ++a) {
-        c += p[a];
-        if (u < c) { act = a; break; }
-    }
+    int act;
+    float lp;
+    categorical_draw(Y + n * A, A, u, p, act, lp);
     if (o_action) o_action[n] = act;
     if (o_env) o_env[n] = act;                                      // convert_action_for_env: action.long()
-    if (o_logprob) o_logprob[n] = logf(fminf(fmaxf(p[act], kCatEps), 1.f - kCatEps));
+    if (o_logprob) o_logprob[n] = lp;
 }
 
 // PPO objective of the discrete actor on gathered rows (AgentPPO.py:189-204 with get_logprob_entropy of :413-418):

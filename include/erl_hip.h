@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ERL_ABI_VERSION 21
+#define ERL_ABI_VERSION 22
 #define ERL_API __attribute__((visibility("default")))
 #define ERL_OK 0
 #define ERL_EINVAL (-1)
@@ -339,6 +339,42 @@ ERL_API int erl_sac_eval_pendulum_f32(const float *actor_params, const int *hidd
                               void *workspace, int64_t workspace_bytes, void *stream);
 ERL_API int erl_eval_episodes_compact_f32(const void *workspace, int64_t workspace_bytes, int64_t N, int64_t H, float *out_rows,
                                   int64_t out_capacity, int32_t *out_count, void *stream);
+
+/* Discrete PPO on the device (ABI 22): a device-resident CartPole-v1 and the one-launch rollout / evaluation of the categorical policy
+ * (csrc/rollout_discrete.hip).
+ *
+ * erl_cartpole_step_f32: one step of N envs.  state (N, 4) = (x, x_dot, theta, theta_dot), action (N,) int64 (any value other than 1
+ * pushes left), gymnasium's CartPole-v1 physics (Euler, dt 0.02, force +-10); terminal = |x| > 2.4 or |theta| > 12 degrees on the NEW
+ * state, truncate = step_count reached max_step and not terminal, reward = 1.  state / step_count / episode are updated in place; a done
+ * row restarts from four U[-0.05, 0.05) Philox draws keyed by (seed, env, episode, component).
+ *
+ * erl_rollout_discrete_cartpole_f32: all H steps of AgentDiscretePPO._explore_vec_env in ONE launch.  Per env and step: normalise the
+ * state, the actor MLP (actor_params = the flat block of [S, h1, h2, A] without std: W1 b1 W2 b2 W3 b3, read in place), softmax, the
+ * inverse-CDF draw with u = uniform[t][env] (uniform (H, N), or NULL: philox_uniform(seed, counter0 + t, env), the keys of
+ * erl_mlpn_rollout_step_discrete_f32 called with counter0 + t), the log-prob of the draw, the env step.  Softmax / draw / log-prob and
+ * the env step are the per-step kernels' own statements.  Outputs, time-major, every cell written: out_states (H, N, 4), out_actions
+ * (H, N) int32, out_logprobs, out_rewards (already times reward_scale), out_undones / out_unmasks (bytes, already inverted);
+ * out_last_state (N, 4) or NULL: a copy of the final state; out_uniform (H, N) or NULL: the u every cell used.  env_state /
+ * step_count / episode are read at entry and written back at exit.
+ *
+ * erl_eval_discrete_cartpole_f32: the same kernel with the greedy policy argmax(logits) (ActorDiscretePPO.forward; the first index on
+ * ties): no draws, no log-prob, no buffer rows; it leaves the records and counts of erl_eval_synenv_f32 in `workspace`
+ * (erl_eval_workspace_bytes(N, H)), for erl_eval_episodes_compact_f32.
+ *
+ * erl_rollout_discrete_supported: the policy shapes of the two: S <= 64, two hidden layers of 32..128 in steps of 32, 2 <= A <= 8
+ * (the CartPole entry points also need S = 4, the env's).  Anything else is ERL_EINVAL ("unsupported dims") before any launch.
+ * No call allocates or synchronises; no workgroup waits for another. */
+ERL_API int erl_rollout_discrete_supported(int S, int h1, int h2, int A);
+ERL_API int erl_cartpole_step_f32(float *state, const int64_t *action, int32_t *step_count, int32_t *episode, float *reward,
+                          uint8_t *terminal, uint8_t *truncate, int64_t N, int max_step, uint64_t seed, void *stream);
+ERL_API int erl_rollout_discrete_cartpole_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2,
+                          int A, float *env_state, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N,
+                          int64_t H, const float *uniform, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states,
+                          int32_t *out_actions, float *out_logprobs, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks,
+                          float *out_last_state, float *out_uniform, void *stream);
+ERL_API int erl_eval_discrete_cartpole_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2, int A,
+                          float *env_state, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
+                          void *workspace, int64_t workspace_bytes, void *stream);
 
 /* K6  one PPO minibatch: gather (K5 indices) + critic fwd/bwd + actor fwd/bwd, both networks in one
  * launch.  Replaces AgentPPO.update_objectives up to (not including) the two optimizer steps
