@@ -644,16 +644,21 @@ class AgentPPO(AgentBase):
         if ids is None:
             ids = th.randint(H * N, size=(update_times, B), device=dev)
         assert ids.shape == (update_times, B) and ids.dtype == th.int64
-        n_slabs = self._n_slabs(B) if self._fused_update else 0
-        if self._fused_update and (self._slabs is None or self._slabs.shape[0] != n_slabs):
-            self._slabs = th.empty((n_slabs, self._stride), dtype=th.float32, device=dev)
-        if self._grads is None or self._grads.shape[0] < update_times:
-            self._grads = th.empty((update_times, self._stride), dtype=th.float32, device=dev)
+        # the categorical policy's fused route (AgentDiscretePPO._update_discrete_fused): its own slab / gradient-row stride
+        fused_d = self._discrete_update_fused(dp)
+        if self._discrete:
+            self.update_path = "fused" if fused_d else "layered"
+        stride = self._stride_discrete_fused if fused_d else self._stride
+        n_slabs = self._n_slabs(B) if self._fused_update or fused_d else 0
+        if (self._fused_update or fused_d) and (self._slabs is None or self._slabs.shape != (n_slabs, stride)):
+            self._slabs = th.empty((n_slabs, stride), dtype=th.float32, device=dev)
+        if self._grads is None or self._grads.shape[0] < update_times or self._grads.shape[1] != stride:
+            self._grads = th.empty((update_times, stride), dtype=th.float32, device=dev)
         a, c = self._act, self.cri
         groups = [(0, self._Pa), (self._Pa, self._Pc)]
         inv_batch = 1.0 / B
         grad_scale = 1.0 / self.world_size
-        if not self._fused_update:      # generic-shape networks: layered path, summed gradient written directly
+        if not self._fused_update and not fused_d:      # generic-shape networks: layered path, summed gradient written directly
             for k in range(update_times):
                 g = self._grads[k]
                 step = ops.mlpn_ppo_step_discrete if self._discrete else ops.mlpn_ppo_step
@@ -674,7 +679,9 @@ class AgentPPO(AgentBase):
             _hip.check_async_faults()          # the stream is drained: a lost look-back predecessor (NaN advantages) raises here
             return obj_critic, obj_actor, obj_entropy
         h1, h2 = self.net_dims
-        if not dp or comm is not None:  # the whole minibatch loop is enqueued by one C call (no interpreter on the launch
+        if fused_d:                     # categorical policy: fused minibatch kernel, the whole loop enqueued by one C call
+            self._update_discrete_fused(states, actions, unmasks, logprobs, advantages, reward_sums, ids, update_times)
+        elif not dp or comm is not None:  # the whole minibatch loop is enqueued by one C call (no interpreter on the launch
             # path); data-parallel ranks pass the library's communicator: the exchange is part of the slab-reduction launch
             # (peer-to-peer route) or an RCCL all-reduce on the same stream
             ops.ppo_update(self._flat, self._exp_avg, self._exp_avg_sq, a.state_avg.data, a.state_std.data, c.state_avg.data,
@@ -722,7 +729,7 @@ class AgentPPO(AgentBase):
                                                      _hip.flag_ptr(undones), _hip.flag_ptr(unmasks), _hip.ptr(values, th.float32), H * N,
                                                      _hip.stream_ptr()), "erl_ppo_finish_f32")
         else:
-            _hip.check(_hip.lib().erl_ppo_logs_mean_f32(_hip.ptr(self._grads, th.float32), self._stride, self._Pa + self._Pc, update_times,
+            _hip.check(_hip.lib().erl_ppo_logs_mean_f32(_hip.ptr(self._grads, th.float32), stride, self._Pa + self._Pc, update_times,
                                                         grad_scale, _hip.ptr(self._logs, th.float32), _hip.stream_ptr()), "erl_ppo_logs_mean_f32")
         if lazy:
             # the three logged means travel to a pinned host block behind the update's last kernel; PendingLogs.result() waits for that
@@ -732,6 +739,12 @@ class AgentPPO(AgentBase):
         obj_critic, obj_actor, obj_entropy = self._logs[:3].tolist()                  # the only host sync of update_net
         _hip.check_async_faults()              # the stream is drained: a lost look-back predecessor (NaN advantages) raises here
         return obj_critic, obj_actor, obj_entropy
+
+    # the categorical policy's fused update route lives in AgentDiscretePPO; update_net asks through these two
+    _stride_discrete_fused = None
+
+    def _discrete_update_fused(self, dp: bool) -> bool:
+        return False
 
     def _n_slabs(self, batch_size: int) -> int:
         from .. import ops
@@ -790,10 +803,22 @@ class AgentDiscretePPO(AgentPPO):
     # the one-launch discrete rollout / evaluation has NOT been timed against the per-step loop yet (tools/discrete_rollout_ab.py has no
     # record in profiles/): until it has, the route is opt-in -- args.fused_rollout = True or ERL_FUSED_ROLLOUT=1
     _fused_rollout_default = "0"
+    # the fused minibatch kernel + one-call update loop (csrc/ppo_step_discrete.hip): on by default, since profiles/discrete_update_ab.txt
+    # has its median below the layered loop's at all three shapes of tools/discrete_update_ab.py;
+    # args.fused_update = False or ERL_FUSED_DISCRETE_UPDATE=0 keep the layered minibatch loop
+    _fused_update_default = "1"
 
     def __init__(self, net_dims: List[int], state_dim: int, action_dim: int, gpu_id: int = 0, args: Config = None):
         args = Config() if args is None else args
+        # (read before the base constructor: it builds `kernel_path`, which names the update route)
+        self.fused_update_discrete = bool(getattr(args, "fused_update",
+                                                  os.environ.get("ERL_FUSED_DISCRETE_UPDATE", self._fused_update_default) != "0"))
+        self.update_path = None                   # which route the last update_net took: "fused" | "layered"
         super().__init__(net_dims, state_dim, action_dim, gpu_id, args)
+        # gradient-row / slab stride of the fused route; None: the shape has no fused kernel, which is what `_discrete_update_fused`
+        # asks from here on (one answer, taken once from erl_ppo_discrete_supported); the layered route keeps `_stride`
+        self._stride_discrete_fused = (_hip.lib().erl_ppo_discrete_slab_stride(state_dim, net_dims[0], net_dims[1], action_dim)
+                                       if self._fused_update_shape() else None)
         self.lambda_entropy_value = float(getattr(args, "lambda_entropy", 0.01))          # AgentPPO.py:318
         self.lambda_entropy = th.tensor(self.lambda_entropy_value, dtype=th.float32, device=self.device)
         self.rollout_path = None                  # which route the last _explore_vec_env took: "one-launch" | "loop"
@@ -802,6 +827,11 @@ class AgentDiscretePPO(AgentPPO):
         """the policy shapes of the one-launch discrete rollout / evaluation: the library's own answer (erl_rollout_discrete_supported)"""
         dims = list(self.net_dims)
         return len(dims) == 2 and bool(_hip.lib().erl_rollout_discrete_supported(self.state_dim, dims[0], dims[1], self.action_dim))
+
+    def _fused_update_shape(self) -> bool:
+        """the policy shapes of the fused discrete minibatch kernel: the library's own answer (erl_ppo_discrete_supported)"""
+        dims = list(self.net_dims)
+        return len(dims) == 2 and bool(_hip.lib().erl_ppo_discrete_supported(self.state_dim, dims[0], dims[1], self.action_dim))
 
     def _describe_kernel_path(self) -> str:
         text = super()._describe_kernel_path()
@@ -814,7 +844,32 @@ class AgentDiscretePPO(AgentPPO):
         else:
             route = (f"per-step rollout loop (the one-launch discrete rollout needs two hidden layers of 32..128 in steps of 32, "
                      f"state_dim <= 64, 2 <= action_dim <= 8; here net_dims {dims}, S={S}, A={A})")
-        return text + "; rollout: " + route
+        ok = self._fused_update_shape()
+        if ok and self.fused_update_discrete:
+            update = ("fused minibatch kernel, the whole loop in one call (csrc/ppo_step_discrete.hip); data-parallel runs keep the layered "
+                      "minibatch loop")
+        elif ok:
+            update = "layered minibatch loop (args.fused_update is off; the shape has the fused minibatch kernel)"
+        else:
+            update = "layered minibatch loop (the fused discrete minibatch kernel covers the one-launch rollout's shapes only)"
+        return text + "; rollout: " + route + "; update: " + update
+
+    def _discrete_update_fused(self, dp: bool) -> bool:
+        """does this update_net take the fused route: the flag is on, the shape has the kernel (`_stride_discrete_fused` is its stride)
+        and the run is not data parallel (the fused loop has no gradient exchange: those runs keep the layered loop)"""
+        return self.fused_update_discrete and not dp and self._stride_discrete_fused is not None
+
+    def _update_discrete_fused(self, states, actions, unmasks, logprobs, advantages, reward_sums, ids, update_times: int):
+        """the minibatch loop of update_net on the fused route (called by AgentPPO.update_net, on its device): one C call enqueues, per
+        minibatch, the fused kernel, the slab reduction into `_grads[k]` and the two-launch clip + Adam tail; advantages are normalised"""
+        from .. import ops
+        a, c = self._act, self.cri
+        h1, h2 = self.net_dims
+        ops.ppo_update_discrete(self._flat, self._exp_avg, self._exp_avg_sq, a.state_avg.data, a.state_std.data, c.state_avg.data,
+                                c.state_std.data, self.state_dim, h1, h2, self.action_dim, states, actions, unmasks, logprobs, advantages,
+                                reward_sums, ids, float(self.ratio_clip), self.lambda_entropy_value, self._slabs, self._grads,
+                                self._adam_step + 1, float(self.learning_rate), float(self.clip_grad_norm))
+        self._adam_step += update_times
 
     def _one_launch_reason(self, env, what: str) -> Optional[str]:
         """None when `env` and this agent take the one-launch route through the env's method `what`, else why not"""

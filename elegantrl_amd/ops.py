@@ -648,6 +648,55 @@ def mlpn_ppo_step_discrete(actor_params: TEN, critic_params: TEN, act_avg: TEN, 
           "erl_mlpn_ppo_step_discrete_f32")
 
 
+def ppo_discrete_supported(S: int, h1: int, h2: int, A: int) -> bool:
+    """the shapes of the fused discrete minibatch kernel (erl_ppo_discrete_supported): those of the one-launch discrete rollout"""
+    return bool(lib().erl_ppo_discrete_supported(int(S), int(h1), int(h2), int(A)))
+
+
+def ppo_discrete_slab_stride(S: int, h1: int, h2: int, A: int) -> int:
+    """floats per gradient slab / gradient row of the fused discrete route: Pa + Pc + 4 rounded up to 32 (-1: unsupported shape)"""
+    return lib().erl_ppo_discrete_slab_stride(int(S), int(h1), int(h2), int(A))
+
+
+def ppo_step_discrete(actor_params: TEN, critic_params: TEN, act_avg: TEN, act_std: TEN, cri_avg: TEN, cri_std: TEN, S: int, h1: int,
+                      h2: int, A: int, states: TEN, actions: TEN, unmasks: TEN, logprobs: TEN, advantages: TEN, reward_sums: TEN,
+                      ids: TEN, ratio_clip: float, lambda_entropy: float, inv_batch: float, slabs: TEN, n_slabs: int) -> None:
+    """one PPO minibatch of the categorical policy in one launch, into `slabs` (n_slabs, ppo_discrete_slab_stride); actions (H, N)
+    int32, `advantages` already normalised.  `grad_reduce(slabs, n_slabs, stride, row)` sums the slabs."""
+    H, N = states.shape[0], states.shape[1]
+    need = n_slabs * ppo_discrete_slab_stride(S, h1, h2, A)
+    if need >= 0 and slabs.numel() < need:
+        raise ValueError(f"slabs holds {slabs.numel()} floats, erl_ppo_step_discrete_f32 writes n_slabs x erl_ppo_discrete_slab_stride = {need}")
+    check(lib().erl_ppo_step_discrete_f32(ptr(actor_params, th.float32), ptr(critic_params, th.float32), ptr(act_avg), ptr(act_std),
+                                          ptr(cri_avg), ptr(cri_std), S, h1, h2, A, ptr(states, th.float32), ptr(actions, th.int32),
+                                          flag_ptr(unmasks), ptr(logprobs, th.float32), ptr(advantages, th.float32),
+                                          ptr(reward_sums, th.float32), H, N, ptr(ids, th.int64), ids.numel(), ratio_clip,
+                                          lambda_entropy, inv_batch, ptr(slabs, th.float32), n_slabs, stream_ptr()),
+          "erl_ppo_step_discrete_f32")
+
+
+def ppo_update_discrete(flat_params: TEN, exp_avg: TEN, exp_avg_sq: TEN, act_avg: TEN, act_std: TEN, cri_avg: TEN, cri_std: TEN, S: int,
+                        h1: int, h2: int, A: int, states: TEN, actions: TEN, unmasks: TEN, logprobs: TEN, advantages: TEN,
+                        reward_sums: TEN, ids: TEN, ratio_clip: float, lambda_entropy: float, slabs: TEN, grads: TEN, first_step: int,
+                        lr: float, max_norm: float, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+    """the whole minibatch loop of AgentDiscretePPO.update_net in one C call; ids: (update_times, B), `advantages` already normalised.
+    Per minibatch: ppo_step_discrete, grad_reduce into grads[k], grad_sq_partials, clip_adam_partials at step first_step + k."""
+    H, N = states.shape[0], states.shape[1]
+    update_times, B = ids.shape
+    stride = ppo_discrete_slab_stride(S, h1, h2, A)
+    n_slabs = slabs.shape[0]
+    if stride >= 0 and (slabs.numel() < n_slabs * stride or grads.numel() < update_times * stride or grads.shape[-1] != stride):
+        raise ValueError(f"slabs {tuple(slabs.shape)} / grads {tuple(grads.shape)}: erl_ppo_update_discrete_f32 needs rows of {stride} floats, "
+                         f"{update_times} gradient rows")
+    check(lib().erl_ppo_update_discrete_f32(ptr(flat_params, th.float32), ptr(exp_avg, th.float32), ptr(exp_avg_sq, th.float32),
+                                            ptr(act_avg), ptr(act_std), ptr(cri_avg), ptr(cri_std), S, h1, h2, A,
+                                            ptr(states, th.float32), ptr(actions, th.int32), flag_ptr(unmasks), ptr(logprobs, th.float32),
+                                            ptr(advantages, th.float32), ptr(reward_sums, th.float32), H, N, ptr(ids, th.int64), B,
+                                            update_times, ratio_clip, lambda_entropy, ptr(slabs, th.float32), n_slabs,
+                                            ptr(grads, th.float32), first_step, lr, betas[0], betas[1], eps, max_norm, stream_ptr()),
+          "erl_ppo_update_discrete_f32")
+
+
 # ------------------------------------------------------------------------------------------------
 # SAC (erl_sac_*)
 # ------------------------------------------------------------------------------------------------

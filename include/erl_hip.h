@@ -652,6 +652,37 @@ ERL_API int erl_mlpn_ppo_step_discrete_f32(const float *actor_params, const floa
                           const int64_t *ids, int64_t B, float ratio_clip, float lambda_entropy, float inv_batch,
                           float *flat_grad, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The categorical policy's minibatch in ONE launch, and its whole update loop from one call (csrc/ppo_step_discrete.hip; additive, ABI 22).
+ *
+ * erl_ppo_step_discrete_f32: what erl_mlpn_ppo_step_discrete_f32 computes (the same objective, statement for statement:
+ * csrc/categorical.h), as K6's 8-wave register-chained fp32-MFMA kernel: grid (erl_ppo_num_slabs(B), 2), one gradient slab per 128
+ * samples, to be summed by erl_grad_reduce_f32.  Parameter blocks: the layered path's [W1 b1 W2 b2 W3 b3] of [S, h1, h2, A] / [S, h1,
+ * h2, 1] (no std slot: Pa, Pc = erl_mlpn_param_count(dims, 4, 0)); actions (H, N) int32, clamped to [0, A); `advantages` are
+ * already normalised.  Slab row: [actor Pa | critic Pc | obj_critic, obj_surrogate, obj_entropy, 0 | zeros], erl_ppo_discrete_slab_stride
+ * = Pa + Pc + 4 rounded up to 32 floats; n_slabs == erl_ppo_num_slabs(B).
+ *
+ * erl_ppo_update_discrete_f32: for k in [0, update_times): erl_ppo_step_discrete_f32(ids + k B) -> erl_grad_reduce_f32 -> grads[k] ->
+ * erl_grad_sq_partials_f32 -> erl_clip_adam_partials_f32(step = first_step + k), grad_scale 1, inv_batch = 1 / B.  flat_params / exp_avg
+ * / exp_avg_sq: [actor (Pa) | critic (Pc)]; grads: (update_times, erl_ppo_discrete_slab_stride); slabs: (n_slabs, the same stride).
+ * Everything is enqueued on the caller's stream: no allocation, no host synchronisation, no side stream, no communicator.
+ *
+ * erl_ppo_discrete_supported: the shapes of erl_rollout_discrete_supported (S <= 64, two hidden layers of 32..128 in steps of 32,
+ * 2 <= A <= 8); anything else is ERL_EINVAL ("unsupported dims") before any launch, erl_ppo_discrete_slab_stride returns -1.  The two
+ * queries are host-only. */
+ERL_API int erl_ppo_discrete_supported(int S, int h1, int h2, int A);
+ERL_API int64_t erl_ppo_discrete_slab_stride(int S, int h1, int h2, int A);
+ERL_API int erl_ppo_step_discrete_f32(const float *actor_params, const float *critic_params, const float *act_avg, const float *act_std,
+                          const float *cri_avg, const float *cri_std, int S, int h1, int h2, int A, const float *states,
+                          const int32_t *actions, const uint8_t *unmasks, const float *logprobs, const float *advantages,
+                          const float *reward_sums, int64_t H, int64_t N, const int64_t *ids, int64_t B, float ratio_clip,
+                          float lambda_entropy, float inv_batch, float *slabs, int n_slabs, void *stream);
+ERL_API int erl_ppo_update_discrete_f32(float *flat_params, float *exp_avg, float *exp_avg_sq, const float *act_avg, const float *act_std,
+                          const float *cri_avg, const float *cri_std, int S, int h1, int h2, int A, const float *states,
+                          const int32_t *actions, const uint8_t *unmasks, const float *logprobs, const float *advantages,
+                          const float *reward_sums, int64_t H, int64_t N, const int64_t *ids, int64_t B, int update_times,
+                          float ratio_clip, float lambda_entropy, float *slabs, int n_slabs, float *grads, int32_t first_step, float lr,
+                          float beta1, float beta2, float eps, float max_norm, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * SAC: everything AgentSAC.update_objectives does after ReplayBuffer.sample
  * (elegantrl/agents/AgentSAC.py:50-86) in ONE call: target computation with the tanh-Gaussian actor (:167-199) and the
