@@ -148,8 +148,8 @@ class AgentSAC(AgentBase):
         self.if_off_policy = True
         if self.if_discrete:
             raise NotImplementedError("SAC is a continuous-action agent")
-        if self.device.type != "cuda":
-            raise _hip.HipExtensionError("AgentSAC runs on the HIP kernels only; no GPU is visible and there is no CPU fallback")
+        # (without a GPU the agent can still be constructed, to read `kernel_path`; it runs on the HIP kernels only and there is no CPU
+        # fallback: its first kernel call raises HipExtensionError, _hip.ptr)
         from .. import ops
         self.num_ensembles = getattr(args, "num_ensembles", self._default_ensembles)
         # update_net draws the sample ids of all its steps with one th.randint (False: one draw per step, the reference's call pattern)
@@ -166,6 +166,7 @@ class AgentSAC(AgentBase):
         # _per_step's six host-driven calls per step
         self.per_loop_in_c = bool(getattr(args, "per_loop_in_c", os.environ.get("ERL_SAC_PER_LOOP_IN_C", "1") != "0"))
         self.per_path = None                       # which route the last prioritised update_net took (None: none yet / not prioritised)
+        self.update_path = None                    # which route the last update_net took: "one C call ..." / "per step: <reason>"
         self._last_state_token = None
         self._spec = ops.SacSpec(state_dim, action_dim, net_dims, self.num_ensembles, actor_variant=self._actor_variant)
         dev, f32 = self.device, th.float32
@@ -198,6 +199,8 @@ class AgentSAC(AgentBase):
                             "layered SAC step (one MFMA GEMM launch per dense layer): " +
                             ("ActorFixSAC / two-time-scale options (AgentModSAC)" if self._actor_variant else
                              f"net_dims {list(net_dims)}, state_dim {state_dim}, action_dim {action_dim} outside the fused step's shapes"))
+        if self._actor_variant:
+            self.kernel_path = self._variant_kernel_path(args)
         if not getattr(args, "quiet", False) and os.environ.get("ERL_QUIET", "0") == "0":
             print(f"| {type(self).__name__}: {self.kernel_path}", flush=True)
 
@@ -310,7 +313,7 @@ class AgentSAC(AgentBase):
         self.rng_counter += 1
         return action
 
-    def _update_from_ring(self, buffer, ring, ids: TEN, objs_out: TEN, noises=None):
+    def _update_from_ring(self, buffer, ring, ids: TEN, objs_out: TEN, noises=None, update_t: int = 0):
         """ReplayBuffer.sample(ids) and the step from one C call; the buffer's stage / ids0 / ids1 end up as after `buffer.sample`"""
         from .. import ops
         self._step += 1
@@ -327,6 +330,31 @@ class AgentSAC(AgentBase):
     def _step_options(self, update_t: int) -> dict:
         """extra keyword arguments of ops.sac_update for this step (AgentModSAC: its two-time-scale rule and actor target)"""
         return {}
+
+    def _variant_kernel_path(self, args) -> str:
+        """`kernel_path` of an agent whose actor is not ActorSAC"""
+        return self.kernel_path
+
+    def _ring_step_reason(self) -> Optional[str]:
+        """None when this agent's step takes the replay sample inside its first launch (the ring forms), else why not"""
+        return "ActorFixSAC / two-time-scale options take the layered step, which reads a finished batch" if self._actor_variant else None
+
+    def _update_ring_loop(self, buffer, ring, id_all: TEN, objs: TEN) -> str:
+        """update_net's whole loop from ONE C call (erl_sac_update_ring_loop_f32, round 6): step t = what _update_from_ring(id_all[t])
+        enqueues; returns the route's name"""
+        from .. import ops
+        arrays, sample_len, stage = ring
+        update_times = id_all.shape[0]
+        ops.sac_update_ring_loop(self._spec, self._actor_flat, self._critic_flat, self._target_flat, self.alpha_log,
+                                 (self.act_optimizer.exp_avg, self.act_optimizer.exp_avg_sq, self.cri_optimizer.exp_avg,
+                                  self.cri_optimizer.exp_avg_sq, self.alpha_optim.exp_avg, self.alpha_optim.exp_avg_sq),
+                                 arrays, id_all, sample_len, stage, self._step + 1, gamma=float(self.gamma),
+                                 target_entropy=float(self.target_entropy), tau=float(self.soft_update_tau), lr=float(self.learning_rate),
+                                 max_norm=float(self.clip_grad_norm), objs_all=objs, seed=self.rng_seed + 1, counter0=self._step + 1)
+        self._step += update_times
+        buffer.ids0, buffer.ids1 = stage.ids
+        self.act_optimizer.step_count = self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
+        return "one C call (erl_sac_update_ring_loop_f32: the sample inside every step's first launch)"
 
     def _update_on_batch(self, batch, objs_out: TEN, noises=None, is_weight=None, td_error_out=None, buffer=None, update_t: int = 0):
         from .. import ops
@@ -402,22 +430,22 @@ class AgentSAC(AgentBase):
             id_rows = id_all.unbind(0)
         # the sample rides in the step's first launch (erl_sac_update_ring_f32) where the buffer is the library's continuous-action ring and
         # nothing needs ids0 / ids1 before the step
-        ring = (id_rows is not None and self.sample_in_step and not self.lambda_fit_cum_r and not self._actor_variant
-                and getattr(buffer, "ring_for_fused_sample", None) and buffer.ring_for_fused_sample(self.batch_size))
+        why = ("prioritised replay (per_path names its route)" if self.if_use_per else
+               "args.sample_ids_ahead is off" if id_rows is None else
+               "args.sample_in_step is off" if not self.sample_in_step else
+               "lambda_fit_cum_r needs ids0 / ids1 on the host side of every step" if self.lambda_fit_cum_r else self._ring_step_reason())
+        ring = None
+        if why is None:
+            ring = getattr(buffer, "ring_for_fused_sample", None) and buffer.ring_for_fused_sample(self.batch_size)
+            if not ring:
+                why = f"{type(buffer).__name__} offers no continuous-action ring of >= 2 rows for the sample inside the step"
+            elif not self.update_loop_in_c:
+                why = "args.update_loop_in_c is off"
         if ring and self.update_loop_in_c:
-            # the whole loop from ONE C call (erl_sac_update_ring_loop_f32, round 6): step t = what _update_from_ring(id_rows[t]) enqueues
-            from .. import ops
-            arrays, sample_len, stage = ring
-            ops.sac_update_ring_loop(self._spec, self._actor_flat, self._critic_flat, self._target_flat, self.alpha_log,
-                                     (self.act_optimizer.exp_avg, self.act_optimizer.exp_avg_sq, self.cri_optimizer.exp_avg,
-                                      self.cri_optimizer.exp_avg_sq, self.alpha_optim.exp_avg, self.alpha_optim.exp_avg_sq),
-                                     arrays, id_all, sample_len, stage, self._step + 1, gamma=float(self.gamma),
-                                     target_entropy=float(self.target_entropy), tau=float(self.soft_update_tau), lr=float(self.learning_rate),
-                                     max_norm=float(self.clip_grad_norm), objs_all=objs, seed=self.rng_seed + 1, counter0=self._step + 1)
-            self._step += update_times
-            buffer.ids0, buffer.ids1 = stage.ids
-            self.act_optimizer.step_count = self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
+            self.update_path = self._update_ring_loop(buffer, ring, id_all, objs)
             update_times = 0                              # (nothing left for the Python loop)
+        else:
+            self.update_path = "per step: " + why
         if self.if_use_per:
             why = self._per_loop_reason(buffer)
             per = None if why else buffer.per_for_fused_loop(self.batch_size)
@@ -450,7 +478,7 @@ class AgentSAC(AgentBase):
             if self.if_use_per:
                 self._per_step(buffer, objs[t], update_t=t, uniform=None if per_uniform is None else per_uniform[t])
             elif ring:
-                self._update_from_ring(buffer, ring, id_rows[t], objs[t])
+                self._update_from_ring(buffer, ring, id_rows[t], objs[t], update_t=t)
             else:       # (the batch is consumed before the next draw)
                 self._update_on_batch(buffer.sample(self.batch_size, ids=None if id_rows is None else id_rows[t], reuse=True), objs[t], buffer=buffer,
                                       update_t=t)
@@ -464,11 +492,16 @@ class AgentModSAC(AgentSAC):
     """Modified SAC (elegantrl/agents/AgentSAC.py:89-165): ActorFixSAC, 8 critics, `target_entropy = -log(action_dim)`, an actor target
     that follows the actor by soft updates, and the "auto two-time-scale update rule": the actor is updated on a step only while
     `update_a / (update_t + 1) < 1 / (2 - reliable_lambda)`, `reliable_lambda = exp(-critic_value ** 2)` (the reference never moves
-    `critic_value` off 1.0, so this is 0.61: the actor skips roughly every third step).  The step itself is erl_sac_update_opt_f32
-    (csrc/sac.hip, layered path; ErlSacOptions carries what differs from AgentSAC)."""
+    `critic_value` off 1.0, so this is 0.61: the actor skips roughly every third step).  The step is erl_sac_update_opt_f32 (csrc/sac.hip,
+    layered path; ErlSacOptions carries what differs from AgentSAC) or, with `fused_step` on and inside the fused step's shapes,
+    erl_sac_update_mod_f32 (csrc/sac_fused.hip: AgentSAC's tile kernels with ActorFixSAC as a run-time variant); update_net's loop on the
+    fused step is one erl_sac_update_mod_ring_loop_f32 call."""
     _actor_class = ActorFixSAC
     _actor_variant = _hip.SAC_ACTOR_FIX
     _default_ensembles = 8
+    # the fused step against the layered one has no A/B record yet (tools/modsac_update_ab.py writes profiles/modsac_update_ab.txt): until
+    # it has, the route is opt-in -- args.fused_step = True or ERL_FUSED_MODSAC_STEP=1
+    _fused_step_default = "0"
 
     def __init__(self, net_dims: List[int], state_dim: int, action_dim: int, gpu_id: int = 0, args: Config = None):
         args = Config() if args is None else args
@@ -488,6 +521,78 @@ class AgentModSAC(AgentSAC):
         if not self._bind_at.is_bound(self.act_target):
             self._bind_at.bind(self.act_target)
 
+    def _fused_step_reason(self, batch_size: Optional[int] = None) -> Optional[str]:
+        """None when a step on `batch_size` rows runs the fused ModSAC step (erl_sac_update_mod_*), else why it is layered.  Asked per call:
+        `fused_step` can be flipped between calls (A/B runs alternate the two routes in one process)."""
+        from .. import ops
+        if not self.fused_step:
+            return "args.fused_step is off (ERL_FUSED_MODSAC_STEP; profiles/modsac_update_ab.txt)"
+        if os.environ.get("ERL_SAC_FUSED", "1") == "0":
+            return "ERL_SAC_FUSED=0"
+        if self.lambda_fit_cum_r:
+            return "lambda_fit_cum_r: the critic's cumulative-reward term is layered only"
+        B = int(self.batch_size if batch_size is None else batch_size)
+        if not ops.sac_mod_fused_supported(self._spec, B):
+            return (f"net_dims {list(self.net_dims)}, state_dim {self.state_dim}, action_dim {self.action_dim}, {self.num_ensembles} critics, "
+                    f"batch {B} outside the fused step's shapes (two hidden layers, widths multiples of 16 up to 256, S + A <= 64, A <= 8, "
+                    "<= 8 critics, batch <= 4096)")
+        return None
+
+    def _variant_kernel_path(self, args) -> str:
+        # (called by the base constructor, which prints `kernel_path`)
+        self.fused_step = bool(getattr(args, "fused_step", os.environ.get("ERL_FUSED_MODSAC_STEP", self._fused_step_default) != "0"))
+        why = self._fused_step_reason()
+        if why is None:
+            return ("fused ModSAC step (erl_sac_update_mod_f32: AgentSAC's tile kernels with ActorFixSAC's raw second layer and head, skipped "
+                    "actor steps end in one small launch, actor target in the actor's clip + Adam launch; update_net's loop is one C call)")
+        return "layered ModSAC step (erl_sac_update_opt_f32: one MFMA GEMM launch per dense layer): " + why
+
+    def _ring_step_reason(self) -> Optional[str]:
+        why = self._fused_step_reason()
+        return None if why is None else "layered ModSAC step, which reads a finished batch: " + why
+
+    def _moments(self):
+        return (self.act_optimizer.exp_avg, self.act_optimizer.exp_avg_sq, self.cri_optimizer.exp_avg, self.cri_optimizer.exp_avg_sq,
+                self.alpha_optim.exp_avg, self.alpha_optim.exp_avg_sq)
+
+    def _update_ring_loop(self, buffer, ring, id_all: TEN, objs: TEN) -> str:
+        """update_net's whole loop from ONE C call (erl_sac_update_mod_ring_loop_f32): the two-time-scale rule is evaluated in C, exactly as
+        _step_options does per step; afterwards the counters are what the per-step route would have left"""
+        from .. import ops
+        arrays, sample_len, stage = ring
+        T = id_all.shape[0]
+        n_upd = ops.sac_update_mod_ring_loop(self._spec, self._actor_flat, self._critic_flat, self._target_flat, self.alpha_log, self._moments(),
+                                             arrays, id_all, sample_len, stage, self._step + 1, self._actor_step, float(self.critic_value),
+                                             gamma=float(self.gamma), target_entropy=float(self.target_entropy), tau=float(self.soft_update_tau),
+                                             lr=float(self.learning_rate), max_norm=float(self.clip_grad_norm), objs_all=objs,
+                                             actor_target=self._actor_target_flat, seed=self.rng_seed + 1, counter0=self._step + 1)
+        bound, ua, do = 1 / (2 - math.exp(-self.critic_value ** 2)), 0, True
+        for t in range(T):                                      # (the last step's flag; the count must be the library's)
+            do = (ua / (t + 1)) < bound
+            ua += do
+        assert ua == n_upd, (ua, n_upd)
+        self.update_a, self._last_actor_updated = n_upd, bool(do)
+        self._actor_step += n_upd
+        self._step += T
+        buffer.ids0, buffer.ids1 = stage.ids
+        self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
+        self.act_optimizer.step_count = self._actor_step
+        return "one C call (erl_sac_update_mod_ring_loop_f32: the sample inside every step's first launch, the two-time-scale rule in C)"
+
+    def _update_from_ring(self, buffer, ring, ids: TEN, objs_out: TEN, noises=None, update_t: int = 0):
+        from .. import ops
+        self._step += 1
+        o = self._step_options(update_t)
+        arrays, sample_len, stage = ring
+        ops.sac_update_mod_from_ring(self._spec, self._actor_flat, self._critic_flat, self._target_flat, self.alpha_log, self._moments(), arrays,
+                                     ids, sample_len, stage, self._step, gamma=float(self.gamma), target_entropy=float(self.target_entropy),
+                                     tau=float(self.soft_update_tau), lr=float(self.learning_rate), max_norm=float(self.clip_grad_norm),
+                                     objs_out=objs_out, update_actor=o["update_actor"], actor_step=o["actor_step"], actor_target=o["actor_target"],
+                                     noises=noises, seed=self.rng_seed + 1, counter=self._step)
+        buffer.ids0, buffer.ids1 = stage.ids
+        self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
+        self.act_optimizer.step_count = self._actor_step
+
     def _step_options(self, update_t: int) -> dict:
         reliable_lambda = math.exp(-self.critic_value ** 2)
         self.update_a = 0 if update_t == 0 else self.update_a                           # (:150)
@@ -498,8 +603,19 @@ class AgentModSAC(AgentSAC):
         self._last_actor_updated = do
         return dict(update_actor=do, actor_step=max(1, self._actor_step), actor_target=self._actor_target_flat)
 
-    def _update_on_batch(self, *a, **k):
-        super()._update_on_batch(*a, **k)
+    def _update_on_batch(self, batch, objs_out: TEN, noises=None, is_weight=None, td_error_out=None, buffer=None, update_t: int = 0):
+        if self._fused_step_reason(batch[0].shape[0]) is None:
+            from .. import ops
+            self._step += 1
+            o = self._step_options(update_t)
+            ops.sac_update_mod(self._spec, self._actor_flat, self._critic_flat, self._target_flat, self.alpha_log, self._moments(), batch,
+                               self._step, gamma=float(self.gamma), target_entropy=float(self.target_entropy), tau=float(self.soft_update_tau),
+                               lr=float(self.learning_rate), max_norm=float(self.clip_grad_norm), objs_out=objs_out,
+                               update_actor=o["update_actor"], actor_step=o["actor_step"], actor_target=o["actor_target"], noises=noises,
+                               seed=self.rng_seed + 1, counter=self._step, is_weight=is_weight, td_error_out=td_error_out)
+            self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
+        else:
+            super()._update_on_batch(batch, objs_out, noises, is_weight=is_weight, td_error_out=td_error_out, buffer=buffer, update_t=update_t)
         self.act_optimizer.step_count = self._actor_step         # (th.optim.Adam's own count: the actor steps only when it is updated)
 
     def save_or_load_agent(self, cwd: str, if_save: bool):

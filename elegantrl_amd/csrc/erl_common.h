@@ -66,13 +66,21 @@ int64_t erl_sac_fused_ws_floats(int S, int A, int h0, int h1, int E, int64_t B, 
 int erl_sac_explore_fused(const float *actor_params, int S, int A, int h0, int h1, const int64_t *aoff, const float *state, int64_t N,
                           const float *noise, uint64_t seed, uint64_t counter, float *action_out, float *state_out, float *lp_scratch,
                           hipStream_t sa);
+// AgentModSAC's options on the fused step (include/erl_hip.h erl_sac_update_mod_f32); nullptr: AgentSAC's step
+struct ErlSacFusedMod {
+    int variant;               // ERL_SAC_ACTOR_*
+    int update_actor;          // 0: the two-time-scale rule skips the actor this step
+    int32_t actor_step;        // the actor optimiser's own Adam step (read when update_actor)
+    float *actor_target;       // soft-updated behind the actor's Adam step; may be NULL
+};
 int erl_sac_update_fused(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m, float *actor_v,
                          float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A, int h0, int h1, int E,
                          const int64_t *aoff, const int64_t *coff, int64_t Pa, int64_t Pc, const float *state, const float *action,
                          const float *reward, const float *undone, const float *unmask, const float *next_state, const float *is_weight,
                          float *td_error_out, int64_t B, const float *eps_next, const float *eps_cur, uint64_t seed, uint64_t counter,
                          float gamma, float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm,
-                         int32_t step, float *objs_out, float *workspace, const ErlRingSample *ring, hipStream_t s);
+                         int32_t step, float *objs_out, float *workspace, const ErlRingSample *ring, hipStream_t s,
+                         const ErlSacFusedMod *mod = nullptr);
 
 #define ERL_REQUIRE(cond, ...)                 \
     do {                                       \

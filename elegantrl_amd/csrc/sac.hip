@@ -561,6 +561,149 @@ extern "C" int erl_sac_update_per_loop_f32(float *actor_params, float *critic_pa
     return ERL_OK;
 }
 
+// ---- AgentModSAC on the fused step (include/erl_hip.h: erl_sac_update_mod_*; sac_fused.hip with ErlSacFusedMod) -------------------------
+// erl_sac_update_opt_f32 above keeps the layered step for the same options: the other arm of every A/B.
+extern "C" int erl_sac_mod_fused_supported(int S, int A, const int *hidden, int n_hidden, int E, int64_t B)
+{
+    return erl_sac_fused_supported(S, A, hidden, n_hidden, E, B) ? 1 : 0;
+}
+
+namespace {
+
+// what the three entries share; the batch pointers are the finished batch or, with a ring, the staging block the first launch fills
+struct SacModCall {
+    float *actor, *critic, *target, *alpha_log, *actor_m, *actor_v, *critic_m, *critic_v, *alpha_m, *alpha_v;
+    int S, A;
+    const int *hidden;
+    int n_hidden, E;
+    const float *state, *action, *reward, *undone, *unmask, *next_state;
+    int64_t B;
+    float gamma, target_entropy, tau, lr, beta1, beta2, eps_adam, max_norm;
+    float *actor_target;
+    void *workspace;
+    int64_t workspace_bytes;
+    void *stream;
+};
+
+// everything an entry refuses, refused before its first launch (`ring`: NULL for a finished batch; need_ids: the entry reads ring->ids)
+int sac_mod_validate(const char *what, const SacModCall &c, const ErlRingSample *ring, bool with_ring, bool need_ids, SacDims *d)
+{
+    ERL_REQUIRE(c.actor && c.critic && c.target && c.alpha_log && c.actor_m && c.actor_v && c.critic_m && c.critic_v && c.alpha_m && c.alpha_v &&
+                    c.state && c.action && c.reward && c.undone && c.unmask && c.next_state && c.workspace && c.hidden,
+                "%s: NULL tensor", what);
+    ERL_REQUIRE(erl_sac_fused_supported(c.S, c.A, c.hidden, c.n_hidden, c.E, c.B) && make_sac_dims(c.S, c.A, c.hidden, c.n_hidden, c.E, d, ERL_SAC_ACTOR_FIX),
+                "%s: S=%d A=%d n_hidden=%d E=%d B=%lld outside the fused step's shapes (two hidden layers, widths multiples of 16 in [16, 256], "
+                "S + A <= 64, A <= 8, E <= 8, B <= 4096); erl_sac_update_opt_f32 is the layered step", what, c.S, c.A, c.n_hidden, c.E, (long long)c.B);
+    ERL_REQUIRE(c.workspace_bytes >= erl_sac_workspace_bytes(c.S, c.A, c.hidden, c.n_hidden, c.E, c.B),
+                "%s: workspace of %lld bytes, erl_sac_workspace_bytes = %lld", what, (long long)c.workspace_bytes,
+                (long long)erl_sac_workspace_bytes(c.S, c.A, c.hidden, c.n_hidden, c.E, c.B));
+    if (!with_ring) return ERL_OK;
+    ERL_REQUIRE(ring && ring->buf_states && (!need_ids || ring->ids) &&
+                    (ring->row_floats || (ring->buf_actions && ring->buf_rewards && ring->buf_undones && ring->buf_unmasks)),
+                "%s: NULL ring tensor", what);
+    ERL_REQUIRE(ring->row_floats == 0 || (ring->row_floats == erl_replay_row_floats(c.S, c.A) && ring->sample_len < ring->max_size &&
+                                          (reinterpret_cast<uintptr_t>(ring->buf_states) & 15) == 0),
+                "%s: interleaved ring with row_floats=%lld (expected %lld), sample_len=%lld", what, (long long)ring->row_floats,
+                (long long)erl_replay_row_floats(c.S, c.A), (long long)ring->sample_len);
+    ERL_REQUIRE(ring->num_seqs >= 1 && ring->sample_len >= 1 && ring->sample_len <= ring->max_size,
+                "%s: bad ring shape max_size=%lld num_seqs=%lld sample_len=%lld", what, (long long)ring->max_size, (long long)ring->num_seqs,
+                (long long)ring->sample_len);
+    return ERL_OK;
+}
+
+// one validated step
+int sac_mod_enqueue(const SacModCall &c, const SacDims &d, const ErlRingSample *ring, const float *is_weight, float *td_error_out,
+                    const float *eps_next, const float *eps_cur, uint64_t seed, uint64_t counter, int32_t step, int update_actor,
+                    int32_t actor_step, float *objs_out)
+{
+    const int64_t aoff[6] = {d.actor.oW[0], d.actor.ob[0], d.actor.oW[1], d.actor.ob[1], d.actor.oW[2], d.actor.ob[2]};
+    const int64_t coff[8] = {d.enc.oW[0], d.enc.ob[0], d.enc.count, d.dec.oW[0], d.dec.ob[0], d.dec.oW[1], d.dec.ob[1], d.dec.count};
+    const ErlSacFusedMod mod{ERL_SAC_ACTOR_FIX, update_actor, actor_step, c.actor_target};
+    return erl_sac_update_fused(c.actor, c.critic, c.target, c.alpha_log, c.actor_m, c.actor_v, c.critic_m, c.critic_v, c.alpha_m, c.alpha_v, c.S, c.A,
+                                c.hidden[0], c.hidden[1], c.E, aoff, coff, d.Pa, d.Pc, c.state, c.action, c.reward, c.undone, c.unmask, c.next_state,
+                                is_weight, td_error_out, c.B, eps_next, eps_cur, seed, counter, c.gamma, c.target_entropy, c.tau, c.lr, c.beta1,
+                                c.beta2, c.eps_adam, c.max_norm, step, objs_out, (float *)c.workspace, ring, (hipStream_t)c.stream, &mod);
+}
+
+}  // namespace
+
+extern "C" int erl_sac_update_mod_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
+                                      float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
+                                      const int *hidden, int n_hidden, int E, const float *state, const float *action, const float *reward,
+                                      const float *undone, const float *unmask, const float *next_state, const float *is_weight,
+                                      float *td_error_out, int64_t B, const float *eps_next, const float *eps_cur, uint64_t seed,
+                                      uint64_t counter, float gamma, float target_entropy, float tau, float lr, float beta1, float beta2,
+                                      float eps_adam, float max_norm, int32_t step, int32_t update_actor, int32_t actor_step,
+                                      float *actor_target_params, float *objs_out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const SacModCall c{actor_params, critic_params, target_params, alpha_log, actor_m, actor_v, critic_m, critic_v, alpha_m, alpha_v, S, A, hidden,
+                       n_hidden, E, state, action, reward, undone, unmask, next_state, B, gamma, target_entropy, tau, lr, beta1, beta2, eps_adam,
+                       max_norm, actor_target_params, workspace, workspace_bytes, stream};
+    SacDims d;
+    ERL_REQUIRE(objs_out, "erl_sac_update_mod_f32: NULL tensor");
+    if (int rc = sac_mod_validate("erl_sac_update_mod_f32", c, nullptr, false, false, &d)) return rc;
+    ERL_REQUIRE(step >= 1 && actor_step >= 0 && (!update_actor || actor_step >= 1), "erl_sac_update_mod_f32: step=%d actor_step=%d update_actor=%d",
+                (int)step, (int)actor_step, (int)update_actor);
+    return sac_mod_enqueue(c, d, nullptr, is_weight, td_error_out, eps_next, eps_cur, seed, counter, step, update_actor != 0, actor_step, objs_out);
+}
+
+extern "C" int erl_sac_update_mod_ring_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
+                                           float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
+                                           const int *hidden, int n_hidden, int E, const ErlRingSample *ring, float *state, float *action,
+                                           float *reward, float *undone, float *unmask, float *next_state, int64_t B, const float *eps_next,
+                                           const float *eps_cur, uint64_t seed, uint64_t counter, float gamma, float target_entropy, float tau,
+                                           float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step, int32_t update_actor,
+                                           int32_t actor_step, float *actor_target_params, float *objs_out, void *workspace,
+                                           int64_t workspace_bytes, void *stream)
+{
+    const SacModCall c{actor_params, critic_params, target_params, alpha_log, actor_m, actor_v, critic_m, critic_v, alpha_m, alpha_v, S, A, hidden,
+                       n_hidden, E, state, action, reward, undone, unmask, next_state, B, gamma, target_entropy, tau, lr, beta1, beta2, eps_adam,
+                       max_norm, actor_target_params, workspace, workspace_bytes, stream};
+    SacDims d;
+    ERL_REQUIRE(objs_out, "erl_sac_update_mod_ring_f32: NULL tensor");
+    if (int rc = sac_mod_validate("erl_sac_update_mod_ring_f32", c, ring, true, true, &d)) return rc;
+    ERL_REQUIRE(step >= 1 && actor_step >= 0 && (!update_actor || actor_step >= 1), "erl_sac_update_mod_ring_f32: step=%d actor_step=%d update_actor=%d",
+                (int)step, (int)actor_step, (int)update_actor);
+    return sac_mod_enqueue(c, d, ring, nullptr, nullptr, eps_next, eps_cur, seed, counter, step, update_actor != 0, actor_step, objs_out);
+}
+
+// AgentModSAC.update_objectives' loop in AgentBase.update_net (AgentSAC.py:113-165): the two-time-scale rule needs nothing from the device
+// (the reference never moves critic_value), so it is evaluated here, in double precision as the interpreter does
+extern "C" int erl_sac_update_mod_ring_loop_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
+                                                float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
+                                                const int *hidden, int n_hidden, int E, const ErlRingSample *ring, const int64_t *ids_all,
+                                                int64_t n_steps, float *state, float *action, float *reward, float *undone, float *unmask,
+                                                float *next_state, int64_t B, uint64_t seed, uint64_t counter0, float gamma, float target_entropy,
+                                                float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step0,
+                                                int32_t actor_step0, double critic_value, float *actor_target_params, float *objs_all,
+                                                int32_t *actor_updates_out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const SacModCall c{actor_params, critic_params, target_params, alpha_log, actor_m, actor_v, critic_m, critic_v, alpha_m, alpha_v, S, A, hidden,
+                       n_hidden, E, state, action, reward, undone, unmask, next_state, B, gamma, target_entropy, tau, lr, beta1, beta2, eps_adam,
+                       max_norm, actor_target_params, workspace, workspace_bytes, stream};
+    SacDims d;
+    ERL_REQUIRE(ids_all && objs_all, "erl_sac_update_mod_ring_loop_f32: NULL tensor");
+    if (int rc = sac_mod_validate("erl_sac_update_mod_ring_loop_f32", c, ring, true, false, &d)) return rc;
+    ERL_REQUIRE(step0 >= 1 && actor_step0 >= 0 && n_steps >= 0 && n_steps < (1LL << 31) - step0 && n_steps < (1LL << 31) - actor_step0 &&
+                    critic_value == critic_value,
+                "erl_sac_update_mod_ring_loop_f32: n_steps=%lld step0=%d actor_step0=%d critic_value=%g", (long long)n_steps, (int)step0,
+                (int)actor_step0, critic_value);
+    const double reliable_lambda = exp(-(critic_value * critic_value));              // (:148)
+    const double bound = 1.0 / (2.0 - reliable_lambda);
+    int32_t update_a = 0, actor_step = actor_step0;
+    for (int64_t t = 0; t < n_steps; ++t) {
+        const bool upd = (double)update_a / (double)(t + 1) < bound;                  // (:151)
+        if (upd) { ++update_a; ++actor_step; }
+        ErlRingSample r = *ring;
+        r.ids = ids_all + t * B;
+        const int rc = sac_mod_enqueue(c, d, &r, nullptr, nullptr, nullptr, nullptr, seed, counter0 + (uint64_t)t, step0 + (int32_t)t, upd,
+                                       actor_step, objs_all + 2 * t);
+        if (rc) return rc;
+    }
+    if (actor_updates_out) *actor_updates_out = update_a;
+    return ERL_OK;
+}
+
 static int sac_update_impl(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
                            float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
                            const int *hidden, int n_hidden, int E, const float *state, const float *action,
@@ -590,7 +733,8 @@ static int sac_update_impl(float *actor_params, float *critic_params, float *tar
     // Off-policy batch sizes with two hidden layers up to 256 wide (config 3): the fused step, 12 launches (sac_fused.hip).
     // ERL_SAC_FUSED=0 keeps the layered step below (A/B runs); lambda_fit_cum_r != 0 (off by default) is layered only.
     static const bool fused_on = [] { const char *e = getenv("ERL_SAC_FUSED"); return !(e && atoi(e) == 0); }();
-    // (the fused step implements ActorSAC's head with every optimiser on one step count: AgentModSAC's options take the layered step)
+    // (AgentModSAC's options take the layered step here: this entry is the other arm of every A/B against erl_sac_update_mod_f32, the
+    // same options on the fused step)
     const bool plain = variant == ERL_SAC_ACTOR_SAC && update_actor && actor_step == step && !actor_target;
     if (fused_on && plain && lambda_fit_cum_r == 0.f && erl_sac_fused_supported(S, A, hidden, n_hidden, E, B)) {
         const int64_t aoff[6] = {d.actor.oW[0], d.actor.ob[0], d.actor.oW[1], d.actor.ob[1], d.actor.oW[2], d.actor.ob[2]};

@@ -36,6 +36,9 @@
 // actor_fwd's prologue when the caller hands over the ring (erl_sac_update_ring_f32).  Every launch goes to the caller's stream: nine at
 // config 3, where the policy-gradient sample's forward rides in launch (1) (actor_fwd_pair_kernel).  The same tile code, looped over H steps with the actor's weights kept in registers /
 // LDS, is the persistent off-policy rollout (sac_rollout_synenv_kernel).
+// AgentModSAC (AgentSAC.py:89-165) runs the same launches with ActorFixSAC as a run-time variant of the actor kernels (ActorFwdArgs::variant)
+// and ErlSacFusedMod's options: the actor's own Adam count, its target's soft update behind that step, and -- on the steps its two-time-scale
+// rule skips -- one small launch (sac_skip_finish_kernel) in place of launches (7)-(10).
 #include "mlpn_common.h"
 
 #include <mutex>
@@ -414,6 +417,10 @@ struct ActorFwdArgs {
     float *H0, *G0, *H1, *G1;      // keep: activations / GELU' for the backward pass and the weight gradients
     const float *alpha_log;        // first call of a step: the temperature BEFORE its update is parked in alpha0 (q_label uses it)
     float *alpha0;
+    // ERL_SAC_ACTOR_FIX: ActorFixSAC (AgentSAC.py:201-243) -- the second hidden layer is raw (H1 = the pre-activation, G1 = 1), log_std
+    // is clamped to [-20, 2], the log-prob is taken AT the sample with the tanh correction in its softplus form.  A run-time,
+    // wavefront-uniform value: the kernels are not instantiated per variant.
+    int variant;
 };
 
 template <int C0, int C1>
@@ -501,7 +508,7 @@ __device__ __forceinline__ void actor_fwd_body(const ActorFwdArgs &g, TileLds &l
     FPROF(0, 4);
     layer_fwd_mma<WClass<C0>::KT, WClass<C1>::NU, true>(w2, g.P + d.ab2 + fo, d.h0, d.h1, lds.T1, L, z);
     FPROF(0, 5);
-    emit_hidden(z, d.h1, true, lds.T0, gk, g.H1 ? g.H1 + fo : nullptr, g.G1 ? g.G1 + fo : nullptr, row, valid, L, h1f);   // (a slice keeps its columns of the full-width matrices)
+    emit_hidden(z, d.h1, g.variant != ERL_SAC_ACTOR_FIX, lds.T0, gk, g.H1 ? g.H1 + fo : nullptr, g.G1 ? g.G1 + fo : nullptr, row, valid, L, h1f);   // (a slice keeps its columns of the full-width matrices)
     lds_barrier();
     FPROF(0, 6);
     layer_small_mma<false, true>(wh, fo == 0 ? g.P + d.abh : nullptr, d.h1, 2 * d.A, lds.T0, lds.part, lds.Yl, L);
@@ -556,17 +563,27 @@ __device__ __forceinline__ void actor_fwd_body(const ActorFwdArgs &g, TileLds &l
         const int64_t b = row0 + L.tid;
         if (b < d.B) {
             const int A = d.A;
+            const bool fix = g.variant == ERL_SAC_ACTOR_FIX;
             float lp = 0.f;
             for (int a = 0; a < A; ++a) {
                 const float mean = lds.Yl[L.tid * 16 + a], ls = lds.Yl[L.tid * 16 + A + a];
-                const float lsc = fminf(fmaxf(ls, -16.f), 2.f);
+                const float lsc = fminf(fmaxf(ls, fix ? -20.f : -16.f), 2.f);
                 const float sd = expf(lsc);
                 const float eps = g.noise ? g.noise[b * A + a] : philox_normal(g.seed, g.counter, (uint32_t)b, (uint32_t)a);
-                const float t = tanhf(mean + sd * eps);
+                const float u = mean + sd * eps;
+                const float t = tanhf(u);
                 g.act_t[b * A + a] = t;
                 if (g.eps_out) g.eps_out[b * A + a] = eps;
                 if (g.Y) { g.Y[b * 2 * A + a] = mean; g.Y[b * 2 * A + A + a] = ls; }
-                lp += (-logf(sd) - kLogSqrt2PiF2) - logf(-(t * t) + 1.000001f);
+                if (fix) {
+                    // ActorFixSAC.get_action_logprob (head_forward_kernel, sac.hip): -log_std - eps^2 / 2 - log sqrt(2 pi), and the tanh
+                    // correction -(log 2 - u - softplus(-2 u)) * 2 (nn.Softplus: beta 1, threshold 20)
+                    const float x = -2.f * u;
+                    const float sp = x > 20.f ? x : log1pf(expf(x));
+                    lp += (-lsc - (eps * eps) * 0.5f - kLogSqrt2PiF2) - (0.69314718055994530942f - u - sp) * 2.f;
+                } else {
+                    lp += (-logf(sd) - kLogSqrt2PiF2) - logf(-(t * t) + 1.000001f);
+                }
             }
             g.lp[b] = lp;
         }
@@ -930,6 +947,7 @@ struct ActorBwdArgs {
     // (head backward, dZ2) is small and done by every slice, stored by slice 0.
     int split, h0_full;
     float *objs_out;
+    int variant;                             // ERL_SAC_ACTOR_FIX: ActorFixSAC's head (ActorFwdArgs::variant); its G1 is all ones
 };
 
 template <int C0, int C1>
@@ -985,16 +1003,21 @@ __global__ __launch_bounds__(FT) void actor_bwd_kernel(ActorBwdArgs g)
         if (b < B) {
             const float alpha = expf(g.alpha_log[0]);
             const float dlp = alpha / (float)B;
+            const bool fix = g.variant == ERL_SAC_ACTOR_FIX;
+            const float lo = fix ? -20.f : -16.f;
             for (int a = 0; a < A; ++a) {
                 const float ls = g.Y[b * 2 * A + A + a];
-                const float lsc = fminf(fmaxf(ls, -16.f), 2.f);
+                const float lsc = fminf(fmaxf(ls, lo), 2.f);
                 const float sd = expf(lsc);
                 const float t = g.act_t[b * A + a];
                 const float one_m = 1.f - t * t;
                 const float *dp = dal + (L.tid * 8 + a) * 4;
                 const float dA = ((dp[0] + dp[1]) + dp[2]) + dp[3];
-                const float du = dA * one_m + dlp * (2.f * t * one_m / (one_m + 1e-6f));
-                const bool inside = ls >= -16.f && ls <= 2.f;
+                // d logprob / du: ActorFixSAC -2 d/du (log 2 - u - softplus(-2 u)) = 2 tanh(u); its eps^2 / 2 term has no gradient
+                float du;
+                if (fix) du = dA * one_m + dlp * (2.f * t);
+                else du = dA * one_m + dlp * (2.f * t * one_m / (one_m + 1e-6f));
+                const bool inside = ls >= lo && ls <= 2.f;
                 const float dls = inside ? du * sd * g.eps[b * A + a] - dlp : 0.f;
                 lds.T0[L.tid * LDT + a] = du;
                 lds.T0[L.tid * LDT + A + a] = dls;
@@ -1038,6 +1061,47 @@ __global__ __launch_bounds__(FT) void actor_bwd_kernel(ActorBwdArgs g)
                     make_float4(dx[u][0] * gate.x, dx[u][1] * gate.y, dx[u][2] * gate.z, dx[u][3] * gate.w);
             }
         }
+    }
+}
+
+// The step on which AgentModSAC's two-time-scale rule skips the actor (ErlSacFusedMod::update_actor == 0) ends here instead of in
+// launches (7)-(10): the critic objective from the training pass's q and labels -- per tile what launch (7) computes, added in tile
+// order as actor_bwd_kernel does --, td_error_out, obj_actor = nan (AgentSAC.py:158) and the temperature's clamp (:146-147).
+// One workgroup of 16 waves; wave w takes the tiles w, w + 16, ...
+struct SkipFinishArgs {
+    const float *qc, *label, *unmask, *is_weight;      // [E][B], (B,), (B,), (B,) or NULL
+    float *td_out, *objs_out, *alpha_log;               // (B,) or NULL, [2], [1]
+    int E, ntiles;
+    int64_t B;
+};
+__global__ __launch_bounds__(1024) void sac_skip_finish_kernel(SkipFinishArgs g)
+{
+    __shared__ float tdl[256];                          // B <= 4096: at most 256 tiles
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int tile = wave; tile < g.ntiles; tile += 16) {
+        const int64_t b = (int64_t)tile * TS + lane;
+        float td = 0.f;
+        if (lane < TS && b < g.B) {
+            const float lab = g.label[b];
+            float s2 = 0.f;
+            for (int k = 0; k < g.E; ++k) {
+                const float diff = g.qc[(size_t)k * g.B + b] - lab;
+                s2 += diff * diff;
+            }
+            td = (s2 / (float)g.E) * g.unmask[b];
+            if (g.td_out) g.td_out[b] = td;
+            td *= g.is_weight ? g.is_weight[b] : 1.f;
+        }
+        td = wave_sum(td);
+        if (lane == 0) tdl[tile] = td;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int t = 0; t < g.ntiles; ++t) s += tdl[t];
+        g.objs_out[0] = s / (float)g.B;
+        g.objs_out[1] = __builtin_nanf("");
+        g.alpha_log[0] = fminf(fmaxf(g.alpha_log[0], -16.f), 2.f);
     }
 }
 
@@ -1627,8 +1691,9 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
                          const float *reward, const float *undone, const float *unmask, const float *next_state, const float *is_weight,
                          float *td_error_out, int64_t B, const float *eps_next, const float *eps_cur, uint64_t seed, uint64_t counter,
                          float gamma, float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm,
-                         int32_t step, float *objs_out, float *workspace, const ErlRingSample *ring, hipStream_t s)
+                         int32_t step, float *objs_out, float *workspace, const ErlRingSample *ring, hipStream_t s, const ErlSacFusedMod *mod)
 {
+    const int variant = mod ? mod->variant : ERL_SAC_ACTOR_SAC;
     FusedDims d{};
     d.S = S; d.A = A; d.E = E; d.h0 = h0; d.h1 = h1; d.B = B;
     d.aW1 = aoff[0]; d.ab1 = aoff[1]; d.aW2 = aoff[2]; d.ab2 = aoff[3]; d.aWh = aoff[4]; d.abh = aoff[5];
@@ -1663,7 +1728,7 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
     // ---- (1) next action / log-prob (actor on next_state)                                                      (:50-51)
     ActorFwdArgs af{};
     af.P = actor_params; af.d = d; af.X = next_state; af.noise = eps_next; af.seed = seed; af.counter = 2 * counter;
-    af.act_t = a_next; af.lp = lp_next; af.alpha_log = alpha_log; af.alpha0 = alpha0;
+    af.act_t = a_next; af.lp = lp_next; af.alpha_log = alpha_log; af.alpha0 = alpha0; af.variant = variant;
     if (ring) {
         // the replay sample rides in this launch: the batch pointers are the staging block it fills (sac.hip erl_sac_update_ring_f32)
         af.rg = *ring;
@@ -1754,6 +1819,15 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
                                                step, lr, beta1, beta2, eps_adam, max_norm, target_params, tau, s)))
             return rc;
     }
+    if (mod && !mod->update_actor) {
+        // AgentModSAC skips the actor this step (AgentSAC.py:152-158): no policy-gradient pass, no actor backward, weight gradients,
+        // clip + Adam or actor-target update -- actor_params, its moments and the actor target are not touched
+        SkipFinishArgs sf{};
+        sf.qc = qc; sf.label = label; sf.unmask = unmask; sf.is_weight = is_weight; sf.td_out = td_error_out; sf.objs_out = objs_out;
+        sf.alpha_log = alpha_log; sf.E = E; sf.ntiles = tiles; sf.B = B;
+        hipLaunchKernelGGL(sac_skip_finish_kernel, dim3(1), dim3(1024), 0, s, sf);
+        return erl_hip_status(hipGetLastError(), "erl_sac_update_mod_f32(fused: skipped actor)");
+    }
     // ---- (7) TARGET ensemble on (state, action_pg): q and d(mean q)/d(action); finishes the critic objective    (:82-83)
     cg = dim3(tiles, E * split);
     ca.d = dsl; ca.split = split; ca.qt_split = 1;
@@ -1765,7 +1839,7 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
         ActorBwdArgs ab{};
         ab.P = actor_params; ab.d = d; ab.Y = Y; ab.act_t = act_pg; ab.eps = eps_used; ab.dAct = dAct; ab.alpha_log = alpha_log; ab.G0 = G0;
         ab.G1 = G1; ab.lp_cur = lp_cur; ab.dY = dY; ab.dZ2 = dZ2; ab.dZ1 = dZ1; ab.tdpart = tdpart; ab.qpart = qpart; ab.ntiles = tiles; ab.nsplit = split;
-        ab.objs_out = objs_out;
+        ab.objs_out = objs_out; ab.variant = variant;
         // (the one heavy layer of this pass, dH0 = W2^T dZ2, is output-split over kCritSplit workgroups per tile like the critic passes above)
         const int bsplit = (h0 == 64 * kCritSplit && tiles * kCritSplit <= 256) ? kCritSplit : 1;
         ab.split = bsplit; ab.h0_full = h0; ab.d.h0 = h0 / bsplit;
@@ -1780,8 +1854,10 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
         dw.clamp_alpha_log = alpha_log;        // (one launch less than a kernel of its own: ~5 us of a 230 us step)
         dw.norm_parts = nparts_a;
         if ((rc = dw_launch(dw, s))) return rc;
-        if ((rc = erl_clip_adam_parts_soft_f32(actor_params, g_actor, actor_m, actor_v, Pa, nparts_a, dw.p[dw.np - 1].tile0 + dw.p[dw.np - 1].ntiles, step,
-                                               lr, beta1, beta2, eps_adam, max_norm, nullptr, 0.f, s)))
+        // (AgentModSAC: the actor optimiser's own step count, and soft_update(act_target, act) behind its step, AgentSAC.py:156)
+        if ((rc = erl_clip_adam_parts_soft_f32(actor_params, g_actor, actor_m, actor_v, Pa, nparts_a, dw.p[dw.np - 1].tile0 + dw.p[dw.np - 1].ntiles,
+                                               mod ? mod->actor_step : step, lr, beta1, beta2, eps_adam, max_norm, mod ? mod->actor_target : nullptr,
+                                               mod ? tau : 0.f, s)))
             return rc;
     }
     return erl_hip_status(hipGetLastError(), "erl_sac_update_f32(fused)");

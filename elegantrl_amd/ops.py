@@ -850,6 +850,90 @@ def sac_update_ring_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, al
           "erl_sac_update_ring_loop_f32")
 
 
+def sac_mod_fused_supported(spec: SacSpec, B: int) -> bool:
+    """the fused AgentModSAC step (erl_sac_update_mod_*) covers this shape (erl_sac_mod_fused_supported)"""
+    return bool(lib().erl_sac_mod_fused_supported(spec.S, spec.A, spec._c, len(spec.hidden), spec.E, int(B)))
+
+
+def _ring_sample(spec: SacSpec, ring, ids: Optional[TEN], sample_len: int, stage: ReplayStage, B: int):
+    """(ErlRingSample, device) of a ReplayRing (interleaved block) or of the five planar tensors"""
+    f32 = th.float32
+    if isinstance(ring, ReplayRing):
+        assert stage.B == B and not stage.discrete and (ring.S, ring.A) == (spec.S, spec.A)
+        return _RingSample(ptr(ring.block, f32), None, None, None, None, ring.max_size, ring.num_seqs, ptr(ids, th.int64), int(sample_len),
+                           stage.p_ids0, stage.p_ids1, ring.row_floats), ring.block.device
+    b_states, b_actions, b_rewards, b_undones, b_unmasks = ring
+    max_size, num_seqs, S = b_states.shape
+    assert stage.B == B and not stage.discrete and b_actions.dtype == th.float32
+    return _RingSample(ptr(b_states, f32), ptr(b_actions, f32), ptr(b_rewards, f32), ptr(b_undones, f32), ptr(b_unmasks, f32), max_size, num_seqs,
+                       ptr(ids, th.int64), int(sample_len), stage.p_ids0, stage.p_ids1, 0), b_states.device
+
+
+def sac_update_mod(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], batch: Sequence[TEN],
+                   step: int, *, gamma: float, target_entropy: float, tau: float, lr: float, max_norm: float, objs_out: TEN,
+                   update_actor: bool, actor_step: int, actor_target: Optional[TEN], noises: Optional[Tuple[TEN, TEN]] = None, seed: int = 0,
+                   counter: int = 0, betas=(0.9, 0.999), eps: float = 1e-8, is_weight: Optional[TEN] = None,
+                   td_error_out: Optional[TEN] = None) -> None:
+    """one AgentModSAC.update_objectives step after the sample on the FUSED step (erl_sac_update_mod_f32): sac_update's arguments without
+    the cum_reward term; `update_actor` False leaves the actor, its moments and `actor_target` untouched and writes nan to objs_out[1]"""
+    state, action, reward, undone, unmask, next_state = batch
+    B = state.shape[0]
+    ws = _workspace(state.device, spec.workspace_bytes(B))
+    n_next, n_cur = (None, None) if noises is None else noises
+    f32 = th.float32
+    check(lib().erl_sac_update_mod_f32(ptr(actor, f32), ptr(critic, f32), ptr(target, f32), ptr(alpha_log, f32), *[ptr(m, f32) for m in moments],
+                                       spec.S, spec.A, spec._c, len(spec.hidden), spec.E, ptr(state, f32), ptr(action, f32), ptr(reward, f32),
+                                       ptr(undone, f32), ptr(unmask, f32), ptr(next_state, f32), ptr(is_weight), ptr(td_error_out), B, ptr(n_next),
+                                       ptr(n_cur), seed & (2 ** 64 - 1), counter & (2 ** 64 - 1), gamma, target_entropy, tau, lr, betas[0],
+                                       betas[1], eps, max_norm, step, int(bool(update_actor)), int(actor_step), ptr(actor_target, f32),
+                                       ptr(objs_out, f32), ptr(ws), ws.numel(), stream_ptr()),
+          "erl_sac_update_mod_f32")
+
+
+def sac_update_mod_from_ring(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring, ids: TEN,
+                             sample_len: int, stage: ReplayStage, step: int, *, gamma: float, target_entropy: float, tau: float, lr: float,
+                             max_norm: float, objs_out: TEN, update_actor: bool, actor_step: int, actor_target: Optional[TEN],
+                             noises: Optional[Tuple[TEN, TEN]] = None, seed: int = 0, counter: int = 0, betas=(0.9, 0.999),
+                             eps: float = 1e-8) -> None:
+    """sac_update_from_ring for AgentModSAC's fused step (erl_sac_update_mod_ring_f32): the sample rides in the step's first launch"""
+    B = ids.numel()
+    f32 = th.float32
+    rs, dev = _ring_sample(spec, ring, ids, sample_len, stage, B)
+    ws = _workspace(dev, spec.workspace_bytes(B))
+    n_next, n_cur = (None, None) if noises is None else noises
+    check(lib().erl_sac_update_mod_ring_f32(ptr(actor, f32), ptr(critic, f32), ptr(target, f32), ptr(alpha_log, f32), *[ptr(m, f32) for m in moments],
+                                            spec.S, spec.A, spec._c, len(spec.hidden), spec.E, ctypes.addressof(rs), stage.p_state, stage.p_action,
+                                            stage.p_reward, stage.p_undone, stage.p_unmask, stage.p_next, B, ptr(n_next), ptr(n_cur),
+                                            seed & (2 ** 64 - 1), counter & (2 ** 64 - 1), gamma, target_entropy, tau, lr, betas[0], betas[1], eps,
+                                            max_norm, step, int(bool(update_actor)), int(actor_step), ptr(actor_target, f32), ptr(objs_out, f32),
+                                            ptr(ws), ws.numel(), stream_ptr()),
+          "erl_sac_update_mod_ring_f32")
+
+
+def sac_update_mod_ring_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring, ids_all: TEN,
+                             sample_len: int, stage: ReplayStage, step0: int, actor_step0: int, critic_value: float, *, gamma: float,
+                             target_entropy: float, tau: float, lr: float, max_norm: float, objs_all: TEN, actor_target: Optional[TEN],
+                             seed: int = 0, counter0: int = 0, betas=(0.9, 0.999), eps: float = 1e-8) -> int:
+    """AgentModSAC's whole update_net loop from ONE C call (erl_sac_update_mod_ring_loop_f32): step t = sac_update_mod_from_ring on
+    ids_all[t], optimiser step step0 + t, noise counter counter0 + t, objs_all[t]; the two-time-scale rule is evaluated in C, the actor's
+    Adam count runs on from `actor_step0`.  Returns the number of actor updates."""
+    T, B = ids_all.shape
+    f32 = th.float32
+    assert ids_all.is_contiguous() and objs_all.shape == (T, 2) and objs_all.is_contiguous()
+    rs, dev = _ring_sample(spec, ring, None, sample_len, stage, B)
+    ws = _workspace(dev, spec.workspace_bytes(B))
+    updates = ctypes.c_int32(0)
+    check(lib().erl_sac_update_mod_ring_loop_f32(ptr(actor, f32), ptr(critic, f32), ptr(target, f32), ptr(alpha_log, f32),
+                                                 *[ptr(m, f32) for m in moments], spec.S, spec.A, spec._c, len(spec.hidden), spec.E,
+                                                 ctypes.addressof(rs), ptr(ids_all, th.int64), T, stage.p_state, stage.p_action, stage.p_reward,
+                                                 stage.p_undone, stage.p_unmask, stage.p_next, B, seed & (2 ** 64 - 1), counter0 & (2 ** 64 - 1),
+                                                 gamma, target_entropy, tau, lr, betas[0], betas[1], eps, max_norm, int(step0), int(actor_step0),
+                                                 float(critic_value), ptr(actor_target, f32), ptr(objs_all, f32), ctypes.byref(updates), ptr(ws),
+                                                 ws.numel(), stream_ptr()),
+          "erl_sac_update_mod_ring_loop_f32")
+    return int(updates.value)
+
+
 class _PerSample(ctypes.Structure):         # include/erl_hip.h ErlPerSample
     _fields_ = [("sum_tree", ctypes.c_void_p), ("min_tree", ctypes.c_void_p), ("max_size", ctypes.c_int64), ("num_seqs", ctypes.c_int64),
                 ("cur_size", ctypes.c_int64), ("cursor", ctypes.c_int64), ("per_alpha", ctypes.c_float), ("per_beta", ctypes.c_float),

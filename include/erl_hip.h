@@ -760,6 +760,51 @@ ERL_API int erl_sac_update_opt_f32(float *actor_params, float *critic_params, fl
                            float gamma, float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam,
                            float max_norm, int32_t step, float *objs_out, void *workspace, int64_t workspace_bytes,
                            const ErlSacOptions *opt, void *stream);
+/* AgentModSAC on the FUSED step (sac_fused.hip: the tile kernels of erl_sac_update_f32 with ActorFixSAC's encoder and head as a run-time
+ * variant).  Additions to ABI 22; erl_sac_update_opt_f32 above keeps the layered step and is the other arm of every A/B.
+ *   erl_sac_mod_fused_supported   1 for the fused step's shapes: two hidden layers, widths multiples of 16 in [16, 256], S + A <= 64,
+ *                                 A <= 8, E <= 8, B <= 4096 (a pure function of the shape: no environment switch is read)
+ *   erl_sac_update_mod_f32        one step on a finished batch: erl_sac_update_opt_f32's arguments without cum_reward / lambda_fit_cum_r
+ *                                 (that term stays layered), ErlSacOptions' fields passed explicitly.  update_actor == 0: the critic and
+ *                                 the temperature step as always, objs_out[0] and td_error_out are written, alpha_log is clamped,
+ *                                 objs_out[1] = nan; actor_params, actor_m, actor_v and actor_target_params are not touched.  Otherwise
+ *                                 the actor's clip + Adam counts actor_step (>= 1) and, with actor_target_params not NULL, the same
+ *                                 launch does soft_update(act_target, act, tau) (:156)
+ *   erl_sac_update_mod_ring_f32   the same with ReplayBuffer.sample inside the first launch, as erl_sac_update_ring_f32
+ *   erl_sac_update_mod_ring_loop_f32   AgentModSAC's whole update_net loop (:113-165): step t is what erl_sac_update_mod_ring_f32 enqueues
+ *                                 with ids_all[t], optimiser step step0 + t, noise counter counter0 + t, objs_all[2 t ..].  The two-time-scale
+ *                                 rule (:150-152) is evaluated on the host in double precision: update_a = 0 at t = 0;
+ *                                 do = update_a / (t + 1) < 1 / (2 - exp(-critic_value^2)); on `do`, update_a and the running actor
+ *                                 step (from actor_step0 >= 0) advance before the step uses them.  *actor_updates_out (host memory,
+ *                                 may be NULL) receives update_a.
+ * Every entry validates everything -- NULL tensors, the shape, the workspace (erl_sac_workspace_bytes), the ring, n_steps >= 0,
+ * step0 >= 1, actor_step0 >= 0 -- before its first launch; none allocates or synchronises the host. */
+ERL_API int erl_sac_mod_fused_supported(int S, int A, const int *hidden, int n_hidden, int E, int64_t B);
+ERL_API int erl_sac_update_mod_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log,
+                           float *actor_m, float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v,
+                           int S, int A, const int *hidden, int n_hidden, int E, const float *state, const float *action,
+                           const float *reward, const float *undone, const float *unmask, const float *next_state,
+                           const float *is_weight, float *td_error_out, int64_t B, const float *eps_next, const float *eps_cur,
+                           uint64_t seed, uint64_t counter, float gamma, float target_entropy, float tau, float lr, float beta1,
+                           float beta2, float eps_adam, float max_norm, int32_t step, int32_t update_actor, int32_t actor_step,
+                           float *actor_target_params, float *objs_out, void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_sac_update_mod_ring_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log,
+                                float *actor_m, float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v,
+                                int S, int A, const int *hidden, int n_hidden, int E, const ErlRingSample *ring, float *state,
+                                float *action, float *reward, float *undone, float *unmask, float *next_state, int64_t B,
+                                const float *eps_next, const float *eps_cur, uint64_t seed, uint64_t counter, float gamma,
+                                float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm,
+                                int32_t step, int32_t update_actor, int32_t actor_step, float *actor_target_params, float *objs_out,
+                                void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_sac_update_mod_ring_loop_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log,
+                                     float *actor_m, float *actor_v, float *critic_m, float *critic_v, float *alpha_m,
+                                     float *alpha_v, int S, int A, const int *hidden, int n_hidden, int E,
+                                     const ErlRingSample *ring, const int64_t *ids_all, int64_t n_steps, float *state, float *action,
+                                     float *reward, float *undone, float *unmask, float *next_state, int64_t B, uint64_t seed,
+                                     uint64_t counter0, float gamma, float target_entropy, float tau, float lr, float beta1,
+                                     float beta2, float eps_adam, float max_norm, int32_t step0, int32_t actor_step0,
+                                     double critic_value, float *actor_target_params, float *objs_all, int32_t *actor_updates_out,
+                                     void *workspace, int64_t workspace_bytes, void *stream);
 /* The off-policy rollout of AgentBase._explore_vec_env (elegantrl/agents/AgentBase.py:130-170) on the device-resident SynVecEnv as ONE
  * launch: H x [ActorSAC.get_action (AgentSAC.py:179-185), states[t] = state, actions[t] = action, env.step, reward / flag stores], then
  * `rewards *= reward_scale` and the two logical_not -- out_undones / out_unmasks are !terminal / !truncate.  A 16-env tile per workgroup
