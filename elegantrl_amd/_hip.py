@@ -29,6 +29,13 @@ COMM_ID_BYTES = 128
 P2P_HANDLE_BYTES = 64
 
 _P = c_void_p
+# what the erl_sac_update_* prototypes share (include/erl_hip.h), in the order they name it
+_SAC_HEAD = [_P] * 10 + [c_int, c_int, POINTER(c_int), c_int, c_int]     # parameter blocks + moments, S, A, hidden, n_hidden, E
+_SAC_BATCH = [_P] * 6                                                    # state, action, reward, undone, unmask, next_state
+_SAC_KEY = [c_uint64, c_uint64]                                          # seed, counter
+_SAC_NOISE = [_P, _P] + _SAC_KEY                                         # eps_next, eps_cur, seed, counter
+_SAC_HYPER = [c_float] * 8                                               # gamma, target_entropy, tau, lr, beta1, beta2, eps_adam, max_norm
+_SAC_TAIL = [_P, c_int64, _P]                                            # workspace, workspace_bytes, stream
 _SIGNATURES = {
     # name: (restype, argtypes)
     "erl_abi_version": (c_int, []),
@@ -131,24 +138,17 @@ _SIGNATURES = {
                                                c_int64, _P, c_int64, c_float, c_float, c_float, _P, _P, c_int64, _P]),
     "erl_sac_param_counts": (c_int, [c_int, c_int, POINTER(c_int), c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
     "erl_sac_workspace_bytes": (c_int64, [c_int, c_int, POINTER(c_int), c_int, c_int, c_int64]),
-    "erl_sac_update_f32": (c_int, [_P] * 10 + [c_int, c_int, POINTER(c_int), c_int, c_int] + [_P] * 9 + [c_float, c_int64, _P, _P, c_uint64,
-                                   c_uint64] + [c_float] * 8 + [c_int32, _P, _P, c_int64, _P]),
-    "erl_sac_update_opt_f32": (c_int, [_P] * 10 + [c_int, c_int, POINTER(c_int), c_int, c_int] + [_P] * 9 + [c_float, c_int64, _P, _P, c_uint64,
-                                       c_uint64] + [c_float] * 8 + [c_int32, _P, _P, c_int64, _P, _P]),
-    "erl_sac_update_ring_f32": (c_int, [_P] * 10 + [c_int, c_int, POINTER(c_int), c_int, c_int, _P] + [_P] * 6 + [c_int64, _P, _P, c_uint64,
-                                        c_uint64] + [c_float] * 8 + [c_int32, _P, _P, c_int64, _P]),
-    "erl_sac_update_ring_loop_f32": (c_int, [_P] * 10 + [c_int, c_int, POINTER(c_int), c_int, c_int, _P, _P, c_int64] + [_P] * 6 + [c_int64, c_uint64,
-                                             c_uint64] + [c_float] * 8 + [c_int32, _P, _P, c_int64, _P]),
-    "erl_sac_update_per_loop_f32": (c_int, [_P] * 10 + [c_int, c_int, POINTER(c_int), c_int, c_int, _P, _P, c_int64] + [_P] * 6 + [c_int64, c_uint64,
-                                            c_uint64] + [c_float] * 8 + [c_int32, _P, _P, c_int64, _P]),
+    "erl_sac_update_f32": (c_int, _SAC_HEAD + _SAC_BATCH + [_P, _P, _P, c_float, c_int64] + _SAC_NOISE + _SAC_HYPER + [c_int32, _P] + _SAC_TAIL),
+    "erl_sac_update_opt_f32": (c_int, _SAC_HEAD + _SAC_BATCH + [_P, _P, _P, c_float, c_int64] + _SAC_NOISE + _SAC_HYPER + [c_int32, _P] +
+                                      _SAC_TAIL[:2] + [_P] + _SAC_TAIL[2:]),                                     # (ErlSacOptions before the stream)
+    "erl_sac_update_ring_f32": (c_int, _SAC_HEAD + [_P] + _SAC_BATCH + [c_int64] + _SAC_NOISE + _SAC_HYPER + [c_int32, _P] + _SAC_TAIL),
+    "erl_sac_update_ring_loop_f32": (c_int, _SAC_HEAD + [_P, _P, c_int64] + _SAC_BATCH + [c_int64] + _SAC_KEY + _SAC_HYPER + [c_int32, _P] + _SAC_TAIL),
+    "erl_sac_update_per_loop_f32": (c_int, _SAC_HEAD + [_P, _P, c_int64] + _SAC_BATCH + [c_int64] + _SAC_KEY + _SAC_HYPER + [c_int32, _P] + _SAC_TAIL),
     "erl_sac_mod_fused_supported": (c_int, [c_int, c_int, POINTER(c_int), c_int, c_int, c_int64]),
-    "erl_sac_update_mod_f32": (c_int, [_P] * 10 + [c_int, c_int, POINTER(c_int), c_int, c_int] + [_P] * 8 + [c_int64, _P, _P, c_uint64, c_uint64] +
-                                      [c_float] * 8 + [c_int32] * 3 + [_P, _P, _P, c_int64, _P]),
-    "erl_sac_update_mod_ring_f32": (c_int, [_P] * 10 + [c_int, c_int, POINTER(c_int), c_int, c_int, _P] + [_P] * 6 + [c_int64, _P, _P, c_uint64,
-                                            c_uint64] + [c_float] * 8 + [c_int32] * 3 + [_P, _P, _P, c_int64, _P]),
-    "erl_sac_update_mod_ring_loop_f32": (c_int, [_P] * 10 + [c_int, c_int, POINTER(c_int), c_int, c_int, _P, _P, c_int64] + [_P] * 6 + [c_int64,
-                                                 c_uint64, c_uint64] + [c_float] * 8 + [c_int32, c_int32, ctypes.c_double, _P, _P,
-                                                 POINTER(c_int32), _P, c_int64, _P]),
+    "erl_sac_update_mod_f32": (c_int, _SAC_HEAD + _SAC_BATCH + [_P, _P, c_int64] + _SAC_NOISE + _SAC_HYPER + [c_int32] * 3 + [_P, _P] + _SAC_TAIL),
+    "erl_sac_update_mod_ring_f32": (c_int, _SAC_HEAD + [_P] + _SAC_BATCH + [c_int64] + _SAC_NOISE + _SAC_HYPER + [c_int32] * 3 + [_P, _P] + _SAC_TAIL),
+    "erl_sac_update_mod_ring_loop_f32": (c_int, _SAC_HEAD + [_P, _P, c_int64] + _SAC_BATCH + [c_int64] + _SAC_KEY + _SAC_HYPER +
+                                                [c_int32, c_int32, c_double, _P, _P, POINTER(c_int32)] + _SAC_TAIL),
     "erl_sac_explore_action_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, c_int64, _P, c_uint64, c_uint64, _P, _P, _P,
                                            c_int64, _P]),
     "erl_sac_explore_action_opt_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, c_int64, _P, c_uint64, c_uint64, _P, _P, _P,

@@ -313,19 +313,31 @@ class AgentSAC(AgentBase):
         self.rng_counter += 1
         return action
 
+    def _nets(self) -> tuple:
+        """the leading arguments of every ops.sac_update* call"""
+        return (self._spec, self._actor_flat, self._critic_flat, self._target_flat, self.alpha_log, self._moments())
+
+    def _moments(self) -> tuple:
+        return (self.act_optimizer.exp_avg, self.act_optimizer.exp_avg_sq, self.cri_optimizer.exp_avg, self.cri_optimizer.exp_avg_sq,
+                self.alpha_optim.exp_avg, self.alpha_optim.exp_avg_sq)
+
+    def _hyper(self) -> dict:
+        return dict(gamma=float(self.gamma), target_entropy=float(self.target_entropy), tau=float(self.soft_update_tau),
+                    lr=float(self.learning_rate), max_norm=float(self.clip_grad_norm))
+
+    def _set_step_counts(self):
+        """the optimisers' `step_count` after a step (th.optim.Adam's own count, what a checkpoint stores)"""
+        self.act_optimizer.step_count = self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
+
     def _update_from_ring(self, buffer, ring, ids: TEN, objs_out: TEN, noises=None, update_t: int = 0):
         """ReplayBuffer.sample(ids) and the step from one C call; the buffer's stage / ids0 / ids1 end up as after `buffer.sample`"""
         from .. import ops
         self._step += 1
         arrays, sample_len, stage = ring
-        ops.sac_update_from_ring(self._spec, self._actor_flat, self._critic_flat, self._target_flat, self.alpha_log,
-                                 (self.act_optimizer.exp_avg, self.act_optimizer.exp_avg_sq, self.cri_optimizer.exp_avg,
-                                  self.cri_optimizer.exp_avg_sq, self.alpha_optim.exp_avg, self.alpha_optim.exp_avg_sq),
-                                 arrays, ids, sample_len, stage, self._step, gamma=float(self.gamma), target_entropy=float(self.target_entropy),
-                                 tau=float(self.soft_update_tau), lr=float(self.learning_rate), max_norm=float(self.clip_grad_norm),
-                                 objs_out=objs_out, noises=noises, seed=self.rng_seed + 1, counter=self._step)
+        ops.sac_update_from_ring(*self._nets(), arrays, ids, sample_len, stage, self._step, **self._hyper(), objs_out=objs_out, noises=noises,
+                                 seed=self.rng_seed + 1, counter=self._step)
         buffer.ids0, buffer.ids1 = stage.ids
-        self.act_optimizer.step_count = self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
+        self._set_step_counts()
 
     def _step_options(self, update_t: int) -> dict:
         """extra keyword arguments of ops.sac_update for this step (AgentModSAC: its two-time-scale rule and actor target)"""
@@ -345,16 +357,31 @@ class AgentSAC(AgentBase):
         from .. import ops
         arrays, sample_len, stage = ring
         update_times = id_all.shape[0]
-        ops.sac_update_ring_loop(self._spec, self._actor_flat, self._critic_flat, self._target_flat, self.alpha_log,
-                                 (self.act_optimizer.exp_avg, self.act_optimizer.exp_avg_sq, self.cri_optimizer.exp_avg,
-                                  self.cri_optimizer.exp_avg_sq, self.alpha_optim.exp_avg, self.alpha_optim.exp_avg_sq),
-                                 arrays, id_all, sample_len, stage, self._step + 1, gamma=float(self.gamma),
-                                 target_entropy=float(self.target_entropy), tau=float(self.soft_update_tau), lr=float(self.learning_rate),
-                                 max_norm=float(self.clip_grad_norm), objs_all=objs, seed=self.rng_seed + 1, counter0=self._step + 1)
+        ops.sac_update_ring_loop(*self._nets(), arrays, id_all, sample_len, stage, self._step + 1, **self._hyper(), objs_all=objs,
+                                 seed=self.rng_seed + 1, counter0=self._step + 1)
         self._step += update_times
         buffer.ids0, buffer.ids1 = stage.ids
-        self.act_optimizer.step_count = self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
+        self._set_step_counts()
         return "one C call (erl_sac_update_ring_loop_f32: the sample inside every step's first launch)"
+
+    def _update_per_loop(self, buffer, per, objs: TEN, per_uniform: Optional[TEN]) -> str:
+        """the prioritised loop from ONE C call (erl_sac_update_per_loop_f32): step t = what _per_step enqueues on uniforms[t].  The
+        uniforms of ALL the steps in one th.rand (sample_for_per draws (num_seqs, batch_size // num_seqs) per step: same distribution,
+        same generator; the trees change inside the loop, the uniforms do not depend on them); returns the route's name"""
+        from .. import ops
+        p_ring, trees, cur_size, cursor, per_alpha, per_beta, stage, per_stage = per
+        update_times = objs.shape[0]
+        shape = (update_times, buffer.num_seqs, self.batch_size // buffer.num_seqs)
+        if per_uniform is None:
+            per_uniform = th.rand(shape, dtype=th.float32, device=self.device)
+        assert per_uniform.shape == shape
+        ops.sac_update_per_loop(*self._nets(), p_ring, trees, per_uniform.contiguous(), cur_size, cursor, per_alpha, per_beta, stage, per_stage,
+                                self._step + 1, **self._hyper(), objs_all=objs, seed=self.rng_seed + 1, counter0=self._step + 1)
+        self._step += update_times
+        buffer.ids0, buffer.ids1 = stage.ids
+        self._td_error = per_stage.td_error
+        self._set_step_counts()
+        return "prioritised update loop in one C call (erl_sac_update_per_loop_f32: draw + gather, step, tree update per step)"
 
     def _update_on_batch(self, batch, objs_out: TEN, noises=None, is_weight=None, td_error_out=None, buffer=None, update_t: int = 0):
         from .. import ops
@@ -362,15 +389,10 @@ class AgentSAC(AgentBase):
         cum_reward = None
         if self.lambda_fit_cum_r:          # AgentSAC.py:66-68: the sampled transitions' n-step returns (the sampler left ids0 / ids1)
             cum_reward = buffer.cum_rewards[buffer.ids0, buffer.ids1].to(th.float32).contiguous()
-        ops.sac_update(self._spec, self._actor_flat, self._critic_flat, self._target_flat, self.alpha_log,
-                       (self.act_optimizer.exp_avg, self.act_optimizer.exp_avg_sq, self.cri_optimizer.exp_avg,
-                        self.cri_optimizer.exp_avg_sq, self.alpha_optim.exp_avg, self.alpha_optim.exp_avg_sq),
-                       batch, self._step, gamma=float(self.gamma), target_entropy=float(self.target_entropy),
-                       tau=float(self.soft_update_tau), lr=float(self.learning_rate), max_norm=float(self.clip_grad_norm),
-                       objs_out=objs_out, noises=noises, seed=self.rng_seed + 1, counter=self._step, is_weight=is_weight,
-                       td_error_out=td_error_out, cum_reward=cum_reward, lambda_fit_cum_r=float(self.lambda_fit_cum_r or 0.0),
-                       **self._step_options(update_t))
-        self.act_optimizer.step_count = self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
+        ops.sac_update(*self._nets(), batch, self._step, **self._hyper(), objs_out=objs_out, noises=noises, seed=self.rng_seed + 1,
+                       counter=self._step, is_weight=is_weight, td_error_out=td_error_out, cum_reward=cum_reward,
+                       lambda_fit_cum_r=float(self.lambda_fit_cum_r or 0.0), **self._step_options(update_t))
+        self._set_step_counts()
 
     @_hip.on_device
     def update_objectives(self, buffer, update_t: int, ids: Optional[TEN] = None,
@@ -450,26 +472,7 @@ class AgentSAC(AgentBase):
             why = self._per_loop_reason(buffer)
             per = None if why else buffer.per_for_fused_loop(self.batch_size)
             if per:
-                # the prioritised loop from ONE C call (erl_sac_update_per_loop_f32): step t = what _per_step enqueues on uniforms[t].  The
-                # uniforms of ALL the steps in one th.rand (sample_for_per draws (num_seqs, batch_size // num_seqs) per step: same
-                # distribution, same generator; the trees change inside the loop, the uniforms do not depend on them)
-                from .. import ops
-                p_ring, trees, cur_size, cursor, per_alpha, per_beta, stage, per_stage = per
-                if per_uniform is None:
-                    per_uniform = th.rand((update_times, buffer.num_seqs, self.batch_size // buffer.num_seqs), dtype=th.float32, device=self.device)
-                assert per_uniform.shape == (update_times, buffer.num_seqs, self.batch_size // buffer.num_seqs)
-                ops.sac_update_per_loop(self._spec, self._actor_flat, self._critic_flat, self._target_flat, self.alpha_log,
-                                        (self.act_optimizer.exp_avg, self.act_optimizer.exp_avg_sq, self.cri_optimizer.exp_avg,
-                                         self.cri_optimizer.exp_avg_sq, self.alpha_optim.exp_avg, self.alpha_optim.exp_avg_sq),
-                                        p_ring, trees, per_uniform.contiguous(), cur_size, cursor, per_alpha, per_beta, stage, per_stage, self._step + 1,
-                                        gamma=float(self.gamma), target_entropy=float(self.target_entropy), tau=float(self.soft_update_tau),
-                                        lr=float(self.learning_rate), max_norm=float(self.clip_grad_norm), objs_all=objs, seed=self.rng_seed + 1,
-                                        counter0=self._step + 1)
-                self._step += update_times
-                buffer.ids0, buffer.ids1 = stage.ids
-                self._td_error = per_stage.td_error
-                self.act_optimizer.step_count = self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
-                self.per_path = "prioritised update loop in one C call (erl_sac_update_per_loop_f32: draw + gather, step, tree update per step)"
+                self.per_path = self._update_per_loop(buffer, per, objs, per_uniform)
                 update_times = 0
             else:
                 self.per_path = "prioritised update loop per step (_per_step: six host-driven calls): " + (
@@ -551,9 +554,9 @@ class AgentModSAC(AgentSAC):
         why = self._fused_step_reason()
         return None if why is None else "layered ModSAC step, which reads a finished batch: " + why
 
-    def _moments(self):
-        return (self.act_optimizer.exp_avg, self.act_optimizer.exp_avg_sq, self.cri_optimizer.exp_avg, self.cri_optimizer.exp_avg_sq,
-                self.alpha_optim.exp_avg, self.alpha_optim.exp_avg_sq)
+    def _set_step_counts(self):
+        self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
+        self.act_optimizer.step_count = self._actor_step         # (th.optim.Adam's own count: the actor steps only when it is updated)
 
     def _update_ring_loop(self, buffer, ring, id_all: TEN, objs: TEN) -> str:
         """update_net's whole loop from ONE C call (erl_sac_update_mod_ring_loop_f32): the two-time-scale rule is evaluated in C, exactly as
@@ -561,11 +564,9 @@ class AgentModSAC(AgentSAC):
         from .. import ops
         arrays, sample_len, stage = ring
         T = id_all.shape[0]
-        n_upd = ops.sac_update_mod_ring_loop(self._spec, self._actor_flat, self._critic_flat, self._target_flat, self.alpha_log, self._moments(),
-                                             arrays, id_all, sample_len, stage, self._step + 1, self._actor_step, float(self.critic_value),
-                                             gamma=float(self.gamma), target_entropy=float(self.target_entropy), tau=float(self.soft_update_tau),
-                                             lr=float(self.learning_rate), max_norm=float(self.clip_grad_norm), objs_all=objs,
-                                             actor_target=self._actor_target_flat, seed=self.rng_seed + 1, counter0=self._step + 1)
+        n_upd = ops.sac_update_mod_ring_loop(*self._nets(), arrays, id_all, sample_len, stage, self._step + 1, self._actor_step,
+                                             float(self.critic_value), **self._hyper(), objs_all=objs, actor_target=self._actor_target_flat,
+                                             seed=self.rng_seed + 1, counter0=self._step + 1)
         bound, ua, do = 1 / (2 - math.exp(-self.critic_value ** 2)), 0, True
         for t in range(T):                                      # (the last step's flag; the count must be the library's)
             do = (ua / (t + 1)) < bound
@@ -575,23 +576,17 @@ class AgentModSAC(AgentSAC):
         self._actor_step += n_upd
         self._step += T
         buffer.ids0, buffer.ids1 = stage.ids
-        self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
-        self.act_optimizer.step_count = self._actor_step
+        self._set_step_counts()
         return "one C call (erl_sac_update_mod_ring_loop_f32: the sample inside every step's first launch, the two-time-scale rule in C)"
 
     def _update_from_ring(self, buffer, ring, ids: TEN, objs_out: TEN, noises=None, update_t: int = 0):
         from .. import ops
         self._step += 1
-        o = self._step_options(update_t)
         arrays, sample_len, stage = ring
-        ops.sac_update_mod_from_ring(self._spec, self._actor_flat, self._critic_flat, self._target_flat, self.alpha_log, self._moments(), arrays,
-                                     ids, sample_len, stage, self._step, gamma=float(self.gamma), target_entropy=float(self.target_entropy),
-                                     tau=float(self.soft_update_tau), lr=float(self.learning_rate), max_norm=float(self.clip_grad_norm),
-                                     objs_out=objs_out, update_actor=o["update_actor"], actor_step=o["actor_step"], actor_target=o["actor_target"],
-                                     noises=noises, seed=self.rng_seed + 1, counter=self._step)
+        ops.sac_update_mod_from_ring(*self._nets(), arrays, ids, sample_len, stage, self._step, **self._hyper(), objs_out=objs_out,
+                                     noises=noises, seed=self.rng_seed + 1, counter=self._step, **self._step_options(update_t))
         buffer.ids0, buffer.ids1 = stage.ids
-        self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
-        self.act_optimizer.step_count = self._actor_step
+        self._set_step_counts()
 
     def _step_options(self, update_t: int) -> dict:
         reliable_lambda = math.exp(-self.critic_value ** 2)
@@ -607,16 +602,11 @@ class AgentModSAC(AgentSAC):
         if self._fused_step_reason(batch[0].shape[0]) is None:
             from .. import ops
             self._step += 1
-            o = self._step_options(update_t)
-            ops.sac_update_mod(self._spec, self._actor_flat, self._critic_flat, self._target_flat, self.alpha_log, self._moments(), batch,
-                               self._step, gamma=float(self.gamma), target_entropy=float(self.target_entropy), tau=float(self.soft_update_tau),
-                               lr=float(self.learning_rate), max_norm=float(self.clip_grad_norm), objs_out=objs_out,
-                               update_actor=o["update_actor"], actor_step=o["actor_step"], actor_target=o["actor_target"], noises=noises,
-                               seed=self.rng_seed + 1, counter=self._step, is_weight=is_weight, td_error_out=td_error_out)
-            self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
+            ops.sac_update_mod(*self._nets(), batch, self._step, **self._hyper(), objs_out=objs_out, noises=noises, seed=self.rng_seed + 1,
+                               counter=self._step, is_weight=is_weight, td_error_out=td_error_out, **self._step_options(update_t))
+            self._set_step_counts()
         else:
             super()._update_on_batch(batch, objs_out, noises, is_weight=is_weight, td_error_out=td_error_out, buffer=buffer, update_t=update_t)
-        self.act_optimizer.step_count = self._actor_step         # (th.optim.Adam's own count: the actor steps only when it is updated)
 
     def save_or_load_agent(self, cwd: str, if_save: bool):
         if if_save:

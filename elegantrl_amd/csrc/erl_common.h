@@ -66,21 +66,52 @@ int64_t erl_sac_fused_ws_floats(int S, int A, int h0, int h1, int E, int64_t B, 
 int erl_sac_explore_fused(const float *actor_params, int S, int A, int h0, int h1, const int64_t *aoff, const float *state, int64_t N,
                           const float *noise, uint64_t seed, uint64_t counter, float *action_out, float *state_out, float *lp_scratch,
                           hipStream_t sa);
-// AgentModSAC's options on the fused step (include/erl_hip.h erl_sac_update_mod_f32); nullptr: AgentSAC's step
-struct ErlSacFusedMod {
-    int variant;               // ERL_SAC_ACTOR_*
-    int update_actor;          // 0: the two-time-scale rule skips the actor this step
-    int32_t actor_step;        // the actor optimiser's own Adam step (read when update_actor)
-    float *actor_target;       // soft-updated behind the actor's Adam step; may be NULL
+// ---- the SAC update step (sac.hip packs and validates, then enqueues the layered step there or the fused one in sac_fused.hip) ----
+// layer table of one dense network as a flat fp32 block (mlpn_common.h make_dims)
+struct NetDims {
+    int n;                 // number of dense layers = hidden + 1
+    int n_act;             // layers 0 .. n_act - 1 are followed by GELU (default n - 1: every layer but the last; ActorFixSAC's encoder
+                           // -- build_mlp([S, *net_dims]) with a RAW last layer, elegantrl/agents/AgentSAC.py:204 -- has n - 2)
+    int d[ERL_MAX_LAYERS + 2];       // d[0] = S, d[1..n-1] hidden, d[n] = out
+    int64_t oW[ERL_MAX_LAYERS + 1], ob[ERL_MAX_LAYERS + 1], oStd, count;
 };
-int erl_sac_update_fused(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m, float *actor_v,
-                         float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A, int h0, int h1, int E,
-                         const int64_t *aoff, const int64_t *coff, int64_t Pa, int64_t Pc, const float *state, const float *action,
-                         const float *reward, const float *undone, const float *unmask, const float *next_state, const float *is_weight,
-                         float *td_error_out, int64_t B, const float *eps_next, const float *eps_cur, uint64_t seed, uint64_t counter,
-                         float gamma, float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm,
-                         int32_t step, float *objs_out, float *workspace, const ErlRingSample *ring, hipStream_t s,
-                         const ErlSacFusedMod *mod = nullptr);
+struct SacDims {
+    int S, A, E, L;
+    NetDims actor, enc, dec;
+    int64_t Pa, Pc;
+};
+// what stays the same over an update loop; the batch pointers are the finished batch or, with a ring, the staging block the sample fills
+struct SacCall {
+    float *actor, *critic, *target, *alpha_log, *actor_m, *actor_v, *critic_m, *critic_v, *alpha_m, *alpha_v;
+    int S, A;
+    const int *hidden;
+    int n_hidden, E;
+    const float *state, *action, *reward, *undone, *unmask, *next_state;
+    int64_t B;
+    float gamma, target_entropy, tau, lr, beta1, beta2, eps_adam, max_norm;
+    uint64_t seed;
+    void *workspace;
+    int64_t workspace_bytes;
+    void *stream;
+    int variant;                          // ERL_SAC_ACTOR_*
+    float *actor_target;                  // AgentModSAC: soft-updated behind the actor's Adam step; may be NULL
+    const float *cum_reward;              // the lambda_fit_cum_r term (layered step only)
+    float lambda_fit_cum_r;
+    bool fused_only;                      // the erl_sac_update_mod_* entries: the fused step or a refusal
+};
+// what changes from step to step
+struct SacStep {
+    const ErlRingSample *ring;            // not NULL: the replay sample is part of the step
+    const float *is_weight;
+    float *td_error_out;
+    const float *eps_next, *eps_cur;
+    uint64_t counter;
+    int32_t step;
+    bool update_actor;                    // false: AgentModSAC's two-time-scale rule skips the actor this step
+    int32_t actor_step;                   // the actor optimiser's own Adam step (read when update_actor)
+    float *objs_out;
+};
+int erl_sac_step_fused(const SacCall &c, const SacDims &d, const SacStep &st);
 
 #define ERL_REQUIRE(cond, ...)                 \
     do {                                       \

@@ -11,14 +11,6 @@ namespace {
 constexpr int MAXL = ERL_MAX_LAYERS;      // hidden layers
 constexpr float kLogSqrt2PiN = 0.91893853320467274178f;
 
-struct NetDims {
-    int n;                 // number of dense layers = hidden + 1
-    int n_act;             // layers 0 .. n_act - 1 are followed by GELU (default n - 1: every layer but the last; ActorFixSAC's encoder
-                           // -- build_mlp([S, *net_dims]) with a RAW last layer, elegantrl/agents/AgentSAC.py:204 -- has n - 2)
-    int d[MAXL + 2];       // d[0] = S, d[1..n-1] hidden, d[n] = out
-    int64_t oW[MAXL + 1], ob[MAXL + 1], oStd, count;
-};
-
 bool make_dims(const int *dims, int n_dims, bool with_std, NetDims *nd)
 {
     if (!dims || n_dims < 2 || n_dims > MAXL + 2) return false;

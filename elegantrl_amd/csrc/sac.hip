@@ -26,12 +26,6 @@ namespace {
 constexpr int MAXE = 16;
 constexpr float kLogSqrt2PiS = 0.91893853320467274178f;
 
-struct SacDims {
-    int S, A, E, L;
-    NetDims actor, enc, dec;
-    int64_t Pa, Pc;
-};
-
 bool make_sac_dims(int S, int A, const int *hidden, int n_hidden, int E, SacDims *d, int variant = ERL_SAC_ACTOR_SAC)
 {
     if (S < 1 || A < 1 || !hidden || n_hidden < 1 || n_hidden > MAXL || E < 1 || E > MAXE) return false;
@@ -415,351 +409,33 @@ extern "C" int64_t erl_sac_workspace_bytes(int S, int A, const int *hidden, int 
     return f * 4 + 8192;
 }
 
-static int sac_update_impl(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
-                           float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
-                           const int *hidden, int n_hidden, int E, const float *state, const float *action,
-                           const float *reward, const float *undone, const float *unmask, const float *next_state,
-                           const float *is_weight, float *td_error_out, const float *cum_reward, float lambda_fit_cum_r, int64_t B,
-                           const float *eps_next, const float *eps_cur, uint64_t seed, uint64_t counter, float gamma,
-                           float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm,
-                           int32_t step, float *objs_out, void *workspace, int64_t workspace_bytes, const ErlRingSample *ring,
-                           const ErlSacOptions *opt, void *stream);
-
-extern "C" int erl_sac_update_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
-                                  float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
-                                  const int *hidden, int n_hidden, int E, const float *state, const float *action,
-                                  const float *reward, const float *undone, const float *unmask, const float *next_state,
-                                  const float *is_weight, float *td_error_out, const float *cum_reward, float lambda_fit_cum_r, int64_t B,
-                                  const float *eps_next, const float *eps_cur, uint64_t seed, uint64_t counter, float gamma,
-                                  float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm,
-                                  int32_t step, float *objs_out, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    return sac_update_impl(actor_params, critic_params, target_params, alpha_log, actor_m, actor_v, critic_m, critic_v, alpha_m, alpha_v, S, A, hidden,
-                           n_hidden, E, state, action, reward, undone, unmask, next_state, is_weight, td_error_out, cum_reward, lambda_fit_cum_r, B,
-                           eps_next, eps_cur, seed, counter, gamma, target_entropy, tau, lr, beta1, beta2, eps_adam, max_norm, step, objs_out,
-                           workspace, workspace_bytes, nullptr, nullptr, stream);
-}
-
-// erl_sac_update_f32 with the options of AgentModSAC (include/erl_hip.h, ErlSacOptions): ActorFixSAC's head, the actor step skipped by
-// the two-time-scale rule, the actor's own Adam step count, the actor target's soft update
-extern "C" int erl_sac_update_opt_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
-                                      float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
-                                      const int *hidden, int n_hidden, int E, const float *state, const float *action,
-                                      const float *reward, const float *undone, const float *unmask, const float *next_state,
-                                      const float *is_weight, float *td_error_out, const float *cum_reward, float lambda_fit_cum_r, int64_t B,
-                                      const float *eps_next, const float *eps_cur, uint64_t seed, uint64_t counter, float gamma,
-                                      float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm,
-                                      int32_t step, float *objs_out, void *workspace, int64_t workspace_bytes, const ErlSacOptions *opt,
-                                      void *stream)
-{
-    return sac_update_impl(actor_params, critic_params, target_params, alpha_log, actor_m, actor_v, critic_m, critic_v, alpha_m, alpha_v, S, A, hidden,
-                           n_hidden, E, state, action, reward, undone, unmask, next_state, is_weight, td_error_out, cum_reward, lambda_fit_cum_r, B,
-                           eps_next, eps_cur, seed, counter, gamma, target_entropy, tau, lr, beta1, beta2, eps_adam, max_norm, step, objs_out,
-                           workspace, workspace_bytes, nullptr, opt, stream);
-}
-
-// ReplayBuffer.sample + the step from one call (include/erl_hip.h): in the fused step the gather rides in the first launch
-extern "C" int erl_sac_update_ring_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
-                                       float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
-                                       const int *hidden, int n_hidden, int E, const ErlRingSample *ring, float *state, float *action,
-                                       float *reward, float *undone, float *unmask, float *next_state, int64_t B, const float *eps_next,
-                                       const float *eps_cur, uint64_t seed, uint64_t counter, float gamma, float target_entropy, float tau,
-                                       float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step, float *objs_out,
-                                       void *workspace, int64_t workspace_bytes, void *stream)
-{
-    ERL_REQUIRE(ring && ring->buf_states && ring->ids && (ring->row_floats || (ring->buf_actions && ring->buf_rewards && ring->buf_undones && ring->buf_unmasks)),
-                "erl_sac_update_ring_f32: NULL ring tensor");
-    ERL_REQUIRE(ring->row_floats == 0 || (ring->row_floats == erl_replay_row_floats(S, A) && ring->sample_len < ring->max_size &&
-                                          (reinterpret_cast<uintptr_t>(ring->buf_states) & 15) == 0),
-                "erl_sac_update_ring_f32: interleaved ring with row_floats=%lld (expected %lld), sample_len=%lld", (long long)ring->row_floats,
-                (long long)erl_replay_row_floats(S, A), (long long)ring->sample_len);
-    ERL_REQUIRE(ring->num_seqs >= 1 && ring->sample_len >= 1 && ring->sample_len <= ring->max_size,
-                "erl_sac_update_ring_f32: bad ring shape max_size=%lld num_seqs=%lld sample_len=%lld", (long long)ring->max_size,
-                (long long)ring->num_seqs, (long long)ring->sample_len);
-    return sac_update_impl(actor_params, critic_params, target_params, alpha_log, actor_m, actor_v, critic_m, critic_v, alpha_m, alpha_v, S, A, hidden,
-                           n_hidden, E, state, action, reward, undone, unmask, next_state, nullptr, nullptr, nullptr, 0.f, B, eps_next, eps_cur, seed,
-                           counter, gamma, target_entropy, tau, lr, beta1, beta2, eps_adam, max_norm, step, objs_out, workspace, workspace_bytes, ring,
-                           nullptr, stream);
-}
-
-// AgentBase.update_net's loop (elegantrl/agents/AgentBase.py:172-189) for the ring form: n_steps x erl_sac_update_ring_f32 from ONE call --
-// step t samples with ids_all[t], counts as optimiser step step0 + t, keys its noise with counter0 + t and logs into objs_all[2 t ..].
-// The interpreter is off the launch path: at config 3 a step is ~12 launches + 3 event operations, and the per-step Python / ctypes
-// work (~35 us) had become longer than what the GPU waits between launches.
-extern "C" int erl_sac_update_ring_loop_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
-                                            float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
-                                            const int *hidden, int n_hidden, int E, const ErlRingSample *ring, const int64_t *ids_all,
-                                            int64_t n_steps, float *state, float *action, float *reward, float *undone, float *unmask,
-                                            float *next_state, int64_t B, uint64_t seed, uint64_t counter0, float gamma, float target_entropy,
-                                            float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step0,
-                                            float *objs_all, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    ERL_REQUIRE(ring && ids_all && objs_all && n_steps >= 0 && B >= 1, "erl_sac_update_ring_loop_f32: bad argument");
-    for (int64_t t = 0; t < n_steps; ++t) {
-        ErlRingSample r = *ring;
-        r.ids = ids_all + t * B;
-        const int rc = erl_sac_update_ring_f32(actor_params, critic_params, target_params, alpha_log, actor_m, actor_v, critic_m, critic_v, alpha_m,
-                                               alpha_v, S, A, hidden, n_hidden, E, &r, state, action, reward, undone, unmask, next_state, B, nullptr,
-                                               nullptr, seed, counter0 + (uint64_t)t, gamma, target_entropy, tau, lr, beta1, beta2, eps_adam,
-                                               max_norm, step0 + (int32_t)t, objs_all + 2 * t, workspace, workspace_bytes, stream);
-        if (rc) return rc;
-    }
-    return ERL_OK;
-}
-
-// The same loop with prioritised replay (AgentSAC.py:45-47, :58-62; include/erl_hip.h): per step the draw + gather (per.hip), the step
-// with the importance weights in and the td errors out, the tree update from the sampler's own indices -- what AgentSAC._per_step issues
-// as six host-driven calls.  Stream order alone makes step t + 1 draw from the trees step t wrote.  Everything the three entry points
-// would refuse is refused here, before the first launch.
-extern "C" int erl_sac_update_per_loop_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
-                                           float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
-                                           const int *hidden, int n_hidden, int E, const ErlRingSample *ring, const ErlPerSample *per,
-                                           int64_t n_steps, float *state, float *action, float *reward, float *undone, float *unmask,
-                                           float *next_state, int64_t B, uint64_t seed, uint64_t counter0, float gamma, float target_entropy,
-                                           float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step0,
-                                           float *objs_all, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    ERL_REQUIRE(ring && per && objs_all, "erl_sac_update_per_loop_f32: NULL argument");
-    ERL_REQUIRE(per->sum_tree && per->min_tree, "erl_sac_update_per_loop_f32: NULL trees");
-    ERL_REQUIRE(ring->buf_states && per->uniform_all && per->is_index && per->is_weight && per->td_error,
-                "erl_sac_update_per_loop_f32: NULL ring / sampler tensor");
-    ERL_REQUIRE(actor_params && critic_params && target_params && alpha_log && actor_m && actor_v && critic_m && critic_v && alpha_m && alpha_v &&
-                    state && action && reward && undone && unmask && next_state && workspace,
-                "erl_sac_update_per_loop_f32: NULL tensor");
-    ERL_REQUIRE(n_steps >= 1 && n_steps < (1LL << 31) - step0 && step0 >= 1, "erl_sac_update_per_loop_f32: n_steps=%lld step0=%d",
-                (long long)n_steps, (int)step0);
-    SacDims d;
-    ERL_REQUIRE(make_sac_dims(S, A, hidden, n_hidden, E, &d), "erl_sac_update_per_loop_f32: unsupported dims");
-    ERL_REQUIRE(ring->row_floats > 0 && ring->row_floats == erl_replay_row_floats(S, A) && (reinterpret_cast<uintptr_t>(ring->buf_states) & 15) == 0,
-                "erl_sac_update_per_loop_f32: row_floats=%lld: the interleaved ring only (erl_replay_row_floats = %lld, 16-byte aligned)",
-                (long long)ring->row_floats, (long long)erl_replay_row_floats(S, A));
-    ERL_REQUIRE(per->max_size >= 2 && per->max_size <= (1LL << 30) && per->num_seqs >= 1 && per->num_seqs < (1 << 30) &&
-                    ring->max_size == per->max_size && ring->num_seqs == per->num_seqs,
-                "erl_sac_update_per_loop_f32: ring (max_size=%lld num_seqs=%lld) and trees (max_size=%lld num_seqs=%lld) do not match",
-                (long long)ring->max_size, (long long)ring->num_seqs, (long long)per->max_size, (long long)per->num_seqs);
-    ERL_REQUIRE(per->cur_size >= 2 && per->cur_size <= per->max_size && per->cursor <= per->max_size,
-                "erl_sac_update_per_loop_f32: cur_size=%lld cursor=%lld max_size=%lld", (long long)per->cur_size, (long long)per->cursor,
-                (long long)per->max_size);
-    ERL_REQUIRE(B >= 1 && B < (1LL << 24) && B % per->num_seqs == 0,
-                "erl_sac_update_per_loop_f32: batch %lld must be num_seqs=%lld x n_per_seq, n_per_seq >= 1", (long long)B, (long long)per->num_seqs);
-    ERL_REQUIRE(workspace_bytes >= erl_sac_workspace_bytes(S, A, hidden, n_hidden, E, B), "erl_sac_update_per_loop_f32: workspace too small");
-    const int64_t n_per_seq = B / per->num_seqs;
-    for (int64_t t = 0; t < n_steps; ++t) {
-        int rc = erl_per_sample_rows_f32(per->sum_tree, per->min_tree, per->max_size, per->num_seqs, per->uniform_all + t * B, n_per_seq,
-                                         per->cur_size, per->cursor, per->per_beta, ring->buf_states, S, A, ring->row_floats, per->is_index,
-                                         per->is_weight, state, action, reward, undone, unmask, next_state, ring->out_ids0, ring->out_ids1, stream);
-        if (rc) return rc;
-        rc = erl_sac_update_f32(actor_params, critic_params, target_params, alpha_log, actor_m, actor_v, critic_m, critic_v, alpha_m, alpha_v, S, A,
-                                hidden, n_hidden, E, state, action, reward, undone, unmask, next_state, per->is_weight, per->td_error, nullptr, 0.f,
-                                B, nullptr, nullptr, seed, counter0 + (uint64_t)t, gamma, target_entropy, tau, lr, beta1, beta2, eps_adam, max_norm,
-                                step0 + (int32_t)t, objs_all + 2 * t, workspace, workspace_bytes, stream);
-        if (rc) return rc;
-        rc = erl_per_update_index_f32(per->sum_tree, per->min_tree, per->max_size, per->num_seqs, per->is_index, per->cur_size, per->td_error, B,
-                                      per->per_alpha, stream);
-        if (rc) return rc;
-    }
-    return ERL_OK;
-}
-
-// ---- AgentModSAC on the fused step (include/erl_hip.h: erl_sac_update_mod_*; sac_fused.hip with ErlSacFusedMod) -------------------------
-// erl_sac_update_opt_f32 above keeps the layered step for the same options: the other arm of every A/B.
-extern "C" int erl_sac_mod_fused_supported(int S, int A, const int *hidden, int n_hidden, int E, int64_t B)
-{
-    return erl_sac_fused_supported(S, A, hidden, n_hidden, E, B) ? 1 : 0;
-}
-
 namespace {
 
-// what the three entries share; the batch pointers are the finished batch or, with a ring, the staging block the first launch fills
-struct SacModCall {
-    float *actor, *critic, *target, *alpha_log, *actor_m, *actor_v, *critic_m, *critic_v, *alpha_m, *alpha_v;
-    int S, A;
-    const int *hidden;
-    int n_hidden, E;
-    const float *state, *action, *reward, *undone, *unmask, *next_state;
-    int64_t B;
-    float gamma, target_entropy, tau, lr, beta1, beta2, eps_adam, max_norm;
-    float *actor_target;
-    void *workspace;
-    int64_t workspace_bytes;
-    void *stream;
-};
+// ---- the update entries: pack a SacCall + the first SacStep, validate once, then enqueue one step or loop (erl_common.h) --------------
 
-// everything an entry refuses, refused before its first launch (`ring`: NULL for a finished batch; need_ids: the entry reads ring->ids)
-int sac_mod_validate(const char *what, const SacModCall &c, const ErlRingSample *ring, bool with_ring, bool need_ids, SacDims *d)
+// The layered step on a validated call: one launch per dense layer, the other arm of every A/B against the fused step (sac_fused.hip)
+int sac_step_layered(const SacCall &c, const SacDims &d, const SacStep &st)
 {
-    ERL_REQUIRE(c.actor && c.critic && c.target && c.alpha_log && c.actor_m && c.actor_v && c.critic_m && c.critic_v && c.alpha_m && c.alpha_v &&
-                    c.state && c.action && c.reward && c.undone && c.unmask && c.next_state && c.workspace && c.hidden,
-                "%s: NULL tensor", what);
-    ERL_REQUIRE(erl_sac_fused_supported(c.S, c.A, c.hidden, c.n_hidden, c.E, c.B) && make_sac_dims(c.S, c.A, c.hidden, c.n_hidden, c.E, d, ERL_SAC_ACTOR_FIX),
-                "%s: S=%d A=%d n_hidden=%d E=%d B=%lld outside the fused step's shapes (two hidden layers, widths multiples of 16 in [16, 256], "
-                "S + A <= 64, A <= 8, E <= 8, B <= 4096); erl_sac_update_opt_f32 is the layered step", what, c.S, c.A, c.n_hidden, c.E, (long long)c.B);
-    ERL_REQUIRE(c.workspace_bytes >= erl_sac_workspace_bytes(c.S, c.A, c.hidden, c.n_hidden, c.E, c.B),
-                "%s: workspace of %lld bytes, erl_sac_workspace_bytes = %lld", what, (long long)c.workspace_bytes,
-                (long long)erl_sac_workspace_bytes(c.S, c.A, c.hidden, c.n_hidden, c.E, c.B));
-    if (!with_ring) return ERL_OK;
-    ERL_REQUIRE(ring && ring->buf_states && (!need_ids || ring->ids) &&
-                    (ring->row_floats || (ring->buf_actions && ring->buf_rewards && ring->buf_undones && ring->buf_unmasks)),
-                "%s: NULL ring tensor", what);
-    ERL_REQUIRE(ring->row_floats == 0 || (ring->row_floats == erl_replay_row_floats(c.S, c.A) && ring->sample_len < ring->max_size &&
-                                          (reinterpret_cast<uintptr_t>(ring->buf_states) & 15) == 0),
-                "%s: interleaved ring with row_floats=%lld (expected %lld), sample_len=%lld", what, (long long)ring->row_floats,
-                (long long)erl_replay_row_floats(c.S, c.A), (long long)ring->sample_len);
-    ERL_REQUIRE(ring->num_seqs >= 1 && ring->sample_len >= 1 && ring->sample_len <= ring->max_size,
-                "%s: bad ring shape max_size=%lld num_seqs=%lld sample_len=%lld", what, (long long)ring->max_size, (long long)ring->num_seqs,
-                (long long)ring->sample_len);
-    return ERL_OK;
-}
-
-// one validated step
-int sac_mod_enqueue(const SacModCall &c, const SacDims &d, const ErlRingSample *ring, const float *is_weight, float *td_error_out,
-                    const float *eps_next, const float *eps_cur, uint64_t seed, uint64_t counter, int32_t step, int update_actor,
-                    int32_t actor_step, float *objs_out)
-{
-    const int64_t aoff[6] = {d.actor.oW[0], d.actor.ob[0], d.actor.oW[1], d.actor.ob[1], d.actor.oW[2], d.actor.ob[2]};
-    const int64_t coff[8] = {d.enc.oW[0], d.enc.ob[0], d.enc.count, d.dec.oW[0], d.dec.ob[0], d.dec.oW[1], d.dec.ob[1], d.dec.count};
-    const ErlSacFusedMod mod{ERL_SAC_ACTOR_FIX, update_actor, actor_step, c.actor_target};
-    return erl_sac_update_fused(c.actor, c.critic, c.target, c.alpha_log, c.actor_m, c.actor_v, c.critic_m, c.critic_v, c.alpha_m, c.alpha_v, c.S, c.A,
-                                c.hidden[0], c.hidden[1], c.E, aoff, coff, d.Pa, d.Pc, c.state, c.action, c.reward, c.undone, c.unmask, c.next_state,
-                                is_weight, td_error_out, c.B, eps_next, eps_cur, seed, counter, c.gamma, c.target_entropy, c.tau, c.lr, c.beta1,
-                                c.beta2, c.eps_adam, c.max_norm, step, objs_out, (float *)c.workspace, ring, (hipStream_t)c.stream, &mod);
-}
-
-}  // namespace
-
-extern "C" int erl_sac_update_mod_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
-                                      float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
-                                      const int *hidden, int n_hidden, int E, const float *state, const float *action, const float *reward,
-                                      const float *undone, const float *unmask, const float *next_state, const float *is_weight,
-                                      float *td_error_out, int64_t B, const float *eps_next, const float *eps_cur, uint64_t seed,
-                                      uint64_t counter, float gamma, float target_entropy, float tau, float lr, float beta1, float beta2,
-                                      float eps_adam, float max_norm, int32_t step, int32_t update_actor, int32_t actor_step,
-                                      float *actor_target_params, float *objs_out, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    const SacModCall c{actor_params, critic_params, target_params, alpha_log, actor_m, actor_v, critic_m, critic_v, alpha_m, alpha_v, S, A, hidden,
-                       n_hidden, E, state, action, reward, undone, unmask, next_state, B, gamma, target_entropy, tau, lr, beta1, beta2, eps_adam,
-                       max_norm, actor_target_params, workspace, workspace_bytes, stream};
-    SacDims d;
-    ERL_REQUIRE(objs_out, "erl_sac_update_mod_f32: NULL tensor");
-    if (int rc = sac_mod_validate("erl_sac_update_mod_f32", c, nullptr, false, false, &d)) return rc;
-    ERL_REQUIRE(step >= 1 && actor_step >= 0 && (!update_actor || actor_step >= 1), "erl_sac_update_mod_f32: step=%d actor_step=%d update_actor=%d",
-                (int)step, (int)actor_step, (int)update_actor);
-    return sac_mod_enqueue(c, d, nullptr, is_weight, td_error_out, eps_next, eps_cur, seed, counter, step, update_actor != 0, actor_step, objs_out);
-}
-
-extern "C" int erl_sac_update_mod_ring_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
-                                           float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
-                                           const int *hidden, int n_hidden, int E, const ErlRingSample *ring, float *state, float *action,
-                                           float *reward, float *undone, float *unmask, float *next_state, int64_t B, const float *eps_next,
-                                           const float *eps_cur, uint64_t seed, uint64_t counter, float gamma, float target_entropy, float tau,
-                                           float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step, int32_t update_actor,
-                                           int32_t actor_step, float *actor_target_params, float *objs_out, void *workspace,
-                                           int64_t workspace_bytes, void *stream)
-{
-    const SacModCall c{actor_params, critic_params, target_params, alpha_log, actor_m, actor_v, critic_m, critic_v, alpha_m, alpha_v, S, A, hidden,
-                       n_hidden, E, state, action, reward, undone, unmask, next_state, B, gamma, target_entropy, tau, lr, beta1, beta2, eps_adam,
-                       max_norm, actor_target_params, workspace, workspace_bytes, stream};
-    SacDims d;
-    ERL_REQUIRE(objs_out, "erl_sac_update_mod_ring_f32: NULL tensor");
-    if (int rc = sac_mod_validate("erl_sac_update_mod_ring_f32", c, ring, true, true, &d)) return rc;
-    ERL_REQUIRE(step >= 1 && actor_step >= 0 && (!update_actor || actor_step >= 1), "erl_sac_update_mod_ring_f32: step=%d actor_step=%d update_actor=%d",
-                (int)step, (int)actor_step, (int)update_actor);
-    return sac_mod_enqueue(c, d, ring, nullptr, nullptr, eps_next, eps_cur, seed, counter, step, update_actor != 0, actor_step, objs_out);
-}
-
-// AgentModSAC.update_objectives' loop in AgentBase.update_net (AgentSAC.py:113-165): the two-time-scale rule needs nothing from the device
-// (the reference never moves critic_value), so it is evaluated here, in double precision as the interpreter does
-extern "C" int erl_sac_update_mod_ring_loop_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
-                                                float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
-                                                const int *hidden, int n_hidden, int E, const ErlRingSample *ring, const int64_t *ids_all,
-                                                int64_t n_steps, float *state, float *action, float *reward, float *undone, float *unmask,
-                                                float *next_state, int64_t B, uint64_t seed, uint64_t counter0, float gamma, float target_entropy,
-                                                float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step0,
-                                                int32_t actor_step0, double critic_value, float *actor_target_params, float *objs_all,
-                                                int32_t *actor_updates_out, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    const SacModCall c{actor_params, critic_params, target_params, alpha_log, actor_m, actor_v, critic_m, critic_v, alpha_m, alpha_v, S, A, hidden,
-                       n_hidden, E, state, action, reward, undone, unmask, next_state, B, gamma, target_entropy, tau, lr, beta1, beta2, eps_adam,
-                       max_norm, actor_target_params, workspace, workspace_bytes, stream};
-    SacDims d;
-    ERL_REQUIRE(ids_all && objs_all, "erl_sac_update_mod_ring_loop_f32: NULL tensor");
-    if (int rc = sac_mod_validate("erl_sac_update_mod_ring_loop_f32", c, ring, true, false, &d)) return rc;
-    ERL_REQUIRE(step0 >= 1 && actor_step0 >= 0 && n_steps >= 0 && n_steps < (1LL << 31) - step0 && n_steps < (1LL << 31) - actor_step0 &&
-                    critic_value == critic_value,
-                "erl_sac_update_mod_ring_loop_f32: n_steps=%lld step0=%d actor_step0=%d critic_value=%g", (long long)n_steps, (int)step0,
-                (int)actor_step0, critic_value);
-    const double reliable_lambda = exp(-(critic_value * critic_value));              // (:148)
-    const double bound = 1.0 / (2.0 - reliable_lambda);
-    int32_t update_a = 0, actor_step = actor_step0;
-    for (int64_t t = 0; t < n_steps; ++t) {
-        const bool upd = (double)update_a / (double)(t + 1) < bound;                  // (:151)
-        if (upd) { ++update_a; ++actor_step; }
-        ErlRingSample r = *ring;
-        r.ids = ids_all + t * B;
-        const int rc = sac_mod_enqueue(c, d, &r, nullptr, nullptr, nullptr, nullptr, seed, counter0 + (uint64_t)t, step0 + (int32_t)t, upd,
-                                       actor_step, objs_all + 2 * t);
-        if (rc) return rc;
-    }
-    if (actor_updates_out) *actor_updates_out = update_a;
-    return ERL_OK;
-}
-
-static int sac_update_impl(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
-                           float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
-                           const int *hidden, int n_hidden, int E, const float *state, const float *action,
-                           const float *reward, const float *undone, const float *unmask, const float *next_state,
-                           const float *is_weight, float *td_error_out, const float *cum_reward, float lambda_fit_cum_r, int64_t B,
-                           const float *eps_next, const float *eps_cur, uint64_t seed, uint64_t counter, float gamma,
-                           float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm,
-                           int32_t step, float *objs_out, void *workspace, int64_t workspace_bytes, const ErlRingSample *ring,
-                           const ErlSacOptions *opt, void *stream)
-{
-    ERL_REQUIRE(actor_params && critic_params && target_params && alpha_log && actor_m && actor_v && critic_m && critic_v && alpha_m &&
-                    alpha_v && state && action && reward && undone && unmask && next_state && objs_out && workspace,
-                "erl_sac_update_f32: NULL tensor");
-    const int variant = opt ? opt->actor_variant : ERL_SAC_ACTOR_SAC;
-    const bool update_actor = opt ? opt->update_actor != 0 : true;
-    const int32_t actor_step = opt && opt->actor_step > 0 ? opt->actor_step : step;
-    float *actor_target = opt ? opt->actor_target_params : nullptr;
-    ERL_REQUIRE(variant == ERL_SAC_ACTOR_SAC || variant == ERL_SAC_ACTOR_FIX, "erl_sac_update_opt_f32: unknown actor_variant %d", variant);
-    SacDims d;
-    ERL_REQUIRE(make_sac_dims(S, A, hidden, n_hidden, E, &d, variant), "erl_sac_update_f32: unsupported dims");
-    ERL_REQUIRE(B >= 1 && B < (1LL << 24) && step >= 1, "erl_sac_update_f32: bad argument");
-    ERL_REQUIRE(lambda_fit_cum_r == 0.f || cum_reward, "erl_sac_update_f32: lambda_fit_cum_r != 0 needs the batch's cum_reward");
-    ERL_REQUIRE(workspace_bytes >= erl_sac_workspace_bytes(S, A, hidden, n_hidden, E, B), "erl_sac_update_f32: workspace too small");
-    hipStream_t s = (hipStream_t)stream;
+    const int S = c.S, A = c.A, E = c.E;
+    const int64_t B = c.B;
+    hipStream_t s = (hipStream_t)c.stream;
     int rc;
-
-    // Off-policy batch sizes with two hidden layers up to 256 wide (config 3): the fused step, 12 launches (sac_fused.hip).
-    // ERL_SAC_FUSED=0 keeps the layered step below (A/B runs); lambda_fit_cum_r != 0 (off by default) is layered only.
-    static const bool fused_on = [] { const char *e = getenv("ERL_SAC_FUSED"); return !(e && atoi(e) == 0); }();
-    // (AgentModSAC's options take the layered step here: this entry is the other arm of every A/B against erl_sac_update_mod_f32, the
-    // same options on the fused step)
-    const bool plain = variant == ERL_SAC_ACTOR_SAC && update_actor && actor_step == step && !actor_target;
-    if (fused_on && plain && lambda_fit_cum_r == 0.f && erl_sac_fused_supported(S, A, hidden, n_hidden, E, B)) {
-        const int64_t aoff[6] = {d.actor.oW[0], d.actor.ob[0], d.actor.oW[1], d.actor.ob[1], d.actor.oW[2], d.actor.ob[2]};
-        const int64_t coff[8] = {d.enc.oW[0], d.enc.ob[0], d.enc.count, d.dec.oW[0], d.dec.ob[0], d.dec.oW[1], d.dec.ob[1], d.dec.count};
-        return erl_sac_update_fused(actor_params, critic_params, target_params, alpha_log, actor_m, actor_v, critic_m, critic_v, alpha_m, alpha_v, S,
-                                    A, hidden[0], hidden[1], E, aoff, coff, d.Pa, d.Pc, state, action, reward, undone, unmask, next_state,
-                                    is_weight, td_error_out, B, eps_next, eps_cur, seed, counter, gamma, target_entropy, tau, lr, beta1, beta2,
-                                    eps_adam, max_norm, step, objs_out, (float *)workspace, ring, s);
-    }
-    if (ring) {        // the layered step reads a finished batch: the sample as a launch of its own
-        rc = ring->row_floats
-                 ? erl_replay_sample_rows_f32(ring->buf_states, ring->max_size, ring->num_seqs, S, A, ring->ids, B, ring->sample_len,
-                                              const_cast<float *>(state), const_cast<float *>(action), const_cast<float *>(reward),
-                                              const_cast<float *>(undone), const_cast<float *>(unmask), const_cast<float *>(next_state),
-                                              ring->out_ids0, ring->out_ids1, stream)
-                 : erl_replay_sample_f32(ring->buf_states, ring->buf_actions, ring->buf_rewards, ring->buf_undones, ring->buf_unmasks, ring->max_size, ring->num_seqs, S,
-                                   A, ring->ids, B, ring->sample_len, const_cast<float *>(state), const_cast<float *>(action),
-                                   const_cast<float *>(reward), const_cast<float *>(undone), const_cast<float *>(unmask),
-                                   const_cast<float *>(next_state), ring->out_ids0, ring->out_ids1, stream);
+    if (const ErlRingSample *r = st.ring) {        // the layered step reads a finished batch: the sample as a launch of its own
+        rc = r->row_floats
+                 ? erl_replay_sample_rows_f32(r->buf_states, r->max_size, r->num_seqs, S, A, r->ids, B, r->sample_len,
+                                              const_cast<float *>(c.state), const_cast<float *>(c.action), const_cast<float *>(c.reward),
+                                              const_cast<float *>(c.undone), const_cast<float *>(c.unmask), const_cast<float *>(c.next_state),
+                                              r->out_ids0, r->out_ids1, c.stream)
+                 : erl_replay_sample_f32(r->buf_states, r->buf_actions, r->buf_rewards, r->buf_undones, r->buf_unmasks, r->max_size, r->num_seqs, S,
+                                   A, r->ids, B, r->sample_len, const_cast<float *>(c.state), const_cast<float *>(c.action),
+                                   const_cast<float *>(c.reward), const_cast<float *>(c.undone), const_cast<float *>(c.unmask),
+                                   const_cast<float *>(c.next_state), r->out_ids0, r->out_ids1, c.stream);
         if (rc) return rc;
     }
 
-    Ws ws{(char *)workspace, 0, workspace_bytes};
+    Ws ws{(char *)c.workspace, 0, c.workspace_bytes};
     int maxd = S + A;
-    for (int i = 0; i < n_hidden; ++i) maxd = hidden[i] > maxd ? hidden[i] : maxd;
+    for (int i = 0; i < c.n_hidden; ++i) maxd = c.hidden[i] > maxd ? c.hidden[i] : maxd;
     maxd = 2 * A > maxd ? 2 * A : maxd;
     float *xa = ws.take(B * (S + A)), *dxa = ws.take(B * (S + A));
     float *aact[MAXL + 2], *agd[MAXL + 2];
@@ -785,93 +461,354 @@ static int sac_update_impl(float *actor_params, float *critic_params, float *tar
     const dim3 rows_grid((unsigned)erl_cdiv(B, 256)), blk(256);
 
     // ---- (1) targets: next action / log-prob from the actor, min over the TARGET ensemble          (:50-55)
-    aact[0] = const_cast<float *>(next_state);                      // the input layer reads the sample in place
-    if ((rc = forward(s, d.actor, actor_params, B, aact, nullptr))) return rc;
-    hipLaunchKernelGGL(head_forward_kernel, rows_grid, blk, 0, s, aact[d.actor.n], eps_next, seed, 2 * counter, A, B, act_t, lp_next,
-                       (float *)nullptr, next_state, S, xa, variant);
-    if ((rc = critic_forward(s, d, target_params, B, xa, cw, false))) return rc;
-    hipLaunchKernelGGL(q_label_kernel, rows_grid, blk, 0, s, cw.q, E, B, reward, undone, lp_next, alpha_log, gamma, label);
+    aact[0] = const_cast<float *>(c.next_state);                      // the input layer reads the sample in place
+    if ((rc = forward(s, d.actor, c.actor, B, aact, nullptr))) return rc;
+    hipLaunchKernelGGL(head_forward_kernel, rows_grid, blk, 0, s, aact[d.actor.n], st.eps_next, c.seed, 2 * st.counter, A, B, act_t, lp_next,
+                       (float *)nullptr, c.next_state, S, xa, c.variant);
+    if ((rc = critic_forward(s, d, c.target, B, xa, cw, false))) return rc;
+    hipLaunchKernelGGL(q_label_kernel, rows_grid, blk, 0, s, cw.q, E, B, c.reward, c.undone, lp_next, c.alpha_log, c.gamma, label);
 
     // ---- (2) critic objective, backward, clip + Adam, soft target update                          (:57-70)
-    hipLaunchKernelGGL(concat_kernel, dim3(grid1d(B * (S + A))), blk, 0, s, state, action, S, A, B, xa);
-    if ((rc = critic_forward(s, d, critic_params, B, xa, cw, true))) return rc;
-    const bool fit_on = lambda_fit_cum_r != 0.f;                     // AgentSAC.py:66-68 (off by default: config.py:52)
-    if (fit_on) hipLaunchKernelGGL(fit_cum_r_kernel, dim3(1), blk, 0, s, cw.q, cum_reward, E, B, lambda_fit_cum_r, fit);
-    hipLaunchKernelGGL(critic_loss_kernel, rows_grid, blk, 0, s, cw.q, label, unmask, is_weight, fit_on ? fit : (const float *)nullptr, E, B, dq,
-                       td_error_out, part);
-    hipLaunchKernelGGL(sum_kernel, dim3(1), blk, 0, s, part, (int64_t)nparts, 1.0f / (float)B, 0.f, objs_out,
+    hipLaunchKernelGGL(concat_kernel, dim3(grid1d(B * (S + A))), blk, 0, s, c.state, c.action, S, A, B, xa);
+    if ((rc = critic_forward(s, d, c.critic, B, xa, cw, true))) return rc;
+    const bool fit_on = c.lambda_fit_cum_r != 0.f;                     // AgentSAC.py:66-68 (off by default: config.py:52)
+    if (fit_on) hipLaunchKernelGGL(fit_cum_r_kernel, dim3(1), blk, 0, s, cw.q, c.cum_reward, E, B, c.lambda_fit_cum_r, fit);
+    hipLaunchKernelGGL(critic_loss_kernel, rows_grid, blk, 0, s, cw.q, label, c.unmask, st.is_weight, fit_on ? fit : (const float *)nullptr, E, B, dq,
+                       st.td_error_out, part);
+    hipLaunchKernelGGL(sum_kernel, dim3(1), blk, 0, s, part, (int64_t)nparts, 1.0f / (float)B, 0.f, st.objs_out,
                        fit_on ? fit + E : (const float *)nullptr);
     if (batched) {
-        if ((rc = decoders_backward(s, d, critic_params + d.enc.count, B, cw, dq, g_critic + d.enc.count, dEnc, dEncE, enc_stride, tmpA, tmpB,
+        if ((rc = decoders_backward(s, d, c.critic + d.enc.count, B, cw, dq, g_critic + d.enc.count, dEnc, dEncE, enc_stride, tmpA, tmpB,
                                     tmp_stride)))
             return rc;
     } else {
         for (int e = 0; e < E; ++e) {
             float *Gdec = g_critic + d.enc.count + (int64_t)e * d.dec.count;
-            if ((rc = backward(s, d.dec, critic_params + d.enc.count + (int64_t)e * d.dec.count, B, cw.act[e], cw.gd[e], dq + (size_t)e * B,
+            if ((rc = backward(s, d.dec, c.critic + d.enc.count + (int64_t)e * d.dec.count, B, cw.act[e], cw.gd[e], dq + (size_t)e * B,
                                Gdec, cs_scr, dEnc, e > 0, tmpA, tmpB)))
                 return rc;
         }
     }
     {   // encoder: one raw linear layer, input xa
         float *ea[2] = {xa, cw.enc};
-        if ((rc = backward(s, d.enc, critic_params, B, ea, nullptr, dEnc, g_critic, cs_scr, nullptr, false, tmpA, tmpB))) return rc;
+        if ((rc = backward(s, d.enc, c.critic, B, ea, nullptr, dEnc, g_critic, cs_scr, nullptr, false, tmpA, tmpB))) return rc;
     }
     {
         const int64_t off = 0, len = d.Pc;
-        if ((rc = erl_clip_adam_f32(critic_params, g_critic, critic_m, critic_v, &off, &len, 1, nullptr, step, lr, beta1, beta2, eps_adam,
-                                    max_norm, 1.0f, stream)))
+        if ((rc = erl_clip_adam_f32(c.critic, g_critic, c.critic_m, c.critic_v, &off, &len, 1, nullptr, st.step, c.lr, c.beta1, c.beta2, c.eps_adam,
+                                    c.max_norm, 1.0f, c.stream)))
             return rc;
     }
-    hipLaunchKernelGGL(soft_update_kernel, dim3(grid1d(d.Pc)), blk, 0, s, target_params, critic_params, tau, d.Pc);
+    hipLaunchKernelGGL(soft_update_kernel, dim3(grid1d(d.Pc)), blk, 0, s, c.target, c.critic, c.tau, d.Pc);
 
     // ---- (3) policy-gradient sample, temperature step                                              (:72-81)
-    aact[0] = const_cast<float *>(state);
-    if ((rc = forward(s, d.actor, actor_params, B, aact, agd))) return rc;
-    hipLaunchKernelGGL(head_forward_kernel, rows_grid, blk, 0, s, aact[d.actor.n], eps_cur, seed, 2 * counter + 1, A, B, act_t, lp_cur,
-                       eps_used, state, S, xa, variant);        // xa = [state | action_pg] for step (4)
+    aact[0] = const_cast<float *>(c.state);
+    if ((rc = forward(s, d.actor, c.actor, B, aact, agd))) return rc;
+    hipLaunchKernelGGL(head_forward_kernel, rows_grid, blk, 0, s, aact[d.actor.n], st.eps_cur, c.seed, 2 * st.counter + 1, A, B, act_t, lp_cur,
+                       eps_used, c.state, S, xa, c.variant);        // xa = [state | action_pg] for step (4)
     // obj_alpha = mean(alpha_log * (target_entropy - logprob)):  d/dalpha_log = target_entropy - mean(logprob)
     {
-        const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-        hipLaunchKernelGGL(alpha_step_kernel, dim3(1), blk, 0, s, lp_cur, B, target_entropy, g_alpha, alpha_log, alpha_m, alpha_v, beta1, beta2,
-                           eps_adam, max_norm, (float)((double)lr / bc1), (float)sqrt(bc2));
+        const double bc1 = 1.0 - pow((double)c.beta1, (double)st.step), bc2 = 1.0 - pow((double)c.beta2, (double)st.step);
+        hipLaunchKernelGGL(alpha_step_kernel, dim3(1), blk, 0, s, lp_cur, B, c.target_entropy, g_alpha, c.alpha_log, c.alpha_m, c.alpha_v, c.beta1, c.beta2,
+                           c.eps_adam, c.max_norm, (float)((double)c.lr / bc1), (float)sqrt(bc2));
     }
 
-    if (!update_actor) {
+    if (!st.update_actor) {
         // AgentModSAC's two-time-scale rule skipped the actor this step (AgentSAC.py:152-158): alpha is clamped as always (:146-147),
         // obj_actor is nan (:158), actor / actor target / their Adam state stay as they are
-        hipLaunchKernelGGL(clamp_alpha_kernel, dim3(1), dim3(64), 0, s, alpha_log);
-        hipLaunchKernelGGL(fillk_kernel, dim3(1), blk, 0, s, objs_out + 1, __builtin_nanf(""), (int64_t)1);
+        hipLaunchKernelGGL(clamp_alpha_kernel, dim3(1), dim3(64), 0, s, c.alpha_log);
+        hipLaunchKernelGGL(fillk_kernel, dim3(1), blk, 0, s, st.objs_out + 1, __builtin_nanf(""), (int64_t)1);
         ERL_LAUNCH_CHECK("erl_sac_update_opt_f32");
     }
     // ---- (4) actor objective against the TARGET ensemble's mean, backward into the action, head, actor   (:82-85)
-    if ((rc = critic_forward(s, d, target_params, B, xa, cw, true))) return rc;
-    hipLaunchKernelGGL(actor_obj_kernel, dim3(1), blk, 0, s, cw.q, E, B, lp_cur, alpha_log, objs_out + 1);
+    if ((rc = critic_forward(s, d, c.target, B, xa, cw, true))) return rc;
+    hipLaunchKernelGGL(actor_obj_kernel, dim3(1), blk, 0, s, cw.q, E, B, lp_cur, c.alpha_log, st.objs_out + 1);
     hipLaunchKernelGGL(fillk_kernel, dim3(grid1d((int64_t)E * B)), blk, 0, s, dq, -1.0f / ((float)E * (float)B), (int64_t)E * B);
     if (batched) {
-        if ((rc = decoders_backward(s, d, target_params + d.enc.count, B, cw, dq, nullptr, dEnc, dEncE, enc_stride, tmpA, tmpB, tmp_stride)))
+        if ((rc = decoders_backward(s, d, c.target + d.enc.count, B, cw, dq, nullptr, dEnc, dEncE, enc_stride, tmpA, tmpB, tmp_stride)))
             return rc;
     } else {
         for (int e = 0; e < E; ++e)
-            if ((rc = backward(s, d.dec, target_params + d.enc.count + (int64_t)e * d.dec.count, B, cw.act[e], cw.gd[e], dq + (size_t)e * B,
+            if ((rc = backward(s, d.dec, c.target + d.enc.count + (int64_t)e * d.dec.count, B, cw.act[e], cw.gd[e], dq + (size_t)e * B,
                                nullptr, cs_scr, dEnc, e > 0, tmpA, tmpB)))
                 return rc;
     }
-    if ((rc = dense_backward_input(s, dEnc, target_params, dxa, nullptr, false, (int)B, d.enc.d[1], S + A))) return rc;   // dL/d[state | action]
+    if ((rc = dense_backward_input(s, dEnc, c.target, dxa, nullptr, false, (int)B, d.enc.d[1], S + A))) return rc;   // dL/d[state | action]
     // dL/daction = the action columns of dxa, read in place (row stride S + A)
-    hipLaunchKernelGGL(head_backward_kernel, rows_grid, blk, 0, s, aact[d.actor.n], act_t, eps_used, dxa + S, S + A, alpha_log, A, B, dHead, variant);
-    hipLaunchKernelGGL(clamp_alpha_kernel, dim3(1), dim3(64), 0, s, alpha_log);                  // after alpha was read (:80-81)
-    if ((rc = backward(s, d.actor, actor_params, B, aact, agd, dHead, g_actor, cs_scr, nullptr, false, tmpA, tmpB))) return rc;
+    hipLaunchKernelGGL(head_backward_kernel, rows_grid, blk, 0, s, aact[d.actor.n], act_t, eps_used, dxa + S, S + A, c.alpha_log, A, B, dHead, c.variant);
+    hipLaunchKernelGGL(clamp_alpha_kernel, dim3(1), dim3(64), 0, s, c.alpha_log);                  // after alpha was read (:80-81)
+    if ((rc = backward(s, d.actor, c.actor, B, aact, agd, dHead, g_actor, cs_scr, nullptr, false, tmpA, tmpB))) return rc;
     {
         const int64_t off = 0, len = d.Pa;
-        if ((rc = erl_clip_adam_f32(actor_params, g_actor, actor_m, actor_v, &off, &len, 1, nullptr, actor_step, lr, beta1, beta2, eps_adam,
-                                    max_norm, 1.0f, stream)))
+        if ((rc = erl_clip_adam_f32(c.actor, g_actor, c.actor_m, c.actor_v, &off, &len, 1, nullptr, st.actor_step, c.lr, c.beta1, c.beta2, c.eps_adam,
+                                    c.max_norm, 1.0f, c.stream)))
             return rc;
     }
-    if (actor_target)      // AgentModSAC: soft_update(act_target, act, tau) after the actor's step (AgentSAC.py:156)
-        hipLaunchKernelGGL(soft_update_kernel, dim3(grid1d(d.Pa)), blk, 0, s, actor_target, actor_params, tau, d.Pa);
+    if (c.actor_target)      // AgentModSAC: soft_update(act_target, act, tau) after the actor's step (AgentSAC.py:156)
+        hipLaunchKernelGGL(soft_update_kernel, dim3(grid1d(d.Pa)), blk, 0, s, c.actor_target, c.actor, c.tau, d.Pa);
     ERL_LAUNCH_CHECK("erl_sac_update_f32");
 }
+
+// everything an entry refuses, refused before its first launch under the entry's own name.  `sample`: the entry samples from a replay ring
+// (st.ring may still be NULL: that is refused); need_ids: it reads ring->ids itself (a loop patches them in per step)
+int sac_validate(const char *what, const SacCall &c, const SacStep &st, bool sample, bool need_ids, SacDims *d)
+{
+    ERL_REQUIRE(c.actor && c.critic && c.target && c.alpha_log && c.actor_m && c.actor_v && c.critic_m && c.critic_v && c.alpha_m && c.alpha_v &&
+                    c.state && c.action && c.reward && c.undone && c.unmask && c.next_state && st.objs_out && c.workspace && c.hidden,
+                "%s: NULL tensor", what);
+    ERL_REQUIRE(c.variant == ERL_SAC_ACTOR_SAC || c.variant == ERL_SAC_ACTOR_FIX, "%s: unknown actor_variant %d", what, c.variant);
+    if (c.fused_only)
+        ERL_REQUIRE(erl_sac_fused_supported(c.S, c.A, c.hidden, c.n_hidden, c.E, c.B),
+                    "%s: S=%d A=%d n_hidden=%d E=%d B=%lld outside the fused step's shapes (two hidden layers, widths multiples of 16 in [16, 256], "
+                    "S + A <= 64, A <= 8, E <= 8, B <= 4096); erl_sac_update_opt_f32 is the layered step", what, c.S, c.A, c.n_hidden, c.E, (long long)c.B);
+    ERL_REQUIRE(make_sac_dims(c.S, c.A, c.hidden, c.n_hidden, c.E, d, c.variant), "%s: unsupported dims", what);
+    ERL_REQUIRE(c.B >= 1 && c.B < (1LL << 24) && st.step >= 1 && st.actor_step >= 0 && (!st.update_actor || st.actor_step >= 1),
+                "%s: bad argument B=%lld step=%d actor_step=%d update_actor=%d", what, (long long)c.B, (int)st.step, (int)st.actor_step,
+                (int)st.update_actor);
+    ERL_REQUIRE(c.lambda_fit_cum_r == 0.f || c.cum_reward, "%s: lambda_fit_cum_r != 0 needs the batch's cum_reward", what);
+    const int64_t need = erl_sac_workspace_bytes(c.S, c.A, c.hidden, c.n_hidden, c.E, c.B);
+    ERL_REQUIRE(c.workspace_bytes >= need, "%s: workspace too small (%lld bytes, erl_sac_workspace_bytes = %lld)", what, (long long)c.workspace_bytes,
+                (long long)need);
+    if (!sample) return ERL_OK;
+    const ErlRingSample *ring = st.ring;
+    ERL_REQUIRE(ring && ring->buf_states && (!need_ids || ring->ids) && (ring->row_floats || (ring->buf_actions && ring->buf_rewards && ring->buf_undones && ring->buf_unmasks)),
+                "%s: NULL ring tensor", what);
+    ERL_REQUIRE(ring->row_floats == 0 || (ring->row_floats == erl_replay_row_floats(c.S, c.A) && ring->sample_len < ring->max_size &&
+                                       (reinterpret_cast<uintptr_t>(ring->buf_states) & 15) == 0),
+                "%s: interleaved ring with row_floats=%lld (expected %lld), sample_len=%lld", what, (long long)ring->row_floats,
+                (long long)erl_replay_row_floats(c.S, c.A), (long long)ring->sample_len);
+    ERL_REQUIRE(ring->num_seqs >= 1 && ring->sample_len >= 1 && ring->sample_len <= ring->max_size, "%s: bad ring shape max_size=%lld num_seqs=%lld sample_len=%lld",
+                what, (long long)ring->max_size, (long long)ring->num_seqs, (long long)ring->sample_len);
+    return ERL_OK;
+}
+
+// One validated step.  Off-policy batch sizes with two hidden layers up to 256 wide (config 3): the fused step, 12 launches
+// (sac_fused.hip).  ERL_SAC_FUSED=0 keeps the layered step (A/B runs); lambda_fit_cum_r != 0 (off by default) is layered only, and so are
+// AgentModSAC's options outside the erl_sac_update_mod_* entries: erl_sac_update_opt_f32 is the other arm of every A/B against those.
+int sac_enqueue(const SacCall &c, const SacDims &d, const SacStep &st)
+{
+    static const bool fused_on = [] { const char *e = getenv("ERL_SAC_FUSED"); return !(e && atoi(e) == 0); }();
+    const bool plain = c.variant == ERL_SAC_ACTOR_SAC && st.update_actor && st.actor_step == st.step && !c.actor_target;
+    if (c.fused_only || (fused_on && plain && c.lambda_fit_cum_r == 0.f && erl_sac_fused_supported(c.S, c.A, c.hidden, c.n_hidden, c.E, c.B)))
+        return erl_sac_step_fused(c, d, st);
+    return sac_step_layered(c, d, st);
+}
+
+// what a one-call update loop adds to its first step
+struct SacLoop {
+    int64_t n_steps;
+    const int64_t *ids_all;               // not NULL: step t samples with ids_all[t * B ..]
+    const ErlPerSample *per;              // not NULL: prioritised replay -- draw + gather before the step, tree update behind it
+    bool two_time_scale;                  // AgentModSAC: the rule decides update_actor per step, the actor's Adam count runs on from st.actor_step
+    double critic_value;
+    int32_t *actor_updates_out;
+};
+
+// AgentBase.update_net's loop (elegantrl/agents/AgentBase.py:172-189) from ONE call: validated before step 0, then step t counts as optimiser
+// step st.step + t, keys its noise with st.counter + t and logs into st.objs_out[2 t ..].  The interpreter is off the launch path: at
+// config 3 a step is ~12 launches + 3 event operations, and the per-step Python / ctypes work (~35 us) had become longer than what the GPU
+// waits between launches.
+int sac_loop(const char *what, const SacCall &c, SacStep st, const SacLoop &lp)
+{
+    ERL_REQUIRE(st.step >= 1 && st.actor_step >= 0 && lp.n_steps >= 0 && lp.n_steps < (1LL << 31) - st.step &&
+                    lp.n_steps < (1LL << 31) - st.actor_step && lp.critic_value == lp.critic_value,
+                "%s: n_steps=%lld step0=%d actor_step0=%d critic_value=%g", what, (long long)lp.n_steps, (int)st.step, (int)st.actor_step,
+                lp.critic_value);
+    SacDims d;
+    if (int rc = sac_validate(what, c, st, lp.ids_all != nullptr, false, &d)) return rc;
+    // AgentModSAC's two-time-scale rule (AgentSAC.py:148-151) needs nothing from the device (the reference never moves critic_value), so it
+    // is evaluated here, in double precision as the interpreter does
+    const double bound = 1.0 / (2.0 - exp(-(lp.critic_value * lp.critic_value)));
+    const ErlPerSample *per = lp.per;
+    ErlRingSample r = st.ring ? *st.ring : ErlRingSample{};       // the loop's ring; a step sees it (with its ids) only when it samples by ids
+    int32_t update_a = 0;
+    for (int64_t t = 0; t < lp.n_steps; ++t) {
+        if (lp.two_time_scale) {
+            st.update_actor = (double)update_a / (double)(t + 1) < bound;
+            if (st.update_actor) { ++update_a; ++st.actor_step; }
+        }
+        int rc;
+        r.ids = lp.ids_all ? lp.ids_all + t * c.B : nullptr;
+        st.ring = lp.ids_all ? &r : nullptr;
+        if (per && (rc = erl_per_sample_rows_f32(per->sum_tree, per->min_tree, per->max_size, per->num_seqs, per->uniform_all + t * c.B, c.B / per->num_seqs,
+                                                 per->cur_size, per->cursor, per->per_beta, r.buf_states, c.S, c.A, r.row_floats, per->is_index,
+                                                 per->is_weight, const_cast<float *>(c.state), const_cast<float *>(c.action),
+                                                 const_cast<float *>(c.reward), const_cast<float *>(c.undone), const_cast<float *>(c.unmask),
+                                                 const_cast<float *>(c.next_state), r.out_ids0, r.out_ids1, c.stream)))
+            return rc;
+        if ((rc = sac_enqueue(c, d, st))) return rc;
+        if (per && (rc = erl_per_update_index_f32(per->sum_tree, per->min_tree, per->max_size, per->num_seqs, per->is_index, per->cur_size,
+                                                  per->td_error, c.B, per->per_alpha, c.stream)))
+            return rc;
+        ++st.step;
+        ++st.counter;
+        st.objs_out += 2;
+        if (!lp.two_time_scale) st.actor_step = st.step;
+    }
+    if (lp.actor_updates_out) *lp.actor_updates_out = update_a;
+    return ERL_OK;
+}
+
+// one step: validate, enqueue
+int sac_single(const char *what, const SacCall &c, const SacStep &st, bool sample)
+{
+    SacDims d;
+    if (int rc = sac_validate(what, c, st, sample, true, &d)) return rc;
+    return sac_enqueue(c, d, st);
+}
+
+}  // namespace
+
+// the arguments every update entry names alike, then: actor variant, actor target, cum_reward, lambda_fit_cum_r, fused_only
+#define SAC_CALL(...)                                                                                                                         \
+    SacCall{actor_params, critic_params, target_params, alpha_log, actor_m, actor_v, critic_m, critic_v, alpha_m, alpha_v, S, A, hidden, n_hidden, E, \
+            state, action, reward, undone, unmask, next_state, B, gamma, target_entropy, tau, lr, beta1, beta2, eps_adam, max_norm, seed, workspace,   \
+            workspace_bytes, stream, __VA_ARGS__}
+
+extern "C" int erl_sac_update_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
+                                  float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
+                                  const int *hidden, int n_hidden, int E, const float *state, const float *action,
+                                  const float *reward, const float *undone, const float *unmask, const float *next_state,
+                                  const float *is_weight, float *td_error_out, const float *cum_reward, float lambda_fit_cum_r, int64_t B,
+                                  const float *eps_next, const float *eps_cur, uint64_t seed, uint64_t counter, float gamma,
+                                  float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm,
+                                  int32_t step, float *objs_out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const SacCall c = SAC_CALL(ERL_SAC_ACTOR_SAC, nullptr, cum_reward, lambda_fit_cum_r, false);
+    return sac_single("erl_sac_update_f32", c, SacStep{nullptr, is_weight, td_error_out, eps_next, eps_cur, counter, step, true, step, objs_out}, false);
+}
+
+// erl_sac_update_f32 with the options of AgentModSAC (include/erl_hip.h, ErlSacOptions): ActorFixSAC's head, the actor step skipped by
+// the two-time-scale rule, the actor's own Adam step count, the actor target's soft update -- on the layered step (sac_enqueue)
+extern "C" int erl_sac_update_opt_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
+                                      float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
+                                      const int *hidden, int n_hidden, int E, const float *state, const float *action,
+                                      const float *reward, const float *undone, const float *unmask, const float *next_state,
+                                      const float *is_weight, float *td_error_out, const float *cum_reward, float lambda_fit_cum_r, int64_t B,
+                                      const float *eps_next, const float *eps_cur, uint64_t seed, uint64_t counter, float gamma,
+                                      float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm,
+                                      int32_t step, float *objs_out, void *workspace, int64_t workspace_bytes, const ErlSacOptions *opt,
+                                      void *stream)
+{
+    const SacCall c = SAC_CALL(opt ? opt->actor_variant : ERL_SAC_ACTOR_SAC, opt ? opt->actor_target_params : nullptr, cum_reward, lambda_fit_cum_r, false);
+    const SacStep st{nullptr, is_weight, td_error_out, eps_next, eps_cur, counter, step, opt ? opt->update_actor != 0 : true,
+                     opt && opt->actor_step > 0 ? opt->actor_step : step, objs_out};
+    return sac_single("erl_sac_update_opt_f32", c, st, false);
+}
+
+// ReplayBuffer.sample + the step from one call (include/erl_hip.h): in the fused step the gather rides in the first launch
+extern "C" int erl_sac_update_ring_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
+                                       float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
+                                       const int *hidden, int n_hidden, int E, const ErlRingSample *ring, float *state, float *action,
+                                       float *reward, float *undone, float *unmask, float *next_state, int64_t B, const float *eps_next,
+                                       const float *eps_cur, uint64_t seed, uint64_t counter, float gamma, float target_entropy, float tau,
+                                       float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step, float *objs_out,
+                                       void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const SacCall c = SAC_CALL(ERL_SAC_ACTOR_SAC, nullptr, nullptr, 0.f, false);
+    return sac_single("erl_sac_update_ring_f32", c, SacStep{ring, nullptr, nullptr, eps_next, eps_cur, counter, step, true, step, objs_out}, true);
+}
+
+// n_steps x erl_sac_update_ring_f32 from ONE call (sac_loop): step t samples with ids_all[t]
+extern "C" int erl_sac_update_ring_loop_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
+                                            float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
+                                            const int *hidden, int n_hidden, int E, const ErlRingSample *ring, const int64_t *ids_all,
+                                            int64_t n_steps, float *state, float *action, float *reward, float *undone, float *unmask,
+                                            float *next_state, int64_t B, uint64_t seed, uint64_t counter0, float gamma, float target_entropy,
+                                            float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step0,
+                                            float *objs_all, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    ERL_REQUIRE(ids_all, "erl_sac_update_ring_loop_f32: bad argument (NULL ids_all)");
+    const SacCall c = SAC_CALL(ERL_SAC_ACTOR_SAC, nullptr, nullptr, 0.f, false);
+    return sac_loop("erl_sac_update_ring_loop_f32", c, SacStep{ring, nullptr, nullptr, nullptr, nullptr, counter0, step0, true, step0, objs_all},
+                    SacLoop{n_steps, ids_all, nullptr, false, 0.0, nullptr});
+}
+
+// The same loop with prioritised replay (AgentSAC.py:45-47, :58-62; include/erl_hip.h): per step the draw + gather (per.hip), the step
+// with the importance weights in and the td errors out, the tree update from the sampler's own indices -- what AgentSAC._per_step issues
+// as six host-driven calls.  Stream order alone makes step t + 1 draw from the trees step t wrote.  Everything the three entry points
+// would refuse is refused here, before the first launch.
+extern "C" int erl_sac_update_per_loop_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
+                                           float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
+                                           const int *hidden, int n_hidden, int E, const ErlRingSample *ring, const ErlPerSample *per,
+                                           int64_t n_steps, float *state, float *action, float *reward, float *undone, float *unmask,
+                                           float *next_state, int64_t B, uint64_t seed, uint64_t counter0, float gamma, float target_entropy,
+                                           float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step0,
+                                           float *objs_all, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    ERL_REQUIRE(ring && per && objs_all, "erl_sac_update_per_loop_f32: NULL argument");
+    ERL_REQUIRE(per->sum_tree && per->min_tree, "erl_sac_update_per_loop_f32: NULL trees");
+    ERL_REQUIRE(ring->buf_states && per->uniform_all && per->is_index && per->is_weight && per->td_error,
+                "erl_sac_update_per_loop_f32: NULL ring / sampler tensor");
+    ERL_REQUIRE(n_steps >= 1 && step0 >= 1, "erl_sac_update_per_loop_f32: n_steps=%lld step0=%d", (long long)n_steps, (int)step0);
+    ERL_REQUIRE(ring->row_floats > 0 && ring->row_floats == erl_replay_row_floats(S, A) && (reinterpret_cast<uintptr_t>(ring->buf_states) & 15) == 0,
+                "erl_sac_update_per_loop_f32: row_floats=%lld: the interleaved ring only (erl_replay_row_floats = %lld, 16-byte aligned)",
+                (long long)ring->row_floats, (long long)erl_replay_row_floats(S, A));
+    ERL_REQUIRE(per->max_size >= 2 && per->max_size <= (1LL << 30) && per->num_seqs >= 1 && per->num_seqs < (1 << 30) &&
+                    ring->max_size == per->max_size && ring->num_seqs == per->num_seqs,
+                "erl_sac_update_per_loop_f32: ring (max_size=%lld num_seqs=%lld) and trees (max_size=%lld num_seqs=%lld) do not match",
+                (long long)ring->max_size, (long long)ring->num_seqs, (long long)per->max_size, (long long)per->num_seqs);
+    ERL_REQUIRE(per->cur_size >= 2 && per->cur_size <= per->max_size && per->cursor <= per->max_size,
+                "erl_sac_update_per_loop_f32: cur_size=%lld cursor=%lld max_size=%lld", (long long)per->cur_size, (long long)per->cursor,
+                (long long)per->max_size);
+    ERL_REQUIRE(B >= 1 && B < (1LL << 24) && B % per->num_seqs == 0,
+                "erl_sac_update_per_loop_f32: batch %lld must be num_seqs=%lld x n_per_seq, n_per_seq >= 1", (long long)B, (long long)per->num_seqs);
+    const SacCall c = SAC_CALL(ERL_SAC_ACTOR_SAC, nullptr, nullptr, 0.f, false);
+    return sac_loop("erl_sac_update_per_loop_f32", c, SacStep{ring, per->is_weight, per->td_error, nullptr, nullptr, counter0, step0, true, step0, objs_all},
+                    SacLoop{n_steps, nullptr, per, false, 0.0, nullptr});
+}
+
+// ---- AgentModSAC on the fused step (include/erl_hip.h: erl_sac_update_mod_*; sac_fused.hip) -------------------------------------------
+// erl_sac_update_opt_f32 above keeps the layered step for the same options: the other arm of every A/B.
+extern "C" int erl_sac_mod_fused_supported(int S, int A, const int *hidden, int n_hidden, int E, int64_t B)
+{
+    return erl_sac_fused_supported(S, A, hidden, n_hidden, E, B) ? 1 : 0;
+}
+
+extern "C" int erl_sac_update_mod_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
+                                      float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
+                                      const int *hidden, int n_hidden, int E, const float *state, const float *action, const float *reward,
+                                      const float *undone, const float *unmask, const float *next_state, const float *is_weight,
+                                      float *td_error_out, int64_t B, const float *eps_next, const float *eps_cur, uint64_t seed,
+                                      uint64_t counter, float gamma, float target_entropy, float tau, float lr, float beta1, float beta2,
+                                      float eps_adam, float max_norm, int32_t step, int32_t update_actor, int32_t actor_step,
+                                      float *actor_target_params, float *objs_out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const SacCall c = SAC_CALL(ERL_SAC_ACTOR_FIX, actor_target_params, nullptr, 0.f, true);
+    const SacStep st{nullptr, is_weight, td_error_out, eps_next, eps_cur, counter, step, update_actor != 0, actor_step, objs_out};
+    return sac_single("erl_sac_update_mod_f32", c, st, false);
+}
+
+extern "C" int erl_sac_update_mod_ring_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
+                                           float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
+                                           const int *hidden, int n_hidden, int E, const ErlRingSample *ring, float *state, float *action,
+                                           float *reward, float *undone, float *unmask, float *next_state, int64_t B, const float *eps_next,
+                                           const float *eps_cur, uint64_t seed, uint64_t counter, float gamma, float target_entropy, float tau,
+                                           float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step, int32_t update_actor,
+                                           int32_t actor_step, float *actor_target_params, float *objs_out, void *workspace,
+                                           int64_t workspace_bytes, void *stream)
+{
+    const SacCall c = SAC_CALL(ERL_SAC_ACTOR_FIX, actor_target_params, nullptr, 0.f, true);
+    const SacStep st{ring, nullptr, nullptr, eps_next, eps_cur, counter, step, update_actor != 0, actor_step, objs_out};
+    return sac_single("erl_sac_update_mod_ring_f32", c, st, true);
+}
+
+// AgentModSAC.update_objectives' loop in AgentBase.update_net (AgentSAC.py:113-165): sac_loop with the two-time-scale rule
+extern "C" int erl_sac_update_mod_ring_loop_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
+                                                float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
+                                                const int *hidden, int n_hidden, int E, const ErlRingSample *ring, const int64_t *ids_all,
+                                                int64_t n_steps, float *state, float *action, float *reward, float *undone, float *unmask,
+                                                float *next_state, int64_t B, uint64_t seed, uint64_t counter0, float gamma, float target_entropy,
+                                                float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step0,
+                                                int32_t actor_step0, double critic_value, float *actor_target_params, float *objs_all,
+                                                int32_t *actor_updates_out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    ERL_REQUIRE(ids_all, "erl_sac_update_mod_ring_loop_f32: NULL tensor");
+    const SacCall c = SAC_CALL(ERL_SAC_ACTOR_FIX, actor_target_params, nullptr, 0.f, true);
+    return sac_loop("erl_sac_update_mod_ring_loop_f32", c, SacStep{ring, nullptr, nullptr, nullptr, nullptr, counter0, step0, false, actor_step0, objs_all},
+                    SacLoop{n_steps, ids_all, nullptr, true, critic_value, actor_updates_out});
+}
+#undef SAC_CALL
 
 // The whole off-policy rollout of AgentBase._explore_vec_env (AgentBase.py:130-170) on the device-resident SynVecEnv as ONE launch
 // (sac_fused.hip sac_rollout_synenv_kernel); needs erl_sac_rollout_synenv_supported(...)
@@ -953,35 +890,13 @@ extern "C" int erl_sac_eval_pendulum_f32(const float *actor_params, const int *h
 }
 
 // ActorSAC.get_action for the off-policy rollout (AgentSAC.py:179-185): action = tanh(mean + std * eps); state_out (may be NULL):
-// the rollout's `states[t] = state` (AgentBase.py:145) written by the same launch
-static int sac_explore_impl(const float *actor_params, int S, int A, const int *hidden, int n_hidden, const float *state, int64_t N,
-                            const float *noise, uint64_t seed, uint64_t counter, float *action_out, float *state_out, void *workspace,
-                            int64_t workspace_bytes, int variant, void *stream);
-
-extern "C" int erl_sac_explore_action_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, const float *state,
-                                          int64_t N, const float *noise, uint64_t seed, uint64_t counter, float *action_out,
-                                          float *state_out, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    return sac_explore_impl(actor_params, S, A, hidden, n_hidden, state, N, noise, seed, counter, action_out, state_out, workspace, workspace_bytes,
-                            ERL_SAC_ACTOR_SAC, stream);
-}
-
-// ... with the actor variant named: ERL_SAC_ACTOR_FIX = ActorFixSAC.get_action (AgentSAC.py:217-224: raw last encoder layer, log_std
-// clamped to [-20, 2]) for AgentModSAC's rollout
+// the rollout's `states[t] = state` (AgentBase.py:145) written by the same launch.  With the actor variant named: ERL_SAC_ACTOR_FIX =
+// ActorFixSAC.get_action (AgentSAC.py:217-224: raw last encoder layer, log_std clamped to [-20, 2]) for AgentModSAC's rollout
 extern "C" int erl_sac_explore_action_opt_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, const float *state,
                                               int64_t N, const float *noise, uint64_t seed, uint64_t counter, float *action_out,
-                                              float *state_out, void *workspace, int64_t workspace_bytes, int actor_variant, void *stream)
+                                              float *state_out, void *workspace, int64_t workspace_bytes, int variant, void *stream)
 {
-    ERL_REQUIRE(actor_variant == ERL_SAC_ACTOR_SAC || actor_variant == ERL_SAC_ACTOR_FIX, "erl_sac_explore_action_opt_f32: unknown actor_variant %d",
-                actor_variant);
-    return sac_explore_impl(actor_params, S, A, hidden, n_hidden, state, N, noise, seed, counter, action_out, state_out, workspace, workspace_bytes,
-                            actor_variant, stream);
-}
-
-static int sac_explore_impl(const float *actor_params, int S, int A, const int *hidden, int n_hidden, const float *state, int64_t N,
-                            const float *noise, uint64_t seed, uint64_t counter, float *action_out, float *state_out, void *workspace,
-                            int64_t workspace_bytes, int variant, void *stream)
-{
+    ERL_REQUIRE(variant == ERL_SAC_ACTOR_SAC || variant == ERL_SAC_ACTOR_FIX, "erl_sac_explore_action_opt_f32: unknown actor_variant %d", variant);
     ERL_REQUIRE(actor_params && state && action_out && workspace, "erl_sac_explore_action_f32: NULL tensor");
     SacDims d;
     ERL_REQUIRE(make_sac_dims(S, A, hidden, n_hidden, 1, &d, variant), "erl_sac_explore_action_f32: unsupported dims");
@@ -1010,4 +925,12 @@ static int sac_explore_impl(const float *actor_params, int S, int A, const int *
     hipLaunchKernelGGL(head_forward_kernel, dim3((unsigned)erl_cdiv(N, 256)), dim3(256), 0, s, aact[d.actor.n], noise, seed, counter, A, N,
                        action_out, lp, (float *)nullptr, (const float *)nullptr, S, (float *)nullptr, variant);
     ERL_LAUNCH_CHECK("erl_sac_explore_action_f32");
+}
+
+extern "C" int erl_sac_explore_action_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, const float *state,
+                                          int64_t N, const float *noise, uint64_t seed, uint64_t counter, float *action_out,
+                                          float *state_out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return erl_sac_explore_action_opt_f32(actor_params, S, A, hidden, n_hidden, state, N, noise, seed, counter, action_out, state_out, workspace,
+                                          workspace_bytes, ERL_SAC_ACTOR_SAC, stream);
 }

@@ -37,7 +37,7 @@
 // config 3, where the policy-gradient sample's forward rides in launch (1) (actor_fwd_pair_kernel).  The same tile code, looped over H steps with the actor's weights kept in registers /
 // LDS, is the persistent off-policy rollout (sac_rollout_synenv_kernel).
 // AgentModSAC (AgentSAC.py:89-165) runs the same launches with ActorFixSAC as a run-time variant of the actor kernels (ActorFwdArgs::variant)
-// and ErlSacFusedMod's options: the actor's own Adam count, its target's soft update behind that step, and -- on the steps its two-time-scale
+// and its options (SacCall / SacStep): the actor's own Adam count, its target's soft update behind that step, and -- on the steps its two-time-scale
 // rule skips -- one small launch (sac_skip_finish_kernel) in place of launches (7)-(10).
 #include "mlpn_common.h"
 
@@ -1064,7 +1064,7 @@ __global__ __launch_bounds__(FT) void actor_bwd_kernel(ActorBwdArgs g)
     }
 }
 
-// The step on which AgentModSAC's two-time-scale rule skips the actor (ErlSacFusedMod::update_actor == 0) ends here instead of in
+// The step on which AgentModSAC's two-time-scale rule skips the actor (SacStep::update_actor false) ends here instead of in
 // launches (7)-(10): the critic objective from the training pass's q and labels -- per tile what launch (7) computes, added in tile
 // order as actor_bwd_kernel does --, td_error_out, obj_actor = nan (AgentSAC.py:158) and the temperature's clamp (:146-147).
 // One workgroup of 16 waves; wave w takes the tiles w, w + 16, ...
@@ -1124,7 +1124,7 @@ struct DwArgs {
     DwProb p[DW_MAXP];
     int np;
     int64_t B;
-    float *clamp_alpha_log;     // not NULL: workgroup 0 also clamps the temperature's logarithm to [-16, 2] (see erl_sac_update_fused)
+    float *clamp_alpha_log;     // not NULL: workgroup 0 also clamps the temperature's logarithm to [-16, 2] (see erl_sac_step_fused)
     double *norm_parts;         // not NULL: [workgroups] the fp64 sum of squares of what each workgroup stores (its dW tile, its db rows): the
                                 // squared gradient norm in pieces, so that clip + Adam needs no pass over the gradient and no grid-wide wait
     // not NULL (al_lp): workgroup 0 first takes the temperature's Adam step (alpha_step_block: obj_alpha, AgentSAC.py:76-79) -- the critic's
@@ -1684,20 +1684,25 @@ int erl_sac_explore_fused(const float *actor_params, int S, int A, int h0, int h
     return erl_hip_status(hipGetLastError(), "erl_sac_explore_action_f32 (fused)");
 }
 
-// The whole step.  Pointers / scalars as erl_sac_update_f32 (sac.hip), which validates them and dispatches here.
-int erl_sac_update_fused(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m, float *actor_v,
-                         float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A, int h0, int h1, int E,
-                         const int64_t *aoff, const int64_t *coff, int64_t Pa, int64_t Pc, const float *state, const float *action,
-                         const float *reward, const float *undone, const float *unmask, const float *next_state, const float *is_weight,
-                         float *td_error_out, int64_t B, const float *eps_next, const float *eps_cur, uint64_t seed, uint64_t counter,
-                         float gamma, float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm,
-                         int32_t step, float *objs_out, float *workspace, const ErlRingSample *ring, hipStream_t s, const ErlSacFusedMod *mod)
+// The whole step on a validated call (sac.hip sac_enqueue).  With AgentModSAC's options (ActorFixSAC, the actor's own Adam count, its
+// target's soft update, a skipped actor step) the same launches; plain calls carry update_actor, actor_step = step and no actor target.
+int erl_sac_step_fused(const SacCall &c, const SacDims &sd, const SacStep &st)
 {
-    const int variant = mod ? mod->variant : ERL_SAC_ACTOR_SAC;
+    float *const actor_params = c.actor, *const critic_params = c.critic, *const target_params = c.target, *const alpha_log = c.alpha_log;
+    const float *const state = c.state, *const action = c.action, *const reward = c.reward, *const undone = c.undone, *const unmask = c.unmask,
+                *const next_state = c.next_state, *const is_weight = st.is_weight;
+    const int S = c.S, A = c.A, E = c.E, h0 = c.hidden[0], h1 = c.hidden[1], variant = c.variant;
+    const int64_t B = c.B, Pa = sd.Pa, Pc = sd.Pc;
+    const float beta1 = c.beta1, beta2 = c.beta2, eps_adam = c.eps_adam, max_norm = c.max_norm, lr = c.lr, tau = c.tau;
+    const int32_t step = st.step;
+    float *const td_error_out = st.td_error_out, *const objs_out = st.objs_out, *const workspace = (float *)c.workspace;
+    const ErlRingSample *const ring = st.ring;
+    const hipStream_t s = (hipStream_t)c.stream;
     FusedDims d{};
     d.S = S; d.A = A; d.E = E; d.h0 = h0; d.h1 = h1; d.B = B;
-    d.aW1 = aoff[0]; d.ab1 = aoff[1]; d.aW2 = aoff[2]; d.ab2 = aoff[3]; d.aWh = aoff[4]; d.abh = aoff[5];
-    d.cWe = coff[0]; d.cbe = coff[1]; d.cdec0 = coff[2]; d.dW1 = coff[3]; d.db1 = coff[4]; d.dWo = coff[5]; d.dbo = coff[6]; d.dec = coff[7];
+    d.aW1 = sd.actor.oW[0]; d.ab1 = sd.actor.ob[0]; d.aW2 = sd.actor.oW[1]; d.ab2 = sd.actor.ob[1]; d.aWh = sd.actor.oW[2]; d.abh = sd.actor.ob[2];
+    d.cWe = sd.enc.oW[0]; d.cbe = sd.enc.ob[0]; d.cdec0 = sd.enc.count; d.dW1 = sd.dec.oW[0]; d.db1 = sd.dec.ob[0]; d.dWo = sd.dec.oW[1];
+    d.dbo = sd.dec.ob[1]; d.dec = sd.dec.count;
     const int tiles = (int)((B + TS - 1) / TS);
     auto r = [](int64_t n) { return (n + 63) / 64 * 64; };
     float *w = workspace;
@@ -1727,10 +1732,10 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
 
     // ---- (1) next action / log-prob (actor on next_state)                                                      (:50-51)
     ActorFwdArgs af{};
-    af.P = actor_params; af.d = d; af.X = next_state; af.noise = eps_next; af.seed = seed; af.counter = 2 * counter;
+    af.P = actor_params; af.d = d; af.X = next_state; af.noise = st.eps_next; af.seed = c.seed; af.counter = 2 * st.counter;
     af.act_t = a_next; af.lp = lp_next; af.alpha_log = alpha_log; af.alpha0 = alpha0; af.variant = variant;
     if (ring) {
-        // the replay sample rides in this launch: the batch pointers are the staging block it fills (sac.hip erl_sac_update_ring_f32)
+        // the replay sample rides in this launch: the batch pointers are the staging block it fills (SacStep::ring)
         af.rg = *ring;
         af.o_state = const_cast<float *>(state); af.o_action = const_cast<float *>(action); af.o_reward = const_cast<float *>(reward);
         af.o_undone = const_cast<float *>(undone); af.o_unmask = const_cast<float *>(unmask); af.o_next = const_cast<float *>(next_state);
@@ -1740,7 +1745,7 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
     // (actor_fwd_pair_kernel), the sample reading its state rows from the ring itself; elsewhere it is the launch right behind (1), reading
     // the rows (1) staged.  The temperature's step (:76-79) rides the critic's weight-gradient launch (4).
     ActorFwdArgs pg = af;
-    pg.X = state; pg.noise = eps_cur; pg.counter = 2 * counter + 1; pg.act_t = act_pg; pg.lp = lp_cur; pg.eps_out = eps_used; pg.Y = Y;
+    pg.X = state; pg.noise = st.eps_cur; pg.counter = 2 * st.counter + 1; pg.act_t = act_pg; pg.lp = lp_cur; pg.eps_out = eps_used; pg.Y = Y;
     pg.H0 = H0; pg.G0 = G0; pg.H1 = H1; pg.G1 = G1; pg.alpha0 = nullptr; pg.rg = ErlRingSample{};
     // (nothing of launch (1) is kept for a backward pass: a 256-wide second layer is split over kCritSplit workgroups per tile -- ActorFwdArgs::split)
     const bool a_split = slot && h1 == 64 * kCritSplit && tiles * kCritSplit <= 256;
@@ -1794,7 +1799,7 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
     }
     ca.P = critic_params; ca.Xs = state; ca.Xa = action; ca.q = qc;
     ca.qt = qt; ca.reward = reward; ca.undone = undone; ca.unmask = unmask; ca.lp_next = lp_next; ca.is_weight = is_weight; ca.alpha0 = alpha0;
-    ca.gamma = gamma; ca.label = label; ca.dq = dq; ca.xa = xa; ca.enc = enc; ca.H1e = H1e; ca.dZ1e = dZ1e; ca.dEncE = dEncE;
+    ca.gamma = c.gamma; ca.label = label; ca.dq = dq; ca.xa = xa; ca.enc = enc; ca.H1e = H1e; ca.dZ1e = dZ1e; ca.dEncE = dEncE;
     ca.span = erl_span_slot(ERL_SPAN_SAC_CRITIC_TRAIN, (int64_t)cg.x * cg.y);
     FUSED_KT_DISPATCH_D(ca.d, LAUNCH_CRITIC1)
     ca.span = nullptr; ca.h1_full = 0;
@@ -1810,16 +1815,16 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
         }
         dw.norm_parts = nparts_c;
         const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-        dw.al_lp = lp_cur; dw.al_n = B; dw.al_target_entropy = target_entropy; dw.al_alpha_log = alpha_log; dw.al_m1 = alpha_m; dw.al_m2 = alpha_v;
+        dw.al_lp = lp_cur; dw.al_n = B; dw.al_target_entropy = c.target_entropy; dw.al_alpha_log = alpha_log; dw.al_m1 = c.alpha_m; dw.al_m2 = c.alpha_v;
         dw.al_beta1 = beta1; dw.al_beta2 = beta2; dw.al_eps = eps_adam; dw.al_max_norm = max_norm; dw.al_step_size = (float)((double)lr / bc1);
         dw.al_bc2_sqrt = (float)sqrt(bc2);
         if ((rc = dw_launch(dw, s))) return rc;
         // ---- (5) clip + Adam on the critic from the launch's squared-norm pieces, soft target update in the same launch  (:69-70)
-        if ((rc = erl_clip_adam_parts_soft_f32(critic_params, g_critic, critic_m, critic_v, Pc, nparts_c, dw.p[dw.np - 1].tile0 + dw.p[dw.np - 1].ntiles,
+        if ((rc = erl_clip_adam_parts_soft_f32(critic_params, g_critic, c.critic_m, c.critic_v, Pc, nparts_c, dw.p[dw.np - 1].tile0 + dw.p[dw.np - 1].ntiles,
                                                step, lr, beta1, beta2, eps_adam, max_norm, target_params, tau, s)))
             return rc;
     }
-    if (mod && !mod->update_actor) {
+    if (!st.update_actor) {
         // AgentModSAC skips the actor this step (AgentSAC.py:152-158): no policy-gradient pass, no actor backward, weight gradients,
         // clip + Adam or actor-target update -- actor_params, its moments and the actor target are not touched
         SkipFinishArgs sf{};
@@ -1855,9 +1860,8 @@ int erl_sac_update_fused(float *actor_params, float *critic_params, float *targe
         dw.norm_parts = nparts_a;
         if ((rc = dw_launch(dw, s))) return rc;
         // (AgentModSAC: the actor optimiser's own step count, and soft_update(act_target, act) behind its step, AgentSAC.py:156)
-        if ((rc = erl_clip_adam_parts_soft_f32(actor_params, g_actor, actor_m, actor_v, Pa, nparts_a, dw.p[dw.np - 1].tile0 + dw.p[dw.np - 1].ntiles,
-                                               mod ? mod->actor_step : step, lr, beta1, beta2, eps_adam, max_norm, mod ? mod->actor_target : nullptr,
-                                               mod ? tau : 0.f, s)))
+        if ((rc = erl_clip_adam_parts_soft_f32(actor_params, g_actor, c.actor_m, c.actor_v, Pa, nparts_a, dw.p[dw.np - 1].tile0 + dw.p[dw.np - 1].ntiles,
+                                               st.actor_step, lr, beta1, beta2, eps_adam, max_norm, c.actor_target, tau, s)))
             return rc;
     }
     return erl_hip_status(hipGetLastError(), "erl_sac_update_f32(fused)");

@@ -746,40 +746,6 @@ class SacSpec:
         return lib().erl_sac_workspace_bytes(self.S, self.A, self._c, len(self.hidden), self.E, B)
 
 
-def sac_update(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], batch: Sequence[TEN],
-               step: int, *, gamma: float, target_entropy: float, tau: float, lr: float, max_norm: float, objs_out: TEN,
-               noises: Optional[Tuple[TEN, TEN]] = None, seed: int = 0, counter: int = 0, betas=(0.9, 0.999), eps: float = 1e-8,
-               is_weight: Optional[TEN] = None, td_error_out: Optional[TEN] = None, cum_reward: Optional[TEN] = None,
-               lambda_fit_cum_r: float = 0.0, update_actor: bool = True, actor_step: int = 0, actor_target: Optional[TEN] = None) -> None:
-    """one AgentSAC.update_objectives step after the sample; `moments` = (actor_m, actor_v, critic_m, critic_v, alpha_m,
-    alpha_v); `batch` = (state, action, reward, undone, unmask, next_state); objs_out: float32[2] on the device.
-    `cum_reward` (B,) + `lambda_fit_cum_r`: the critic's fit-the-batch's-mean-return term (AgentSAC.py:66-68)."""
-    state, action, reward, undone, unmask, next_state = batch
-    B = state.shape[0]
-    ws = _workspace(state.device, spec.workspace_bytes(B))
-    n_next, n_cur = (None, None) if noises is None else noises
-    f32 = th.float32
-    if spec.actor_variant or not update_actor or actor_step or actor_target is not None:
-        # AgentModSAC's step (include/erl_hip.h, ErlSacOptions): ActorFixSAC's head, the actor skipped by the two-time-scale rule, the
-        # actor optimiser's own step count, the actor target's soft update
-        opt = _SacOptions(spec.actor_variant, int(bool(update_actor)), int(actor_step), 0, ptr(actor_target, f32))
-        check(lib().erl_sac_update_opt_f32(ptr(actor, f32), ptr(critic, f32), ptr(target, f32), ptr(alpha_log, f32), *[ptr(m, f32) for m in moments],
-                                           spec.S, spec.A, spec._c, len(spec.hidden), spec.E, ptr(state, f32), ptr(action, f32),
-                                           ptr(reward, f32), ptr(undone, f32), ptr(unmask, f32), ptr(next_state, f32), ptr(is_weight),
-                                           ptr(td_error_out), ptr(cum_reward), float(lambda_fit_cum_r), B, ptr(n_next), ptr(n_cur),
-                                           seed & (2 ** 64 - 1), counter & (2 ** 64 - 1), gamma, target_entropy, tau, lr, betas[0], betas[1], eps,
-                                           max_norm, step, ptr(objs_out, f32), ptr(ws), ws.numel(), ctypes.byref(opt), stream_ptr()),
-              "erl_sac_update_opt_f32")
-        return
-    check(lib().erl_sac_update_f32(ptr(actor, f32), ptr(critic, f32), ptr(target, f32), ptr(alpha_log, f32), *[ptr(m, f32) for m in moments],
-                                   spec.S, spec.A, spec._c, len(spec.hidden), spec.E, ptr(state, f32), ptr(action, f32),
-                                   ptr(reward, f32), ptr(undone, f32), ptr(unmask, f32), ptr(next_state, f32), ptr(is_weight), ptr(td_error_out),
-                                   ptr(cum_reward), float(lambda_fit_cum_r), B, ptr(n_next),
-                                   ptr(n_cur), seed & (2 ** 64 - 1), counter & (2 ** 64 - 1), gamma, target_entropy, tau, lr, betas[0],
-                                   betas[1], eps, max_norm, step, ptr(objs_out, f32), ptr(ws), ws.numel(), stream_ptr()),
-          "erl_sac_update_f32")
-
-
 class _SacOptions(ctypes.Structure):        # include/erl_hip.h ErlSacOptions
     _fields_ = [("actor_variant", ctypes.c_int32), ("update_actor", ctypes.c_int32), ("actor_step", ctypes.c_int32),
                 ("reserved", ctypes.c_int32), ("actor_target_params", ctypes.c_void_p)]
@@ -792,67 +758,41 @@ class _RingSample(ctypes.Structure):        # include/erl_hip.h ErlRingSample
                 ("row_floats", ctypes.c_int64)]
 
 
-def sac_update_from_ring(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring: Sequence[TEN],
-                         ids: TEN, sample_len: int, stage: ReplayStage, step: int, *, gamma: float, target_entropy: float, tau: float, lr: float,
-                         max_norm: float, objs_out: TEN, noises: Optional[Tuple[TEN, TEN]] = None, seed: int = 0, counter: int = 0,
-                         betas=(0.9, 0.999), eps: float = 1e-8) -> None:
-    """ReplayBuffer.sample(ids) + one AgentSAC.update_objectives step from ONE call (erl_sac_update_ring_f32): `ring` = the buffer's
-    ReplayRing (interleaved block) or its five planar tensors (states, actions, rewards, undones, unmasks), `stage` receives the batch (stage.out / stage.ids: what replay_sample would have left)."""
-    B = ids.numel()
+class _PerSample(ctypes.Structure):         # include/erl_hip.h ErlPerSample
+    _fields_ = [("sum_tree", ctypes.c_void_p), ("min_tree", ctypes.c_void_p), ("max_size", ctypes.c_int64), ("num_seqs", ctypes.c_int64),
+                ("cur_size", ctypes.c_int64), ("cursor", ctypes.c_int64), ("per_alpha", ctypes.c_float), ("per_beta", ctypes.c_float),
+                ("uniform_all", ctypes.c_void_p), ("is_index", ctypes.c_void_p), ("is_weight", ctypes.c_void_p), ("td_error", ctypes.c_void_p)]
+
+
+# The erl_sac_update_* entries name the same arguments in the same order (_hip._SAC_HEAD / _SAC_BATCH / _SAC_KEY / _SAC_HYPER / _SAC_TAIL);
+# the wrappers below put them together from these pieces.
+_U64 = 2 ** 64 - 1
+
+
+def _sac_head(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN]) -> tuple:
+    """parameter blocks, the six moments, S, A, hidden, n_hidden, E"""
     f32 = th.float32
-    if isinstance(ring, ReplayRing):        # the interleaved block: one base pointer + its row width
-        assert stage.B == B and not stage.discrete and (ring.S, ring.A) == (spec.S, spec.A)
-        dev = ring.block.device
-        rs = _RingSample(ptr(ring.block, f32), None, None, None, None, ring.max_size, ring.num_seqs, ptr(ids, th.int64), int(sample_len),
-                         stage.p_ids0, stage.p_ids1, ring.row_floats)
-    else:
-        b_states, b_actions, b_rewards, b_undones, b_unmasks = ring
-        max_size, num_seqs, S = b_states.shape
-        assert stage.B == B and not stage.discrete and b_actions.dtype == th.float32
-        dev = b_states.device
-        rs = _RingSample(ptr(b_states, f32), ptr(b_actions, f32), ptr(b_rewards, f32), ptr(b_undones, f32), ptr(b_unmasks, f32), max_size, num_seqs,
-                         ptr(ids, th.int64), int(sample_len), stage.p_ids0, stage.p_ids1, 0)
-    ws = _workspace(dev, spec.workspace_bytes(B))
-    n_next, n_cur = (None, None) if noises is None else noises
-    check(lib().erl_sac_update_ring_f32(ptr(actor, f32), ptr(critic, f32), ptr(target, f32), ptr(alpha_log, f32), *[ptr(m, f32) for m in moments],
-                                        spec.S, spec.A, spec._c, len(spec.hidden), spec.E, ctypes.addressof(rs), stage.p_state, stage.p_action,
-                                        stage.p_reward, stage.p_undone, stage.p_unmask, stage.p_next, B, ptr(n_next), ptr(n_cur),
-                                        seed & (2 ** 64 - 1), counter & (2 ** 64 - 1), gamma, target_entropy, tau, lr, betas[0], betas[1], eps,
-                                        max_norm, step, ptr(objs_out, f32), ptr(ws), ws.numel(), stream_ptr()),
-          "erl_sac_update_ring_f32")
+    return (ptr(actor, f32), ptr(critic, f32), ptr(target, f32), ptr(alpha_log, f32), *[ptr(m, f32) for m in moments],
+            spec.S, spec.A, spec._c, len(spec.hidden), spec.E)
 
 
-def sac_update_ring_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring, ids_all: TEN,
-                         sample_len: int, stage: ReplayStage, step0: int, *, gamma: float, target_entropy: float, tau: float, lr: float,
-                         max_norm: float, objs_all: TEN, seed: int = 0, counter0: int = 0, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
-    """`ids_all.shape[0]` steps of sac_update_from_ring from ONE C call (erl_sac_update_ring_loop_f32): step t uses ids_all[t], optimiser
-    step step0 + t, noise counter counter0 + t, and writes objs_all[t]; `stage` ends up holding the last step's batch and ids0 / ids1."""
-    T, B = ids_all.shape
-    f32 = th.float32
-    assert ids_all.is_contiguous() and objs_all.shape == (T, 2) and objs_all.is_contiguous() and stage.B == B and not stage.discrete
-    if isinstance(ring, ReplayRing):
-        assert (ring.S, ring.A) == (spec.S, spec.A)
-        dev = ring.block.device
-        rs = _RingSample(ptr(ring.block, f32), None, None, None, None, ring.max_size, ring.num_seqs, None, int(sample_len), stage.p_ids0,
-                         stage.p_ids1, ring.row_floats)
-    else:
-        b_states, b_actions, b_rewards, b_undones, b_unmasks = ring
-        max_size, num_seqs, S = b_states.shape
-        dev = b_states.device
-        rs = _RingSample(ptr(b_states, f32), ptr(b_actions, f32), ptr(b_rewards, f32), ptr(b_undones, f32), ptr(b_unmasks, f32), max_size, num_seqs,
-                         None, int(sample_len), stage.p_ids0, stage.p_ids1, 0)
-    ws = _workspace(dev, spec.workspace_bytes(B))
-    check(lib().erl_sac_update_ring_loop_f32(ptr(actor, f32), ptr(critic, f32), ptr(target, f32), ptr(alpha_log, f32), *[ptr(m, f32) for m in moments],
-                                             spec.S, spec.A, spec._c, len(spec.hidden), spec.E, ctypes.addressof(rs), ptr(ids_all, th.int64), T,
-                                             stage.p_state, stage.p_action, stage.p_reward, stage.p_undone, stage.p_unmask, stage.p_next, B,
-                                             seed & (2 ** 64 - 1), counter0 & (2 ** 64 - 1), gamma, target_entropy, tau, lr, betas[0], betas[1], eps,
-                                             max_norm, int(step0), ptr(objs_all, f32), ptr(ws), ws.numel(), stream_ptr()),
-          "erl_sac_update_ring_loop_f32")
+def _sac_batch(batch: Sequence[TEN]) -> tuple:
+    return tuple(ptr(t, th.float32) for t in batch)
 
 
-def sac_mod_fused_supported(spec: SacSpec, B: int) -> bool:
-    """the fused AgentModSAC step (erl_sac_update_mod_*) covers this shape (erl_sac_mod_fused_supported)"""
-    return bool(lib().erl_sac_mod_fused_supported(spec.S, spec.A, spec._c, len(spec.hidden), spec.E, int(B)))
+def _sac_stage(stage: ReplayStage) -> tuple:
+    """the staging block a ring entry's sample fills, as the batch pointers"""
+    return stage.p_state, stage.p_action, stage.p_reward, stage.p_undone, stage.p_unmask, stage.p_next
+
+
+def _sac_hyper(seed: int, counter: int, gamma, target_entropy, tau, lr, betas, eps, max_norm) -> tuple:
+    """seed and counter as 64-bit words, then the eight hyper-parameter floats"""
+    return seed & _U64, counter & _U64, gamma, target_entropy, tau, lr, betas[0], betas[1], eps, max_norm
+
+
+def _sac_tail(spec: SacSpec, device: th.device, B: int) -> tuple:
+    ws = _workspace(device, spec.workspace_bytes(B))
+    return ptr(ws), ws.numel(), stream_ptr()
 
 
 def _ring_sample(spec: SacSpec, ring, ids: Optional[TEN], sample_len: int, stage: ReplayStage, B: int):
@@ -869,6 +809,64 @@ def _ring_sample(spec: SacSpec, ring, ids: Optional[TEN], sample_len: int, stage
                        ptr(ids, th.int64), int(sample_len), stage.p_ids0, stage.p_ids1, 0), b_states.device
 
 
+def sac_update(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], batch: Sequence[TEN],
+               step: int, *, gamma: float, target_entropy: float, tau: float, lr: float, max_norm: float, objs_out: TEN,
+               noises: Optional[Tuple[TEN, TEN]] = None, seed: int = 0, counter: int = 0, betas=(0.9, 0.999), eps: float = 1e-8,
+               is_weight: Optional[TEN] = None, td_error_out: Optional[TEN] = None, cum_reward: Optional[TEN] = None,
+               lambda_fit_cum_r: float = 0.0, update_actor: bool = True, actor_step: int = 0, actor_target: Optional[TEN] = None) -> None:
+    """one AgentSAC.update_objectives step after the sample; `moments` = (actor_m, actor_v, critic_m, critic_v, alpha_m,
+    alpha_v); `batch` = (state, action, reward, undone, unmask, next_state); objs_out: float32[2] on the device.
+    `cum_reward` (B,) + `lambda_fit_cum_r`: the critic's fit-the-batch's-mean-return term (AgentSAC.py:66-68)."""
+    B = batch[0].shape[0]
+    n_next, n_cur = (None, None) if noises is None else noises
+    args = (*_sac_head(spec, actor, critic, target, alpha_log, moments), *_sac_batch(batch), ptr(is_weight), ptr(td_error_out), ptr(cum_reward),
+            float(lambda_fit_cum_r), B, ptr(n_next), ptr(n_cur), *_sac_hyper(seed, counter, gamma, target_entropy, tau, lr, betas, eps, max_norm),
+            step, ptr(objs_out, th.float32))
+    ws, ws_bytes, stream = _sac_tail(spec, batch[0].device, B)
+    if spec.actor_variant or not update_actor or actor_step or actor_target is not None:
+        # AgentModSAC's step (include/erl_hip.h, ErlSacOptions): ActorFixSAC's head, the actor skipped by the two-time-scale rule, the
+        # actor optimiser's own step count, the actor target's soft update
+        opt = _SacOptions(spec.actor_variant, int(bool(update_actor)), int(actor_step), 0, ptr(actor_target, th.float32))
+        check(lib().erl_sac_update_opt_f32(*args, ws, ws_bytes, ctypes.byref(opt), stream), "erl_sac_update_opt_f32")
+        return
+    check(lib().erl_sac_update_f32(*args, ws, ws_bytes, stream), "erl_sac_update_f32")
+
+
+def sac_update_from_ring(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring: Sequence[TEN],
+                         ids: TEN, sample_len: int, stage: ReplayStage, step: int, *, gamma: float, target_entropy: float, tau: float, lr: float,
+                         max_norm: float, objs_out: TEN, noises: Optional[Tuple[TEN, TEN]] = None, seed: int = 0, counter: int = 0,
+                         betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+    """ReplayBuffer.sample(ids) + one AgentSAC.update_objectives step from ONE call (erl_sac_update_ring_f32): `ring` = the buffer's
+    ReplayRing (interleaved block) or its five planar tensors (states, actions, rewards, undones, unmasks), `stage` receives the batch (stage.out / stage.ids: what replay_sample would have left)."""
+    B = ids.numel()
+    rs, dev = _ring_sample(spec, ring, ids, sample_len, stage, B)
+    n_next, n_cur = (None, None) if noises is None else noises
+    check(lib().erl_sac_update_ring_f32(*_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs), *_sac_stage(stage), B,
+                                        ptr(n_next), ptr(n_cur), *_sac_hyper(seed, counter, gamma, target_entropy, tau, lr, betas, eps, max_norm),
+                                        step, ptr(objs_out, th.float32), *_sac_tail(spec, dev, B)),
+          "erl_sac_update_ring_f32")
+
+
+def sac_update_ring_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring, ids_all: TEN,
+                         sample_len: int, stage: ReplayStage, step0: int, *, gamma: float, target_entropy: float, tau: float, lr: float,
+                         max_norm: float, objs_all: TEN, seed: int = 0, counter0: int = 0, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+    """`ids_all.shape[0]` steps of sac_update_from_ring from ONE C call (erl_sac_update_ring_loop_f32): step t uses ids_all[t], optimiser
+    step step0 + t, noise counter counter0 + t, and writes objs_all[t]; `stage` ends up holding the last step's batch and ids0 / ids1."""
+    T, B = ids_all.shape
+    assert ids_all.is_contiguous() and objs_all.shape == (T, 2) and objs_all.is_contiguous()
+    rs, dev = _ring_sample(spec, ring, None, sample_len, stage, B)
+    check(lib().erl_sac_update_ring_loop_f32(*_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs),
+                                             ptr(ids_all, th.int64), T, *_sac_stage(stage), B,
+                                             *_sac_hyper(seed, counter0, gamma, target_entropy, tau, lr, betas, eps, max_norm), int(step0),
+                                             ptr(objs_all, th.float32), *_sac_tail(spec, dev, B)),
+          "erl_sac_update_ring_loop_f32")
+
+
+def sac_mod_fused_supported(spec: SacSpec, B: int) -> bool:
+    """the fused AgentModSAC step (erl_sac_update_mod_*) covers this shape (erl_sac_mod_fused_supported)"""
+    return bool(lib().erl_sac_mod_fused_supported(spec.S, spec.A, spec._c, len(spec.hidden), spec.E, int(B)))
+
+
 def sac_update_mod(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], batch: Sequence[TEN],
                    step: int, *, gamma: float, target_entropy: float, tau: float, lr: float, max_norm: float, objs_out: TEN,
                    update_actor: bool, actor_step: int, actor_target: Optional[TEN], noises: Optional[Tuple[TEN, TEN]] = None, seed: int = 0,
@@ -876,17 +874,13 @@ def sac_update_mod(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_lo
                    td_error_out: Optional[TEN] = None) -> None:
     """one AgentModSAC.update_objectives step after the sample on the FUSED step (erl_sac_update_mod_f32): sac_update's arguments without
     the cum_reward term; `update_actor` False leaves the actor, its moments and `actor_target` untouched and writes nan to objs_out[1]"""
-    state, action, reward, undone, unmask, next_state = batch
-    B = state.shape[0]
-    ws = _workspace(state.device, spec.workspace_bytes(B))
+    B = batch[0].shape[0]
     n_next, n_cur = (None, None) if noises is None else noises
-    f32 = th.float32
-    check(lib().erl_sac_update_mod_f32(ptr(actor, f32), ptr(critic, f32), ptr(target, f32), ptr(alpha_log, f32), *[ptr(m, f32) for m in moments],
-                                       spec.S, spec.A, spec._c, len(spec.hidden), spec.E, ptr(state, f32), ptr(action, f32), ptr(reward, f32),
-                                       ptr(undone, f32), ptr(unmask, f32), ptr(next_state, f32), ptr(is_weight), ptr(td_error_out), B, ptr(n_next),
-                                       ptr(n_cur), seed & (2 ** 64 - 1), counter & (2 ** 64 - 1), gamma, target_entropy, tau, lr, betas[0],
-                                       betas[1], eps, max_norm, step, int(bool(update_actor)), int(actor_step), ptr(actor_target, f32),
-                                       ptr(objs_out, f32), ptr(ws), ws.numel(), stream_ptr()),
+    check(lib().erl_sac_update_mod_f32(*_sac_head(spec, actor, critic, target, alpha_log, moments), *_sac_batch(batch), ptr(is_weight),
+                                       ptr(td_error_out), B, ptr(n_next), ptr(n_cur),
+                                       *_sac_hyper(seed, counter, gamma, target_entropy, tau, lr, betas, eps, max_norm), step,
+                                       int(bool(update_actor)), int(actor_step), ptr(actor_target, th.float32), ptr(objs_out, th.float32),
+                                       *_sac_tail(spec, batch[0].device, B)),
           "erl_sac_update_mod_f32")
 
 
@@ -897,16 +891,13 @@ def sac_update_mod_from_ring(spec: SacSpec, actor: TEN, critic: TEN, target: TEN
                              eps: float = 1e-8) -> None:
     """sac_update_from_ring for AgentModSAC's fused step (erl_sac_update_mod_ring_f32): the sample rides in the step's first launch"""
     B = ids.numel()
-    f32 = th.float32
     rs, dev = _ring_sample(spec, ring, ids, sample_len, stage, B)
-    ws = _workspace(dev, spec.workspace_bytes(B))
     n_next, n_cur = (None, None) if noises is None else noises
-    check(lib().erl_sac_update_mod_ring_f32(ptr(actor, f32), ptr(critic, f32), ptr(target, f32), ptr(alpha_log, f32), *[ptr(m, f32) for m in moments],
-                                            spec.S, spec.A, spec._c, len(spec.hidden), spec.E, ctypes.addressof(rs), stage.p_state, stage.p_action,
-                                            stage.p_reward, stage.p_undone, stage.p_unmask, stage.p_next, B, ptr(n_next), ptr(n_cur),
-                                            seed & (2 ** 64 - 1), counter & (2 ** 64 - 1), gamma, target_entropy, tau, lr, betas[0], betas[1], eps,
-                                            max_norm, step, int(bool(update_actor)), int(actor_step), ptr(actor_target, f32), ptr(objs_out, f32),
-                                            ptr(ws), ws.numel(), stream_ptr()),
+    check(lib().erl_sac_update_mod_ring_f32(*_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs), *_sac_stage(stage),
+                                            B, ptr(n_next), ptr(n_cur),
+                                            *_sac_hyper(seed, counter, gamma, target_entropy, tau, lr, betas, eps, max_norm), step,
+                                            int(bool(update_actor)), int(actor_step), ptr(actor_target, th.float32), ptr(objs_out, th.float32),
+                                            *_sac_tail(spec, dev, B)),
           "erl_sac_update_mod_ring_f32")
 
 
@@ -918,26 +909,16 @@ def sac_update_mod_ring_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN
     ids_all[t], optimiser step step0 + t, noise counter counter0 + t, objs_all[t]; the two-time-scale rule is evaluated in C, the actor's
     Adam count runs on from `actor_step0`.  Returns the number of actor updates."""
     T, B = ids_all.shape
-    f32 = th.float32
     assert ids_all.is_contiguous() and objs_all.shape == (T, 2) and objs_all.is_contiguous()
     rs, dev = _ring_sample(spec, ring, None, sample_len, stage, B)
-    ws = _workspace(dev, spec.workspace_bytes(B))
     updates = ctypes.c_int32(0)
-    check(lib().erl_sac_update_mod_ring_loop_f32(ptr(actor, f32), ptr(critic, f32), ptr(target, f32), ptr(alpha_log, f32),
-                                                 *[ptr(m, f32) for m in moments], spec.S, spec.A, spec._c, len(spec.hidden), spec.E,
-                                                 ctypes.addressof(rs), ptr(ids_all, th.int64), T, stage.p_state, stage.p_action, stage.p_reward,
-                                                 stage.p_undone, stage.p_unmask, stage.p_next, B, seed & (2 ** 64 - 1), counter0 & (2 ** 64 - 1),
-                                                 gamma, target_entropy, tau, lr, betas[0], betas[1], eps, max_norm, int(step0), int(actor_step0),
-                                                 float(critic_value), ptr(actor_target, f32), ptr(objs_all, f32), ctypes.byref(updates), ptr(ws),
-                                                 ws.numel(), stream_ptr()),
+    check(lib().erl_sac_update_mod_ring_loop_f32(*_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs),
+                                                 ptr(ids_all, th.int64), T, *_sac_stage(stage), B,
+                                                 *_sac_hyper(seed, counter0, gamma, target_entropy, tau, lr, betas, eps, max_norm), int(step0),
+                                                 int(actor_step0), float(critic_value), ptr(actor_target, th.float32), ptr(objs_all, th.float32),
+                                                 ctypes.byref(updates), *_sac_tail(spec, dev, B)),
           "erl_sac_update_mod_ring_loop_f32")
     return int(updates.value)
-
-
-class _PerSample(ctypes.Structure):         # include/erl_hip.h ErlPerSample
-    _fields_ = [("sum_tree", ctypes.c_void_p), ("min_tree", ctypes.c_void_p), ("max_size", ctypes.c_int64), ("num_seqs", ctypes.c_int64),
-                ("cur_size", ctypes.c_int64), ("cursor", ctypes.c_int64), ("per_alpha", ctypes.c_float), ("per_beta", ctypes.c_float),
-                ("uniform_all", ctypes.c_void_p), ("is_index", ctypes.c_void_p), ("is_weight", ctypes.c_void_p), ("td_error", ctypes.c_void_p)]
 
 
 def sac_update_per_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring: ReplayRing,
@@ -950,20 +931,15 @@ def sac_update_per_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alp
     T, Q, n = uniform_all.shape
     B = Q * n
     f32 = th.float32
-    assert isinstance(ring, ReplayRing) and (ring.S, ring.A) == (spec.S, spec.A) and Q == trees.num_seqs == ring.num_seqs
+    assert isinstance(ring, ReplayRing) and Q == trees.num_seqs == ring.num_seqs and per_stage.B == B
     assert uniform_all.is_contiguous() and objs_all.shape == (T, 2) and objs_all.is_contiguous()
-    assert stage.B == B and per_stage.B == B and not stage.discrete
-    rs = _RingSample(ptr(ring.block, f32), None, None, None, None, ring.max_size, ring.num_seqs, None, 0, stage.p_ids0, stage.p_ids1,
-                     ring.row_floats)
+    rs, dev = _ring_sample(spec, ring, None, 0, stage, B)
     pr = _PerSample(ptr(trees.sum, f32), ptr(trees.min, f32), trees.max_size, trees.num_seqs, int(cur_size), int(cursor), float(per_alpha),
                     float(per_beta), ptr(uniform_all, f32), ptr(per_stage.is_index, th.int64), ptr(per_stage.is_weight, f32),
                     ptr(per_stage.td_error, f32))
-    ws = _workspace(ring.block.device, spec.workspace_bytes(B))
-    check(lib().erl_sac_update_per_loop_f32(ptr(actor, f32), ptr(critic, f32), ptr(target, f32), ptr(alpha_log, f32), *[ptr(m, f32) for m in moments],
-                                            spec.S, spec.A, spec._c, len(spec.hidden), spec.E, ctypes.addressof(rs), ctypes.addressof(pr), T,
-                                            stage.p_state, stage.p_action, stage.p_reward, stage.p_undone, stage.p_unmask, stage.p_next, B,
-                                            seed & (2 ** 64 - 1), counter0 & (2 ** 64 - 1), gamma, target_entropy, tau, lr, betas[0], betas[1], eps,
-                                            max_norm, int(step0), ptr(objs_all, f32), ptr(ws), ws.numel(), stream_ptr()),
+    check(lib().erl_sac_update_per_loop_f32(*_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs), ctypes.addressof(pr),
+                                            T, *_sac_stage(stage), B, *_sac_hyper(seed, counter0, gamma, target_entropy, tau, lr, betas, eps, max_norm),
+                                            int(step0), ptr(objs_all, f32), *_sac_tail(spec, dev, B)),
           "erl_sac_update_per_loop_f32")
 
 
