@@ -5,8 +5,8 @@ elegantrl/envs/PointChasingEnv.py:84-182 as the in-tree exemplar).
 
 They additionally expose `step_into(action, reward_row, terminal_row, truncate_row) -> state`, which lets the
 rollout write step outputs straight into row t of its time-major buffers (no copies, no host sync).
-The dynamics run in erl_synenv_step_f32 / erl_pendulum_step_f32 (elegantrl_amd/csrc/envs.hip) and erl_cartpole_step_f32
-(elegantrl_amd/csrc/rollout_discrete.hip).
+The dynamics run in erl_synenv_step_f32 / erl_pendulum_step_f32 (elegantrl_amd/csrc/envs.hip) and erl_cartpole_step_f32 /
+erl_acrobot_step_f32 (elegantrl_amd/csrc/rollout_discrete.hip).
 """
 from __future__ import annotations
 
@@ -339,6 +339,78 @@ class CartPoleGpuVecEnv(_GpuVecEnv):
         _hip.check(_hip.lib().erl_eval_discrete_cartpole_f32(
             *self._policy_args(agent), horizon_len, _hip.ptr(workspace, th.uint8), workspace.numel(), _hip.stream_ptr()),
             "erl_eval_discrete_cartpole_f32")
+
+
+class AcrobotGpuVecEnv(_GpuVecEnv):
+    """Acrobot-v1 for N envs on the device (erl_acrobot_step_f32): gymnasium's "book" dynamics -- two unit links, g 9.8, dt 0.2, one RK4
+    step, angles wrapped into [-pi, pi], velocities clipped to +-4 pi / +-9 pi; action 0 / 1 / 2 is torque -1 / 0 / +1 (any other value:
+    0); terminal when -cos(theta1) - cos(theta1 + theta2) > 1 on the new state; reward 0 on the terminal step, -1 otherwise; truncation
+    at max_step -- in one launch per step, and behind `fused_rollout_discrete` / `fused_evaluate_discrete` the whole horizon of a discrete
+    agent in one launch.  `phys` (N, 4) = (theta1, theta2, omega1, omega2) is the state of record; `state` (N, 6) = (cos theta1,
+    sin theta1, cos theta2, sin theta2, omega1, omega2) is the live observation.  A done row restarts from four U[-0.1, 0.1) Philox draws
+    keyed by (seed, env, episode, component)."""
+    env_name = "Acrobot-v1"
+    if_discrete = True
+
+    def __init__(self, num_envs: int = 1024, max_step: int = 500, gpu_id: int = 0, seed: int = 0, **_):
+        super().__init__(num_envs, 6, 3, max_step, gpu_id, seed)
+        self.phys = th.zeros((num_envs, 4), dtype=th.float32, device=self.device)
+        self.state = self._observe(self.phys)
+
+    @staticmethod
+    def _observe(phys: TEN) -> TEN:
+        return th.stack((phys[:, 0].cos(), phys[:, 0].sin(), phys[:, 1].cos(), phys[:, 1].sin(), phys[:, 2], phys[:, 3]), dim=1).contiguous()
+
+    def reset(self) -> Tuple[TEN, dict]:
+        self.state_epoch += 1
+        g = th.Generator(device=self.device).manual_seed(self.seed)
+        self.phys = th.rand((self.num_envs, 4), device=self.device, generator=g) * 0.2 - 0.1
+        self.state = self._observe(self.phys)
+        self.step_count.zero_()
+        self.episode.zero_()
+        return self.state.clone(), {}
+
+    @_hip.on_device
+    def step_into(self, action: TEN, reward_row: TEN, terminal_row: TEN, truncate_row: TEN) -> TEN:
+        from .. import ops
+        self.state_epoch += 1
+        action = action.to(self.device).reshape(-1)
+        if action.dtype != th.int64:
+            action = action.long()
+        ops.acrobot_step(self.phys, self.state, action.contiguous(), self.step_count, self.episode, reward_row, terminal_row, truncate_row,
+                         self.max_step, self.seed)
+        return self.state
+
+    def _policy_args(self, agent):
+        p, f32 = _hip.ptr, th.float32
+        a = agent._act
+        h1, h2 = agent.net_dims
+        return (p(agent._flat_a.flat, f32), p(a.state_avg.data, f32), p(a.state_std.data, f32), self.state_dim, h1, h2, agent.action_dim,
+                p(self.phys, f32), p(self.state, f32), p(self.step_count, th.int32), p(self.episode, th.int32), self.max_step,
+                self.seed & (2 ** 64 - 1), self.num_envs)
+
+    @_hip.on_device
+    def fused_rollout_discrete(self, agent, horizon_len: int, uniform, bufs, last_state_out, uniform_out=None) -> None:
+        """all `horizon_len` steps of AgentDiscretePPO._explore_vec_env in ONE launch (erl_rollout_discrete_acrobot_f32); arguments as
+        CartPoleGpuVecEnv.fused_rollout_discrete, states (H, N, 6) and `last_state_out` (N, 6).  The policy's input at t = 0 is `state` as
+        it stands (the caller may have written its own last state there; `phys` is not disturbed by that), from t = 1 on the
+        observation of `phys`.  `phys`, `state` and the counters advance."""
+        self.state_epoch += 1
+        p, f32 = _hip.ptr, th.float32
+        states, actions, logprobs, rewards, undones, unmasks = bufs
+        _hip.check(_hip.lib().erl_rollout_discrete_acrobot_f32(
+            *self._policy_args(agent), horizon_len, p(uniform, f32), agent.rng_seed & (2 ** 64 - 1), agent.rng_counter & (2 ** 64 - 1),
+            float(agent.reward_scale), p(states, f32), p(actions, th.int32), p(logprobs, f32), p(rewards, f32), _hip.flag_ptr(undones),
+            _hip.flag_ptr(unmasks), p(last_state_out, f32), p(uniform_out, f32), _hip.stream_ptr()), "erl_rollout_discrete_acrobot_f32")
+
+    @_hip.on_device
+    def fused_evaluate_discrete(self, agent, horizon_len: int, workspace) -> None:
+        """`horizon_len` steps of the greedy policy argmax(logits) of a discrete agent in ONE launch (erl_eval_discrete_acrobot_f32: the
+        evaluation form of `fused_rollout_discrete`); records and counts go to `workspace` as SynVecEnv.fused_evaluate leaves them."""
+        self.state_epoch += 1
+        _hip.check(_hip.lib().erl_eval_discrete_acrobot_f32(
+            *self._policy_args(agent), horizon_len, _hip.ptr(workspace, th.uint8), workspace.numel(), _hip.stream_ptr()),
+            "erl_eval_discrete_acrobot_f32")
 
 
 class CartPoleVecEnv:

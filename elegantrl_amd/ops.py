@@ -995,6 +995,15 @@ def cartpole_step(state: TEN, action: TEN, step_count: TEN, episode: TEN, reward
           "erl_cartpole_step_f32")
 
 
+def acrobot_step(phys: TEN, obs: TEN, action: TEN, step_count: TEN, episode: TEN, reward: TEN, terminal: TEN, truncate: TEN, max_step: int,
+                 seed: int) -> None:
+    """one Acrobot-v1 step of every env (erl_acrobot_step_f32): phys (N, 4) in place, obs (N, 6) written from it, action (N,) int64"""
+    check(lib().erl_acrobot_step_f32(ptr(phys, th.float32), ptr(obs, th.float32), ptr(action, th.int64), ptr(step_count, th.int32),
+                                     ptr(episode, th.int32), ptr(reward, th.float32), flag_ptr(terminal), flag_ptr(truncate),
+                                     phys.shape[0], max_step, seed & (2 ** 64 - 1), stream_ptr()),
+          "erl_acrobot_step_f32")
+
+
 def rollout_discrete_supported(S: int, h1: int, h2: int, A: int) -> bool:
     """the policy shapes of the one-launch discrete rollout / evaluation (erl_rollout_discrete_supported)"""
     return bool(lib().erl_rollout_discrete_supported(int(S), int(h1), int(h2), int(A)))

@@ -362,7 +362,7 @@ ERL_API int erl_eval_episodes_compact_f32(const void *workspace, int64_t workspa
  * (erl_eval_workspace_bytes(N, H)), for erl_eval_episodes_compact_f32.
  *
  * erl_rollout_discrete_supported: the policy shapes of the two: S <= 64, two hidden layers of 32..128 in steps of 32, 2 <= A <= 8
- * (the CartPole entry points also need S = 4, the env's).  Anything else is ERL_EINVAL ("unsupported dims") before any launch.
+ * (the CartPole entry points also need S = 4, the env's; the Acrobot ones S = 6 and A = 3).  Anything else is ERL_EINVAL ("unsupported dims") before any launch.
  * No call allocates or synchronises; no workgroup waits for another. */
 ERL_API int erl_rollout_discrete_supported(int S, int h1, int h2, int A);
 ERL_API int erl_cartpole_step_f32(float *state, const int64_t *action, int32_t *step_count, int32_t *episode, float *reward,
@@ -375,6 +375,32 @@ ERL_API int erl_rollout_discrete_cartpole_f32(const float *actor_params, const f
 ERL_API int erl_eval_discrete_cartpole_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2, int A,
                           float *env_state, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
                           void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Acrobot-v1 behind the same kernels (additions to ABI 22; csrc/acrobot_step.h, csrc/rollout_discrete.hip).
+ *
+ * erl_acrobot_step_f32: one step of N envs.  phys (N, 4) = (theta1, theta2, omega1, omega2) is the state of record, obs (N, 6) =
+ * (cos theta1, sin theta1, cos theta2, sin theta2, omega1, omega2) is written from it; action (N,) int64: 0 / 1 / 2 is torque -1 / 0 /
+ * +1, any other value torque 0.  gymnasium's Acrobot-v1 "book" dynamics (m = l = 1, lc = 0.5, I = 1, g = 9.8, dt 0.2, one RK4 step,
+ * angles wrapped into [-pi, pi], omega1 clipped to +-4 pi, omega2 to +-9 pi); terminal = -cos theta1 - cos(theta1 + theta2) > 1 on the
+ * NEW state, truncate = step_count reached max_step and not terminal, reward = 0 on the terminal step and -1 otherwise.  phys / obs /
+ * step_count / episode are updated in place; a done row restarts from four U[-0.1, 0.1) Philox draws keyed by (seed, env, episode,
+ * component), and obs is the observation of the state the env holds after the step.
+ *
+ * erl_rollout_discrete_acrobot_f32 / erl_eval_discrete_acrobot_f32: the CartPole entries above with Acrobot behind the kernel: S must
+ * be 6 and A must be 3; out_states is (H, N, 6), out_last_state (N, 6), out_rewards the env's reward times reward_scale.  The policy's
+ * input at t = 0 is `obs` as handed in (so states[0] is the caller's last state, whatever phys says); from t = 1 on it is the
+ * observation of phys, as in the per-step loop.  phys / obs / step_count / episode are read at entry and written back at exit.  The env
+ * rows are bit-identical to erl_acrobot_step_f32 fed the recorded actions. */
+ERL_API int erl_acrobot_step_f32(float *phys, float *obs, const int64_t *action, int32_t *step_count, int32_t *episode, float *reward,
+                          uint8_t *terminal, uint8_t *truncate, int64_t N, int max_step, uint64_t seed, void *stream);
+ERL_API int erl_rollout_discrete_acrobot_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2,
+                          int A, float *phys, float *obs, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
+                          int64_t N, int64_t H, const float *uniform, uint64_t seed, uint64_t counter0, float reward_scale,
+                          float *out_states, int32_t *out_actions, float *out_logprobs, float *out_rewards, uint8_t *out_undones,
+                          uint8_t *out_unmasks, float *out_last_state, float *out_uniform, void *stream);
+ERL_API int erl_eval_discrete_acrobot_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2, int A,
+                          float *phys, float *obs, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N,
+                          int64_t H, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* K6  one PPO minibatch: gather (K5 indices) + critic fwd/bwd + actor fwd/bwd, both networks in one
  * launch.  Replaces AgentPPO.update_objectives up to (not including) the two optimizer steps

@@ -1,0 +1,99 @@
+"""CPU-side checks of the Acrobot entry points (csrc/rollout_discrete.hip, csrc/acrobot_step.h): the three symbols in the header, the
+binding and the library at ABI 22, argument validation before any launch, and the compat import of the new env (no GPU)."""
+import ctypes
+import os
+import re
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("erl_acrobot_step_f32", "erl_rollout_discrete_acrobot_f32", "erl_eval_discrete_acrobot_f32")
+UNSUPPORTED = ((4, 100, 32, 2), (65, 64, 32, 2), (4, 64, 32, 9), (4, 64, 32, 1), (4, 256, 64, 2))        # those of the CartPole ABI test
+
+
+def test_abi_is_still_22_with_the_three_symbols():
+    from elegantrl_amd import _hip
+    txt = open(os.path.join(ROOT, "include", "erl_hip.h")).read()
+    assert int(re.search(r"#define ERL_ABI_VERSION (\d+)", txt).group(1)) == _hip.ABI_VERSION == _hip.lib().erl_abi_version() == 22
+    for name in NAMES:
+        assert name in _hip.EXPORTED_SYMBOLS and re.search(r"ERL_API int " + name + r"\(", txt)
+        assert getattr(_hip.lib(), name) is not None
+    # the header's parameter count is the binding's
+    for name in NAMES:
+        proto = re.search(r"ERL_API int " + name + r"\(([^;]*)\);", txt).group(1)
+        assert len(proto.split(",")) == len(_hip._SIGNATURES[name][1]), name
+    # the shape query is what it was: Acrobot's shape is inside it
+    assert _hip.lib().erl_rollout_discrete_supported(6, 64, 32, 3) == 1
+
+
+def test_entry_points_validate_before_any_launch():
+    from elegantrl_amd import _hip
+    L = _hip.lib()
+    err = L.erl_last_error_string
+    ro, ev = L.erl_rollout_discrete_acrobot_f32, L.erl_eval_discrete_acrobot_f32
+    # NULL tensors
+    rc = L.erl_acrobot_step_f32(None, None, None, None, None, None, None, None, 64, 5, 0, None)
+    assert rc == -1 and b"erl_acrobot_step_f32" in err() and b"NULL" in err()
+    rc = ro(None, None, None, 6, 64, 32, 3, None, None, None, None, 5, 0, 64, 8, None, 0, 0, 1.0, None, None, None, None, None, None, None,
+            None, None)
+    assert rc == -1 and b"erl_rollout_discrete_acrobot_f32" in err() and b"NULL" in err()
+    rc = ev(None, None, None, 6, 64, 32, 3, None, None, None, None, 5, 0, 64, 8, None, 0, None)
+    assert rc == -1 and b"erl_eval_discrete_acrobot_f32" in err() and b"NULL" in err()
+    # dummy non-NULL host addresses: never dereferenced, nothing is launched
+    buf = (ctypes.c_char * 4096)()
+    p = ctypes.addressof(buf)
+    # one NULL among them is enough: the observation buffer, the physical state, an output row
+    rc = ro(p, p, p, 6, 64, 32, 3, p, None, p, p, 5, 0, 64, 8, None, 0, 0, 1.0, p, p, p, p, p, p, None, None, None)
+    assert rc == -1 and b"NULL" in err()
+    rc = ev(p, p, p, 6, 64, 32, 3, None, p, p, p, 5, 0, 64, 8, p, 1 << 20, None)
+    assert rc == -1 and b"NULL" in err()
+    rc = ro(p, p, p, 6, 64, 32, 3, p, p, p, p, 5, 0, 64, 8, None, 0, 0, 1.0, p, p, p, None, p, p, None, None, None)
+    assert rc == -1 and b"NULL" in err()
+    # unsupported dims are refused whatever the pointers are
+    for dims in UNSUPPORTED:
+        rc = ro(p, p, p, *dims, p, p, p, p, 5, 0, 64, 8, None, 0, 0, 1.0, p, p, p, p, p, p, None, None, None)
+        assert rc == -1 and b"erl_rollout_discrete_acrobot_f32" in err() and b"unsupported dims" in err(), dims
+        rc = ev(p, p, p, *dims, p, p, p, p, 5, 0, 64, 8, p, 1 << 20, None)
+        assert rc == -1 and b"erl_eval_discrete_acrobot_f32" in err() and b"unsupported dims" in err(), dims
+    # a policy shape the kernel has, on an env that is not Acrobot's (state_dim 6, action_dim 3)
+    for dims, msg in (((4, 64, 32, 3), b"state_dim is 6"), ((6, 64, 32, 2), b"action_dim is 3"), ((4, 64, 32, 2), b"state_dim is 6")):
+        rc = ro(p, p, p, *dims, p, p, p, p, 5, 0, 64, 8, None, 0, 0, 1.0, p, p, p, p, p, p, None, None, None)
+        assert rc == -1 and b"erl_rollout_discrete_acrobot_f32" in err() and msg in err(), (dims, err())
+        rc = ev(p, p, p, *dims, p, p, p, p, 5, 0, 64, 8, p, 1 << 20, None)
+        assert rc == -1 and b"erl_eval_discrete_acrobot_f32" in err() and msg in err(), (dims, err())
+    # a workspace smaller than the query says
+    need = L.erl_eval_workspace_bytes(64, 8)
+    rc = ev(p, p, p, 6, 64, 32, 3, p, p, p, p, 5, 0, 64, 8, p, need - 1, None)
+    assert rc == -1 and b"erl_eval_discrete_acrobot_f32" in err() and b"erl_eval_workspace_bytes" in err()
+    # bad shapes: N = 0, max_step = 0
+    rc = L.erl_acrobot_step_f32(p, p, p, p, p, p, p, p, 0, 5, 0, None)
+    assert rc == -1 and b"erl_acrobot_step_f32" in err() and b"bad shape" in err()
+    rc = L.erl_acrobot_step_f32(p, p, p, p, p, p, p, p, 64, 0, 0, None)
+    assert rc == -1 and b"erl_acrobot_step_f32" in err() and b"bad shape" in err()
+    for n, ms in ((0, 5), (64, 0)):
+        rc = ro(p, p, p, 6, 64, 32, 3, p, p, p, p, ms, 0, n, 8, None, 0, 0, 1.0, p, p, p, p, p, p, None, None, None)
+        assert rc == -1 and b"erl_rollout_discrete_acrobot_f32" in err() and b"bad shape" in err()
+        rc = ev(p, p, p, 6, 64, 32, 3, p, p, p, p, ms, 0, n, 8, p, 1 << 20, None)
+        assert rc == -1 and b"erl_eval_discrete_acrobot_f32" in err() and b"bad shape" in err()
+
+
+def test_kernel_path_names_both_envs(monkeypatch):
+    """the text is built without a device"""
+    monkeypatch.delenv("ERL_FUSED_ROLLOUT", raising=False)
+    from elegantrl_amd.agents import AgentDiscretePPO
+    from elegantrl_amd.train import Config
+    args = Config(AgentDiscretePPO, None, {"env_name": "Acrobot-v1", "num_envs": 8, "max_step": 10, "state_dim": 6, "action_dim": 3,
+                                           "if_discrete": True})
+    args.net_dims, args.quiet, args.fused_rollout = [64, 32], True, True
+    path = AgentDiscretePPO(args.net_dims, 6, 3, gpu_id=-1, args=args).kernel_path
+    assert "one-launch rollout and evaluation" in path and "AcrobotGpuVecEnv" in path and "CartPoleGpuVecEnv" in path
+
+
+def test_compat_import_of_the_new_env():
+    code = ("from elegantrl.envs import AcrobotGpuVecEnv\nimport elegantrl_amd.envs as real\n"
+            "assert AcrobotGpuVecEnv is real.AcrobotGpuVecEnv and AcrobotGpuVecEnv.if_discrete and AcrobotGpuVecEnv.env_name == 'Acrobot-v1'\n"
+            "print('ok')\n")
+    env = dict(os.environ, PYTHONPATH=ROOT, PYTHONDONTWRITEBYTECODE="1")
+    out = subprocess.run([sys.executable, "-c", code], cwd="/", env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    assert out.stdout.strip().endswith("ok")
