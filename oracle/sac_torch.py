@@ -208,3 +208,57 @@ class ModSacStepper(SacStepper):
                     tar.data.copy_(cur.data * self.tau + tar.data * (1.0 - self.tau))
             return obj_critic.item(), obj_actor.item()
         return obj_critic.item(), float("nan")
+
+
+def step_gradients(stepper: SacStepper, batch, eps_next: TEN, eps_cur: TEN, *, dtype, is_weight: Optional[TEN] = None,
+                   cum_reward: Optional[TEN] = None, lambda_fit_cum_r: float = 0.0, update_actor: bool = True):
+    """The raw (unclipped) gradients of one `step()` of a SacStepper / ModSacStepper whose optimisers do not move anything (lr = 0), on a
+    deep copy of its networks cast to `dtype`; the stepper itself is left alone.  Order of events as in `step()`: labels from the target,
+    critic gradient of obj_critic, soft update of the target with the (unchanged) critic, temperature gradient
+    target_entropy - mean(logprob), actor gradient of -obj_actor against the updated target.
+
+    Returns (grads, info): `grads` maps state_dict names of the actor and the critic, and "alpha_log", to gradients (an actor that is not
+    updated has none); `info` holds "obj_critic", "obj_actor" (nan without the actor step), the per-sample "td_error", the head's
+    pre-clamp "log_std" on `state` and "log_std_next" on `next_state` (B, A), and "target": the soft-updated target's state_dict."""
+    cast = lambda x: None if x is None else x.detach().to(dtype)  # noqa: E731
+    act, cri, tar = (deepcopy(m).to(dtype) for m in (stepper.act, stepper.cri, stepper.cri_target))
+    alpha_log = stepper.alpha_log.detach().to(dtype).requires_grad_(True)
+    state, action, reward, undone, unmask, next_state = (cast(x) for x in batch)
+    eps_next, eps_cur, is_weight, cum_reward = cast(eps_next), cast(eps_cur), cast(is_weight), cast(cum_reward)
+    gamma, tau = stepper.gamma, stepper.tau
+    for m in (act, cri, tar):
+        m.zero_grad()
+
+    def head_log_std(x: TEN) -> TEN:
+        if isinstance(act, ActorFixSAC):
+            return act.decoder_a_std(act.encoder_s(x))
+        return act.net_a(act.net_s(x)).chunk(2, dim=1)[1]
+
+    with th.enable_grad():
+        with th.no_grad():
+            next_action, next_logprob = act.get_action_logprob(next_state, eps_next)
+            next_q = th.min(tar.get_q_values(next_state, next_action), dim=1)[0]
+            q_label = reward + undone * gamma * (next_q - next_logprob * alpha_log.exp())
+            log_std, log_std_next = head_log_std(state), head_log_std(next_state)
+        q_values = cri.get_q_values(state, action)
+        td = ((q_values - q_label.view(-1, 1)) ** 2).mean(dim=1) * unmask
+        obj_critic = td.mean() if is_weight is None else (td * is_weight).mean()
+        if lambda_fit_cum_r:
+            cum_reward_mean = cum_reward.mean().repeat(q_values.shape[1])
+            obj_critic = obj_critic + ((cum_reward_mean - q_values.mean(dim=0)) ** 2).mean() * lambda_fit_cum_r
+        obj_critic.backward()
+        with th.no_grad():
+            for t, c in zip(tar.parameters(), cri.parameters()):
+                t.copy_(c * tau + t * (1.0 - tau))
+        action_pg, logprob = act.get_action_logprob(state, eps_cur)
+        (alpha_log * (stepper.target_entropy - logprob).detach()).mean().backward()
+        grads = {k: p.grad.detach().clone() for k, p in cri.named_parameters()}
+        grads["alpha_log"] = alpha_log.grad.detach().clone()
+        obj_actor = th.tensor(float("nan"), dtype=dtype)
+        if update_actor:
+            obj_actor = (tar(state, action_pg).mean() - logprob * alpha_log.exp().detach()).mean()
+            (-obj_actor).backward()
+            grads.update({k: p.grad.detach().clone() for k, p in act.named_parameters()})
+    info = {"obj_critic": obj_critic.item(), "obj_actor": obj_actor.item(), "td_error": td.detach().clone(), "log_std": log_std,
+            "log_std_next": log_std_next, "target": {k: v.detach().clone() for k, v in tar.state_dict().items()}}
+    return grads, info
