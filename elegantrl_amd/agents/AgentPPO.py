@@ -609,13 +609,20 @@ class AgentPPO(AgentBase):
         # the job's exchange route (selected once, by a self-test: parallel.gradient_comm); None: torch.distributed
         comm = parallel.gradient_comm(self._stride) if dp else None
         c_loop = self._fused_update and (not dp or comm is not None)       # the whole minibatch loop in one C call (below)
+        # the categorical policy's fused route (AgentDiscretePPO._update_discrete_fused): its own slab / gradient-row stride
+        fused_d = self._discrete_update_fused(dp)
         cached = self._cached_values(states)
         from_rollout = None
         if cached is not None:                                                        # left by the fused rollout (same critic)
-            values, next_value = cached
-            if c_loop:
+            if c_loop or fused_d:
                 from_rollout = self._cached_advantages(rewards, undones, unmasks)     # ... and get_advantages + its sums
             self._rollout_cache = None                                                # the GAE below mutates rewards / undones
+            if self._discrete and from_rollout is None:
+                # a discrete agent takes what its rollout left whole or not at all (the layered and data-parallel routes, a cache an
+                # edit has invalidated in part): the values of the rollout's register chain are not the pre-pass's bits
+                cached = None
+        if cached is not None:
+            values, next_value = cached
         else:
             values, next_value = self.get_values(states), None                        # (H, N)
         if from_rollout is not None:
@@ -623,12 +630,14 @@ class AgentPPO(AgentBase):
             # explore_env returned: get_advantages' in-place fix-up of truncated steps rides the last launch (erl_ppo_finish_f32)
             advantages, reward_sums, stats, adv_parts, n_parts = from_rollout
             self._stats = stats                # (the sums this update normalised with stay inspectable, as on the other path)
-            if self.world_size > 1:            # the sums are all-reduced below: fold them now (one small launch)
-                ops.adv_stats_fold(adv_parts, n_parts, H, N, stats)
+            if self.world_size > 1 or not c_loop:    # the sums are all-reduced below, or (the discrete fused route) the normalisation
+                ops.adv_stats_fold(adv_parts, n_parts, H, N, stats)     # below is a launch of its own: fold them now (one small launch)
                 adv_parts = None
         else:
             stats, adv_parts, n_parts = self._stats, None, 0
             advantages, reward_sums = self._gae(rewards, undones, unmasks, values, stats=stats, next_value=next_value)
+        if self._discrete:
+            self.advantage_path = "rollout" if from_rollout is not None else "scan"
         if self.world_size > 1:                                                       # one normalisation for the whole job:
             if comm is not None:                                                      # the 5 sums ride the gradient's route
                 comm.all_reduce_sum(stats)
@@ -644,8 +653,6 @@ class AgentPPO(AgentBase):
         if ids is None:
             ids = th.randint(H * N, size=(update_times, B), device=dev)
         assert ids.shape == (update_times, B) and ids.dtype == th.int64
-        # the categorical policy's fused route (AgentDiscretePPO._update_discrete_fused): its own slab / gradient-row stride
-        fused_d = self._discrete_update_fused(dp)
         if self._discrete:
             self.update_path = "fused" if fused_d else "layered"
         stride = self._stride_discrete_fused if fused_d else self._stride
@@ -724,7 +731,7 @@ class AgentPPO(AgentBase):
         if self._logs is None:
             self._logs = th.empty(4, dtype=th.float32, device=dev)
         if from_rollout is not None:           # the logged means + get_advantages' side effect on rewards / undones (AgentPPO.py:211-214)
-            _hip.check(_hip.lib().erl_ppo_finish_f32(_hip.ptr(self._grads, th.float32), self._stride, self._Pa + self._Pc, update_times,
+            _hip.check(_hip.lib().erl_ppo_finish_f32(_hip.ptr(self._grads, th.float32), stride, self._Pa + self._Pc, update_times,
                                                      grad_scale, _hip.ptr(self._logs, th.float32), _hip.ptr(rewards, th.float32),
                                                      _hip.flag_ptr(undones), _hip.flag_ptr(unmasks), _hip.ptr(values, th.float32), H * N,
                                                      _hip.stream_ptr()), "erl_ppo_finish_f32")
@@ -807,6 +814,7 @@ class AgentDiscretePPO(AgentPPO):
     # has its median below the layered loop's at all three shapes of tools/discrete_update_ab.py;
     # args.fused_update = False or ERL_FUSED_DISCRETE_UPDATE=0 keep the layered minibatch loop
     _fused_update_default = "1"
+    _fused_gae_default = "0"
 
     def __init__(self, net_dims: List[int], state_dim: int, action_dim: int, gpu_id: int = 0, args: Config = None):
         args = Config() if args is None else args
@@ -814,7 +822,14 @@ class AgentDiscretePPO(AgentPPO):
         self.fused_update_discrete = bool(getattr(args, "fused_update",
                                                   os.environ.get("ERL_FUSED_DISCRETE_UPDATE", self._fused_update_default) != "0"))
         self.update_path = None                   # which route the last update_net took: "fused" | "layered"
+        # values + get_advantages in the one-launch rollout (csrc/rollout_discrete.hip, "The GAE_ form") is opt-in: args.fused_gae = True,
+        # or ERL_FUSED_DISCRETE_GAE=1 where args does not say; the continuous agents' ERL_FUSED_GAE (default on) does not reach here.
+        # profiles/discrete_iteration_ab.txt holds its timing against the pre-pass + scan; DESIGN.md section 9 has the rule for a flip
+        self.fused_gae_discrete = (bool(args.fused_gae) if hasattr(args, "fused_gae")
+                                   else os.environ.get("ERL_FUSED_DISCRETE_GAE", self._fused_gae_default) == "1")
+        self.advantage_path = None                # where the last update_net's advantages came from: "rollout" | "scan"
         super().__init__(net_dims, state_dim, action_dim, gpu_id, args)
+        self.fused_gae = self.fused_gae_discrete  # (the base constructor read the continuous agents' switch)
         # gradient-row / slab stride of the fused route; None: the shape has no fused kernel, which is what `_discrete_update_fused`
         # asks from here on (one answer, taken once from erl_ppo_discrete_supported); the layered route keeps `_stride`
         self._stride_discrete_fused = (_hip.lib().erl_ppo_discrete_slab_stride(state_dim, net_dims[0], net_dims[1], action_dim)
@@ -852,7 +867,15 @@ class AgentDiscretePPO(AgentPPO):
             update = "layered minibatch loop (args.fused_update is off; the shape has the fused minibatch kernel)"
         else:
             update = "layered minibatch loop (the fused discrete minibatch kernel covers the one-launch rollout's shapes only)"
-        return text + "; rollout: " + route + "; update: " + update
+        ok = self._one_launch_shape() and self.fused_rollout and self._fused_update_shape() and self.fused_update_discrete
+        if self.fused_gae_discrete and ok:
+            adv = ("critic values and get_advantages inside the one-launch rollout, consumed by the fused update while the cache is valid "
+                   "(else, and on data-parallel runs: value pre-pass + scan)")
+        elif self.fused_gae_discrete:
+            adv = "value pre-pass + scan (args.fused_gae is on, but it needs the one-launch rollout and the fused update)"
+        else:
+            adv = "value pre-pass + scan (args.fused_gae is off, the default for discrete agents)"
+        return text + "; rollout: " + route + "; update: " + update + "; advantages: " + adv
 
     def _discrete_update_fused(self, dp: bool) -> bool:
         """does this update_net take the fused route: the flag is on, the shape has the kernel (`_stride_discrete_fused` is its stride)
@@ -937,6 +960,7 @@ class AgentDiscretePPO(AgentPPO):
         state = self.last_state
         assert state.shape == (N, S), f"last_state {tuple(state.shape)} != {(N, S)}"
         state = state.to(dev, th.float32).contiguous()
+        self._rollout_cache = None
         if self._one_launch_reason(env, "fused_rollout_discrete") is None:
             # one launch for all H steps: policy, draw, log-prob, env, buffer rows, reward scaling and flag inversion
             # (csrc/rollout_discrete.hip); the env owns the live state buffer, the agent gets a copy of the final state
@@ -950,12 +974,29 @@ class AgentDiscretePPO(AgentPPO):
                     env.state.copy_(state)
                     env.state_epoch += 1
             last_out = th.empty((N, S), dtype=th.float32, device=dev)
+            extra = {}
+            if self.fused_gae:
+                # the same launch leaves cri(states), cri(last_state), get_advantages (raw), the reward sums and the sums of the
+                # normalisation: planes values | raw advantages | reward sums; [8 doubles: the folded sums | 3 per 16-env tile]
+                planes = th.empty((3, H, N), dtype=th.float32, device=dev)
+                values, adv_raw, ret = planes[0], planes[1], planes[2]
+                next_value = th.empty((N,), dtype=th.float32, device=dev)
+                n_parts = ops.rollout_discrete_gae_partials(N)
+                sums = th.empty(8 + 3 * n_parts, dtype=th.float64, device=dev)
+                stats, gae_parts = sums[:8], sums[8:]
+                extra["epilogue"] = (values, next_value, adv_raw, ret, gae_parts, float(self.gamma), float(self.lambda_gae_adv),
+                                     bool(self.if_use_v_trace))
             env.fused_rollout_discrete(self, H, None if noise is None else noise.contiguous(),
-                                       (states, actions, logprobs, rewards, terminals, truncates), last_out)
+                                       (states, actions, logprobs, rewards, terminals, truncates), last_out, **extra)
             self.rng_counter += H
             self.last_state = last_out
             self._last_state_token = (last_out, last_out._version, env, getattr(env, "state_epoch", None), (id(env.state), env.state._version))
             self.rollout_path = "one-launch"
+            if self.fused_gae:       # (the keys of AgentPPO._explore_vec_env: _cached_values / _cached_advantages serve both)
+                self._rollout_cache = dict(states=states, values=values, next_value=next_value, last_state=self.last_state,
+                                           key=self._value_cache_key(states, self.last_state), adv=adv_raw, ret=ret, stats=stats,
+                                           parts=gae_parts, n_parts=n_parts, rewards=rewards, undones=terminals, unmasks=truncates,
+                                           adv_key=self._adv_cache_key(rewards, terminals, truncates))
             return states, actions, logprobs, rewards, terminals, truncates          # (the kernel wrote the inverted flags)
         self._last_state_token = None
         self.rollout_path = "loop"

@@ -32,6 +32,15 @@ def _epilogue_args(epilogue):
             None if ws is None else p(ws, th.float64), 0 if ws is None else ws.numel() * 8, float(gamma), float(lam), int(bool(vtrace)))
 
 
+def _discrete_epilogue_args(agent, epilogue):
+    """the twelve arguments erl_rollout_discrete_*_gae_f32 takes behind the rollout entries' from `epilogue` = (values, next_value,
+    advantages, reward_sums, partials, gamma, lambda_gae, use_v_trace) and the agent's critic"""
+    values, next_value, adv, ret, parts, gamma, lam, vtrace = epilogue
+    p, f32, c = _hip.ptr, th.float32, agent.cri
+    return (p(agent._flat_c.flat, f32), p(c.state_avg.data, f32), p(c.state_std.data, f32), p(values, f32), p(next_value, f32), p(adv, f32),
+            p(ret, f32), p(parts, th.float64), parts.numel() * 8, float(gamma), float(lam), int(bool(vtrace)))
+
+
 class _GpuVecEnv:
     env_name = "GpuVecEnv"
     if_discrete = False
@@ -318,14 +327,24 @@ class CartPoleGpuVecEnv(_GpuVecEnv):
                 self.num_envs)
 
     @_hip.on_device
-    def fused_rollout_discrete(self, agent, horizon_len: int, uniform, bufs, last_state_out, uniform_out=None) -> None:
+    def fused_rollout_discrete(self, agent, horizon_len: int, uniform, bufs, last_state_out, uniform_out=None, epilogue=None) -> None:
         """all `horizon_len` steps of AgentDiscretePPO._explore_vec_env in ONE launch (erl_rollout_discrete_cartpole_f32): `bufs` = (states,
         actions int32, logprobs, rewards, undones, unmasks) time-major, written in place (rewards scaled, flags inverted); `uniform` (H, N)
         injects the U[0,1) draws or None (Philox keyed by (agent.rng_seed, agent.rng_counter + t, env)); `last_state_out` (N, 4) or None:
-        the agent's own copy of the final state; `uniform_out` (H, N) or None: the u every cell used.  The env's state / counters advance."""
+        the agent's own copy of the final state; `uniform_out` (H, N) or None: the u every cell used.  The env's state / counters advance.
+        `epilogue` = (values (H, N), next_value (N,), advantages (H, N), reward_sums (H, N), partials (3 * erl_rollout_discrete_gae_partials(N),)
+        float64, gamma, lambda_gae, use_v_trace) or None: the same launch also leaves the critic's values, get_advantages (raw), the reward
+        sums and the per-tile sums of the normalisation (erl_rollout_discrete_cartpole_gae_f32); everything else is what it is without."""
         self.state_epoch += 1
         p, f32 = _hip.ptr, th.float32
         states, actions, logprobs, rewards, undones, unmasks = bufs
+        if epilogue is not None:
+            _hip.check(_hip.lib().erl_rollout_discrete_cartpole_gae_f32(
+                *self._policy_args(agent), horizon_len, p(uniform, f32), agent.rng_seed & (2 ** 64 - 1), agent.rng_counter & (2 ** 64 - 1),
+                float(agent.reward_scale), p(states, f32), p(actions, th.int32), p(logprobs, f32), p(rewards, f32), _hip.flag_ptr(undones),
+                _hip.flag_ptr(unmasks), p(last_state_out, f32), p(uniform_out, f32), *_discrete_epilogue_args(agent, epilogue),
+                _hip.stream_ptr()), "erl_rollout_discrete_cartpole_gae_f32")
+            return
         _hip.check(_hip.lib().erl_rollout_discrete_cartpole_f32(
             *self._policy_args(agent), horizon_len, p(uniform, f32), agent.rng_seed & (2 ** 64 - 1), agent.rng_counter & (2 ** 64 - 1),
             float(agent.reward_scale), p(states, f32), p(actions, th.int32), p(logprobs, f32), p(rewards, f32), _hip.flag_ptr(undones),
@@ -390,14 +409,21 @@ class AcrobotGpuVecEnv(_GpuVecEnv):
                 self.seed & (2 ** 64 - 1), self.num_envs)
 
     @_hip.on_device
-    def fused_rollout_discrete(self, agent, horizon_len: int, uniform, bufs, last_state_out, uniform_out=None) -> None:
+    def fused_rollout_discrete(self, agent, horizon_len: int, uniform, bufs, last_state_out, uniform_out=None, epilogue=None) -> None:
         """all `horizon_len` steps of AgentDiscretePPO._explore_vec_env in ONE launch (erl_rollout_discrete_acrobot_f32); arguments as
         CartPoleGpuVecEnv.fused_rollout_discrete, states (H, N, 6) and `last_state_out` (N, 6).  The policy's input at t = 0 is `state` as
         it stands (the caller may have written its own last state there; `phys` is not disturbed by that), from t = 1 on the
-        observation of `phys`.  `phys`, `state` and the counters advance."""
+        observation of `phys`.  `phys`, `state` and the counters advance.  `epilogue`: as on CartPole (erl_rollout_discrete_acrobot_gae_f32)."""
         self.state_epoch += 1
         p, f32 = _hip.ptr, th.float32
         states, actions, logprobs, rewards, undones, unmasks = bufs
+        if epilogue is not None:
+            _hip.check(_hip.lib().erl_rollout_discrete_acrobot_gae_f32(
+                *self._policy_args(agent), horizon_len, p(uniform, f32), agent.rng_seed & (2 ** 64 - 1), agent.rng_counter & (2 ** 64 - 1),
+                float(agent.reward_scale), p(states, f32), p(actions, th.int32), p(logprobs, f32), p(rewards, f32), _hip.flag_ptr(undones),
+                _hip.flag_ptr(unmasks), p(last_state_out, f32), p(uniform_out, f32), *_discrete_epilogue_args(agent, epilogue),
+                _hip.stream_ptr()), "erl_rollout_discrete_acrobot_gae_f32")
+            return
         _hip.check(_hip.lib().erl_rollout_discrete_acrobot_f32(
             *self._policy_args(agent), horizon_len, p(uniform, f32), agent.rng_seed & (2 ** 64 - 1), agent.rng_counter & (2 ** 64 - 1),
             float(agent.reward_scale), p(states, f32), p(actions, th.int32), p(logprobs, f32), p(rewards, f32), _hip.flag_ptr(undones),

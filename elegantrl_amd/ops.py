@@ -1007,3 +1007,11 @@ def acrobot_step(phys: TEN, obs: TEN, action: TEN, step_count: TEN, episode: TEN
 def rollout_discrete_supported(S: int, h1: int, h2: int, A: int) -> bool:
     """the policy shapes of the one-launch discrete rollout / evaluation (erl_rollout_discrete_supported)"""
     return bool(lib().erl_rollout_discrete_supported(int(S), int(h1), int(h2), int(A)))
+
+
+def rollout_discrete_gae_partials(N: int) -> int:
+    """rows of 3 doubles the discrete rollout's GAE phase leaves for N envs: one per 16-env tile (erl_rollout_discrete_gae_partials)"""
+    n = int(lib().erl_rollout_discrete_gae_partials(int(N)))
+    if n < 1:
+        raise ValueError(f"erl_rollout_discrete_gae_partials({N}) = {n}")
+    return n

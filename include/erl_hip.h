@@ -402,6 +402,42 @@ ERL_API int erl_eval_discrete_acrobot_f32(const float *actor_params, const float
                           float *phys, float *obs, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N,
                           int64_t H, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The discrete rollout with the critic's values and get_advantages in the same launch (additions to ABI 22; csrc/rollout_discrete.hip,
+ * "The GAE_ form").
+ *
+ * erl_rollout_discrete_cartpole_gae_f32 / erl_rollout_discrete_acrobot_gae_f32: the arguments of erl_rollout_discrete_cartpole_f32 /
+ * erl_rollout_discrete_acrobot_f32 and, before `stream`: critic_params (the flat block of [S, h1, h2, 1]: W1 b1 W2 b2 W3 b3, read in
+ * place), cri_avg / cri_std (S,) (the critic's own state_avg / state_std); out_values (H, N) = cri(out_states), out_next_value (N,) =
+ * cri(the final state), out_advantages (H, N) RAW (not normalised), out_reward_sums (H, N) = advantage + value; gae_partials:
+ * erl_rollout_discrete_gae_partials(N) = ceil(N / 16) rows of 3 doubles, one per 16-env tile in env order (sum of the advantages, sum
+ * and sum of squares over the [::4, ::4] subsample), the format erl_adv_stats_fold_f32 folds; gae_partials_bytes >=
+ * erl_rollout_discrete_gae_workspace_bytes(N) (24 bytes per row; -1 for N < 1: host only); gamma, lambda_gae, use_v_trace: the scan's.
+ * Every one of the new pointers is required (NULL: ERL_EINVAL naming it), a short gae_partials is ERL_EINVAL naming both sizes, dims and
+ * env are checked as by the entries above, all before any launch.
+ * What equals what: the six buffers, out_last_state, out_uniform and the env's state / counters are bit-identical to the entry without
+ * _gae given the same arguments (the steps are the same statements; the second phase runs behind them).  out_advantages / out_reward_sums
+ * are bit-identical to erl_gae_scan_f32(ERL_GAE_ALGO_EXACT) on (out_rewards, out_undones, out_unmasks, out_values, out_next_value): the
+ * two share csrc/gae_step.h.  out_rewards / out_undones are NOT given get_advantages' truncation fix-up (erl_ppo_finish_f32 applies it at
+ * the end of the update).  The values are the register-chained fp32-MFMA forward of the rollout's policy, not erl_mlpn_value_forward_f32's
+ * GEMMs: equal to fp64 within that entry's tolerance (rtol 1e-4, atol 2e-5), not bit for bit.  No result depends on the launch geometry.
+ * No call allocates or synchronises; no workgroup waits for another. */
+ERL_API int erl_rollout_discrete_gae_partials(int64_t N);
+ERL_API int64_t erl_rollout_discrete_gae_workspace_bytes(int64_t N);
+ERL_API int erl_rollout_discrete_cartpole_gae_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2,
+                          int A, float *env_state, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N,
+                          int64_t H, const float *uniform, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states,
+                          int32_t *out_actions, float *out_logprobs, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks,
+                          float *out_last_state, float *out_uniform, const float *critic_params, const float *cri_avg, const float *cri_std,
+                          float *out_values, float *out_next_value, float *out_advantages, float *out_reward_sums, void *gae_partials,
+                          int64_t gae_partials_bytes, float gamma, float lambda_gae, int use_v_trace, void *stream);
+ERL_API int erl_rollout_discrete_acrobot_gae_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2,
+                          int A, float *phys, float *obs, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
+                          int64_t N, int64_t H, const float *uniform, uint64_t seed, uint64_t counter0, float reward_scale,
+                          float *out_states, int32_t *out_actions, float *out_logprobs, float *out_rewards, uint8_t *out_undones,
+                          uint8_t *out_unmasks, float *out_last_state, float *out_uniform, const float *critic_params, const float *cri_avg,
+                          const float *cri_std, float *out_values, float *out_next_value, float *out_advantages, float *out_reward_sums,
+                          void *gae_partials, int64_t gae_partials_bytes, float gamma, float lambda_gae, int use_v_trace, void *stream);
+
 /* K6  one PPO minibatch: gather (K5 indices) + critic fwd/bwd + actor fwd/bwd, both networks in one
  * launch.  Replaces AgentPPO.update_objectives up to (not including) the two optimizer steps
  * (AgentPPO.py:173-204) and ActorPPO.get_logprob_entropy (:378-386):
