@@ -33,6 +33,23 @@ namespace {
 
 __device__ __forceinline__ int phi(int i) { return (i & 0x13) | ((i & 4) << 1) | ((i & 8) >> 1); }   // bits 2 and 3 swapped
 
+// v_mfma_f32_4x4x1_16b_f32 with the instruction's own A broadcast (CBSZ = 3): the sixteen 4-lane blocks form two groups of eight (lanes
+// 0..31, 32..63) and every block of a group takes its A column from block `abid` of ITS group -- one register holds eight k-steps'
+// A operands for both halves of the wave.  abid must be an immediate: the callers' loops are unrolled and the switch folds.
+__device__ __forceinline__ f32x4 mfma4_bc8(float a, float b, f32x4 c, int abid)
+{
+    switch (abid) {
+    case 0: return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 3, 0, 0);
+    case 1: return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 3, 1, 0);
+    case 2: return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 3, 2, 0);
+    case 3: return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 3, 3, 0);
+    case 4: return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 3, 4, 0);
+    case 5: return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 3, 5, 0);
+    case 6: return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 3, 6, 0);
+    default: return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 3, 7, 0);
+    }
+}
+
 template <int CP>
 __device__ __forceinline__ u8 *img_at(u8 *img, int row, int part, int chunk)
 {
@@ -609,6 +626,12 @@ __device__ __forceinline__ void ppo_block_s3(const Ppo2Args &g, u8 *smem, SpanSt
     const float bias_raw = P[tid < 128 ? d.ob1() + min(tid, h1 - 1) : d.ob2() + min(tid - 128, h2 - 1)];
     const float b3_raw = P[d.ob3() + min(tid, OUT - 1)];
     const float sd_raw = g.sd[net][min(tid, S - 1)], avg_raw = g.avg[net][min(tid, S - 1)];
+    // the logged entropy is a sum over the actions of 1.4189 + log(exp(std_log[a])), written by thread 0 at the kernel's very end.  Formed there
+    // it was a serial loop of A loads, each returning behind the write-through stores of dW3, and A exp / log chains: ~2.5k cycles on the
+    // one wave the workgroup ends with.  Lane l forms the term of action l & 7 here, in the shadow of the row loads; thread 0 adds them
+    // in the same order at the end (the same bits).
+    float ent_term_l = 0.f;
+    if constexpr (ACTOR) ent_term_l = std_log[min(lane & 7, OUT - 1)];
 
     // ---- trip 2: id -> (t = id % H, n = id // H) -> buffer row t*N + n  (AgentPPO.py:179-187) and its data
     int64_t n_, t_;
@@ -698,6 +721,10 @@ __device__ __forceinline__ void ppo_block_s3(const Ppo2Args &g, u8 *smem, SpanSt
         }
     }
     PROF_NV(18);                                            // (W2 image pieces issued / FAST: row loads issued)
+    if constexpr (ACTOR) {
+        ent_term_l = 1.4189385332046727418f + logf(expf(ent_term_l));
+        asm volatile("" : "+v"(ent_term_l));                // (pinned: left alone it sinks to its use at the kernel's end)
+    }
     if constexpr (FAST) {
         // the rows through the wave-private tile (8 KB per wave at the start of the W2 image's region, which is still free):
         // [32 samples][16 chunks of 16 bytes], chunk c of sample s at c ^ (s & 15) -- conflict-free for the 16-byte stores by
@@ -822,47 +849,70 @@ __device__ __forceinline__ void ppo_block_s3(const Ppo2Args &g, u8 *smem, SpanSt
         }
         stage_s3<2 * KX, CP1, 0>(SB, Xs, col, hi);
     }
-#if defined(ERL_PROFILE) && defined(ERL_PROFILE_FINE)
+    // The actor's output layer takes its A operands -- W3 rows 0..3 and 4..7 -- through the MFMA's own broadcast (mfma4_bc8): lane (block b =
+    // lane >> 2, row i = lane & 3) holds W3[i (+ 4)][16 n + b] in w3bc[.][n]; b = 8 hi + abid is exactly the feature offset of the lanes that
+    // take it.  2 x 2 N2 four-byte reads per lane for the whole layer instead of 2 x 4 N2 sixteen-byte ones in its loop (every lane of a wave
+    // fetched one of eight addresses: 128 KB through the LDS port per workgroup for 4 KB of weights), requested behind the MFMAs of the
+    // second layer's last tile, where H1's fp32 tiles are dead.
+    float w3bc[2][2 * N2];
     {
-        // fine stamps: the second layer's tile boundaries (slots 21..23) and the end of its MFMA loop (24)
-        auto fine = [&](int c) {
+        constexpr int C0 = (N2 - 1) * 2 * N1, PER = (2 * N2 + 2 * N1 - 1) / (2 * N1);      // the last tile's first k-step; registers per k-step
+        const float *w3b = RW3 + (lane & 3) * ld3 + (lane >> 2);
+        auto l2_side = [&](int c) {
+#if defined(ERL_PROFILE) && defined(ERL_PROFILE_FINE)
+            // fine stamps: the second layer's tile boundaries (slots 21..23) and the end of its MFMA loop (24)
             if (c > 0 && c % (2 * N1) == 0) { if (c / (2 * N1) == 1) PROF_NV(21); else if (c / (2 * N1) == 2) PROF_NV(22); else if (c / (2 * N1) == 3) PROF_NV(23); else PROF_NV(24); }
-        };
-        fwd_s3<2 * N1, N2, CP2>(IMG2, s_b2, H1p, H1, H2, G2, m, hi, fine);
-    }
-#else
-    fwd_s3<2 * N1, N2, CP2>(IMG2, s_b2, H1p, H1, H2, G2, m, hi);       // splits H1 into H1p on the way
 #endif
+            if constexpr (ACTOR) {
+#pragma unroll
+                for (int u = 0; u < PER; ++u) {
+                    const int n = PER * (c - C0) + u;
+                    if (c >= C0 && n < 2 * N2) {
+                        w3bc[0][n] = w3b[16 * n];
+                        w3bc[1][n] = w3b[4 * ld3 + 16 * n];
+                    }
+                }
+            }
+        };
+        fwd_s3<2 * N1, N2, CP2>(IMG2, s_b2, H1p, H1, H2, G2, m, hi, l2_side);       // splits H1 into H1p on the way
+    }
     SPAN_STAMP(sps, 3);                                              // phase 2: second layer forward
     PROF(4);
 
     // ---- output layer (fp32, as in ppo_step_w4_impl.h; H2[T][4 gq + j] is feature 32 T + 16 (gq >> 1) + 8 hi + 4 (gq & 1) + j here)
     float Y[4] = {0.f, 0.f, 0.f, 0.f};
+    float ivar_pre[4] = {0.f, 0.f, 0.f, 0.f};
     if (ACTOR) {
         f32x4 ya[2][2];
 #pragma unroll
         for (int q = 0; q < 4; ++q) ya[q >> 1][q & 1] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const float *w3a = RW3 + (lane & 3) * ld3 + 8 * hi;
-        constexpr int DEPTH = 2;
-        float4 wq[DEPTH + 1][2];
-        auto issue = [&](int c, float4(&dst)[2]) {
-            const int T = c >> 2, gq = c & 3;
-            dst[0] = *reinterpret_cast<const float4 *>(w3a + 32 * T + 16 * (gq >> 1) + 4 * (gq & 1));
-            dst[1] = *reinterpret_cast<const float4 *>(w3a + 4 * ld3 + 32 * T + 16 * (gq >> 1) + 4 * (gq & 1));
-        };
+        // (the products, their order and their accumulators are those of the form that read a0 / a1 = W3[lane & 3 (+ 4)][feature] per lane: the same bits)
+        // A 4x4x1 MFMA holds the matrix pipe for ~16 cycles (measured: 128 of them 2.1k) and its issue slot for 4: the slots between them
+        // are free.  ~500 registers are live and H2 waits in the upper half of the register file, from where an operand is MOVED to where
+        // the MFMA reads it; the move for element e + 2 is pinned between the two MFMAs of element e (left at its use it costs its slot and
+        // the wait states between a vector write and an MFMA's read, 64 times); the last elements' free slots carry exp(-2 std_log), which
+        // the objective would otherwise start with.
+        float hb[3];
+        hb[0] = H2[0][0];
+        hb[1] = H2[0][1];
+        asm volatile("" : "+v"(hb[0]), "+v"(hb[1]));
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int c = 0; c < DEPTH; ++c) issue(c, wq[c]);
-#pragma unroll
-        for (int c = 0; c < 4 * N2; ++c) {
-            const int T = c >> 2, gq = c & 3;
-            if (c + DEPTH < 4 * N2) issue(c + DEPTH, wq[(c + DEPTH) % (DEPTH + 1)]);
-            const float4 w0 = wq[c % (DEPTH + 1)][0], w1 = wq[c % (DEPTH + 1)][1];
-            const float a0[4] = {w0.x, w0.y, w0.z, w0.w}, a1[4] = {w1.x, w1.y, w1.z, w1.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                ya[0][j & 1] = __builtin_amdgcn_mfma_f32_4x4x1f32(a0[j], H2[T][4 * gq + j], ya[0][j & 1], 0, 0, 0);
-                ya[1][j & 1] = __builtin_amdgcn_mfma_f32_4x4x1f32(a1[j], H2[T][4 * gq + j], ya[1][j & 1], 0, 0, 0);
+        for (int e = 0; e < 16 * N2; ++e) {
+            const int c = e >> 2, j = e & 3;
+            ya[0][j & 1] = mfma4_bc8(w3bc[0][c >> 1], hb[e % 3], ya[0][j & 1], 4 * (c & 1) + j);
+            __builtin_amdgcn_sched_barrier(0);
+            if (e + 2 < 16 * N2) {
+                hb[(e + 2) % 3] = H2[(e + 2) >> 4][(e + 2) & 15];
+                asm volatile("" : "+v"(hb[(e + 2) % 3]));
             }
+            if (e >= 16 * N2 - 8 && (e & 1)) {
+                const int k = (e - (16 * N2 - 8)) >> 1;
+                ivar_pre[k] = __expf(-2.f * sl_pre[k]);
+                asm volatile("" : "+v"(ivar_pre[k]));
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            ya[1][j & 1] = mfma4_bc8(w3bc[1][c >> 1], hb[e % 3], ya[1][j & 1], 4 * (c & 1) + j);
             __builtin_amdgcn_sched_barrier(0);
         }
         const float4 b4 = *reinterpret_cast<const float4 *>(s_b3 + 4 * hi);
@@ -908,7 +958,7 @@ __device__ __forceinline__ void ppo_block_s3(const Ppo2Args &g, u8 *smem, SpanSt
             const float sl = sl_pre[j];
             const float diff = act_pre[j] - Y[j];
             const bool on = a < OUT;
-            ivar[j] = __expf(-2.f * sl);
+            ivar[j] = ivar_pre[j];                         // exp(-2 std_log), formed beside the output layer's MFMAs
             diffv[j] = on ? diff : 0.f;
             const float term = -(diff * diff) * (0.5f * ivar[j]) - sl - kLogSqrt2PiF;
             lp += on ? term : 0.f;
@@ -1242,7 +1292,7 @@ __device__ __forceinline__ void ppo_block_s3(const Ppo2Args &g, u8 *smem, SpanSt
         float *logs = g.slabs + (size_t)slab_ix * g.stride + g.Pa + g.Pc;
         if (ACTOR) {
             float ent = 0.f;
-            for (int a = 0; a < OUT; ++a) ent += 1.4189385332046727418f + logf(expf(std_log[a]));
+            for (int a = 0; a < OUT; ++a) ent += __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(ent_term_l), a));   // (lane a's term: see the prologue)
             logs[1] = t0 * g.inv_batch;
             logs[2] = ent * t1 * g.inv_batch;
         } else {
