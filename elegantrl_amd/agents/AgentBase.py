@@ -130,6 +130,28 @@ class AgentBase:
         seed = getattr(args, "random_seed", None)
         self.rng_seed = (int(seed) if seed is not None else max(0, gpu_id)) * 1000003 + 7919 * self.rank
         self.rng_counter = 0
+        self._last_state_token = None
+
+    # ---- the last state between two one-launch rollouts: the env owns the live buffer, the agent holds the copy the launch wrote ------
+    def _hand_state_to_env(self, env, state: TEN) -> None:
+        """`state` (`last_state` on the device) becomes `env.state`, the live buffer -- unless `_last_state_token` says the buffer already
+        holds it: `last_state` is the very tensor the last one-launch rollout of THIS env wrote as its copy of the final state, nobody
+        has written to it, and the env has not moved since (no copy-back launch).  A copy counts as a move of the env."""
+        if state.data_ptr() == env.state.data_ptr():
+            return
+        tok = self._last_state_token
+        same = (tok is not None and tok[0] is self.last_state and tok[1] == self.last_state._version and tok[2] is env
+                and tok[3] == getattr(env, "state_epoch", None) and tok[4] == (id(env.state), env.state._version))
+        if not same:
+            env.state.copy_(state)
+            if hasattr(env, "state_epoch"):
+                env.state_epoch += 1
+
+    def _record_last_state(self, env, last_out: TEN) -> None:
+        """`last_out`, the copy of its final state a one-launch rollout of `env` has just written, is `last_state`; the token is what
+        `_hand_state_to_env` compares at the next call"""
+        self.last_state = last_out
+        self._last_state_token = (last_out, last_out._version, env, getattr(env, "state_epoch", None), (id(env.state), env.state._version))
 
     # ---- evaluation on the device (csrc/rollout_eval.hip) ---------------------------------------------
     def evaluate_env(self, env) -> Optional[TEN]:

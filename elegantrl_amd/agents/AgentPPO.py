@@ -192,7 +192,6 @@ class AgentPPO(AgentBase):
         # steps back from memory costs more than the scan kernels do (200 x 4096: explore_env +33 us against +25 us in update_net:
         # profiles/r06_c2_fused_gae_ab.txt), so longer horizons take them unless args.fused_gae / ERL_FUSED_GAE says otherwise
         self._fused_gae_explicit = hasattr(args, "fused_gae") or "ERL_FUSED_GAE" in _os.environ
-        self._last_state_token = None
         self.ppo_arith = str(getattr(args, "ppo_arith", "auto"))
         assert self.ppo_arith in ("auto", "f32", "split"), f"args.ppo_arith = {self.ppo_arith!r}"
         if self._wide and self.ppo_arith == "f32":
@@ -372,16 +371,8 @@ class AgentPPO(AgentBase):
         state = self.last_state
         assert state.shape == (N, S), f"last_state {tuple(state.shape)} != {(N, S)}"
         state = state.to(dev, th.float32).contiguous()
-        if hasattr(env, "raw_stepper") and state.data_ptr() != env.state.data_ptr():
-            tok = self._last_state_token
-            # `state` is the very tensor the last fused rollout of THIS env wrote as its copy of the final state, nobody has written
-            # to it, and the env has not moved since: the live buffer already holds it (no copy-back launch)
-            same = (tok is not None and tok[0] is self.last_state and tok[1] == self.last_state._version and tok[2] is env
-                    and tok[3] == getattr(env, "state_epoch", None) and tok[4] == (id(env.state), env.state._version))
-            if not same:
-                env.state.copy_(state)             # the env owns the live state buffer; keep it authoritative
-                if hasattr(env, "state_epoch"):
-                    env.state_epoch += 1
+        if hasattr(env, "raw_stepper"):
+            self._hand_state_to_env(env, state)    # the env owns the live state buffer; keep it authoritative
         self._last_state_token = None
         self._rollout_cache = None
         if (self.fused_rollout and self._fused and hasattr(env, "fused_rollout") and getattr(env, "num_envs", None) == N
@@ -410,14 +401,12 @@ class AgentPPO(AgentBase):
             # the agent's copy of the final state is written by the rollout kernel itself (no clone, and no copy back at the next
             # call while nobody touches either side: _last_state_token); args.snapshot_last_state = False hands out the env's
             # live buffer instead
-            self.last_state = last_out if last_out is not None else env.state
             if last_out is not None:
-                self._last_state_token = (last_out, last_out._version, env, getattr(env, "state_epoch", None), (id(env.state), env.state._version))
-            self._rollout_cache = dict(states=states, values=values, next_value=next_value, last_state=self.last_state,
-                                       key=self._value_cache_key(states, self.last_state))
-            if fused_gae:
-                self._rollout_cache.update(adv=adv_raw, ret=ret, stats=stats, parts=gae_parts, n_parts=n_parts, rewards=rewards,
-                                           undones=undones, unmasks=unmasks, adv_key=self._adv_cache_key(rewards, undones, unmasks))
+                self._record_last_state(env, last_out)
+            else:
+                self.last_state = env.state
+            self._cache_rollout(states, values, next_value, self.last_state,
+                                (adv_raw, ret, stats, gae_parts, n_parts, rewards, undones, unmasks) if fused_gae else None)
             return states, actions, logprobs, rewards, undones, unmasks
         rollout_step = ops.rollout_step if self._fused else ops.mlpn_rollout_step
         if hasattr(env, "raw_stepper") and self._fused:
@@ -558,6 +547,16 @@ class AgentPPO(AgentBase):
         were written (an in-place edit by the caller bumps _version) and the scan's hyper-parameters"""
         return (rewards.data_ptr(), rewards._version, undones.data_ptr(), undones._version, unmasks.data_ptr(), unmasks._version,
                 float(self.gamma), float(self.lambda_gae_adv), bool(self.if_use_v_trace))
+
+    def _cache_rollout(self, states: TEN, values: TEN, next_value: TEN, last_state: TEN, gae=None) -> None:
+        """what a one-launch rollout left for update_net: the critic's values (_cached_values) and, with `gae` = (raw advantages,
+        reward sums, stats block, partial sums, their count, rewards, undones, unmasks), its epilogue's planes (_cached_advantages)"""
+        c = dict(states=states, values=values, next_value=next_value, last_state=last_state, key=self._value_cache_key(states, last_state))
+        if gae is not None:
+            adv, ret, stats, parts, n_parts, rewards, undones, unmasks = gae
+            c.update(adv=adv, ret=ret, stats=stats, parts=parts, n_parts=n_parts, rewards=rewards, undones=undones, unmasks=unmasks,
+                     adv_key=self._adv_cache_key(rewards, undones, unmasks))
+        self._rollout_cache = c
 
     def _cached_advantages(self, rewards: TEN, undones: TEN, unmasks: TEN):
         """(raw advantages, reward_sums, stats block, partial sums, their count) computed by the fused rollout's epilogue for exactly these tensors, else None
@@ -964,15 +963,7 @@ class AgentDiscretePPO(AgentPPO):
         if self._one_launch_reason(env, "fused_rollout_discrete") is None:
             # one launch for all H steps: policy, draw, log-prob, env, buffer rows, reward scaling and flag inversion
             # (csrc/rollout_discrete.hip); the env owns the live state buffer, the agent gets a copy of the final state
-            if state.data_ptr() != env.state.data_ptr():
-                tok = self._last_state_token
-                # `state` is the copy of the final state the last one-launch rollout of THIS env wrote, untouched, and the env has
-                # not moved since: the live buffer already holds it (no copy-back launch)
-                same = (tok is not None and tok[0] is self.last_state and tok[1] == self.last_state._version and tok[2] is env
-                        and tok[3] == getattr(env, "state_epoch", None) and tok[4] == (id(env.state), env.state._version))
-                if not same:
-                    env.state.copy_(state)
-                    env.state_epoch += 1
+            self._hand_state_to_env(env, state)
             last_out = th.empty((N, S), dtype=th.float32, device=dev)
             extra = {}
             if self.fused_gae:
@@ -989,14 +980,10 @@ class AgentDiscretePPO(AgentPPO):
             env.fused_rollout_discrete(self, H, None if noise is None else noise.contiguous(),
                                        (states, actions, logprobs, rewards, terminals, truncates), last_out, **extra)
             self.rng_counter += H
-            self.last_state = last_out
-            self._last_state_token = (last_out, last_out._version, env, getattr(env, "state_epoch", None), (id(env.state), env.state._version))
+            self._record_last_state(env, last_out)
             self.rollout_path = "one-launch"
-            if self.fused_gae:       # (the keys of AgentPPO._explore_vec_env: _cached_values / _cached_advantages serve both)
-                self._rollout_cache = dict(states=states, values=values, next_value=next_value, last_state=self.last_state,
-                                           key=self._value_cache_key(states, self.last_state), adv=adv_raw, ret=ret, stats=stats,
-                                           parts=gae_parts, n_parts=n_parts, rewards=rewards, undones=terminals, unmasks=truncates,
-                                           adv_key=self._adv_cache_key(rewards, terminals, truncates))
+            if self.fused_gae:       # (_cached_values / _cached_advantages serve both agents)
+                self._cache_rollout(states, values, next_value, last_out, (adv_raw, ret, stats, gae_parts, n_parts, rewards, terminals, truncates))
             return states, actions, logprobs, rewards, terminals, truncates          # (the kernel wrote the inverted flags)
         self._last_state_token = None
         self.rollout_path = "loop"

@@ -167,7 +167,6 @@ class AgentSAC(AgentBase):
         self.per_loop_in_c = bool(getattr(args, "per_loop_in_c", os.environ.get("ERL_SAC_PER_LOOP_IN_C", "1") != "0"))
         self.per_path = None                       # which route the last prioritised update_net took (None: none yet / not prioritised)
         self.update_path = None                    # which route the last update_net took: "one C call ..." / "per step: <reason>"
-        self._last_state_token = None
         self._spec = ops.SacSpec(state_dim, action_dim, net_dims, self.num_ensembles, actor_variant=self._actor_variant)
         dev, f32 = self.device, th.float32
         self._actor_flat = th.zeros(self._spec.actor_count, dtype=f32, device=dev)
@@ -250,15 +249,7 @@ class AgentSAC(AgentBase):
         self._sync_modules()
         state = self.last_state.to(dev, th.float32)
         assert state.shape == (N, S)
-        if state.data_ptr() != env.state.data_ptr():
-            tok = self._last_state_token
-            # `state` is the copy of the final state the last fused rollout of THIS env wrote, untouched, and the env has not moved since:
-            # the env's live buffer already holds it; otherwise the env takes the agent's state (it owns the live buffer)
-            same = (tok is not None and tok[0] is self.last_state and tok[1] == self.last_state._version and tok[2] is env
-                    and tok[3] == getattr(env, "state_epoch", None) and tok[4] == (id(env.state), env.state._version))
-            if not same:
-                env.state.copy_(state)
-                env.state_epoch += 1
+        self._hand_state_to_env(env, state)
         states = th.empty((H, N, S), dtype=th.float32, device=dev)
         actions = th.empty((H, N, A), dtype=th.float32, device=dev)
         rewards = th.empty((H, N), dtype=th.float32, device=dev)
@@ -267,8 +258,7 @@ class AgentSAC(AgentBase):
         last_out = th.empty((N, S), dtype=th.float32, device=dev)
         env.fused_rollout_offpolicy(self, H, None if noise is None else noise.contiguous(), (states, actions, rewards, undones, unmasks), last_out)
         self.rng_counter += H
-        self.last_state = last_out
-        self._last_state_token = (last_out, last_out._version, env, getattr(env, "state_epoch", None), (id(env.state), env.state._version))
+        self._record_last_state(env, last_out)
         return states, actions, rewards, undones, unmasks
 
     def _fused_eval_reason(self, env) -> Optional[str]:

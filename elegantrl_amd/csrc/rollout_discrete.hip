@@ -1,19 +1,23 @@
 // Discrete PPO on the device: the per-step kernels of the discrete envs (CartPole-v1, Acrobot-v1), and the one-launch rollout /
 // evaluation of the categorical policy on either of them.
 //
-//   erl_cartpole_step_f32 / erl_acrobot_step_f32    one thread per env: cartpole_step.h / acrobot_step.h on the live state, reward /
-//                                                   flag rows out.
-//   erl_rollout_discrete_{cartpole,acrobot}_f32     all H steps of AgentDiscretePPO._explore_vec_env in ONE launch
+// Every extern "C" entry is one statement that forwards to the body of its form, templated on the env:
+//   erl_cartpole_step_f32 / erl_acrobot_step_f32    rd_step<Env>: env_step_kernel<Env>, one thread per env: cartpole_step.h /
+//                                                   acrobot_step.h on the live state, reward / flag rows out.
+//   erl_rollout_discrete_{cartpole,acrobot}_f32     rd_rollout<Env, false>: all H steps of AgentDiscretePPO._explore_vec_env in ONE launch
 //                                                   (rollout_discrete_kernel<Env, false>).
-//   erl_eval_discrete_{cartpole,acrobot}_f32        its evaluation form (EV_): the greedy policy argmax(logits), per-episode accounts
-//                                                   (eval_ws.h) instead of buffer rows.
-//   erl_rollout_discrete_{cartpole,acrobot}_gae_f32 the rollout with a second phase in the same launch (GAE_): the critic's values of
-//                                                   every visited state and of the final one, get_advantages, reward sums and the
-//                                                   partial sums of the advantage normalisation (below, "The GAE_ form").
+//   erl_rollout_discrete_{cartpole,acrobot}_gae_f32 rd_rollout<Env, true>: the rollout with a second phase in the same launch (GAE_): the
+//                                                   critic's values of every visited state and of the final one, get_advantages, reward
+//                                                   sums and the partial sums of the advantage normalisation (below, "The GAE_ form").
+//   erl_eval_discrete_{cartpole,acrobot}_f32        rd_eval<Env>: the evaluation form (EV_): the greedy policy argmax(logits), per-episode
+//                                                   accounts (eval_ws.h) instead of buffer rows.
+// The arguments travel in three packs (RdHead: policy and env up to N, H; RdPlanes: the rollout's draws and planes; RdGaeTail: the GAE_
+// form's twelve); rd_fill checks the head for every form, and the kernel's argument is filled in one place per pack.
 //
-// The env behind the kernel is a trait (CartPoleEnv, AcrobotEnv below): P physical floats per env, an S-wide observation, how the env's
-// lane loads and stores both, how it forms the observation from the physical state, and a step that returns the reward.  A further env
-// is a header with its step and one such struct.
+// The env behind the kernels is a trait (CartPoleEnv, AcrobotEnv below): P physical floats per env, an S-wide observation, how an env's
+// thread loads and stores both, how it forms the observation from the physical state, the action of an int64, and a step that returns
+// the reward.  A further env costs a header with its step, one such struct, its extern "C" forwards (include/erl_hip.h, _hip._SIGNATURES)
+// and one Python subclass of _DiscreteGpuVecEnv (envs/vec_envs.py).
 //
 // rollout_discrete_kernel.  A WAVE owns 16 envs for the whole horizon and never talks to another one: the actor's three layers run
 // register-chained on the fp32 matrix cores (mlp_chain.h forward_layer: every layer transposed on the 16-env tile, a layer's result tile
@@ -100,62 +104,18 @@ size_t rd_lds_floats(int h1, int h2, int waves)
     return (size_t)h1 * RD_LD1 + (size_t)h2 * lds_ld(h1) + 16 * (size_t)lds_ld(h2) + 128 + 128 + 16 + (size_t)waves * 16 * RD_SLOT;
 }
 
-__global__ __launch_bounds__(256) void cartpole_step_kernel(float *__restrict__ state, const int64_t *__restrict__ action,
-                                                            int32_t *__restrict__ step_count, int32_t *__restrict__ episode,
-                                                            float *__restrict__ reward, uint8_t *__restrict__ terminal,
-                                                            uint8_t *__restrict__ truncate, int64_t N, int max_step, uint64_t seed)
-{
-    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (n >= N) return;
-    const float4 v = *reinterpret_cast<const float4 *>(state + 4 * n);
-    float s[4] = {v.x, v.y, v.z, v.w};
-    int sc = step_count[n], ep = episode[n];
-    bool term, trunc;
-    cartpole_step(s, action[n] == 1 ? 1 : 0, sc, ep, max_step, seed, (uint32_t)n, term, trunc);      // (compared as int64)
-    *reinterpret_cast<float4 *>(state + 4 * n) = make_float4(s[0], s[1], s[2], s[3]);
-    reward[n] = 1.0f;
-    terminal[n] = term;
-    truncate[n] = trunc;
-    step_count[n] = sc;
-    episode[n] = ep;
-}
-
-__global__ __launch_bounds__(256) void acrobot_step_kernel(float *__restrict__ phys, float *__restrict__ obs,
-                                                           const int64_t *__restrict__ action, int32_t *__restrict__ step_count,
-                                                           int32_t *__restrict__ episode, float *__restrict__ reward,
-                                                           uint8_t *__restrict__ terminal, uint8_t *__restrict__ truncate, int64_t N,
-                                                           int max_step, uint64_t seed)
-{
-    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (n >= N) return;
-    const float4 v = *reinterpret_cast<const float4 *>(phys + 4 * n);
-    float s[4] = {v.x, v.y, v.z, v.w}, ob[6];
-    int sc = step_count[n], ep = episode[n];
-    const int64_t a = action[n];
-    bool term, trunc;
-    const float r = acrobot_step(s, a == 0 ? 0 : (a == 2 ? 2 : 1), sc, ep, max_step, seed, (uint32_t)n, term, trunc);      // (compared as int64)
-    acrobot_observe(s, ob);
-    *reinterpret_cast<float4 *>(phys + 4 * n) = make_float4(s[0], s[1], s[2], s[3]);
-#pragma unroll
-    for (int c = 0; c < 6; c += 2) *reinterpret_cast<float2 *>(obs + 6 * n + c) = make_float2(ob[c], ob[c + 1]);
-    reward[n] = r;
-    terminal[n] = term;
-    truncate[n] = trunc;
-    step_count[n] = sc;
-    episode[n] = ep;
-}
-
-// ---- the envs of the one-launch kernel.  P: physical floats per env (g.env_state rows), S: observation width (the policy's input);
-// load / store: the env's lane and the live buffers; observe: the observation of a physical state; step: one env step on the physical
-// state and the counters, returns the reward.
-struct CartPoleEnv {                        // the observation IS the physical state, the reward is 1
+// ---- the envs.  P: physical floats per env (env_state rows), S: observation width (the policy's input); load / store: an env's thread
+// and the live buffers (env_state (N, P), obs (N, S)); observe: the observation of a physical state; action: the env's action of the
+// int64 the per-step entry is handed; step: one env step on the physical state and the counters, returns the reward.
+struct CartPoleEnv {                        // the observation IS the physical state (obs is env_state), the reward is 1
     static constexpr int P = 4, S = 4, A = 0;                  // A = 0: any action_dim the policy shapes allow (actions other than 1 push left)
     static constexpr const char *kName = "CartPole";
-    static __device__ __forceinline__ void load(const RdArgs &g, int64_t row, float (&p)[P], float (&ob)[S])
+    static __device__ __forceinline__ void load(const float *env_state, const float *, int64_t row, float (&p)[P], float (&ob)[S])
     {
-        const float4 v = *reinterpret_cast<const float4 *>(g.env_state + 4 * row);
+        const float4 v = *reinterpret_cast<const float4 *>(env_state + 4 * row);
         p[0] = ob[0] = v.x; p[1] = ob[1] = v.y; p[2] = ob[2] = v.z; p[3] = ob[3] = v.w;
     }
+    static __device__ __forceinline__ int action(int64_t a) { return a == 1 ? 1 : 0; }
     static __device__ __forceinline__ void observe(const float (&p)[P], float (&ob)[S])
     {
 #pragma unroll
@@ -170,9 +130,9 @@ struct CartPoleEnv {                        // the observation IS the physical s
         const float4 v = *reinterpret_cast<const float4 *>(src);
         ob[0] = v.x; ob[1] = v.y; ob[2] = v.z; ob[3] = v.w;
     }
-    static __device__ __forceinline__ void store(const RdArgs &g, int64_t row, const float (&p)[P], const float (&ob)[S])
+    static __device__ __forceinline__ void store(float *env_state, float *, int64_t row, const float (&p)[P], const float (&ob)[S])
     {
-        *reinterpret_cast<float4 *>(g.env_state + 4 * row) = make_float4(p[0], p[1], p[2], p[3]);
+        *reinterpret_cast<float4 *>(env_state + 4 * row) = make_float4(p[0], p[1], p[2], p[3]);
     }
     static __device__ __forceinline__ float step(float (&p)[P], int act, int &sc, int &ep, int max_step, uint64_t seed, uint32_t env,
                                                  bool &term, bool &trunc)
@@ -182,19 +142,16 @@ struct CartPoleEnv {                        // the observation IS the physical s
     }
 };
 
-struct AcrobotEnv {                         // the physical state (theta1, theta2, omega1, omega2) is of record; g.obs is the live observation
+struct AcrobotEnv {                         // the physical state (theta1, theta2, omega1, omega2) is of record; obs is the live observation
     static constexpr int P = 4, S = 6, A = 3;
     static constexpr const char *kName = "Acrobot";
-    static __device__ __forceinline__ void load(const RdArgs &g, int64_t row, float (&p)[P], float (&ob)[S])
+    static __device__ __forceinline__ void load(const float *env_state, const float *obs, int64_t row, float (&p)[P], float (&ob)[S])
     {
-        const float4 v = *reinterpret_cast<const float4 *>(g.env_state + 4 * row);
+        const float4 v = *reinterpret_cast<const float4 *>(env_state + 4 * row);
         p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
-#pragma unroll
-        for (int c = 0; c < 6; c += 2) {    // the policy's input at t = 0 is the live observation as handed in, not observe(p)
-            const float2 o = *reinterpret_cast<const float2 *>(g.obs + 6 * row + c);
-            ob[c] = o.x; ob[c + 1] = o.y;
-        }
+        load_obs(obs + 6 * row, ob);        // the policy's input at t = 0 is the live observation as handed in, not observe(p)
     }
+    static __device__ __forceinline__ int action(int64_t a) { return a == 0 ? 0 : (a == 2 ? 2 : 1); }
     static __device__ __forceinline__ void observe(const float (&p)[P], float (&ob)[S]) { acrobot_observe(p, ob); }
     static __device__ __forceinline__ void store_obs(float *dst, const float (&ob)[S])
     {
@@ -209,10 +166,10 @@ struct AcrobotEnv {                         // the physical state (theta1, theta
             ob[c] = o.x; ob[c + 1] = o.y;
         }
     }
-    static __device__ __forceinline__ void store(const RdArgs &g, int64_t row, const float (&p)[P], const float (&ob)[S])
+    static __device__ __forceinline__ void store(float *env_state, float *obs, int64_t row, const float (&p)[P], const float (&ob)[S])
     {
-        *reinterpret_cast<float4 *>(g.env_state + 4 * row) = make_float4(p[0], p[1], p[2], p[3]);
-        store_obs(g.obs + 6 * row, ob);
+        *reinterpret_cast<float4 *>(env_state + 4 * row) = make_float4(p[0], p[1], p[2], p[3]);
+        store_obs(obs + 6 * row, ob);
     }
     static __device__ __forceinline__ float step(float (&p)[P], int act, int &sc, int &ep, int max_step, uint64_t seed, uint32_t env,
                                                  bool &term, bool &trunc)
@@ -220,6 +177,30 @@ struct AcrobotEnv {                         // the physical state (theta1, theta
         return acrobot_step(p, act, sc, ep, max_step, seed, env, term, trunc);
     }
 };
+
+// the per-step env kernel: one thread per env, the trait's statements on the live buffers, reward / flag rows out.  env_state and obs are
+// not __restrict__: CartPole hands the same buffer in as both.  What load reads of obs is dead here (observe overwrites it before store).
+template <typename Env>
+__global__ __launch_bounds__(256) void env_step_kernel(float *env_state, float *obs, const int64_t *__restrict__ action,
+                                                       int32_t *__restrict__ step_count, int32_t *__restrict__ episode,
+                                                       float *__restrict__ reward, uint8_t *__restrict__ terminal,
+                                                       uint8_t *__restrict__ truncate, int64_t N, int max_step, uint64_t seed)
+{
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    float s[Env::P], ob[Env::S];
+    Env::load(env_state, obs, n, s, ob);
+    int sc = step_count[n], ep = episode[n];
+    bool term, trunc;
+    const float r = Env::step(s, Env::action(action[n]), sc, ep, max_step, seed, (uint32_t)n, term, trunc);
+    Env::observe(s, ob);
+    Env::store(env_state, obs, n, s, ob);
+    reward[n] = r;
+    terminal[n] = term;
+    truncate[n] = trunc;
+    step_count[n] = sc;
+    episode[n] = ep;
+}
 
 // forward_layer (mlp_chain.h) on U tiles at once (the GAE_ form's value pass): one pass over the weight copy, the U accumulation chains
 // interleaved in the matrix pipe.  A tile's own products and sums come in forward_layer's order, so its result does not depend on U.
@@ -416,7 +397,7 @@ __global__ __launch_bounds__(256) void rollout_discrete_kernel(std::conditional_
     float *slot = ZP + (wave * 16 + l15) * RD_SLOT;
 
     float s[Env::P], ob[S], avg[S], den[S];                   // physical state, its observation (the env's lane), the normalisation
-    Env::load(g, row, s, ob);
+    Env::load(g.env_state, g.obs, row, s, ob);
 #pragma unroll
     for (int c = 0; c < S; ++c) { avg[c] = g.avg[c]; den[c] = g.std[c] + 1e-4f; }
     int sc = g.step_count[row], ep = g.episode[row];
@@ -433,6 +414,7 @@ __global__ __launch_bounds__(256) void rollout_discrete_kernel(std::conditional_
 
         // (ob - avg) / (std + 1e-4) in the env's lane; feature k is element k & 3 of lane group q = k >> 2: features 0..3 stay, those
         // past 3 move to the env's q >= 1 lanes inside the wave (every lane takes part); every other operand element is zero
+        // (rd_values restates these statements: as one function shared by both, five of the six forms come out as other machine code)
         f32x4 x[8], ha[8], hb[8], z[8], gd[8];
         float xn[S];
 #pragma unroll
@@ -490,7 +472,7 @@ __global__ __launch_bounds__(256) void rollout_discrete_kernel(std::conditional_
 
     // ---- hand the environment back: live state, observation and counters; the agent's own copy of the final state
     if (own && valid) {
-        Env::store(g, row, s, ob);
+        Env::store(g.env_state, g.obs, row, s, ob);
         if (g.o_last_state) Env::store_obs(g.o_last_state + S * row, ob);
         g.step_count[row] = sc;
         g.episode[row] = ep;
@@ -608,35 +590,130 @@ int rd_launch(const std::conditional_t<GAE_, RdGaeArgs, RdArgs> &g, const char *
     return erl_hip_status(hipGetLastError(), what);
 }
 
+// ---- the entries' argument packs as the C ABI spells them (include/erl_hip.h), in its order
+struct RdHead {                             // the policy and the env, up to N, H (CartPole: obs is env_state)
+    const float *actor_params, *act_avg, *act_std;
+    int S, h1, h2, A;
+    float *env_state, *obs;
+    int32_t *step_count, *episode;
+    int max_step;
+    uint64_t env_seed;
+    int64_t N, H;
+};
+
+struct RdPlanes {                           // the rollout's draws and the planes it writes
+    const float *uniform;
+    uint64_t seed, counter0;
+    float reward_scale;
+    float *out_states;
+    int32_t *out_actions;
+    float *out_logprobs, *out_rewards;
+    uint8_t *out_undones, *out_unmasks;
+    float *out_last_state, *out_uniform;
+};
+
+struct RdGaeTail {                          // the GAE_ form's twelve: the critic, the four planes it leaves, the rows of partial sums, the scan
+    const float *critic_params, *cri_avg, *cri_std;
+    float *out_values, *out_next_value, *out_advantages, *out_reward_sums;
+    void *gae_partials;
+    int64_t gae_partials_bytes;
+    float gamma, lambda_gae;
+    int use_v_trace;
+};
+
 template <typename Env>
-int rd_fill(RdArgs &g, const char *what, const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2, int A,
-            float *env_state, float *obs, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H)
+int rd_fill(RdArgs &g, const char *what, const RdHead &e)
 {
-    ERL_REQUIRE(actor_params && act_avg && act_std && env_state && obs && step_count && episode, "%s: NULL tensor", what);
-    ERL_REQUIRE(rd_dims_ok(S, h1, h2, A), "%s: unsupported dims S=%d net=[%d,%d] A=%d (one-launch discrete rollout: state_dim <= 64, 2 hidden "
-                "layers of 32..128 in steps of 32, 2 <= action_dim <= %d)", what, S, h1, h2, A, RD_MAX_A);
-    ERL_REQUIRE(S == Env::S, "%s: bad environment argument: %s's state_dim is %d, not %d", what, Env::kName, Env::S, S);
-    ERL_REQUIRE(Env::A == 0 || A == Env::A, "%s: bad environment argument: %s's action_dim is %d, not %d", what, Env::kName, Env::A, A);
-    ERL_REQUIRE(N >= 1 && H >= 1 && H < (1LL << 30) && N <= ((1LL << 31) - 1) / H && max_step >= 1, "%s: bad shape N=%lld H=%lld max_step=%d", what,
-                (long long)N, (long long)H, max_step);
-    g.P = actor_params; g.avg = act_avg; g.std = act_std;
-    g.h1 = h1; g.h2 = h2; g.A = A; g.N = N; g.H = (int)H;
-    g.env_state = env_state; g.obs = obs; g.step_count = step_count; g.episode = episode; g.max_step = max_step; g.env_seed = env_seed;
+    ERL_REQUIRE(e.actor_params && e.act_avg && e.act_std && e.env_state && e.obs && e.step_count && e.episode, "%s: NULL tensor", what);
+    ERL_REQUIRE(rd_dims_ok(e.S, e.h1, e.h2, e.A), "%s: unsupported dims S=%d net=[%d,%d] A=%d (one-launch discrete rollout: state_dim <= 64, 2 "
+                "hidden layers of 32..128 in steps of 32, 2 <= action_dim <= %d)", what, e.S, e.h1, e.h2, e.A, RD_MAX_A);
+    ERL_REQUIRE(e.S == Env::S, "%s: bad environment argument: %s's state_dim is %d, not %d", what, Env::kName, Env::S, e.S);
+    ERL_REQUIRE(Env::A == 0 || e.A == Env::A, "%s: bad environment argument: %s's action_dim is %d, not %d", what, Env::kName, Env::A, e.A);
+    ERL_REQUIRE(e.N >= 1 && e.H >= 1 && e.H < (1LL << 30) && e.N <= ((1LL << 31) - 1) / e.H && e.max_step >= 1,
+                "%s: bad shape N=%lld H=%lld max_step=%d", what, (long long)e.N, (long long)e.H, e.max_step);
+    g.P = e.actor_params; g.avg = e.act_avg; g.std = e.act_std;
+    g.h1 = e.h1; g.h2 = e.h2; g.A = e.A; g.N = e.N; g.H = (int)e.H;
+    g.env_state = e.env_state; g.obs = e.obs; g.step_count = e.step_count; g.episode = e.episode; g.max_step = e.max_step; g.env_seed = e.env_seed;
     return ERL_OK;
+}
+
+// the rollout entries' body; the plain form is the GAE_ form without its tail (`c` is not read).  Every pointer of the tail is required.
+template <typename Env, bool GAE_>
+int rd_rollout(const char *what, const RdHead &e, const RdPlanes &o, const RdGaeTail &c, void *stream)
+{
+    ERL_REQUIRE(o.out_states && o.out_actions && o.out_logprobs && o.out_rewards && o.out_undones && o.out_unmasks, "%s: NULL tensor", what);
+    if constexpr (GAE_) {
+        ERL_REQUIRE(c.critic_params, "%s: NULL tensor (critic_params)", what);
+        ERL_REQUIRE(c.cri_avg, "%s: NULL tensor (cri_avg)", what);
+        ERL_REQUIRE(c.cri_std, "%s: NULL tensor (cri_std)", what);
+        ERL_REQUIRE(c.out_values, "%s: NULL tensor (out_values)", what);
+        ERL_REQUIRE(c.out_next_value, "%s: NULL tensor (out_next_value)", what);
+        ERL_REQUIRE(c.out_advantages, "%s: NULL tensor (out_advantages)", what);
+        ERL_REQUIRE(c.out_reward_sums, "%s: NULL tensor (out_reward_sums)", what);
+        ERL_REQUIRE(c.gae_partials, "%s: NULL tensor (gae_partials)", what);
+    }
+    std::conditional_t<GAE_, RdGaeArgs, RdArgs> g{};
+    int rc = rd_fill<Env>(g, what, e);
+    if (rc) return rc;
+    g.uniform = o.uniform; g.seed = o.seed; g.counter0 = o.counter0; g.reward_scale = o.reward_scale;
+    g.o_states = o.out_states; g.o_actions = o.out_actions; g.o_logprobs = o.out_logprobs; g.o_rewards = o.out_rewards;
+    g.o_undones = o.out_undones; g.o_unmasks = o.out_unmasks; g.o_last_state = o.out_last_state; g.o_uniform = o.out_uniform;
+    if constexpr (GAE_) {
+        const int64_t need = erl_rollout_discrete_gae_workspace_bytes(e.N);
+        ERL_REQUIRE(need > 0 && c.gae_partials_bytes >= need, "%s: gae_partials of %lld bytes, erl_rollout_discrete_gae_workspace_bytes(N) = %lld",
+                    what, (long long)c.gae_partials_bytes, (long long)need);
+        g.Pc = c.critic_params; g.cavg = c.cri_avg; g.cstd = c.cri_std;
+        g.o_values = c.out_values; g.o_next_value = c.out_next_value; g.o_adv = c.out_advantages; g.o_ret = c.out_reward_sums;
+        g.gae_ws = (double *)c.gae_partials; g.gamma = c.gamma; g.lam = c.lambda_gae; g.vtrace = c.use_v_trace ? 1 : 0;
+    }
+    return rd_launch<Env, false, GAE_>(g, what, (hipStream_t)stream);
+}
+
+// the evaluation entries' body
+template <typename Env>
+int rd_eval(const char *what, const RdHead &e, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    ERL_REQUIRE(workspace, "%s: NULL tensor (workspace)", what);
+    RdArgs g{};
+    int rc = rd_fill<Env>(g, what, e);
+    if (rc) return rc;
+    ERL_REQUIRE(erl_eval_ws_bytes(e.N, e.H) > 0 && workspace_bytes >= erl_eval_ws_bytes(e.N, e.H),
+                "%s: workspace of %lld bytes, erl_eval_workspace_bytes(N, H) = %lld", what, (long long)workspace_bytes,
+                (long long)erl_eval_ws_bytes(e.N, e.H));
+    const ErlEvalWs w = erl_eval_ws_layout(workspace, e.N, e.H);
+    g.ev_rec = w.rec; g.ev_cnt = w.cnt;
+    return rd_launch<Env, true>(g, what, (hipStream_t)stream);
+}
+
+// the per-step entries' body (CartPole: obs is env_state)
+template <typename Env>
+int rd_step(const char *what, float *env_state, float *obs, const int64_t *action, int32_t *step_count, int32_t *episode, float *reward,
+            uint8_t *terminal, uint8_t *truncate, int64_t N, int max_step, uint64_t seed, void *stream)
+{
+    ERL_REQUIRE(env_state && obs && action && step_count && episode && reward && terminal && truncate, "%s: NULL tensor", what);
+    ERL_REQUIRE(N >= 1 && N < (1LL << 31) && max_step >= 1, "%s: bad shape N=%lld max_step=%d", what, (long long)N, max_step);
+    hipLaunchKernelGGL(env_step_kernel<Env>, dim3((unsigned)erl_cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, env_state, obs, action,
+                       step_count, episode, reward, terminal, truncate, N, max_step, seed);
+    ERL_LAUNCH_CHECK(what);
 }
 
 }  // namespace
 
 extern "C" int erl_rollout_discrete_supported(int S, int h1, int h2, int A) { return rd_dims_ok(S, h1, h2, A) ? 1 : 0; }
 
+extern "C" int erl_rollout_discrete_gae_partials(int64_t N) { return N >= 1 && N < (1LL << 31) ? (int)erl_cdiv(N, 16) : -1; }
+
+extern "C" int64_t erl_rollout_discrete_gae_workspace_bytes(int64_t N)
+{
+    return N >= 1 && N < (1LL << 31) ? erl_cdiv(N, 16) * 3 * (int64_t)sizeof(double) : -1;
+}
+
+// ---- CartPole-v1: env_state is both live buffers
 extern "C" int erl_cartpole_step_f32(float *state, const int64_t *action, int32_t *step_count, int32_t *episode, float *reward,
                                      uint8_t *terminal, uint8_t *truncate, int64_t N, int max_step, uint64_t seed, void *stream)
 {
-    ERL_REQUIRE(state && action && step_count && episode && reward && terminal && truncate, "erl_cartpole_step_f32: NULL tensor");
-    ERL_REQUIRE(N >= 1 && N < (1LL << 31) && max_step >= 1, "erl_cartpole_step_f32: bad shape N=%lld max_step=%d", (long long)N, max_step);
-    hipLaunchKernelGGL(cartpole_step_kernel, dim3((unsigned)erl_cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, state, action, step_count,
-                       episode, reward, terminal, truncate, N, max_step, seed);
-    ERL_LAUNCH_CHECK("erl_cartpole_step_f32");
+    return rd_step<CartPoleEnv>("erl_cartpole_step_f32", state, state, action, step_count, episode, reward, terminal, truncate, N, max_step, seed,
+                                stream);
 }
 
 extern "C" int erl_rollout_discrete_cartpole_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2,
@@ -646,125 +723,11 @@ extern "C" int erl_rollout_discrete_cartpole_f32(const float *actor_params, cons
                                                  float *out_logprobs, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks,
                                                  float *out_last_state, float *out_uniform, void *stream)
 {
-    const char *what = "erl_rollout_discrete_cartpole_f32";
-    ERL_REQUIRE(out_states && out_actions && out_logprobs && out_rewards && out_undones && out_unmasks, "%s: NULL tensor", what);
-    RdArgs g{};
-    int rc = rd_fill<CartPoleEnv>(g, what, actor_params, act_avg, act_std, S, h1, h2, A, env_state, env_state, step_count, episode, max_step,
-                                  env_seed, N, H);
-    if (rc) return rc;
-    g.uniform = uniform; g.seed = seed; g.counter0 = counter0; g.reward_scale = reward_scale;
-    g.o_states = out_states; g.o_actions = out_actions; g.o_logprobs = out_logprobs; g.o_rewards = out_rewards;
-    g.o_undones = out_undones; g.o_unmasks = out_unmasks; g.o_last_state = out_last_state; g.o_uniform = out_uniform;
-    return rd_launch<CartPoleEnv, false>(g, what, (hipStream_t)stream);
-}
-
-extern "C" int erl_eval_discrete_cartpole_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2, int A,
-                                              float *env_state, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
-                                              int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    const char *what = "erl_eval_discrete_cartpole_f32";
-    ERL_REQUIRE(workspace, "%s: NULL tensor (workspace)", what);
-    RdArgs g{};
-    int rc = rd_fill<CartPoleEnv>(g, what, actor_params, act_avg, act_std, S, h1, h2, A, env_state, env_state, step_count, episode, max_step,
-                                  env_seed, N, H);
-    if (rc) return rc;
-    ERL_REQUIRE(erl_eval_ws_bytes(N, H) > 0 && workspace_bytes >= erl_eval_ws_bytes(N, H),
-                "%s: workspace of %lld bytes, erl_eval_workspace_bytes(N, H) = %lld", what, (long long)workspace_bytes,
-                (long long)erl_eval_ws_bytes(N, H));
-    const ErlEvalWs w = erl_eval_ws_layout(workspace, N, H);
-    g.ev_rec = w.rec; g.ev_cnt = w.cnt;
-    return rd_launch<CartPoleEnv, true>(g, what, (hipStream_t)stream);
-}
-
-extern "C" int erl_acrobot_step_f32(float *phys, float *obs, const int64_t *action, int32_t *step_count, int32_t *episode, float *reward,
-                                    uint8_t *terminal, uint8_t *truncate, int64_t N, int max_step, uint64_t seed, void *stream)
-{
-    ERL_REQUIRE(phys && obs && action && step_count && episode && reward && terminal && truncate, "erl_acrobot_step_f32: NULL tensor");
-    ERL_REQUIRE(N >= 1 && N < (1LL << 31) && max_step >= 1, "erl_acrobot_step_f32: bad shape N=%lld max_step=%d", (long long)N, max_step);
-    hipLaunchKernelGGL(acrobot_step_kernel, dim3((unsigned)erl_cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, phys, obs, action,
-                       step_count, episode, reward, terminal, truncate, N, max_step, seed);
-    ERL_LAUNCH_CHECK("erl_acrobot_step_f32");
-}
-
-extern "C" int erl_rollout_discrete_acrobot_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2,
-                                                int A, float *phys, float *obs, int32_t *step_count, int32_t *episode, int max_step,
-                                                uint64_t env_seed, int64_t N, int64_t H, const float *uniform, uint64_t seed,
-                                                uint64_t counter0, float reward_scale, float *out_states, int32_t *out_actions,
-                                                float *out_logprobs, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks,
-                                                float *out_last_state, float *out_uniform, void *stream)
-{
-    const char *what = "erl_rollout_discrete_acrobot_f32";
-    ERL_REQUIRE(out_states && out_actions && out_logprobs && out_rewards && out_undones && out_unmasks, "%s: NULL tensor", what);
-    RdArgs g{};
-    int rc = rd_fill<AcrobotEnv>(g, what, actor_params, act_avg, act_std, S, h1, h2, A, phys, obs, step_count, episode, max_step, env_seed, N, H);
-    if (rc) return rc;
-    g.uniform = uniform; g.seed = seed; g.counter0 = counter0; g.reward_scale = reward_scale;
-    g.o_states = out_states; g.o_actions = out_actions; g.o_logprobs = out_logprobs; g.o_rewards = out_rewards;
-    g.o_undones = out_undones; g.o_unmasks = out_unmasks; g.o_last_state = out_last_state; g.o_uniform = out_uniform;
-    return rd_launch<AcrobotEnv, false>(g, what, (hipStream_t)stream);
-}
-
-extern "C" int erl_eval_discrete_acrobot_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2, int A,
-                                             float *phys, float *obs, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
-                                             int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream)
-{
-    const char *what = "erl_eval_discrete_acrobot_f32";
-    ERL_REQUIRE(workspace, "%s: NULL tensor (workspace)", what);
-    RdArgs g{};
-    int rc = rd_fill<AcrobotEnv>(g, what, actor_params, act_avg, act_std, S, h1, h2, A, phys, obs, step_count, episode, max_step, env_seed, N, H);
-    if (rc) return rc;
-    ERL_REQUIRE(erl_eval_ws_bytes(N, H) > 0 && workspace_bytes >= erl_eval_ws_bytes(N, H),
-                "%s: workspace of %lld bytes, erl_eval_workspace_bytes(N, H) = %lld", what, (long long)workspace_bytes,
-                (long long)erl_eval_ws_bytes(N, H));
-    const ErlEvalWs w = erl_eval_ws_layout(workspace, N, H);
-    g.ev_rec = w.rec; g.ev_cnt = w.cnt;
-    return rd_launch<AcrobotEnv, true>(g, what, (hipStream_t)stream);
-}
-
-// ---- the GAE_ form: the rollout entries' arguments, the critic, the four planes it leaves, the rows of partial sums, the scan's
-// hyper-parameters.  Every new pointer is required.
-namespace {
-
-template <typename Env>
-int rd_rollout_gae(const char *what, const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2, int A,
-                   float *env_state, float *obs, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
-                   const float *uniform, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states, int32_t *out_actions,
-                   float *out_logprobs, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state,
-                   float *out_uniform, const float *critic_params, const float *cri_avg, const float *cri_std, float *out_values,
-                   float *out_next_value, float *out_advantages, float *out_reward_sums, void *gae_partials, int64_t gae_partials_bytes,
-                   float gamma, float lambda_gae, int use_v_trace, void *stream)
-{
-    ERL_REQUIRE(out_states && out_actions && out_logprobs && out_rewards && out_undones && out_unmasks, "%s: NULL tensor", what);
-    ERL_REQUIRE(critic_params, "%s: NULL tensor (critic_params)", what);
-    ERL_REQUIRE(cri_avg, "%s: NULL tensor (cri_avg)", what);
-    ERL_REQUIRE(cri_std, "%s: NULL tensor (cri_std)", what);
-    ERL_REQUIRE(out_values, "%s: NULL tensor (out_values)", what);
-    ERL_REQUIRE(out_next_value, "%s: NULL tensor (out_next_value)", what);
-    ERL_REQUIRE(out_advantages, "%s: NULL tensor (out_advantages)", what);
-    ERL_REQUIRE(out_reward_sums, "%s: NULL tensor (out_reward_sums)", what);
-    ERL_REQUIRE(gae_partials, "%s: NULL tensor (gae_partials)", what);
-    RdGaeArgs g{};
-    int rc = rd_fill<Env>(g, what, actor_params, act_avg, act_std, S, h1, h2, A, env_state, obs, step_count, episode, max_step, env_seed, N, H);
-    if (rc) return rc;
-    const int64_t need = erl_rollout_discrete_gae_workspace_bytes(N);
-    ERL_REQUIRE(need > 0 && gae_partials_bytes >= need, "%s: gae_partials of %lld bytes, erl_rollout_discrete_gae_workspace_bytes(N) = %lld",
-                what, (long long)gae_partials_bytes, (long long)need);
-    g.uniform = uniform; g.seed = seed; g.counter0 = counter0; g.reward_scale = reward_scale;
-    g.o_states = out_states; g.o_actions = out_actions; g.o_logprobs = out_logprobs; g.o_rewards = out_rewards;
-    g.o_undones = out_undones; g.o_unmasks = out_unmasks; g.o_last_state = out_last_state; g.o_uniform = out_uniform;
-    g.Pc = critic_params; g.cavg = cri_avg; g.cstd = cri_std;
-    g.o_values = out_values; g.o_next_value = out_next_value; g.o_adv = out_advantages; g.o_ret = out_reward_sums;
-    g.gae_ws = (double *)gae_partials; g.gamma = gamma; g.lam = lambda_gae; g.vtrace = use_v_trace ? 1 : 0;
-    return rd_launch<Env, false, true>(g, what, (hipStream_t)stream);
-}
-
-}  // namespace
-
-extern "C" int erl_rollout_discrete_gae_partials(int64_t N) { return N >= 1 && N < (1LL << 31) ? (int)erl_cdiv(N, 16) : -1; }
-
-extern "C" int64_t erl_rollout_discrete_gae_workspace_bytes(int64_t N)
-{
-    return N >= 1 && N < (1LL << 31) ? erl_cdiv(N, 16) * 3 * (int64_t)sizeof(double) : -1;
+    return rd_rollout<CartPoleEnv, false>(
+        "erl_rollout_discrete_cartpole_f32",
+        {actor_params, act_avg, act_std, S, h1, h2, A, env_state, env_state, step_count, episode, max_step, env_seed, N, H},
+        {uniform, seed, counter0, reward_scale, out_states, out_actions, out_logprobs, out_rewards, out_undones, out_unmasks, out_last_state,
+         out_uniform}, {}, stream);
 }
 
 extern "C" int erl_rollout_discrete_cartpole_gae_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1,
@@ -777,11 +740,43 @@ extern "C" int erl_rollout_discrete_cartpole_gae_f32(const float *actor_params, 
                                                      float *out_advantages, float *out_reward_sums, void *gae_partials,
                                                      int64_t gae_partials_bytes, float gamma, float lambda_gae, int use_v_trace, void *stream)
 {
-    return rd_rollout_gae<CartPoleEnv>("erl_rollout_discrete_cartpole_gae_f32", actor_params, act_avg, act_std, S, h1, h2, A, env_state,
-                                       env_state, step_count, episode, max_step, env_seed, N, H, uniform, seed, counter0, reward_scale,
-                                       out_states, out_actions, out_logprobs, out_rewards, out_undones, out_unmasks, out_last_state,
-                                       out_uniform, critic_params, cri_avg, cri_std, out_values, out_next_value, out_advantages,
-                                       out_reward_sums, gae_partials, gae_partials_bytes, gamma, lambda_gae, use_v_trace, stream);
+    return rd_rollout<CartPoleEnv, true>(
+        "erl_rollout_discrete_cartpole_gae_f32",
+        {actor_params, act_avg, act_std, S, h1, h2, A, env_state, env_state, step_count, episode, max_step, env_seed, N, H},
+        {uniform, seed, counter0, reward_scale, out_states, out_actions, out_logprobs, out_rewards, out_undones, out_unmasks, out_last_state,
+         out_uniform},
+        {critic_params, cri_avg, cri_std, out_values, out_next_value, out_advantages, out_reward_sums, gae_partials, gae_partials_bytes, gamma,
+         lambda_gae, use_v_trace}, stream);
+}
+
+extern "C" int erl_eval_discrete_cartpole_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2, int A,
+                                              float *env_state, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
+                                              int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return rd_eval<CartPoleEnv>("erl_eval_discrete_cartpole_f32",
+                                {actor_params, act_avg, act_std, S, h1, h2, A, env_state, env_state, step_count, episode, max_step, env_seed, N, H},
+                                workspace, workspace_bytes, stream);
+}
+
+// ---- Acrobot-v1: phys is of record, obs is the live observation
+extern "C" int erl_acrobot_step_f32(float *phys, float *obs, const int64_t *action, int32_t *step_count, int32_t *episode, float *reward,
+                                    uint8_t *terminal, uint8_t *truncate, int64_t N, int max_step, uint64_t seed, void *stream)
+{
+    return rd_step<AcrobotEnv>("erl_acrobot_step_f32", phys, obs, action, step_count, episode, reward, terminal, truncate, N, max_step, seed,
+                               stream);
+}
+
+extern "C" int erl_rollout_discrete_acrobot_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2,
+                                                int A, float *phys, float *obs, int32_t *step_count, int32_t *episode, int max_step,
+                                                uint64_t env_seed, int64_t N, int64_t H, const float *uniform, uint64_t seed,
+                                                uint64_t counter0, float reward_scale, float *out_states, int32_t *out_actions,
+                                                float *out_logprobs, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks,
+                                                float *out_last_state, float *out_uniform, void *stream)
+{
+    return rd_rollout<AcrobotEnv, false>(
+        "erl_rollout_discrete_acrobot_f32", {actor_params, act_avg, act_std, S, h1, h2, A, phys, obs, step_count, episode, max_step, env_seed, N, H},
+        {uniform, seed, counter0, reward_scale, out_states, out_actions, out_logprobs, out_rewards, out_undones, out_unmasks, out_last_state,
+         out_uniform}, {}, stream);
 }
 
 extern "C" int erl_rollout_discrete_acrobot_gae_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1,
@@ -794,9 +789,19 @@ extern "C" int erl_rollout_discrete_acrobot_gae_f32(const float *actor_params, c
                                                     float *out_advantages, float *out_reward_sums, void *gae_partials,
                                                     int64_t gae_partials_bytes, float gamma, float lambda_gae, int use_v_trace, void *stream)
 {
-    return rd_rollout_gae<AcrobotEnv>("erl_rollout_discrete_acrobot_gae_f32", actor_params, act_avg, act_std, S, h1, h2, A, phys, obs,
-                                      step_count, episode, max_step, env_seed, N, H, uniform, seed, counter0, reward_scale, out_states,
-                                      out_actions, out_logprobs, out_rewards, out_undones, out_unmasks, out_last_state, out_uniform,
-                                      critic_params, cri_avg, cri_std, out_values, out_next_value, out_advantages, out_reward_sums,
-                                      gae_partials, gae_partials_bytes, gamma, lambda_gae, use_v_trace, stream);
+    return rd_rollout<AcrobotEnv, true>(
+        "erl_rollout_discrete_acrobot_gae_f32", {actor_params, act_avg, act_std, S, h1, h2, A, phys, obs, step_count, episode, max_step, env_seed, N, H},
+        {uniform, seed, counter0, reward_scale, out_states, out_actions, out_logprobs, out_rewards, out_undones, out_unmasks, out_last_state,
+         out_uniform},
+        {critic_params, cri_avg, cri_std, out_values, out_next_value, out_advantages, out_reward_sums, gae_partials, gae_partials_bytes, gamma,
+         lambda_gae, use_v_trace}, stream);
+}
+
+extern "C" int erl_eval_discrete_acrobot_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2, int A,
+                                             float *phys, float *obs, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
+                                             int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return rd_eval<AcrobotEnv>("erl_eval_discrete_acrobot_f32",
+                               {actor_params, act_avg, act_std, S, h1, h2, A, phys, obs, step_count, episode, max_step, env_seed, N, H}, workspace,
+                               workspace_bytes, stream);
 }

@@ -287,17 +287,86 @@ class PendulumVecEnv(_GpuVecEnv):
             workspace.numel(), _hip.stream_ptr()), "erl_sac_eval_pendulum_f32")
 
 
-class CartPoleGpuVecEnv(_GpuVecEnv):
+class _DiscreteGpuVecEnv(_GpuVecEnv):
+    """what the device-resident discrete envs share: the per-step launch and the one-launch rollout / evaluation of a discrete agent
+    (csrc/rollout_discrete.hip).  An env adds its constructor, `reset`, the names of its three C entries, `_live` and `_step`."""
+    if_discrete = True
+    _rollout_entry = _gae_entry = _eval_entry = ""
+
+    def _live(self) -> Tuple[TEN, ...]:
+        """the live buffers the C entries take, in their order (looked up per call: `reset` rebinds them)"""
+        raise NotImplementedError
+
+    def _step(self, *rows) -> None:
+        """the env's `ops.*_step` on its live buffers; `rows` = what follows them, from the action on"""
+        raise NotImplementedError
+
+    @_hip.on_device
+    def step_into(self, action: TEN, reward_row: TEN, terminal_row: TEN, truncate_row: TEN) -> TEN:
+        self.state_epoch += 1
+        action = action.to(self.device).reshape(-1)
+        if action.dtype != th.int64:
+            action = action.long()
+        self._step(action.contiguous(), self.step_count, self.episode, reward_row, terminal_row, truncate_row, self.max_step, self.seed)
+        return self.state
+
+    def _policy_args(self, agent):
+        p, f32 = _hip.ptr, th.float32
+        a = agent._act
+        h1, h2 = agent.net_dims
+        return (p(agent._flat_a.flat, f32), p(a.state_avg.data, f32), p(a.state_std.data, f32), self.state_dim, h1, h2, agent.action_dim,
+                *[p(t, f32) for t in self._live()], p(self.step_count, th.int32), p(self.episode, th.int32), self.max_step,
+                self.seed & (2 ** 64 - 1), self.num_envs)
+
+    @_hip.on_device
+    def fused_rollout_discrete(self, agent, horizon_len: int, uniform, bufs, last_state_out, uniform_out=None, epilogue=None) -> None:
+        """all `horizon_len` steps of AgentDiscretePPO._explore_vec_env in ONE launch (erl_rollout_discrete_<env>_f32): `bufs` = (states,
+        actions int32, logprobs, rewards, undones, unmasks) time-major, written in place (rewards scaled, flags inverted); `uniform` (H, N)
+        injects the U[0,1) draws or None (Philox keyed by (agent.rng_seed, agent.rng_counter + t, env)); `last_state_out` (N, state_dim)
+        or None: the agent's own copy of the final state; `uniform_out` (H, N) or None: the u every cell used.  The env's live buffers
+        and counters advance.
+        `epilogue` = (values (H, N), next_value (N,), advantages (H, N), reward_sums (H, N), partials (3 * erl_rollout_discrete_gae_partials(N),)
+        float64, gamma, lambda_gae, use_v_trace) or None: the same launch also leaves the critic's values, get_advantages (raw), the reward
+        sums and the per-tile sums of the normalisation (erl_rollout_discrete_<env>_gae_f32); everything else is what it is without."""
+        self.state_epoch += 1
+        p, f32 = _hip.ptr, th.float32
+        states, actions, logprobs, rewards, undones, unmasks = bufs
+        name = self._rollout_entry if epilogue is None else self._gae_entry
+        tail = () if epilogue is None else _discrete_epilogue_args(agent, epilogue)
+        _hip.check(getattr(_hip.lib(), name)(
+            *self._policy_args(agent), horizon_len, p(uniform, f32), agent.rng_seed & (2 ** 64 - 1), agent.rng_counter & (2 ** 64 - 1),
+            float(agent.reward_scale), p(states, f32), p(actions, th.int32), p(logprobs, f32), p(rewards, f32), _hip.flag_ptr(undones),
+            _hip.flag_ptr(unmasks), p(last_state_out, f32), p(uniform_out, f32), *tail, _hip.stream_ptr()), name)
+
+    @_hip.on_device
+    def fused_evaluate_discrete(self, agent, horizon_len: int, workspace) -> None:
+        """`horizon_len` steps of the greedy policy argmax(logits) of a discrete agent in ONE launch (erl_eval_discrete_<env>_f32: the
+        evaluation form of `fused_rollout_discrete`); records and counts go to `workspace` as SynVecEnv.fused_evaluate leaves them."""
+        self.state_epoch += 1
+        name = self._eval_entry
+        _hip.check(getattr(_hip.lib(), name)(
+            *self._policy_args(agent), horizon_len, _hip.ptr(workspace, th.uint8), workspace.numel(), _hip.stream_ptr()), name)
+
+
+class CartPoleGpuVecEnv(_DiscreteGpuVecEnv):
     """CartPole-v1 for N envs on the device (erl_cartpole_step_f32): CartPoleVecEnv's dynamics -- gymnasium's physics, Euler, dt 0.02,
     force +-10, any action other than 1 pushes left, terminal when |x| > 2.4 or |theta| > 12 degrees on the new state, reward 1,
     truncation at max_step -- in one launch per step, and behind `fused_rollout_discrete` / `fused_evaluate_discrete` the whole horizon of
     a discrete agent in one launch.  A done row restarts from four U[-0.05, 0.05) Philox draws keyed by (seed, env, episode, component)."""
     env_name = "CartPole-v1"
-    if_discrete = True
+    _rollout_entry, _gae_entry = "erl_rollout_discrete_cartpole_f32", "erl_rollout_discrete_cartpole_gae_f32"
+    _eval_entry = "erl_eval_discrete_cartpole_f32"
 
     def __init__(self, num_envs: int = 1024, max_step: int = 500, gpu_id: int = 0, seed: int = 0, **_):
         super().__init__(num_envs, 4, 2, max_step, gpu_id, seed)
         self.state = th.zeros((num_envs, 4), dtype=th.float32, device=self.device)
+
+    def _live(self):
+        return (self.state,)
+
+    def _step(self, *rows):
+        from .. import ops
+        ops.cartpole_step(self.state, *rows)
 
     def reset(self) -> Tuple[TEN, dict]:
         self.state_epoch += 1
@@ -307,74 +376,32 @@ class CartPoleGpuVecEnv(_GpuVecEnv):
         self.episode.zero_()
         return self.state.clone(), {}
 
-    @_hip.on_device
-    def step_into(self, action: TEN, reward_row: TEN, terminal_row: TEN, truncate_row: TEN) -> TEN:
-        from .. import ops
-        self.state_epoch += 1
-        action = action.to(self.device).reshape(-1)
-        if action.dtype != th.int64:
-            action = action.long()
-        ops.cartpole_step(self.state, action.contiguous(), self.step_count, self.episode, reward_row, terminal_row, truncate_row,
-                          self.max_step, self.seed)
-        return self.state
 
-    def _policy_args(self, agent):
-        p, f32 = _hip.ptr, th.float32
-        a = agent._act
-        h1, h2 = agent.net_dims
-        return (p(agent._flat_a.flat, f32), p(a.state_avg.data, f32), p(a.state_std.data, f32), self.state_dim, h1, h2, agent.action_dim,
-                p(self.state, f32), p(self.step_count, th.int32), p(self.episode, th.int32), self.max_step, self.seed & (2 ** 64 - 1),
-                self.num_envs)
-
-    @_hip.on_device
-    def fused_rollout_discrete(self, agent, horizon_len: int, uniform, bufs, last_state_out, uniform_out=None, epilogue=None) -> None:
-        """all `horizon_len` steps of AgentDiscretePPO._explore_vec_env in ONE launch (erl_rollout_discrete_cartpole_f32): `bufs` = (states,
-        actions int32, logprobs, rewards, undones, unmasks) time-major, written in place (rewards scaled, flags inverted); `uniform` (H, N)
-        injects the U[0,1) draws or None (Philox keyed by (agent.rng_seed, agent.rng_counter + t, env)); `last_state_out` (N, 4) or None:
-        the agent's own copy of the final state; `uniform_out` (H, N) or None: the u every cell used.  The env's state / counters advance.
-        `epilogue` = (values (H, N), next_value (N,), advantages (H, N), reward_sums (H, N), partials (3 * erl_rollout_discrete_gae_partials(N),)
-        float64, gamma, lambda_gae, use_v_trace) or None: the same launch also leaves the critic's values, get_advantages (raw), the reward
-        sums and the per-tile sums of the normalisation (erl_rollout_discrete_cartpole_gae_f32); everything else is what it is without."""
-        self.state_epoch += 1
-        p, f32 = _hip.ptr, th.float32
-        states, actions, logprobs, rewards, undones, unmasks = bufs
-        if epilogue is not None:
-            _hip.check(_hip.lib().erl_rollout_discrete_cartpole_gae_f32(
-                *self._policy_args(agent), horizon_len, p(uniform, f32), agent.rng_seed & (2 ** 64 - 1), agent.rng_counter & (2 ** 64 - 1),
-                float(agent.reward_scale), p(states, f32), p(actions, th.int32), p(logprobs, f32), p(rewards, f32), _hip.flag_ptr(undones),
-                _hip.flag_ptr(unmasks), p(last_state_out, f32), p(uniform_out, f32), *_discrete_epilogue_args(agent, epilogue),
-                _hip.stream_ptr()), "erl_rollout_discrete_cartpole_gae_f32")
-            return
-        _hip.check(_hip.lib().erl_rollout_discrete_cartpole_f32(
-            *self._policy_args(agent), horizon_len, p(uniform, f32), agent.rng_seed & (2 ** 64 - 1), agent.rng_counter & (2 ** 64 - 1),
-            float(agent.reward_scale), p(states, f32), p(actions, th.int32), p(logprobs, f32), p(rewards, f32), _hip.flag_ptr(undones),
-            _hip.flag_ptr(unmasks), p(last_state_out, f32), p(uniform_out, f32), _hip.stream_ptr()), "erl_rollout_discrete_cartpole_f32")
-
-    @_hip.on_device
-    def fused_evaluate_discrete(self, agent, horizon_len: int, workspace) -> None:
-        """`horizon_len` steps of the greedy policy argmax(logits) of a discrete agent in ONE launch (erl_eval_discrete_cartpole_f32: the
-        evaluation form of `fused_rollout_discrete`); records and counts go to `workspace` as SynVecEnv.fused_evaluate leaves them."""
-        self.state_epoch += 1
-        _hip.check(_hip.lib().erl_eval_discrete_cartpole_f32(
-            *self._policy_args(agent), horizon_len, _hip.ptr(workspace, th.uint8), workspace.numel(), _hip.stream_ptr()),
-            "erl_eval_discrete_cartpole_f32")
-
-
-class AcrobotGpuVecEnv(_GpuVecEnv):
+class AcrobotGpuVecEnv(_DiscreteGpuVecEnv):
     """Acrobot-v1 for N envs on the device (erl_acrobot_step_f32): gymnasium's "book" dynamics -- two unit links, g 9.8, dt 0.2, one RK4
     step, angles wrapped into [-pi, pi], velocities clipped to +-4 pi / +-9 pi; action 0 / 1 / 2 is torque -1 / 0 / +1 (any other value:
     0); terminal when -cos(theta1) - cos(theta1 + theta2) > 1 on the new state; reward 0 on the terminal step, -1 otherwise; truncation
     at max_step -- in one launch per step, and behind `fused_rollout_discrete` / `fused_evaluate_discrete` the whole horizon of a discrete
     agent in one launch.  `phys` (N, 4) = (theta1, theta2, omega1, omega2) is the state of record; `state` (N, 6) = (cos theta1,
     sin theta1, cos theta2, sin theta2, omega1, omega2) is the live observation.  A done row restarts from four U[-0.1, 0.1) Philox draws
-    keyed by (seed, env, episode, component)."""
+    keyed by (seed, env, episode, component).
+    In `fused_rollout_discrete` the policy's input at t = 0 is `state` as it stands (the caller may have written its own last state
+    there; `phys` is not disturbed by that), from t = 1 on the observation of `phys`.  `phys`, `state` and the counters advance."""
     env_name = "Acrobot-v1"
-    if_discrete = True
+    _rollout_entry, _gae_entry = "erl_rollout_discrete_acrobot_f32", "erl_rollout_discrete_acrobot_gae_f32"
+    _eval_entry = "erl_eval_discrete_acrobot_f32"
 
     def __init__(self, num_envs: int = 1024, max_step: int = 500, gpu_id: int = 0, seed: int = 0, **_):
         super().__init__(num_envs, 6, 3, max_step, gpu_id, seed)
         self.phys = th.zeros((num_envs, 4), dtype=th.float32, device=self.device)
         self.state = self._observe(self.phys)
+
+    def _live(self):
+        return (self.phys, self.state)
+
+    def _step(self, *rows):
+        from .. import ops
+        ops.acrobot_step(self.phys, self.state, *rows)
 
     @staticmethod
     def _observe(phys: TEN) -> TEN:
@@ -388,55 +415,6 @@ class AcrobotGpuVecEnv(_GpuVecEnv):
         self.step_count.zero_()
         self.episode.zero_()
         return self.state.clone(), {}
-
-    @_hip.on_device
-    def step_into(self, action: TEN, reward_row: TEN, terminal_row: TEN, truncate_row: TEN) -> TEN:
-        from .. import ops
-        self.state_epoch += 1
-        action = action.to(self.device).reshape(-1)
-        if action.dtype != th.int64:
-            action = action.long()
-        ops.acrobot_step(self.phys, self.state, action.contiguous(), self.step_count, self.episode, reward_row, terminal_row, truncate_row,
-                         self.max_step, self.seed)
-        return self.state
-
-    def _policy_args(self, agent):
-        p, f32 = _hip.ptr, th.float32
-        a = agent._act
-        h1, h2 = agent.net_dims
-        return (p(agent._flat_a.flat, f32), p(a.state_avg.data, f32), p(a.state_std.data, f32), self.state_dim, h1, h2, agent.action_dim,
-                p(self.phys, f32), p(self.state, f32), p(self.step_count, th.int32), p(self.episode, th.int32), self.max_step,
-                self.seed & (2 ** 64 - 1), self.num_envs)
-
-    @_hip.on_device
-    def fused_rollout_discrete(self, agent, horizon_len: int, uniform, bufs, last_state_out, uniform_out=None, epilogue=None) -> None:
-        """all `horizon_len` steps of AgentDiscretePPO._explore_vec_env in ONE launch (erl_rollout_discrete_acrobot_f32); arguments as
-        CartPoleGpuVecEnv.fused_rollout_discrete, states (H, N, 6) and `last_state_out` (N, 6).  The policy's input at t = 0 is `state` as
-        it stands (the caller may have written its own last state there; `phys` is not disturbed by that), from t = 1 on the
-        observation of `phys`.  `phys`, `state` and the counters advance.  `epilogue`: as on CartPole (erl_rollout_discrete_acrobot_gae_f32)."""
-        self.state_epoch += 1
-        p, f32 = _hip.ptr, th.float32
-        states, actions, logprobs, rewards, undones, unmasks = bufs
-        if epilogue is not None:
-            _hip.check(_hip.lib().erl_rollout_discrete_acrobot_gae_f32(
-                *self._policy_args(agent), horizon_len, p(uniform, f32), agent.rng_seed & (2 ** 64 - 1), agent.rng_counter & (2 ** 64 - 1),
-                float(agent.reward_scale), p(states, f32), p(actions, th.int32), p(logprobs, f32), p(rewards, f32), _hip.flag_ptr(undones),
-                _hip.flag_ptr(unmasks), p(last_state_out, f32), p(uniform_out, f32), *_discrete_epilogue_args(agent, epilogue),
-                _hip.stream_ptr()), "erl_rollout_discrete_acrobot_gae_f32")
-            return
-        _hip.check(_hip.lib().erl_rollout_discrete_acrobot_f32(
-            *self._policy_args(agent), horizon_len, p(uniform, f32), agent.rng_seed & (2 ** 64 - 1), agent.rng_counter & (2 ** 64 - 1),
-            float(agent.reward_scale), p(states, f32), p(actions, th.int32), p(logprobs, f32), p(rewards, f32), _hip.flag_ptr(undones),
-            _hip.flag_ptr(unmasks), p(last_state_out, f32), p(uniform_out, f32), _hip.stream_ptr()), "erl_rollout_discrete_acrobot_f32")
-
-    @_hip.on_device
-    def fused_evaluate_discrete(self, agent, horizon_len: int, workspace) -> None:
-        """`horizon_len` steps of the greedy policy argmax(logits) of a discrete agent in ONE launch (erl_eval_discrete_acrobot_f32: the
-        evaluation form of `fused_rollout_discrete`); records and counts go to `workspace` as SynVecEnv.fused_evaluate leaves them."""
-        self.state_epoch += 1
-        _hip.check(_hip.lib().erl_eval_discrete_acrobot_f32(
-            *self._policy_args(agent), horizon_len, _hip.ptr(workspace, th.uint8), workspace.numel(), _hip.stream_ptr()),
-            "erl_eval_discrete_acrobot_f32")
 
 
 class CartPoleVecEnv:
