@@ -153,6 +153,26 @@ class AgentBase:
         self.last_state = last_out
         self._last_state_token = (last_out, last_out._version, env, getattr(env, "state_epoch", None), (id(env.state), env.state._version))
 
+    # ---- the env-pairing rule of every one-launch rollout and evaluation --------------------------------
+    def _one_launch_reason(self, env, what: str) -> Optional[str]:
+        """None when `env` and this agent take the one-launch route through the env's method `what` (a rollout or its evaluation
+        twin: one rule, so the two cannot drift apart), else why not.  `_one_launch_agent_reason()` is the agent class's own part:
+        its switches and the shapes its one-launch kernels cover."""
+        if self.device.type != "cuda":
+            return "no GPU"
+        reason = self._one_launch_agent_reason()
+        if reason is not None:
+            return reason
+        if not hasattr(env, what):
+            return f"{type(env).__name__} has no {what}"
+        if getattr(env, "device", None) != self.device:
+            return f"the env lives on {getattr(env, 'device', None)}, the agent on {self.device}"
+        if getattr(env, "num_envs", None) != self.num_envs:
+            return f"the env has {getattr(env, 'num_envs', None)} envs, the agent {self.num_envs}"
+        if getattr(env, "state_dim", None) != self.state_dim or getattr(env, "action_dim", None) != self.action_dim:
+            return "the env's state / action dims are not the agent's"
+        return None
+
     # ---- evaluation on the device (csrc/rollout_eval.hip) ---------------------------------------------
     def evaluate_env(self, env) -> Optional[TEN]:
         """(n_episodes, 2) float32 CPU tensor of (return, length) of every episode `env` finishes within `env.max_step` steps of the

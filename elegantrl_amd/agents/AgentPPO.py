@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import os
 import weakref
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch as th
 from torch import nn
@@ -110,6 +110,18 @@ class FlatAdam:
         self.param_groups = [{"lr": lr, "betas": (0.9, 0.999), "eps": 1e-8}]
 
 
+class UpdateRoute(NamedTuple):
+    """which minibatch loop one `update_net` runs and what follows from that choice (`AgentPPO._update_route`)"""
+    name: str                            # "c_loop" | "torch_dp" | "layered" | "discrete_fused": the loop method (_LOOPS)
+    stride: int                          # floats per gradient row (`_grads`) and per slab
+    slabs: bool                          # the minibatch kernel writes partial gradients into `_slabs`
+    normalises_in_kernel: bool           # the minibatch kernels normalise the advantages at their row loads (no launch for it)
+    takes_rollout_advantages: bool       # may consume what a one-launch rollout's epilogue left (_cached_advantages)
+
+
+_LOOPS = {"c_loop": "_loop_c", "torch_dp": "_loop_torch_dp", "layered": "_loop_layered", "discrete_fused": "_loop_discrete_fused"}
+
+
 class PendingLogs:
     """update_net(..., lazy=True): the logged objectives of an update whose kernels are still running.  `result()` -> the three floats
     update_net returns otherwise (and the device-fault check that goes with its host sync).  Two pinned host blocks are used in turn;
@@ -165,10 +177,9 @@ class AgentPPO(AgentBase):
         # net_dims = (256, 64 | 128) (examples/demo_A2C_PPO.py:117 trains (256, 128)): rollout and value pre-pass on the layered path,
         # the minibatch loop on its own fused kernel (csrc/ppo_step_wd.hip) with the fused path's slabs, optimiser tail and C loop;
         # args.wide_fused = False / ERL_WIDE_FUSED=0 keeps the layered minibatch step (A/B runs, parity tests)
-        import os as _os0
         self._wide = (not self._fused and not self._discrete and len(net_dims) == 2 and net_dims[0] == 256 and net_dims[1] in (64, 128)
                       and state_dim <= 64 and action_dim <= 8
-                      and bool(getattr(args, "wide_fused", _os0.environ.get("ERL_WIDE_FUSED", "1") != "0")))
+                      and bool(getattr(args, "wide_fused", os.environ.get("ERL_WIDE_FUSED", "1") != "0")))
         self._fused_update = self._fused or self._wide
 
         self.ratio_clip = getattr(args, "ratio_clip", 0.25)
@@ -186,12 +197,11 @@ class AgentPPO(AgentBase):
         self.snapshot_last_state = bool(getattr(args, "snapshot_last_state", True))
         # the persistent rollout's epilogue also runs get_advantages + its statistics (three launches less per iteration);
         # args.fused_gae = False / ERL_FUSED_GAE=0 keeps them in update_net (A/B runs, parity tests)
-        import os as _os
-        self.fused_gae = bool(getattr(args, "fused_gae", _os.environ.get("ERL_FUSED_GAE", "1") != "0"))
+        self.fused_gae = bool(getattr(args, "fused_gae", os.environ.get("ERL_FUSED_GAE", "1") != "0"))
         # left to itself the epilogue serves horizons up to 128 steps (its inputs wait in LDS); beyond, a 16-env workgroup walking its
         # steps back from memory costs more than the scan kernels do (200 x 4096: explore_env +33 us against +25 us in update_net:
         # profiles/r06_c2_fused_gae_ab.txt), so longer horizons take them unless args.fused_gae / ERL_FUSED_GAE says otherwise
-        self._fused_gae_explicit = hasattr(args, "fused_gae") or "ERL_FUSED_GAE" in _os.environ
+        self._fused_gae_explicit = hasattr(args, "fused_gae") or "ERL_FUSED_GAE" in os.environ
         self.ppo_arith = str(getattr(args, "ppo_arith", "auto"))
         assert self.ppo_arith in ("auto", "f32", "split"), f"args.ppo_arith = {self.ppo_arith!r}"
         if self._wide and self.ppo_arith == "f32":
@@ -238,7 +248,6 @@ class AgentPPO(AgentBase):
         # GPU-resident envs that expose `fused_rollout` get the whole horizon in ONE launch (csrc/rollout_fused.hip), which
         # also leaves the critic's values of the visited states for update_net; ERL_FUSED_ROLLOUT=0 / args.fused_rollout=False
         # keep the per-step launches (A/B runs, parity tests)
-        import os
         self.fused_rollout = bool(getattr(args, "fused_rollout", os.environ.get("ERL_FUSED_ROLLOUT", self._fused_rollout_default) != "0"))
         self._rollout_cache = None
         self._norm_version = 0
@@ -375,9 +384,7 @@ class AgentPPO(AgentBase):
             self._hand_state_to_env(env, state)    # the env owns the live state buffer; keep it authoritative
         self._last_state_token = None
         self._rollout_cache = None
-        if (self.fused_rollout and self._fused and hasattr(env, "fused_rollout") and getattr(env, "num_envs", None) == N
-                and getattr(env, "device", None) == dev
-                and _hip.lib().erl_rollout_fused_supported(S, self.net_dims[0], self.net_dims[1], A)):
+        if self._one_launch_reason(env, "fused_rollout") is None:
             # one persistent launch for all H steps: policy, env, buffer rows, reward scaling, flag inversion AND the critic's
             # values of every visited state + cri(last_state) (update_net's pre-pass, AgentPPO.py:141-143, :219-220)
             undones, unmasks = terminals, truncates          # the kernel writes the inverted flags straight into these planes
@@ -453,26 +460,19 @@ class AgentPPO(AgentBase):
         return states, actions, logprobs, rewards, undones, unmasks
 
     # ---- evaluation: the deterministic policy on a device-resident env, two launches ----------------
-    def _fused_eval_reason(self, env) -> Optional[str]:
-        """None when `evaluate_env(env)` runs the fused evaluation, else why not"""
-        if self.device.type != "cuda":
-            return "no GPU"
+    def _one_launch_agent_reason(self) -> Optional[str]:
         if not self._fused:
             return "the agent is not on the fused path (" + self.kernel_path.split(":")[0] + ")"
-        if not self.fused_rollout:           # (the conditions of the training twin, _explore_vec_env)
+        if not self.fused_rollout:
             return "args.fused_rollout is off (the persistent rollout and its evaluation form go together)"
-        if not hasattr(env, "fused_evaluate"):
-            return f"{type(env).__name__} has no fused_evaluate"
-        if getattr(env, "device", None) != self.device:
-            return f"the env lives on {getattr(env, 'device', None)}, the agent on {self.device}"
-        if getattr(env, "num_envs", None) != self.num_envs:
-            return f"the env has {getattr(env, 'num_envs', None)} envs, the agent {self.num_envs}"
         S, A = self.state_dim, self.action_dim
-        if getattr(env, "state_dim", None) != S or getattr(env, "action_dim", None) != A:
-            return "the env's state / action dims are not the agent's"
         if not _hip.lib().erl_rollout_fused_supported(S, self.net_dims[0], self.net_dims[1], A):
             return f"S={S} net_dims={list(self.net_dims)} A={A} outside the persistent rollout's shapes"
         return None
+
+    def _fused_eval_reason(self, env) -> Optional[str]:
+        """None when `evaluate_env(env)` runs the fused evaluation, else why not"""
+        return self._one_launch_reason(env, "fused_evaluate")
 
     @_hip.on_device
     def evaluate_env(self, env) -> Optional[TEN]:
@@ -486,26 +486,24 @@ class AgentPPO(AgentBase):
 
     @_hip.on_device
     def _explore_one_env(self, env, horizon_len: int, if_random: bool = False):
-        """single (numpy, non-vectorised) env: AgentPPO.py:34-85; the policy still runs on the GPU."""
-        from .. import ops
+        """single (numpy, non-vectorised) env: AgentPPO.py:34-85; the policy still runs on the GPU.  The categorical agents differ in
+        `_one_env_parts` only: actions (H, 1) int32, env.step gets a python int."""
         self._require_gpu("explore_env")
         self._sync_modules()
-        H, S, A, dev = horizon_len, self.state_dim, self.action_dim, self.device
+        H, S, dev = horizon_len, self.state_dim, self.device
         states = th.zeros((H, 1, S), dtype=th.float32, device=dev)
-        actions = th.zeros((H, 1, A), dtype=th.float32, device=dev)
+        actions, env_action, step, for_env = self._one_env_parts(H)
         logprobs = th.zeros((H, 1), dtype=th.float32, device=dev)
         rewards = th.zeros((H, 1), dtype=th.float32, device=dev)
         terminals = th.zeros((H, 1), dtype=th.bool, device=dev)
         truncates = th.zeros((H, 1), dtype=th.bool, device=dev)
-        env_action = th.empty((1, A), dtype=th.float32, device=dev)
         state = self.last_state.to(dev, th.float32).reshape(1, S).contiguous()
         for t in range(H):
-            (ops.rollout_step if self._fused else ops.mlpn_rollout_step)(
-                self._flat_a.flat, self._spec_a, self._act.state_avg.data, self._act.state_std.data, state,
-                seed=self.rng_seed, counter=self.rng_counter, out_state=states[t], out_action=actions[t],
-                out_logprob=logprobs[t], out_env_action=env_action)
+            step(self._flat_a.flat, self._spec_a, self._act.state_avg.data, self._act.state_std.data, state,
+                 seed=self.rng_seed, counter=self.rng_counter, out_state=states[t], out_action=actions[t],
+                 out_logprob=logprobs[t], out_env_action=env_action)
             self.rng_counter += 1
-            ary_state, reward, terminal, truncate, _ = env.step(env_action[0].cpu().numpy())
+            ary_state, reward, terminal, truncate, _ = env.step(for_env(env_action[0]))
             if terminal or truncate:
                 ary_state, _ = env.reset()
             state = th.as_tensor(ary_state, dtype=th.float32, device=dev).reshape(1, S)
@@ -515,6 +513,14 @@ class AgentPPO(AgentBase):
         self.last_state = state
         rewards *= self.reward_scale
         return states, actions, logprobs, rewards, th.logical_not(terminals), th.logical_not(truncates)
+
+    def _one_env_parts(self, H: int):
+        """what `_explore_one_env` takes from the policy head: the action buffer, the row the step kernel writes for the env, that
+        kernel, and what `env.step` receives of the row"""
+        from .. import ops
+        A, dev = self.action_dim, self.device
+        return (th.zeros((H, 1, A), dtype=th.float32, device=dev), th.empty((1, A), dtype=th.float32, device=dev),
+                ops.rollout_step if self._fused else ops.mlpn_rollout_step, lambda row: row.cpu().numpy())
 
     # ---- GAE: AgentPPO.py:207-232 ---------------------------------------------------------------------
     @_hip.on_device
@@ -587,156 +593,187 @@ class AgentPPO(AgentBase):
                             stats=stats)
 
     # ---- update: AgentPPO.py:135-205 ------------------------------------------------------------------
+    def _update_route(self, dp: bool, has_comm: bool) -> UpdateRoute:
+        """which minibatch loop `update_net` runs: `dp` = the run is data parallel, `has_comm` = the library's own exchange route
+        carries the gradients (else torch.distributed).  Decided from what the constructor cached alone: no library call, no GPU."""
+        if not self._fused_update:      # generic-shape networks: the summed gradient row is written directly, [actor | critic | 4 logged]
+            return UpdateRoute("layered", self._stride, False, False, False)
+        if dp and not has_comm:         # gloo tests, ERL_DP_COLLECTIVE=torch: the interpreter drives the loop around torch's all-reduce
+            return UpdateRoute("torch_dp", self._stride, True, False, False)
+        return UpdateRoute("c_loop", self._stride, True, True, True)
+
     @_hip.on_device
     def update_net(self, buffer, ids: Optional[TEN] = None, lazy: bool = False) -> Tuple[float, float, float]:
         """One PPO update on the rollout `buffer`; returns (obj_critic, obj_surrogate, obj_entropy) means.
         `ids` (update_times, batch_size) int64 injects the minibatch indices (tests); otherwise they are drawn
         with th.randint(H*N, ...) like the reference."""
-        from .. import ops, parallel
+        from .. import parallel
         self._require_gpu("update_net")
         self._sync_modules()
-        # the minibatch kernels' arithmetic travels with every call (ERL_PPO_MODE: objective | arith << 8, ABI 17), not through the
-        # library's process-wide setting: two agents of one process keep their own `ppo_arith`
-        mode = self._objective | ({"auto": 0, "f32": 1, "split": 2}[self.ppo_arith] << 8)
-        states, actions, logprobs, rewards, undones, unmasks = buffer
-        H, N = rewards.shape
-        dev = self.device
-        if self._stats is None:
-            self._stats = th.zeros(8, dtype=th.float64, device=dev)
-
         dp = self.world_size > 1 or parallel.force_dp()
         # the job's exchange route (selected once, by a self-test: parallel.gradient_comm); None: torch.distributed
         comm = parallel.gradient_comm(self._stride) if dp else None
-        c_loop = self._fused_update and (not dp or comm is not None)       # the whole minibatch loop in one C call (below)
-        # the categorical policy's fused route (AgentDiscretePPO._update_discrete_fused): its own slab / gradient-row stride
-        fused_d = self._discrete_update_fused(dp)
-        cached = self._cached_values(states)
-        from_rollout = None
-        if cached is not None:                                                        # left by the fused rollout (same critic)
-            if c_loop or fused_d:
-                from_rollout = self._cached_advantages(rewards, undones, unmasks)     # ... and get_advantages + its sums
-            self._rollout_cache = None                                                # the GAE below mutates rewards / undones
-            if self._discrete and from_rollout is None:
-                # a discrete agent takes what its rollout left whole or not at all (the layered and data-parallel routes, a cache an
-                # edit has invalidated in part): the values of the rollout's register chain are not the pre-pass's bits
-                cached = None
-        if cached is not None:
-            values, next_value = cached
-        else:
-            values, next_value = self.get_values(states), None                        # (H, N)
-        if from_rollout is not None:
-            # raw advantages, reward sums and the five sums come from the rollout's epilogue; rewards / undones still are what
-            # explore_env returned: get_advantages' in-place fix-up of truncated steps rides the last launch (erl_ppo_finish_f32)
-            advantages, reward_sums, stats, adv_parts, n_parts = from_rollout
-            self._stats = stats                # (the sums this update normalised with stay inspectable, as on the other path)
-            if self.world_size > 1 or not c_loop:    # the sums are all-reduced below, or (the discrete fused route) the normalisation
-                ops.adv_stats_fold(adv_parts, n_parts, H, N, stats)     # below is a launch of its own: fold them now (one small launch)
-                adv_parts = None
-        else:
-            stats, adv_parts, n_parts = self._stats, None, 0
-            advantages, reward_sums = self._gae(rewards, undones, unmasks, values, stats=stats, next_value=next_value)
-        if self._discrete:
-            self.advantage_path = "rollout" if from_rollout is not None else "scan"
-        if self.world_size > 1:                                                       # one normalisation for the whole job:
-            if comm is not None:                                                      # the 5 sums ride the gradient's route
-                comm.all_reduce_sum(stats)
-            else:
-                parallel.all_reduce_sum(stats)
-        if not c_loop:     # (the C loop's minibatch kernels normalise at their row loads from `stats`: no launch for it)
-            advantages = ops.adv_normalize(advantages, stats, out=advantages)
+        route = self._update_route(dp, comm is not None)
+        states, actions, logprobs, rewards, undones, unmasks = buffer
+        H, N = rewards.shape
+        advantages, reward_sums, norm, values, from_rollout = self._advantage_stage(buffer, route, comm)
         assert logprobs.shape == advantages.shape == reward_sums.shape == (H, N)
 
         B = int(self.batch_size)
         update_times = int(H * self.repeat_times / B)
         assert update_times >= 1
         if ids is None:
-            ids = th.randint(H * N, size=(update_times, B), device=dev)
+            ids = th.randint(H * N, size=(update_times, B), device=self.device)
         assert ids.shape == (update_times, B) and ids.dtype == th.int64
-        if self._discrete:
-            self.update_path = "fused" if fused_d else "layered"
-        stride = self._stride_discrete_fused if fused_d else self._stride
-        n_slabs = self._n_slabs(B) if self._fused_update or fused_d else 0
-        if (self._fused_update or fused_d) and (self._slabs is None or self._slabs.shape != (n_slabs, stride)):
-            self._slabs = th.empty((n_slabs, stride), dtype=th.float32, device=dev)
-        if self._grads is None or self._grads.shape[0] < update_times or self._grads.shape[1] != stride:
-            self._grads = th.empty((update_times, stride), dtype=th.float32, device=dev)
+        self._ensure_update_buffers(route, B, update_times)
+        logs = getattr(self, _LOOPS[route.name])((states, actions, unmasks, logprobs, advantages, reward_sums), ids, comm, dp, norm)
+        self.act_optimizer.step_count = self.cri_optimizer.step_count = self._adam_step
+        if logs is not None:            # (the layered loop: its means come from torch)
+            return logs
+        return self._finish_logs(update_times, (rewards, undones, unmasks, values) if from_rollout else None, lazy)
+
+    def _rollout_leftovers(self, buffer, route: UpdateRoute):
+        """what the one-launch rollout of this very buffer left: (_cached_values or None, _cached_advantages -- if the route takes them -- or None)"""
+        states, _, _, rewards, undones, unmasks = buffer
+        cached, from_rollout = self._cached_values(states), None
+        if cached is not None:                                                        # left by the fused rollout (same critic)
+            if route.takes_rollout_advantages:
+                from_rollout = self._cached_advantages(rewards, undones, unmasks)     # ... and get_advantages + its sums
+            self._rollout_cache = None                                                # the GAE below mutates rewards / undones
+        return cached, from_rollout
+
+    def _advantage_stage(self, buffer, route: UpdateRoute, comm):
+        """-> (advantages as the route's kernels want them: normalised here unless they do it themselves, reward_sums, `norm` = what
+        `_loop_c` normalises with, values, from_rollout): from the rollout's epilogue where it left them, else from pre-pass + scan"""
+        from .. import ops, parallel
+        states, _, _, rewards, undones, unmasks = buffer
+        H, N = rewards.shape
+        if self._stats is None:
+            self._stats = th.zeros(8, dtype=th.float64, device=self.device)
+        cached, from_rollout = self._rollout_leftovers(buffer, route)
+        values, next_value = cached if cached is not None else (self.get_values(states), None)      # (H, N)
+        if from_rollout is not None:
+            # raw advantages, reward sums and the five sums come from the rollout's epilogue; rewards / undones still are what
+            # explore_env returned: get_advantages' in-place fix-up of truncated steps rides the last launch (erl_ppo_finish_f32)
+            advantages, reward_sums, stats, adv_parts, n_parts = from_rollout
+            self._stats = stats                # (the sums this update normalised with stay inspectable, as on the other path)
+            if self.world_size > 1 or not route.normalises_in_kernel:   # the sums are all-reduced below, or the normalisation below
+                ops.adv_stats_fold(adv_parts, n_parts, H, N, stats)     # is a launch of its own: fold them now (one small launch)
+                adv_parts = None
+        else:
+            stats, adv_parts, n_parts = self._stats, None, 0
+            advantages, reward_sums = self._gae(rewards, undones, unmasks, values, stats=stats, next_value=next_value)
+        if self.world_size > 1:                # one normalisation for the whole job: the 5 sums ride the gradient's route
+            (parallel if comm is None else comm).all_reduce_sum(stats)
+        if not route.normalises_in_kernel:
+            advantages = ops.adv_normalize(advantages, stats, out=advantages)
+        return advantages, reward_sums, dict(adv_stats=stats, adv_partials=adv_parts, n_partials=n_parts), values, from_rollout is not None
+
+    def _ensure_update_buffers(self, route: UpdateRoute, B: int, update_times: int) -> None:
+        """`_slabs` (the minibatch kernel's partial gradients, where the route has them) and `_grads` (one row per minibatch)"""
+        from .. import ops
+        if route.slabs and (self._slabs is None or self._slabs.shape != (ops.ppo_num_slabs(B), route.stride)):
+            self._slabs = th.empty((ops.ppo_num_slabs(B), route.stride), dtype=th.float32, device=self.device)
+        if self._grads is None or self._grads.shape[0] < update_times or self._grads.shape[1] != route.stride:
+            self._grads = th.empty((update_times, route.stride), dtype=th.float32, device=self.device)
+
+    def _arith_mode(self) -> int:
+        """ERL_PPO_MODE (objective | arith << 8, ABI 17) travels with every call: two agents of one process keep their own `ppo_arith`"""
+        return self._objective | ({"auto": 0, "f32": 1, "split": 2}[self.ppo_arith] << 8)
+
+    def _layered_step(self, *args) -> None:
+        from .. import ops
+        ops.mlpn_ppo_step(*args, objective=self._objective)
+
+    def _loop_layered(self, batch, ids, comm, dp, norm):
+        """generic-shape networks: one launch per dense layer, the summed gradient written directly; returns its own log means"""
+        from .. import ops, parallel
+        update_times, B = ids.shape
         a, c = self._act, self.cri
         groups = [(0, self._Pa), (self._Pa, self._Pc)]
-        inv_batch = 1.0 / B
-        grad_scale = 1.0 / self.world_size
-        if not self._fused_update and not fused_d:      # generic-shape networks: layered path, summed gradient written directly
-            for k in range(update_times):
-                g = self._grads[k]
-                step = ops.mlpn_ppo_step_discrete if self._discrete else ops.mlpn_ppo_step
-                extra = {} if self._discrete else {"objective": self._objective}
-                step(self._flat_a.flat, self._flat_c.flat, a.state_avg.data, a.state_std.data, c.state_avg.data,
-                     c.state_std.data, self._spec_a, states, actions, unmasks, logprobs, advantages, reward_sums,
-                     ids[k], float(self.ratio_clip), self.lambda_entropy_value, inv_batch, g, **extra)
-                if comm is not None:
-                    comm.all_reduce_sum(g)
-                elif dp:
-                    parallel.all_reduce_sum(g)
-                self._adam_step += 1
-                ops.clip_adam(self._flat, g, self._exp_avg, self._exp_avg_sq, groups, self._adam_step, float(self.learning_rate),
-                              float(self.clip_grad_norm), grad_scale=grad_scale)
-            self.act_optimizer.step_count = self.cri_optimizer.step_count = self._adam_step
-            logs = self._grads[:update_times, self._Pa + self._Pc:self._Pa + self._Pc + 3].mean(dim=0) * grad_scale
-            obj_critic, obj_actor, obj_entropy = (float(x) for x in logs.cpu())
-            _hip.check_async_faults()          # the stream is drained: a lost look-back predecessor (NaN advantages) raises here
-            return obj_critic, obj_actor, obj_entropy
+        inv_batch, grad_scale = 1.0 / B, 1.0 / self.world_size
+        for k in range(update_times):
+            g = self._grads[k]
+            self._layered_step(self._flat_a.flat, self._flat_c.flat, a.state_avg.data, a.state_std.data, c.state_avg.data,
+                               c.state_std.data, self._spec_a, *batch, ids[k], float(self.ratio_clip), self.lambda_entropy_value, inv_batch, g)
+            if dp:
+                (parallel if comm is None else comm).all_reduce_sum(g)
+            self._adam_step += 1
+            ops.clip_adam(self._flat, g, self._exp_avg, self._exp_avg_sq, groups, self._adam_step, float(self.learning_rate),
+                          float(self.clip_grad_norm), grad_scale=grad_scale)
+        logs = self._grads[:update_times, self._Pa + self._Pc:self._Pa + self._Pc + 3].mean(dim=0) * grad_scale
+        obj_critic, obj_actor, obj_entropy = (float(x) for x in logs.cpu())
+        _hip.check_async_faults()          # the stream is drained: a lost look-back predecessor (NaN advantages) raises here
+        return obj_critic, obj_actor, obj_entropy
+
+    def _loop_c(self, batch, ids, comm, dp, norm) -> None:
+        """the whole minibatch loop enqueued by one C call (no interpreter on the launch path); data-parallel ranks pass the library's
+        communicator: the exchange is part of the slab-reduction launch (peer-to-peer route) or an RCCL all-reduce on the same stream"""
+        from .. import ops
+        self._one_call_loop(ops.ppo_update, batch, ids, comm=comm, objective=self._arith_mode(), **norm)
+
+    def _one_call_loop(self, op, batch, ids, **extra) -> None:
+        a, c = self._act, self.cri
         h1, h2 = self.net_dims
-        if fused_d:                     # categorical policy: fused minibatch kernel, the whole loop enqueued by one C call
-            self._update_discrete_fused(states, actions, unmasks, logprobs, advantages, reward_sums, ids, update_times)
-        elif not dp or comm is not None:  # the whole minibatch loop is enqueued by one C call (no interpreter on the launch
-            # path); data-parallel ranks pass the library's communicator: the exchange is part of the slab-reduction launch
-            # (peer-to-peer route) or an RCCL all-reduce on the same stream
-            ops.ppo_update(self._flat, self._exp_avg, self._exp_avg_sq, a.state_avg.data, a.state_std.data, c.state_avg.data,
-                           c.state_std.data, self.state_dim, h1, h2, self.action_dim, states, actions, unmasks, logprobs,
-                           advantages, reward_sums, ids, float(self.ratio_clip), self.lambda_entropy_value, self._slabs,
-                           self._grads, self._adam_step + 1, float(self.learning_rate), float(self.clip_grad_norm), comm=comm,
-                           objective=mode, adv_stats=stats, adv_partials=adv_parts, n_partials=n_parts)
-            self._adam_step += update_times
-        else:                           # data parallel through torch.distributed (gloo tests, ERL_DP_COLLECTIVE=torch)
-            # raw pointers + direct C-ABI calls: the interpreter spends ~3 us per launch instead of ~10 (ptr checks, views)
-            L, sp = _hip.lib(), _hip.stream_ptr()
-            pf = _hip.ptr(self._flat, th.float32)
-            p_avg_a, p_std_a, p_avg_c, p_std_c = (_hip.ptr(x) for x in (a.state_avg.data, a.state_std.data, c.state_avg.data,
-                                                                         c.state_std.data))
-            p_s, p_ac, p_um = _hip.ptr(states, th.float32), _hip.ptr(actions, th.float32), _hip.flag_ptr(unmasks)
-            p_lp, p_adv, p_rs = (_hip.ptr(x, th.float32) for x in (logprobs, advantages, reward_sums))
-            p_ids, p_slabs, p_g = _hip.ptr(ids, th.int64), _hip.ptr(self._slabs, th.float32), _hip.ptr(self._grads, th.float32)
-            p_m1, p_m2 = _hip.ptr(self._exp_avg, th.float32), _hip.ptr(self._exp_avg_sq, th.float32)
-            import ctypes
-            off = (ctypes.c_int64 * 2)(0, self._Pa)
-            ln = (ctypes.c_int64 * 2)(self._Pa, self._Pc)
-            S_, A_, clip, lam_e = self.state_dim, self.action_dim, float(self.ratio_clip), self.lambda_entropy_value
-            lr, max_norm, stride = float(self.learning_rate), float(self.clip_grad_norm), self._stride
-            for k in range(update_times):
-                rc = L.erl_ppo_step_f32(pf, pf + 4 * self._Pa, p_avg_a, p_std_a, p_avg_c, p_std_c, S_, h1, h2, A_, p_s, p_ac, p_um,
-                                        p_lp, p_adv, p_rs, H, N, p_ids + 8 * k * B, B, clip, lam_e, inv_batch, mode, p_slabs,
-                                        n_slabs, sp)
-                rc = rc or L.erl_grad_reduce_f32(p_slabs, n_slabs, stride, p_g + 4 * k * stride, sp)
-                if rc:
-                    _hip.check(rc, "erl_ppo_step_f32 / erl_grad_reduce_f32")
-                parallel.all_reduce_sum(self._grads[k])
-                self._adam_step += 1
-                # the same two-launch tail as the C loop (partial norms, then clip + Adam): bit-identical weights on every route
-                rc = L.erl_grad_sq_partials_f32(p_g + 4 * k * stride, stride, off, ln, 2, grad_scale, sp)
-                rc = rc or L.erl_clip_adam_partials_f32(pf, p_g + 4 * k * stride, p_m1, p_m2, stride, off, ln, 2, self._adam_step, lr,
-                                                        0.9, 0.999, 1e-8, max_norm, grad_scale, sp)
-                if rc:
-                    _hip.check(rc, "erl_grad_sq_partials_f32 / erl_clip_adam_partials_f32")
-        self.act_optimizer.step_count = self.cri_optimizer.step_count = self._adam_step
+        op(self._flat, self._exp_avg, self._exp_avg_sq, a.state_avg.data, a.state_std.data, c.state_avg.data, c.state_std.data,
+           self.state_dim, h1, h2, self.action_dim, *batch, ids, float(self.ratio_clip), self.lambda_entropy_value, self._slabs,
+           self._grads, self._adam_step + 1, float(self.learning_rate), float(self.clip_grad_norm), **extra)
+        self._adam_step += ids.shape[0]
+
+    def _loop_torch_dp(self, batch, ids, comm, dp, norm) -> None:
+        """data parallel through torch.distributed (gloo tests, ERL_DP_COLLECTIVE=torch)"""
+        from .. import parallel
+        states, actions, unmasks, logprobs, advantages, reward_sums = batch
+        update_times, B = ids.shape
+        H, N = logprobs.shape
+        a, c = self._act, self.cri
+        h1, h2 = self.net_dims
+        mode, inv_batch, grad_scale, n_slabs = self._arith_mode(), 1.0 / B, 1.0 / self.world_size, self._slabs.shape[0]
+        # raw pointers + direct C-ABI calls: the interpreter spends ~3 us per launch instead of ~10 (ptr checks, views)
+        L, sp = _hip.lib(), _hip.stream_ptr()
+        pf = _hip.ptr(self._flat, th.float32)
+        p_avg_a, p_std_a, p_avg_c, p_std_c = (_hip.ptr(x) for x in (a.state_avg.data, a.state_std.data, c.state_avg.data,
+                                                                     c.state_std.data))
+        p_s, p_ac, p_um = _hip.ptr(states, th.float32), _hip.ptr(actions, th.float32), _hip.flag_ptr(unmasks)
+        p_lp, p_adv, p_rs = (_hip.ptr(x, th.float32) for x in (logprobs, advantages, reward_sums))
+        p_ids, p_slabs, p_g = _hip.ptr(ids, th.int64), _hip.ptr(self._slabs, th.float32), _hip.ptr(self._grads, th.float32)
+        p_m1, p_m2 = _hip.ptr(self._exp_avg, th.float32), _hip.ptr(self._exp_avg_sq, th.float32)
+        import ctypes
+        off = (ctypes.c_int64 * 2)(0, self._Pa)
+        ln = (ctypes.c_int64 * 2)(self._Pa, self._Pc)
+        S_, A_, clip, lam_e = self.state_dim, self.action_dim, float(self.ratio_clip), self.lambda_entropy_value
+        lr, max_norm, stride = float(self.learning_rate), float(self.clip_grad_norm), self._stride
+        for k in range(update_times):
+            rc = L.erl_ppo_step_f32(pf, pf + 4 * self._Pa, p_avg_a, p_std_a, p_avg_c, p_std_c, S_, h1, h2, A_, p_s, p_ac, p_um,
+                                    p_lp, p_adv, p_rs, H, N, p_ids + 8 * k * B, B, clip, lam_e, inv_batch, mode, p_slabs,
+                                    n_slabs, sp)
+            rc = rc or L.erl_grad_reduce_f32(p_slabs, n_slabs, stride, p_g + 4 * k * stride, sp)
+            if rc:
+                _hip.check(rc, "erl_ppo_step_f32 / erl_grad_reduce_f32")
+            parallel.all_reduce_sum(self._grads[k])
+            self._adam_step += 1
+            # the same two-launch tail as the C loop (partial norms, then clip + Adam): bit-identical weights on every route
+            rc = L.erl_grad_sq_partials_f32(p_g + 4 * k * stride, stride, off, ln, 2, grad_scale, sp)
+            rc = rc or L.erl_clip_adam_partials_f32(pf, p_g + 4 * k * stride, p_m1, p_m2, stride, off, ln, 2, self._adam_step, lr,
+                                                    0.9, 0.999, 1e-8, max_norm, grad_scale, sp)
+            if rc:
+                _hip.check(rc, "erl_grad_sq_partials_f32 / erl_clip_adam_partials_f32")
+
+    def _finish_logs(self, update_times: int, fixup, lazy: bool):
+        """the logged means of `_grads[:update_times]` -> three floats or, `lazy`, a PendingLogs.  `fixup` = (rewards, undones, unmasks,
+        values) where the advantages came from the rollout: the same launch applies get_advantages' side effect (AgentPPO.py:211-214)"""
         if self._logs is None:
-            self._logs = th.empty(4, dtype=th.float32, device=dev)
-        if from_rollout is not None:           # the logged means + get_advantages' side effect on rewards / undones (AgentPPO.py:211-214)
-            _hip.check(_hip.lib().erl_ppo_finish_f32(_hip.ptr(self._grads, th.float32), stride, self._Pa + self._Pc, update_times,
-                                                     grad_scale, _hip.ptr(self._logs, th.float32), _hip.ptr(rewards, th.float32),
-                                                     _hip.flag_ptr(undones), _hip.flag_ptr(unmasks), _hip.ptr(values, th.float32), H * N,
-                                                     _hip.stream_ptr()), "erl_ppo_finish_f32")
+            self._logs = th.empty(4, dtype=th.float32, device=self.device)
+        stride, grad_scale = self._grads.shape[1], 1.0 / self.world_size
+        p_grads, p_logs = _hip.ptr(self._grads, th.float32), _hip.ptr(self._logs, th.float32)
+        if fixup is not None:
+            rewards, undones, unmasks, values = fixup
+            _hip.check(_hip.lib().erl_ppo_finish_f32(p_grads, stride, self._Pa + self._Pc, update_times, grad_scale, p_logs,
+                                                     _hip.ptr(rewards, th.float32), _hip.flag_ptr(undones), _hip.flag_ptr(unmasks),
+                                                     _hip.ptr(values, th.float32), rewards.numel(), _hip.stream_ptr()), "erl_ppo_finish_f32")
         else:
-            _hip.check(_hip.lib().erl_ppo_logs_mean_f32(_hip.ptr(self._grads, th.float32), stride, self._Pa + self._Pc, update_times,
-                                                        grad_scale, _hip.ptr(self._logs, th.float32), _hip.stream_ptr()), "erl_ppo_logs_mean_f32")
+            _hip.check(_hip.lib().erl_ppo_logs_mean_f32(p_grads, stride, self._Pa + self._Pc, update_times, grad_scale, p_logs,
+                                                        _hip.stream_ptr()), "erl_ppo_logs_mean_f32")
         if lazy:
             # the three logged means travel to a pinned host block behind the update's last kernel; PendingLogs.result() waits for that
             # copy only.  The caller enqueues the next rollout first (train_agent does): the GPU no longer idles behind this host sync
@@ -745,16 +782,6 @@ class AgentPPO(AgentBase):
         obj_critic, obj_actor, obj_entropy = self._logs[:3].tolist()                  # the only host sync of update_net
         _hip.check_async_faults()              # the stream is drained: a lost look-back predecessor (NaN advantages) raises here
         return obj_critic, obj_actor, obj_entropy
-
-    # the categorical policy's fused update route lives in AgentDiscretePPO; update_net asks through these two
-    _stride_discrete_fused = None
-
-    def _discrete_update_fused(self, dp: bool) -> bool:
-        return False
-
-    def _n_slabs(self, batch_size: int) -> int:
-        from .. import ops
-        return ops.ppo_num_slabs(batch_size)
 
     # ---- running state normalisation: AgentPPO.py:234-249 (never called by the reference's loops) -----
     def update_avg_std_for_normalization(self, states: TEN):
@@ -827,12 +854,14 @@ class AgentDiscretePPO(AgentPPO):
         self.fused_gae_discrete = (bool(args.fused_gae) if hasattr(args, "fused_gae")
                                    else os.environ.get("ERL_FUSED_DISCRETE_GAE", self._fused_gae_default) == "1")
         self.advantage_path = None                # where the last update_net's advantages came from: "rollout" | "scan"
+        # gradient-row / slab stride of the fused route; None: the shape has no fused kernel, which is what `_update_route` asks from
+        # here on (one answer, taken once from erl_ppo_discrete_supported); the layered route keeps `_stride`
+        lib = _hip.lib()
+        self._stride_discrete_fused = (lib.erl_ppo_discrete_slab_stride(state_dim, net_dims[0], net_dims[1], action_dim)
+                                       if len(net_dims) == 2 and lib.erl_ppo_discrete_supported(state_dim, net_dims[0], net_dims[1], action_dim)
+                                       else None)
         super().__init__(net_dims, state_dim, action_dim, gpu_id, args)
         self.fused_gae = self.fused_gae_discrete  # (the base constructor read the continuous agents' switch)
-        # gradient-row / slab stride of the fused route; None: the shape has no fused kernel, which is what `_discrete_update_fused`
-        # asks from here on (one answer, taken once from erl_ppo_discrete_supported); the layered route keeps `_stride`
-        self._stride_discrete_fused = (_hip.lib().erl_ppo_discrete_slab_stride(state_dim, net_dims[0], net_dims[1], action_dim)
-                                       if self._fused_update_shape() else None)
         self.lambda_entropy_value = float(getattr(args, "lambda_entropy", 0.01))          # AgentPPO.py:318
         self.lambda_entropy = th.tensor(self.lambda_entropy_value, dtype=th.float32, device=self.device)
         self.rollout_path = None                  # which route the last _explore_vec_env took: "one-launch" | "loop"
@@ -841,11 +870,6 @@ class AgentDiscretePPO(AgentPPO):
         """the policy shapes of the one-launch discrete rollout / evaluation: the library's own answer (erl_rollout_discrete_supported)"""
         dims = list(self.net_dims)
         return len(dims) == 2 and bool(_hip.lib().erl_rollout_discrete_supported(self.state_dim, dims[0], dims[1], self.action_dim))
-
-    def _fused_update_shape(self) -> bool:
-        """the policy shapes of the fused discrete minibatch kernel: the library's own answer (erl_ppo_discrete_supported)"""
-        dims = list(self.net_dims)
-        return len(dims) == 2 and bool(_hip.lib().erl_ppo_discrete_supported(self.state_dim, dims[0], dims[1], self.action_dim))
 
     def _describe_kernel_path(self) -> str:
         text = super()._describe_kernel_path()
@@ -858,15 +882,14 @@ class AgentDiscretePPO(AgentPPO):
         else:
             route = (f"per-step rollout loop (the one-launch discrete rollout needs two hidden layers of 32..128 in steps of 32, "
                      f"state_dim <= 64, 2 <= action_dim <= 8; here net_dims {dims}, S={S}, A={A})")
-        ok = self._fused_update_shape()
-        if ok and self.fused_update_discrete:
+        if self._update_route(False, False).name == "discrete_fused":
             update = ("fused minibatch kernel, the whole loop in one call (csrc/ppo_step_discrete.hip); data-parallel runs keep the layered "
                       "minibatch loop")
-        elif ok:
+        elif self._stride_discrete_fused is not None:
             update = "layered minibatch loop (args.fused_update is off; the shape has the fused minibatch kernel)"
         else:
             update = "layered minibatch loop (the fused discrete minibatch kernel covers the one-launch rollout's shapes only)"
-        ok = self._one_launch_shape() and self.fused_rollout and self._fused_update_shape() and self.fused_update_discrete
+        ok = self._one_launch_agent_reason() is None and self._update_route(False, False).takes_rollout_advantages
         if self.fused_gae_discrete and ok:
             adv = ("critic values and get_advantages inside the one-launch rollout, consumed by the fused update while the cache is valid "
                    "(else, and on data-parallel runs: value pre-pass + scan)")
@@ -876,39 +899,40 @@ class AgentDiscretePPO(AgentPPO):
             adv = "value pre-pass + scan (args.fused_gae is off, the default for discrete agents)"
         return text + "; rollout: " + route + "; update: " + update + "; advantages: " + adv
 
-    def _discrete_update_fused(self, dp: bool) -> bool:
-        """does this update_net take the fused route: the flag is on, the shape has the kernel (`_stride_discrete_fused` is its stride)
-        and the run is not data parallel (the fused loop has no gradient exchange: those runs keep the layered loop)"""
-        return self.fused_update_discrete and not dp and self._stride_discrete_fused is not None
+    def _update_route(self, dp: bool, has_comm: bool) -> UpdateRoute:
+        """the fused route: the flag is on, the shape has the kernel (`_stride_discrete_fused` is its stride) and the run is not data
+        parallel (the fused loop has no gradient exchange: those runs keep the layered loop).  Its kernel takes normalised advantages."""
+        if self.fused_update_discrete and not dp and self._stride_discrete_fused is not None:
+            return UpdateRoute("discrete_fused", self._stride_discrete_fused, True, False, True)
+        return super()._update_route(dp, has_comm)
 
-    def _update_discrete_fused(self, states, actions, unmasks, logprobs, advantages, reward_sums, ids, update_times: int):
-        """the minibatch loop of update_net on the fused route (called by AgentPPO.update_net, on its device): one C call enqueues, per
-        minibatch, the fused kernel, the slab reduction into `_grads[k]` and the two-launch clip + Adam tail; advantages are normalised"""
+    def _rollout_leftovers(self, buffer, route: UpdateRoute):
+        """a discrete agent takes what its rollout left whole or not at all (the layered and data-parallel routes, a cache an edit has
+        invalidated in part): the values of the rollout's register chain are not the pre-pass's bits"""
+        cached, from_rollout = super()._rollout_leftovers(buffer, route)
+        return (cached if from_rollout is not None else None), from_rollout
+
+    def _advantage_stage(self, buffer, route: UpdateRoute, comm):
+        out = super()._advantage_stage(buffer, route, comm)
+        self.advantage_path = "rollout" if out[-1] else "scan"
+        self.update_path = "fused" if route.name == "discrete_fused" else "layered"
+        return out
+
+    def _layered_step(self, *args) -> None:
         from .. import ops
-        a, c = self._act, self.cri
-        h1, h2 = self.net_dims
-        ops.ppo_update_discrete(self._flat, self._exp_avg, self._exp_avg_sq, a.state_avg.data, a.state_std.data, c.state_avg.data,
-                                c.state_std.data, self.state_dim, h1, h2, self.action_dim, states, actions, unmasks, logprobs, advantages,
-                                reward_sums, ids, float(self.ratio_clip), self.lambda_entropy_value, self._slabs, self._grads,
-                                self._adam_step + 1, float(self.learning_rate), float(self.clip_grad_norm))
-        self._adam_step += update_times
+        ops.mlpn_ppo_step_discrete(*args)
 
-    def _one_launch_reason(self, env, what: str) -> Optional[str]:
-        """None when `env` and this agent take the one-launch route through the env's method `what`, else why not"""
-        if self.device.type != "cuda":
-            return "no GPU"
+    def _loop_discrete_fused(self, batch, ids, comm, dp, norm) -> None:
+        """one C call enqueues, per minibatch, the fused kernel, the slab reduction into `_grads[k]` and the two-launch clip + Adam
+        tail; advantages are normalised"""
+        from .. import ops
+        self._one_call_loop(ops.ppo_update_discrete, batch, ids)
+
+    def _one_launch_agent_reason(self) -> Optional[str]:
         if not self.fused_rollout:
             return "args.fused_rollout is off (the one-launch rollout and its evaluation form go together)"
         if not self._one_launch_shape():
             return f"S={self.state_dim} net_dims={list(self.net_dims)} A={self.action_dim} outside the one-launch discrete rollout's shapes"
-        if not hasattr(env, what):
-            return f"{type(env).__name__} has no {what}"
-        if getattr(env, "device", None) != self.device:
-            return f"the env lives on {getattr(env, 'device', None)}, the agent on {self.device}"
-        if getattr(env, "num_envs", None) != self.num_envs:
-            return f"the env has {getattr(env, 'num_envs', None)} envs, the agent {self.num_envs}"
-        if getattr(env, "state_dim", None) != self.state_dim or getattr(env, "action_dim", None) != self.action_dim:
-            return "the env's state / action dims are not the agent's"
         return None
 
     def _fused_eval_reason(self, env) -> Optional[str]:
@@ -1003,36 +1027,11 @@ class AgentDiscretePPO(AgentPPO):
             rewards *= self.reward_scale
         return states, actions, logprobs, rewards, th.logical_not(terminals), th.logical_not(truncates)
 
-    @_hip.on_device
-    def _explore_one_env(self, env, horizon_len: int, if_random: bool = False):
-        """single (numpy) env, AgentPPO.py:34-85 with if_discrete: actions (H, 1) int32, env.step gets a python int."""
+    def _one_env_parts(self, H: int):
         from .. import ops
-        self._require_gpu("explore_env")
-        self._sync_modules()
-        H, S, dev = horizon_len, self.state_dim, self.device
-        states = th.zeros((H, 1, S), dtype=th.float32, device=dev)
-        actions = th.zeros((H, 1), dtype=th.int32, device=dev)
-        logprobs = th.zeros((H, 1), dtype=th.float32, device=dev)
-        rewards = th.zeros((H, 1), dtype=th.float32, device=dev)
-        terminals = th.zeros((H, 1), dtype=th.bool, device=dev)
-        truncates = th.zeros((H, 1), dtype=th.bool, device=dev)
-        env_action = th.empty((1,), dtype=th.int64, device=dev)
-        state = self.last_state.to(dev, th.float32).reshape(1, S).contiguous()
-        for t in range(H):
-            ops.mlpn_rollout_step_discrete(self._flat_a.flat, self._spec_a, self._act.state_avg.data, self._act.state_std.data, state,
-                                           seed=self.rng_seed, counter=self.rng_counter, out_state=states[t], out_action=actions[t],
-                                           out_logprob=logprobs[t], out_env_action=env_action)
-            self.rng_counter += 1
-            ary_state, reward, terminal, truncate, _ = env.step(int(env_action[0].item()))
-            if terminal or truncate:
-                ary_state, _ = env.reset()
-            state = th.as_tensor(ary_state, dtype=th.float32, device=dev).reshape(1, S)
-            rewards[t, 0] = float(reward)
-            terminals[t, 0] = bool(terminal)
-            truncates[t, 0] = bool(truncate)
-        self.last_state = state
-        rewards *= self.reward_scale
-        return states, actions, logprobs, rewards, th.logical_not(terminals), th.logical_not(truncates)
+        dev = self.device
+        return (th.zeros((H, 1), dtype=th.int32, device=dev), th.empty((1,), dtype=th.int64, device=dev),
+                ops.mlpn_rollout_step_discrete, lambda row: int(row.item()))
 
 
 class AgentDiscreteA2C(AgentDiscretePPO):

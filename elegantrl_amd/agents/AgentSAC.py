@@ -241,9 +241,7 @@ class AgentSAC(AgentBase):
         whole loop is ONE launch (erl_sac_rollout_synenv_f32: same five tensors, final state and env counters, bit for bit, as the
         per-step loop; `args.fused_rollout = False` keeps the loop)."""
         H, N, S, A, dev = horizon_len, self.num_envs, self.state_dim, self.action_dim, self.device
-        if not (self.fused_rollout and not self._actor_variant and hasattr(env, "fused_rollout_offpolicy") and getattr(env, "num_envs", None) == N
-                and getattr(env, "device", None) == dev and getattr(env, "state_dim", None) == S
-                and _hip.lib().erl_sac_rollout_synenv_supported(self._spec.S, self._spec.A, self._spec._c, len(self._spec.hidden), N)):
+        if self._one_launch_reason(env, "fused_rollout_offpolicy") is not None:
             self._last_state_token = None
             return super()._explore_vec_env(env, horizon_len, noise)
         self._sync_modules()
@@ -261,27 +259,19 @@ class AgentSAC(AgentBase):
         self._record_last_state(env, last_out)
         return states, actions, rewards, undones, unmasks
 
-    def _fused_eval_reason(self, env) -> Optional[str]:
-        """None when `evaluate_env(env)` runs the fused evaluation, else why not"""
-        # (the conditions of the training twin, _explore_vec_env: support is exactly that of the persistent rollout)
-        if self.device.type != "cuda":
-            return "no GPU"
+    def _one_launch_agent_reason(self) -> Optional[str]:
         if self._actor_variant:
             return "ActorFixSAC (AgentModSAC) has no persistent rollout"
         if not self.fused_rollout:
             return "args.fused_rollout is off (the persistent rollout and its evaluation form go together)"
-        if not hasattr(env, "fused_evaluate_offpolicy"):
-            return f"{type(env).__name__} has no fused_evaluate_offpolicy"
-        if getattr(env, "device", None) != self.device:
-            return f"the env lives on {getattr(env, 'device', None)}, the agent on {self.device}"
-        if getattr(env, "num_envs", None) != self.num_envs:
-            return f"the env has {getattr(env, 'num_envs', None)} envs, the agent {self.num_envs}"
-        if getattr(env, "state_dim", None) != self.state_dim or getattr(env, "action_dim", None) != self.action_dim:
-            return "the env's state / action dims are not the agent's"
         sp = self._spec
         if not _hip.lib().erl_sac_rollout_synenv_supported(sp.S, sp.A, sp._c, len(sp.hidden), self.num_envs):
             return f"S={sp.S} A={sp.A} net_dims={list(self.net_dims)} N={self.num_envs} outside the persistent off-policy rollout's shapes"
         return None
+
+    def _fused_eval_reason(self, env) -> Optional[str]:
+        """None when `evaluate_env(env)` runs the fused evaluation, else why not"""
+        return self._one_launch_reason(env, "fused_evaluate_offpolicy")
 
     @_hip.on_device
     def evaluate_env(self, env) -> Optional[TEN]:
