@@ -158,6 +158,17 @@ _SIGNATURES = {
                                            c_uint64, c_uint64, c_float, _P, _P, _P, _P, _P, _P, _P]),
     "erl_sac_rollout_pendulum_f32": (c_int, [_P, POINTER(c_int), c_int, _P, _P, _P, _P, c_int, c_uint64, c_int64, c_int64, _P, c_uint64, c_uint64,
                                              c_float, _P, _P, _P, _P, _P, _P, _P]),
+    # AgentModSAC's one-launch rollout / evaluation (ActorFixSAC): the argument lists of their AgentSAC twins
+    "erl_sac_rollout_mod_supported": (c_int, [c_int, c_int, POINTER(c_int), c_int, c_int64]),
+    "erl_sac_rollout_mod_synenv_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, _P, _P, _P, _P, c_int, c_uint64, c_int64, c_int64, _P,
+                                               c_uint64, c_uint64, c_float, _P, _P, _P, _P, _P, _P, _P]),
+    "erl_sac_rollout_mod_pendulum_f32": (c_int, [_P, POINTER(c_int), c_int, _P, _P, _P, _P, c_int, c_uint64, c_int64, c_int64, _P, c_uint64,
+                                                 c_uint64, c_float, _P, _P, _P, _P, _P, _P, _P]),
+    "erl_sac_eval_mod_synenv_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, _P, _P, _P, _P, c_int, c_uint64, c_int64, c_int64, _P,
+                                            c_int64, _P]),
+    "erl_sac_eval_mod_pendulum_f32": (c_int, [_P, POINTER(c_int), c_int, _P, _P, _P, _P, c_int, c_uint64, c_int64, c_int64, _P, c_int64, _P]),
+    "erl_sac_explore_action_tile_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, c_int64, _P, c_uint64, c_uint64, _P, _P, _P,
+                                                c_int64, c_int, _P]),
     "erl_eval_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "erl_eval_synenv_f32": (c_int, [_P] * 3 + [c_int] * 4 + [_P] * 5 + [c_int, c_uint64, c_int64, c_int64, _P, c_int64, _P]),
     "erl_eval_pendulum_f32": (c_int, [_P] * 3 + [c_int] * 2 + [_P] * 4 + [c_int, c_uint64, c_int64, c_int64, _P, c_int64, _P]),

@@ -167,6 +167,8 @@ class AgentSAC(AgentBase):
         self.per_loop_in_c = bool(getattr(args, "per_loop_in_c", os.environ.get("ERL_SAC_PER_LOOP_IN_C", "1") != "0"))
         self.per_path = None                       # which route the last prioritised update_net took (None: none yet / not prioritised)
         self.update_path = None                    # which route the last update_net took: "one C call ..." / "per step: <reason>"
+        self.rollout_path = None                   # which route the last _explore_vec_env took: "one launch ..." / "per-step loop ...: <reason>"
+        self.fused_mod_rollout = False             # AgentModSAC's switch for the ActorFixSAC forms of the rollout launches (_variant_kernel_path)
         self._spec = ops.SacSpec(state_dim, action_dim, net_dims, self.num_ensembles, actor_variant=self._actor_variant)
         dev, f32 = self.device, th.float32
         self._actor_flat = th.zeros(self._spec.actor_count, dtype=f32, device=dev)
@@ -239,11 +241,15 @@ class AgentSAC(AgentBase):
     def _explore_vec_env(self, env, horizon_len: int, noise: Optional[TEN] = None) -> Tuple[TEN, ...]:
         """AgentBase._explore_vec_env (AgentBase.py:130-170); on a device-resident env that offers `fused_rollout_offpolicy` (SynVecEnv) the
         whole loop is ONE launch (erl_sac_rollout_synenv_f32: same five tensors, final state and env counters, bit for bit, as the
-        per-step loop; `args.fused_rollout = False` keeps the loop)."""
+        per-step loop; `args.fused_rollout = False` keeps the loop).  `rollout_path` says which route ran and, for the loop, why."""
         H, N, S, A, dev = horizon_len, self.num_envs, self.state_dim, self.action_dim, self.device
-        if self._one_launch_reason(env, "fused_rollout_offpolicy") is not None:
+        why = self._one_launch_reason(env, "fused_rollout_offpolicy")
+        if why is not None:
             self._last_state_token = None
+            self.rollout_path = f"per-step loop ({self._explore_action_route(N)} + env.step per step): {why}"
             return super()._explore_vec_env(env, horizon_len, noise)
+        self.rollout_path = (f"one launch ({'erl_sac_rollout_mod_' if self._actor_variant else 'erl_sac_rollout_'}*_f32 through "
+                             f"{type(env).__name__}.fused_rollout_offpolicy)")
         self._sync_modules()
         state = self.last_state.to(dev, th.float32)
         assert state.shape == (N, S)
@@ -260,14 +266,33 @@ class AgentSAC(AgentBase):
         return states, actions, rewards, undones, unmasks
 
     def _one_launch_agent_reason(self) -> Optional[str]:
-        if self._actor_variant:
-            return "ActorFixSAC (AgentModSAC) has no persistent rollout"
+        if self._actor_variant and not self.fused_mod_rollout:
+            return ("ActorFixSAC (AgentModSAC) has no persistent rollout unless args.fused_mod_rollout is on (ERL_FUSED_MODSAC_ROLLOUT; "
+                    "profiles/modsac_rollout_ab.txt)")
         if not self.fused_rollout:
             return "args.fused_rollout is off (the persistent rollout and its evaluation form go together)"
         sp = self._spec
-        if not _hip.lib().erl_sac_rollout_synenv_supported(sp.S, sp.A, sp._c, len(sp.hidden), self.num_envs):
+        supported = _hip.lib().erl_sac_rollout_mod_supported if self._actor_variant else _hip.lib().erl_sac_rollout_synenv_supported
+        if not supported(sp.S, sp.A, sp._c, len(sp.hidden), self.num_envs):
             return f"S={sp.S} A={sp.A} net_dims={list(self.net_dims)} N={self.num_envs} outside the persistent off-policy rollout's shapes"
         return None
+
+    def _tile_action_reason(self, n_rows: int) -> Optional[str]:
+        """None when `explore_action` on `n_rows` states is erl_sac_explore_action_tile_f32 (the per-step twin of the one-launch rollouts),
+        else why it is erl_sac_explore_action_f32 / _opt_f32 with their own routes"""
+        if not self._actor_variant:
+            return "ActorSAC: erl_sac_explore_action_f32 picks the tile kernel itself"
+        if not self.fused_mod_rollout:
+            return "args.fused_mod_rollout is off"
+        sp = self._spec
+        if not _hip.lib().erl_sac_rollout_mod_supported(sp.S, sp.A, sp._c, len(sp.hidden), int(n_rows)):
+            return f"S={sp.S} A={sp.A} net_dims={list(self.net_dims)} rows={n_rows} outside the tile kernel's shapes"
+        return None
+
+    def _explore_action_route(self, n_rows: int) -> str:
+        if self._tile_action_reason(n_rows) is None:
+            return "tile action erl_sac_explore_action_tile_f32"
+        return "erl_sac_explore_action_opt_f32" if self._actor_variant else "erl_sac_explore_action_f32"
 
     def _fused_eval_reason(self, env) -> Optional[str]:
         """None when `evaluate_env(env)` runs the fused evaluation, else why not"""
@@ -275,8 +300,9 @@ class AgentSAC(AgentBase):
 
     @_hip.on_device
     def evaluate_env(self, env) -> Optional[TEN]:
-        """AgentBase.evaluate_env on the persistent off-policy rollout's evaluation form (erl_sac_eval_synenv_f32 / erl_sac_eval_pendulum_f32):
-        env.reset(), env.max_step steps of ActorSAC.forward in one launch, the episode table from a second; None outside its shapes."""
+        """AgentBase.evaluate_env on the persistent off-policy rollout's evaluation form (erl_sac_eval_synenv_f32 / erl_sac_eval_pendulum_f32;
+        AgentModSAC with `fused_mod_rollout`: erl_sac_eval_mod_*): env.reset(), env.max_step steps of the actor's `forward` in one launch,
+        the episode table from a second; None outside its shapes."""
         if self._fused_eval_reason(env) is not None:
             return None
         self._sync_modules()
@@ -289,7 +315,8 @@ class AgentSAC(AgentBase):
         from .. import ops
         self._sync_modules()
         action = ops.sac_explore_action(self._spec, self._actor_flat, state.contiguous(), noise=noise, seed=self.rng_seed,
-                                        counter=self.rng_counter, out=out, out_state=out_state)
+                                        counter=self.rng_counter, out=out, out_state=out_state,
+                                        tile=self._tile_action_reason(state.shape[0]) is None)
         self.rng_counter += 1
         return action
 
@@ -478,13 +505,20 @@ class AgentModSAC(AgentSAC):
     `critic_value` off 1.0, so this is 0.61: the actor skips roughly every third step).  The step is erl_sac_update_opt_f32 (csrc/sac.hip,
     layered path; ErlSacOptions carries what differs from AgentSAC) or, with `fused_step` on and inside the fused step's shapes,
     erl_sac_update_mod_f32 (csrc/sac_fused.hip: AgentSAC's tile kernels with ActorFixSAC as a run-time variant); update_net's loop on the
-    fused step is one erl_sac_update_mod_ring_loop_f32 call."""
+    fused step is one erl_sac_update_mod_ring_loop_f32 call.  With `fused_mod_rollout` on and inside the same shapes, `explore_action` is the
+    tile kernel (erl_sac_explore_action_tile_f32) and, on SynVecEnv / PendulumVecEnv with `fused_rollout`, `explore_env` and `evaluate_env` are
+    one launch each (erl_sac_rollout_mod_*, erl_sac_eval_mod_*: csrc/sac_fused.hip sac_rollout_synenv_kernel<.., FIX>); `rollout_path` names
+    the route the last rollout took."""
     _actor_class = ActorFixSAC
     _actor_variant = _hip.SAC_ACTOR_FIX
     _default_ensembles = 8
     # the fused step against the layered one has no A/B record yet (tools/modsac_update_ab.py writes profiles/modsac_update_ab.txt): until
     # it has, the route is opt-in -- args.fused_step = True or ERL_FUSED_MODSAC_STEP=1
     _fused_step_default = "0"
+    # the one-launch rollout / evaluation and the tile action (erl_sac_rollout_mod_*, erl_sac_eval_mod_*, erl_sac_explore_action_tile_f32):
+    # opt-in as well -- args.fused_mod_rollout = True or ERL_FUSED_MODSAC_ROLLOUT=1 (tools/modsac_rollout_ab.py writes
+    # profiles/modsac_rollout_ab.txt); off, the rollout and the evaluation are the per-step loops on erl_sac_explore_action_opt_f32
+    _fused_mod_rollout_default = "0"
 
     def __init__(self, net_dims: List[int], state_dim: int, action_dim: int, gpu_id: int = 0, args: Config = None):
         args = Config() if args is None else args
@@ -524,11 +558,19 @@ class AgentModSAC(AgentSAC):
     def _variant_kernel_path(self, args) -> str:
         # (called by the base constructor, which prints `kernel_path`)
         self.fused_step = bool(getattr(args, "fused_step", os.environ.get("ERL_FUSED_MODSAC_STEP", self._fused_step_default) != "0"))
+        self.fused_mod_rollout = bool(getattr(args, "fused_mod_rollout",
+                                              os.environ.get("ERL_FUSED_MODSAC_ROLLOUT", self._fused_mod_rollout_default) != "0"))
         why = self._fused_step_reason()
         if why is None:
-            return ("fused ModSAC step (erl_sac_update_mod_f32: AgentSAC's tile kernels with ActorFixSAC's raw second layer and head, skipped "
+            step = ("fused ModSAC step (erl_sac_update_mod_f32: AgentSAC's tile kernels with ActorFixSAC's raw second layer and head, skipped "
                     "actor steps end in one small launch, actor target in the actor's clip + Adam launch; update_net's loop is one C call)")
-        return "layered ModSAC step (erl_sac_update_opt_f32: one MFMA GEMM launch per dense layer): " + why
+        else:
+            step = "layered ModSAC step (erl_sac_update_opt_f32: one MFMA GEMM launch per dense layer): " + why
+        why = self._one_launch_agent_reason()
+        if why is None:
+            return step + ("; rollout: one launch on device-resident envs, and so the evaluation (erl_sac_rollout_mod_*, erl_sac_eval_mod_*), "
+                           "per-step action on the tile kernel (erl_sac_explore_action_tile_f32)")
+        return step + "; rollout: per-step loop: " + why
 
     def _ring_step_reason(self) -> Optional[str]:
         why = self._fused_step_reason()

@@ -61,11 +61,12 @@ int erl_sac_rollout_fused(const float *actor_params, int S, int A, int h0, int h
                           const float *Wa, float *phys, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
                           const float *noise, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states, float *out_actions,
                           float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, hipStream_t stream,
-                          float2 *ev_rec = nullptr, int32_t *ev_cnt = nullptr);       // ev_*: the evaluation form (eval_ws.h)
+                          float2 *ev_rec = nullptr, int32_t *ev_cnt = nullptr,        // ev_*: the evaluation form (eval_ws.h)
+                          int variant = 0);                                           // ERL_SAC_ACTOR_FIX: ActorFixSAC (AgentModSAC)
 int64_t erl_sac_fused_ws_floats(int S, int A, int h0, int h1, int E, int64_t B, int64_t Pa, int64_t Pc);
 int erl_sac_explore_fused(const float *actor_params, int S, int A, int h0, int h1, const int64_t *aoff, const float *state, int64_t N,
                           const float *noise, uint64_t seed, uint64_t counter, float *action_out, float *state_out, float *lp_scratch,
-                          hipStream_t sa);
+                          hipStream_t sa, int variant = 0);
 // ---- the SAC update step (sac.hip packs and validates, then enqueues the layered step there or the fused one in sac_fused.hip) ----
 // layer table of one dense network as a flat fp32 block (mlpn_common.h make_dims)
 struct NetDims {

@@ -810,84 +810,116 @@ extern "C" int erl_sac_update_mod_ring_loop_f32(float *actor_params, float *crit
 }
 #undef SAC_CALL
 
-// The whole off-policy rollout of AgentBase._explore_vec_env (AgentBase.py:130-170) on the device-resident SynVecEnv as ONE launch
-// (sac_fused.hip sac_rollout_synenv_kernel); needs erl_sac_rollout_synenv_supported(...)
-extern "C" int erl_sac_rollout_synenv_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state,
-                                          const float *Ws, const float *Wa, int32_t *step_count, int32_t *episode, int max_step,
-                                          uint64_t env_seed, int64_t N, int64_t H, const float *noise, uint64_t seed, uint64_t counter0,
-                                          float reward_scale, float *out_states, float *out_actions, float *out_rewards,
-                                          uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, void *stream)
+// The whole off-policy rollout of AgentBase._explore_vec_env (AgentBase.py:130-170) on a device-resident env as ONE launch
+// (sac_fused.hip sac_rollout_synenv_kernel); needs erl_sac_rollout_synenv_supported(...).  `what`: the entry's name; `phys` NULL: SynVecEnv,
+// else PendulumVecEnv (S = 3, A = 1; phys: (N, 2) theta, theta_dot; env_state: (N, 3) the live observation); `variant`:
+// ERL_SAC_ACTOR_FIX = ActorFixSAC.get_action (the erl_sac_rollout_mod_* entries, AgentModSAC)
+static int sac_rollout_impl(const char *what, int variant, const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state,
+                            const float *Ws, const float *Wa, float *phys, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
+                            int64_t N, int64_t H, const float *noise, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states,
+                            float *out_actions, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, void *stream)
 {
-    ERL_REQUIRE(actor_params && env_state && Ws && Wa && step_count && episode && out_states && out_actions && out_rewards && out_undones &&
-                out_unmasks, "erl_sac_rollout_synenv_f32: NULL tensor");
-    ERL_REQUIRE(erl_sac_rollout_synenv_supported(S, A, hidden, n_hidden, N), "erl_sac_rollout_synenv_f32: unsupported dims S=%d A=%d N=%lld (two "
-                "hidden layers <= 256 wide in steps of 16, S + A <= 64, A <= 8, N <= 4096; ERL_SAC_FUSED=0 turns it off)", S, A, (long long)N);
-    ERL_REQUIRE(H >= 1 && H < (1LL << 30) && max_step >= 1, "erl_sac_rollout_synenv_f32: bad H=%lld max_step=%d", (long long)H, max_step);
+    ERL_REQUIRE(actor_params && env_state && (phys || (Ws && Wa)) && step_count && episode && out_states && out_actions && out_rewards &&
+                out_undones && out_unmasks, "%s: NULL tensor", what);
+    if (phys)
+        ERL_REQUIRE(erl_sac_rollout_synenv_supported(S, A, hidden, n_hidden, N), "%s: unsupported dims N=%lld (two hidden "
+                    "layers <= 256 wide in steps of 16, N <= 4096; ERL_SAC_FUSED=0 turns it off)", what, (long long)N);
+    else
+        ERL_REQUIRE(erl_sac_rollout_synenv_supported(S, A, hidden, n_hidden, N), "%s: unsupported dims S=%d A=%d N=%lld (two "
+                    "hidden layers <= 256 wide in steps of 16, S + A <= 64, A <= 8, N <= 4096; ERL_SAC_FUSED=0 turns it off)", what, S, A, (long long)N);
+    ERL_REQUIRE(H >= 1 && H < (1LL << 30) && max_step >= 1, "%s: bad H=%lld max_step=%d", what, (long long)H, max_step);
     SacDims d;
-    ERL_REQUIRE(make_sac_dims(S, A, hidden, n_hidden, 1, &d), "erl_sac_rollout_synenv_f32: unsupported dims");
+    ERL_REQUIRE(make_sac_dims(S, A, hidden, n_hidden, 1, &d, variant), "%s: unsupported dims", what);
     const int64_t aoff[6] = {d.actor.oW[0], d.actor.ob[0], d.actor.oW[1], d.actor.ob[1], d.actor.oW[2], d.actor.ob[2]};
-    return erl_sac_rollout_fused(actor_params, S, A, hidden[0], hidden[1], aoff, env_state, Ws, Wa, nullptr, step_count, episode, max_step, env_seed,
+    return erl_sac_rollout_fused(actor_params, S, A, hidden[0], hidden[1], aoff, env_state, Ws, Wa, phys, step_count, episode, max_step, env_seed,
                                  N, H, noise, seed, counter0, reward_scale, out_states, out_actions, out_rewards, out_undones, out_unmasks,
-                                 out_last_state, (hipStream_t)stream);
+                                 out_last_state, (hipStream_t)stream, nullptr, nullptr, variant);
 }
 
+#define SAC_ROLLOUT_SYNENV(NAME, VARIANT)                                                                                                    \
+    extern "C" int NAME(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state, const float *Ws,         \
+                        const float *Wa, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,       \
+                        const float *noise, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states, float *out_actions,     \
+                        float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, void *stream)                 \
+    {                                                                                                                                        \
+        ERL_REQUIRE(Ws && Wa, #NAME ": NULL tensor");                                                                                        \
+        return sac_rollout_impl(#NAME, VARIANT, actor_params, S, A, hidden, n_hidden, env_state, Ws, Wa, nullptr, step_count, episode,       \
+                                max_step, env_seed, N, H, noise, seed, counter0, reward_scale, out_states, out_actions, out_rewards,         \
+                                out_undones, out_unmasks, out_last_state, stream);                                                           \
+    }
 // the same loop on the device-resident PendulumVecEnv (S = 3, A = 1; phys: (N, 2) theta, theta_dot; obs: (N, 3) the live observation)
-extern "C" int erl_sac_rollout_pendulum_f32(const float *actor_params, const int *hidden, int n_hidden, float *phys, float *obs,
-                                            int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
-                                            const float *noise, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states,
-                                            float *out_actions, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks,
-                                            float *out_last_state, void *stream)
+#define SAC_ROLLOUT_PENDULUM(NAME, VARIANT)                                                                                                  \
+    extern "C" int NAME(const float *actor_params, const int *hidden, int n_hidden, float *phys, float *obs, int32_t *step_count,            \
+                        int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H, const float *noise, uint64_t seed,          \
+                        uint64_t counter0, float reward_scale, float *out_states, float *out_actions, float *out_rewards,                    \
+                        uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, void *stream)                                     \
+    {                                                                                                                                        \
+        ERL_REQUIRE(phys, #NAME ": NULL tensor");                                                                                            \
+        return sac_rollout_impl(#NAME, VARIANT, actor_params, 3, 1, hidden, n_hidden, obs, nullptr, nullptr, phys, step_count, episode,      \
+                                max_step, env_seed, N, H, noise, seed, counter0, reward_scale, out_states, out_actions, out_rewards,         \
+                                out_undones, out_unmasks, out_last_state, stream);                                                           \
+    }
+SAC_ROLLOUT_SYNENV(erl_sac_rollout_synenv_f32, ERL_SAC_ACTOR_SAC)
+SAC_ROLLOUT_PENDULUM(erl_sac_rollout_pendulum_f32, ERL_SAC_ACTOR_SAC)
+// ActorFixSAC.get_action (AgentSAC.py:217-224) in the same launches: AgentModSAC's rollout
+SAC_ROLLOUT_SYNENV(erl_sac_rollout_mod_synenv_f32, ERL_SAC_ACTOR_FIX)
+SAC_ROLLOUT_PENDULUM(erl_sac_rollout_mod_pendulum_f32, ERL_SAC_ACTOR_FIX)
+#undef SAC_ROLLOUT_SYNENV
+#undef SAC_ROLLOUT_PENDULUM
+
+// the ActorFixSAC launches cover the shapes of their AgentSAC twins
+extern "C" int erl_sac_rollout_mod_supported(int S, int A, const int *hidden, int n_hidden, int64_t N)
 {
-    ERL_REQUIRE(actor_params && phys && obs && step_count && episode && out_states && out_actions && out_rewards && out_undones && out_unmasks,
-                "erl_sac_rollout_pendulum_f32: NULL tensor");
-    ERL_REQUIRE(erl_sac_rollout_synenv_supported(3, 1, hidden, n_hidden, N), "erl_sac_rollout_pendulum_f32: unsupported dims N=%lld (two hidden "
-                "layers <= 256 wide in steps of 16, N <= 4096; ERL_SAC_FUSED=0 turns it off)", (long long)N);
-    ERL_REQUIRE(H >= 1 && H < (1LL << 30) && max_step >= 1, "erl_sac_rollout_pendulum_f32: bad H=%lld max_step=%d", (long long)H, max_step);
-    SacDims d;
-    ERL_REQUIRE(make_sac_dims(3, 1, hidden, n_hidden, 1, &d), "erl_sac_rollout_pendulum_f32: unsupported dims");
-    const int64_t aoff[6] = {d.actor.oW[0], d.actor.ob[0], d.actor.oW[1], d.actor.ob[1], d.actor.oW[2], d.actor.ob[2]};
-    return erl_sac_rollout_fused(actor_params, 3, 1, hidden[0], hidden[1], aoff, obs, nullptr, nullptr, phys, step_count, episode, max_step, env_seed,
-                                 N, H, noise, seed, counter0, reward_scale, out_states, out_actions, out_rewards, out_undones, out_unmasks,
-                                 out_last_state, (hipStream_t)stream);
+    return erl_sac_rollout_synenv_supported(S, A, hidden, n_hidden, N);
 }
 
-// The evaluation form of the two launches above (sac_fused.hip sac_rollout_synenv_kernel<.., EV>): H steps of the deterministic policy
-// ActorSAC.forward, per-episode (return, length) records and per-env episode counts into `workspace` (erl_eval_workspace_bytes(N, H));
-// erl_eval_episodes_compact_f32 (rollout_eval.hip) turns them into the evaluator's table.  Support is that of the training twin.
-static int sac_eval_impl(const char *what, const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state,
+// The evaluation form of the launches above (sac_fused.hip sac_rollout_synenv_kernel<.., EV>): H steps of the deterministic policy
+// ActorSAC.forward (variant ERL_SAC_ACTOR_FIX: ActorFixSAC.forward), per-episode (return, length) records and per-env episode counts into
+// `workspace` (erl_eval_workspace_bytes(N, H)); erl_eval_episodes_compact_f32 (rollout_eval.hip) turns them into the evaluator's table.
+// Support is that of the training twin.
+static int sac_eval_impl(const char *what, int variant, const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state,
                          const float *Ws, const float *Wa, float *phys, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
                          int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream)
 {
+    ERL_REQUIRE(actor_params && env_state && (phys || (Ws && Wa)) && step_count && episode && workspace, "%s: NULL tensor", what);
     ERL_REQUIRE(hidden && n_hidden >= 1 && erl_sac_rollout_synenv_supported(S, A, hidden, n_hidden, N), "%s: unsupported dims S=%d A=%d N=%lld (two "
                 "hidden layers <= 256 wide in steps of 16, S + A <= 64, A <= 8, N <= 4096; ERL_SAC_FUSED=0 turns it off)", what, S, A, (long long)N);
     ERL_REQUIRE(H >= 1 && H < (1LL << 30) && max_step >= 1 && erl_eval_ws_bytes(N, H) > 0, "%s: bad H=%lld max_step=%d", what, (long long)H, max_step);
     ERL_REQUIRE(workspace_bytes >= erl_eval_ws_bytes(N, H), "%s: workspace of %lld bytes, erl_eval_workspace_bytes(N, H) = %lld", what,
                 (long long)workspace_bytes, (long long)erl_eval_ws_bytes(N, H));
     SacDims d;
-    ERL_REQUIRE(make_sac_dims(S, A, hidden, n_hidden, 1, &d), "%s: unsupported dims", what);
+    ERL_REQUIRE(make_sac_dims(S, A, hidden, n_hidden, 1, &d, variant), "%s: unsupported dims", what);
     const int64_t aoff[6] = {d.actor.oW[0], d.actor.ob[0], d.actor.oW[1], d.actor.ob[1], d.actor.oW[2], d.actor.ob[2]};
     const ErlEvalWs w = erl_eval_ws_layout(workspace, N, H);
     return erl_sac_rollout_fused(actor_params, S, A, hidden[0], hidden[1], aoff, env_state, Ws, Wa, phys, step_count, episode, max_step, env_seed,
-                                 N, H, nullptr, 0, 0, 1.0f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, w.rec, w.cnt);
+                                 N, H, nullptr, 0, 0, 1.0f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, w.rec, w.cnt,
+                                 variant);
 }
 
-extern "C" int erl_sac_eval_synenv_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state, const float *Ws,
-                                       const float *Wa, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
-                                       void *workspace, int64_t workspace_bytes, void *stream)
-{
-    ERL_REQUIRE(actor_params && env_state && Ws && Wa && step_count && episode && workspace, "erl_sac_eval_synenv_f32: NULL tensor");
-    return sac_eval_impl("erl_sac_eval_synenv_f32", actor_params, S, A, hidden, n_hidden, env_state, Ws, Wa, nullptr, step_count, episode, max_step,
-                         env_seed, N, H, workspace, workspace_bytes, stream);
-}
-
-extern "C" int erl_sac_eval_pendulum_f32(const float *actor_params, const int *hidden, int n_hidden, float *phys, float *obs, int32_t *step_count,
-                                         int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H, void *workspace,
-                                         int64_t workspace_bytes, void *stream)
-{
-    ERL_REQUIRE(actor_params && phys && obs && step_count && episode && workspace, "erl_sac_eval_pendulum_f32: NULL tensor");
-    return sac_eval_impl("erl_sac_eval_pendulum_f32", actor_params, 3, 1, hidden, n_hidden, obs, nullptr, nullptr, phys, step_count, episode, max_step,
-                         env_seed, N, H, workspace, workspace_bytes, stream);
-}
+#define SAC_EVAL_SYNENV(NAME, VARIANT)                                                                                                       \
+    extern "C" int NAME(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state, const float *Ws,         \
+                        const float *Wa, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,       \
+                        void *workspace, int64_t workspace_bytes, void *stream)                                                              \
+    {                                                                                                                                        \
+        ERL_REQUIRE(Ws && Wa, #NAME ": NULL tensor");                                                                                        \
+        return sac_eval_impl(#NAME, VARIANT, actor_params, S, A, hidden, n_hidden, env_state, Ws, Wa, nullptr, step_count, episode, max_step, \
+                             env_seed, N, H, workspace, workspace_bytes, stream);                                                            \
+    }
+#define SAC_EVAL_PENDULUM(NAME, VARIANT)                                                                                                     \
+    extern "C" int NAME(const float *actor_params, const int *hidden, int n_hidden, float *phys, float *obs, int32_t *step_count,            \
+                        int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H, void *workspace, int64_t workspace_bytes,   \
+                        void *stream)                                                                                                        \
+    {                                                                                                                                        \
+        ERL_REQUIRE(phys, #NAME ": NULL tensor");                                                                                            \
+        return sac_eval_impl(#NAME, VARIANT, actor_params, 3, 1, hidden, n_hidden, obs, nullptr, nullptr, phys, step_count, episode, max_step, \
+                             env_seed, N, H, workspace, workspace_bytes, stream);                                                            \
+    }
+SAC_EVAL_SYNENV(erl_sac_eval_synenv_f32, ERL_SAC_ACTOR_SAC)
+SAC_EVAL_PENDULUM(erl_sac_eval_pendulum_f32, ERL_SAC_ACTOR_SAC)
+SAC_EVAL_SYNENV(erl_sac_eval_mod_synenv_f32, ERL_SAC_ACTOR_FIX)
+SAC_EVAL_PENDULUM(erl_sac_eval_mod_pendulum_f32, ERL_SAC_ACTOR_FIX)
+#undef SAC_EVAL_SYNENV
+#undef SAC_EVAL_PENDULUM
 
 // ActorSAC.get_action for the off-policy rollout (AgentSAC.py:179-185): action = tanh(mean + std * eps); state_out (may be NULL):
 // the rollout's `states[t] = state` (AgentBase.py:145) written by the same launch.  With the actor variant named: ERL_SAC_ACTOR_FIX =
@@ -933,4 +965,27 @@ extern "C" int erl_sac_explore_action_f32(const float *actor_params, int S, int 
 {
     return erl_sac_explore_action_opt_f32(actor_params, S, A, hidden, n_hidden, state, N, noise, seed, counter, action_out, state_out, workspace,
                                           workspace_bytes, ERL_SAC_ACTOR_SAC, stream);
+}
+
+// The per-step action on the fused step's actor kernel (sac_fused.hip actor_fwd_kernel: one launch) for either actor variant -- the
+// per-step twin of erl_sac_rollout_*_f32 / erl_sac_rollout_mod_*_f32, bit for bit.  Arguments of erl_sac_explore_action_opt_f32, which
+// keeps its own routes; outside erl_sac_fused_supported (or under ERL_SAC_FUSED=0) the call is refused: there is no layered form here.
+extern "C" int erl_sac_explore_action_tile_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, const float *state,
+                                               int64_t N, const float *noise, uint64_t seed, uint64_t counter, float *action_out,
+                                               float *state_out, void *workspace, int64_t workspace_bytes, int variant, void *stream)
+{
+    ERL_REQUIRE(variant == ERL_SAC_ACTOR_SAC || variant == ERL_SAC_ACTOR_FIX, "erl_sac_explore_action_tile_f32: unknown actor_variant %d", variant);
+    ERL_REQUIRE(actor_params && state && action_out && workspace, "erl_sac_explore_action_tile_f32: NULL tensor");
+    static const bool fused_on = [] { const char *e = getenv("ERL_SAC_FUSED"); return !(e && atoi(e) == 0); }();
+    ERL_REQUIRE(fused_on && hidden && erl_sac_fused_supported(S, A, hidden, n_hidden, 1, N),
+                "erl_sac_explore_action_tile_f32: S=%d A=%d N=%lld outside the tile kernel's shapes (two hidden layers <= 256 wide in steps of 16, "
+                "S + A <= 64, A <= 8, N <= 4096; ERL_SAC_FUSED=0 turns it off)", S, A, (long long)N);
+    SacDims d;
+    ERL_REQUIRE(make_sac_dims(S, A, hidden, n_hidden, 1, &d, variant), "erl_sac_explore_action_tile_f32: unsupported dims");
+    Ws ws{(char *)workspace, 0, workspace_bytes};
+    float *lp_s = ws.take(N);
+    ERL_REQUIRE(lp_s != nullptr, "erl_sac_explore_action_tile_f32: workspace too small");
+    const int64_t aoff[6] = {d.actor.oW[0], d.actor.ob[0], d.actor.oW[1], d.actor.ob[1], d.actor.oW[2], d.actor.ob[2]};
+    return erl_sac_explore_fused(actor_params, S, A, hidden[0], hidden[1], aoff, state, N, noise, seed, counter, action_out, state_out, lp_s,
+                                 (hipStream_t)stream, variant);
 }

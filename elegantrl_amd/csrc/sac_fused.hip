@@ -38,7 +38,8 @@
 // LDS, is the persistent off-policy rollout (sac_rollout_synenv_kernel).
 // AgentModSAC (AgentSAC.py:89-165) runs the same launches with ActorFixSAC as a run-time variant of the actor kernels (ActorFwdArgs::variant)
 // and its options (SacCall / SacStep): the actor's own Adam count, its target's soft update behind that step, and -- on the steps its two-time-scale
-// rule skips -- one small launch (sac_skip_finish_kernel) in place of launches (7)-(10).
+// rule skips -- one small launch (sac_skip_finish_kernel) in place of launches (7)-(10).  Its rollout and evaluation are the FIX forms of the
+// persistent rollout (a template parameter there: sac_rollout_synenv_kernel).
 #include "mlpn_common.h"
 
 #include <mutex>
@@ -1377,7 +1378,14 @@ enum { SR_ENV_SYN = 0, SR_ENV_PENDULUM = 1 };
 // step are the statements of the training form (which under an all-zero injected noise computes tanh(mean + std * 0)), so rewards,
 // flags, final state and counters are its own, bit for bit; the thread that owns an env's reward keeps a running return (fp32 rewards
 // summed in fp64, in time order) and length instead, and leaves a record where an episode ends (rollout_eval.hip compacts them).
-template <int C0, int C1, int ENV, bool EV = false>
+//
+// FIX (behind erl_sac_rollout_mod_*_f32 / erl_sac_eval_mod_*_f32): ActorFixSAC (AgentSAC.py:201-243), AgentModSAC's actor -- the second hidden
+// layer is raw and log_std is clamped to [-20, 2] (ActorFixSAC.get_action; actor_fwd_kernel under ERL_SAC_ACTOR_FIX, statement for
+// statement); the EV action is unchanged, tanh of the first A head outputs: decoder_a_avg is the first row half of the head block, so that
+// is ActorFixSAC.forward.  A template parameter, not the run-time value ActorFwdArgs::variant is: as a run-time value it cost every
+// training form two registers and put the [256,256] SynVecEnv one, which sits at 255, into scratch
+// (profiles/modsac_rollout_kernel_resources.txt); this way the ActorSAC instantiations are the code they were.
+template <int C0, int C1, int ENV, bool EV = false, bool FIX = false>
 __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g)
 {
     __shared__ TileLds lds;
@@ -1460,18 +1468,18 @@ __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g
         emit_hidden(z, d.h0, true, lds.T1, gk, nullptr, nullptr, row, valid, L);
         lds_barrier();
         layer_fwd_mma<WClass<C0>::KT, WClass<C1>::NU, true>(w2, BIA + FMAXW, d.h0, d.h1, lds.T1, L, z);
-        emit_hidden(z, d.h1, true, lds.T0, gk, nullptr, nullptr, row, valid, L);
+        emit_hidden(z, d.h1, !FIX, lds.T0, gk, nullptr, nullptr, row, valid, L);
         lds_barrier();
         layer_small_mma<false, true>(wh, BIA + 2 * FMAXW, d.h1, 2 * d.A, lds.T0, lds.part, lds.Yl, L);
         if (L.tid < TS) {                                  // actor_fwd_kernel's tail: action = tanh(mean + std * eps)
             const int64_t b = row0 + L.tid, bc = min(b, N - 1);
-            if constexpr (EV) {                            // ActorSAC.forward (AgentSAC.py:47-48): tanh of the first A head outputs
+            if constexpr (EV) {                            // ActorSAC.forward (AgentSAC.py:47-48): tanh of the first A head outputs (ActorFixSAC.forward: decoder_a_avg is that row half)
 #pragma unroll 1
                 for (int a = 0; a < A; ++a) ACT[L.tid * 16 + a] = tanhf(lds.Yl[L.tid * 16 + a]);
             }
             for (int a = 0; !EV && a < A; ++a) {
                 const float mean = lds.Yl[L.tid * 16 + a], ls = lds.Yl[L.tid * 16 + A + a];
-                const float lsc = fminf(fmaxf(ls, -16.f), 2.f);
+                const float lsc = fminf(fmaxf(ls, FIX ? -20.f : -16.f), 2.f);
                 const float sd = expf(lsc);
                 const float eps = g.noise ? g.noise[((size_t)t * N + bc) * A + a]
                                           : philox_normal(g.seed, g.counter0 + (uint64_t)t, (uint32_t)bc, (uint32_t)a);
@@ -1669,14 +1677,14 @@ int64_t erl_sac_fused_ws_floats(int S, int A, int h0, int h1, int E, int64_t B, 
 // arithmetic per element as the layered form (erl_sac_explore_action_f32's four launches), summed in this kernel's order.
 int erl_sac_explore_fused(const float *actor_params, int S, int A, int h0, int h1, const int64_t *aoff, const float *state, int64_t N,
                           const float *noise, uint64_t seed, uint64_t counter, float *action_out, float *state_out, float *lp_scratch,
-                          hipStream_t sa)
+                          hipStream_t sa, int variant)
 {
     FusedDims d{};
     d.S = S; d.A = A; d.E = 1; d.h0 = h0; d.h1 = h1; d.B = N;
     d.aW1 = aoff[0]; d.ab1 = aoff[1]; d.aW2 = aoff[2]; d.ab2 = aoff[3]; d.aWh = aoff[4]; d.abh = aoff[5];
     ActorFwdArgs af{};
     af.P = actor_params; af.d = d; af.X = state; af.noise = noise; af.seed = seed; af.counter = counter;
-    af.act_t = action_out; af.lp = lp_scratch; af.Xcopy = state_out;
+    af.act_t = action_out; af.lp = lp_scratch; af.Xcopy = state_out; af.variant = variant;
     const dim3 tgrid((unsigned)((N + TS - 1) / TS)), blk(FT);
 #define LAUNCH_ACTOR_EXPLORE(K0, K1) hipLaunchKernelGGL((actor_fwd_kernel<K0, K1>), tgrid, blk, 0, sa, af)
     FUSED_KT_DISPATCH(LAUNCH_ACTOR_EXPLORE)
@@ -1878,7 +1886,7 @@ int erl_sac_rollout_fused(const float *actor_params, int S, int A, int h0, int h
                           const float *Wa, float *phys, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
                           const float *noise, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states, float *out_actions,
                           float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, hipStream_t stream,
-                          float2 *ev_rec, int32_t *ev_cnt)
+                          float2 *ev_rec, int32_t *ev_cnt, int variant)
 {
     FusedDims d{};
     d.S = S; d.A = A; d.E = 1; d.h0 = h0; d.h1 = h1; d.B = N;
@@ -1891,28 +1899,37 @@ int erl_sac_rollout_fused(const float *actor_params, int S, int A, int h0, int h
     g.ev_rec = ev_rec; g.ev_cnt = ev_cnt;
     const dim3 grid((unsigned)((N + TS - 1) / TS)), blk(FT);
     const size_t lds_bytes = (size_t)SR_FLOATS * sizeof(float);
-    static bool attr[2][2][9] = {};                      // (the dynamic part alone is beyond 64 KB)
-#define LAUNCH_SAC_ROLLOUT_E(K0, K1, ENV_, EVAL_)                                                                               \
+    static bool attr[2][2][2][9] = {};                   // (the dynamic part alone is beyond 64 KB)
+#define LAUNCH_SAC_ROLLOUT_E(K0, K1, ENV_, EVAL_, FIX_)                                                                         \
     do {                                                                                                                        \
-        if (!attr[EVAL_][ENV_][K0 * 3 + K1]) {                                                                                  \
-            int rc = erl_hip_status(hipFuncSetAttribute((const void *)sac_rollout_synenv_kernel<K0, K1, ENV_, EVAL_>,           \
+        if (!attr[FIX_][EVAL_][ENV_][K0 * 3 + K1]) {                                                                            \
+            int rc = erl_hip_status(hipFuncSetAttribute((const void *)sac_rollout_synenv_kernel<K0, K1, ENV_, EVAL_, FIX_>,     \
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes),            \
                                     "hipFuncSetAttribute(sac_rollout_synenv_kernel)");                                          \
             if (rc) return rc;                                                                                                  \
-            attr[EVAL_][ENV_][K0 * 3 + K1] = true;                                                                              \
+            attr[FIX_][EVAL_][ENV_][K0 * 3 + K1] = true;                                                                        \
         }                                                                                                                       \
-        hipLaunchKernelGGL((sac_rollout_synenv_kernel<K0, K1, ENV_, EVAL_>), grid, blk, lds_bytes, stream, g);                  \
+        hipLaunchKernelGGL((sac_rollout_synenv_kernel<K0, K1, ENV_, EVAL_, FIX_>), grid, blk, lds_bytes, stream, g);            \
     } while (0)
-#define LAUNCH_SAC_ROLLOUT_SYN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_SYN, false)
-#define LAUNCH_SAC_ROLLOUT_PEN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_PENDULUM, false)
-#define LAUNCH_SAC_EVAL_SYN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_SYN, true)
-#define LAUNCH_SAC_EVAL_PEN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_PENDULUM, true)
-    if (ev_rec) {                                        // the evaluation form (erl_sac_eval_*_f32)
-        if (phys) { FUSED_KT_DISPATCH(LAUNCH_SAC_EVAL_PEN) }
-        else { FUSED_KT_DISPATCH(LAUNCH_SAC_EVAL_SYN) }
+#define LAUNCH_SAC_ROLLOUT_SYN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_SYN, false, false)
+#define LAUNCH_SAC_ROLLOUT_PEN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_PENDULUM, false, false)
+#define LAUNCH_SAC_EVAL_SYN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_SYN, true, false)
+#define LAUNCH_SAC_EVAL_PEN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_PENDULUM, true, false)
+#define LAUNCH_MOD_ROLLOUT_SYN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_SYN, false, true)
+#define LAUNCH_MOD_ROLLOUT_PEN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_PENDULUM, false, true)
+#define LAUNCH_MOD_EVAL_SYN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_SYN, true, true)
+#define LAUNCH_MOD_EVAL_PEN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_PENDULUM, true, true)
+    const bool fix = variant == ERL_SAC_ACTOR_FIX;
+    if (ev_rec) {                                        // the evaluation form (erl_sac_eval_*_f32, erl_sac_eval_mod_*_f32)
+        if (phys) { if (fix) { FUSED_KT_DISPATCH(LAUNCH_MOD_EVAL_PEN) } else { FUSED_KT_DISPATCH(LAUNCH_SAC_EVAL_PEN) } }
+        else { if (fix) { FUSED_KT_DISPATCH(LAUNCH_MOD_EVAL_SYN) } else { FUSED_KT_DISPATCH(LAUNCH_SAC_EVAL_SYN) } }
     }
-    else if (phys) { FUSED_KT_DISPATCH(LAUNCH_SAC_ROLLOUT_PEN) }
-    else { FUSED_KT_DISPATCH(LAUNCH_SAC_ROLLOUT_SYN) }
+    else if (phys) { if (fix) { FUSED_KT_DISPATCH(LAUNCH_MOD_ROLLOUT_PEN) } else { FUSED_KT_DISPATCH(LAUNCH_SAC_ROLLOUT_PEN) } }
+    else { if (fix) { FUSED_KT_DISPATCH(LAUNCH_MOD_ROLLOUT_SYN) } else { FUSED_KT_DISPATCH(LAUNCH_SAC_ROLLOUT_SYN) } }
+#undef LAUNCH_MOD_EVAL_SYN
+#undef LAUNCH_MOD_EVAL_PEN
+#undef LAUNCH_MOD_ROLLOUT_SYN
+#undef LAUNCH_MOD_ROLLOUT_PEN
 #undef LAUNCH_SAC_EVAL_SYN
 #undef LAUNCH_SAC_EVAL_PEN
 #undef LAUNCH_SAC_ROLLOUT_SYN

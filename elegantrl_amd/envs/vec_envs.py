@@ -147,18 +147,20 @@ class SynVecEnv(_GpuVecEnv):
     def fused_rollout_offpolicy(self, agent, horizon_len: int, noise, bufs, last_state_out) -> None:
         """all `horizon_len` steps of the off-policy AgentBase._explore_vec_env in ONE launch (erl_sac_rollout_synenv_f32): `bufs` = (states,
         actions, rewards, undones, unmasks) time-major, written in place (rewards scaled, flags inverted); `last_state_out` (N, S) or None:
-        the agent's own copy of the final state; the env's state / counters advance."""
+        the agent's own copy of the final state; the env's state / counters advance.  An agent whose actor is ActorFixSAC (AgentModSAC,
+        `agent._spec.actor_variant`) takes the launch's ActorFixSAC form, erl_sac_rollout_mod_synenv_f32."""
         from .. import _hip
         self.state_epoch += 1
         p, f32 = _hip.ptr, th.float32
         states, actions, rewards, undones, unmasks = bufs
         spec = agent._spec
-        _hip.check(_hip.lib().erl_sac_rollout_synenv_f32(
+        entry = "erl_sac_rollout_mod_synenv_f32" if spec.actor_variant else "erl_sac_rollout_synenv_f32"        # (ActorFixSAC: AgentModSAC)
+        _hip.check(getattr(_hip.lib(), entry)(
             p(agent._actor_flat, f32), spec.S, spec.A, spec._c, len(spec.hidden), p(self.state, f32), p(self.Ws, f32), p(self.Wa, f32),
             p(self.step_count, th.int32), p(self.episode, th.int32), self.max_step, self.seed & (2 ** 64 - 1), self.num_envs, horizon_len,
             p(noise, f32), agent.rng_seed & (2 ** 64 - 1), agent.rng_counter & (2 ** 64 - 1), float(agent.reward_scale), p(states, f32),
             p(actions, f32), p(rewards, f32), _hip.flag_ptr(undones), _hip.flag_ptr(unmasks),
-            p(last_state_out, f32) if last_state_out is not None else None, _hip.stream_ptr()), "erl_sac_rollout_synenv_f32")
+            p(last_state_out, f32) if last_state_out is not None else None, _hip.stream_ptr()), entry)
 
 
     def fused_evaluate(self, agent, horizon_len: int, workspace) -> None:
@@ -177,15 +179,17 @@ class SynVecEnv(_GpuVecEnv):
             "erl_eval_synenv_f32")
 
     def fused_evaluate_offpolicy(self, agent, horizon_len: int, workspace) -> None:
-        """... of the deterministic policy of a fused-path AgentSAC (erl_sac_eval_synenv_f32: the evaluation form of `fused_rollout_offpolicy`)"""
+        """... of the deterministic policy of a fused-path AgentSAC (erl_sac_eval_synenv_f32: the evaluation form of `fused_rollout_offpolicy`;
+        AgentModSAC: erl_sac_eval_mod_synenv_f32, ActorFixSAC.forward)"""
         from .. import _hip
         self.state_epoch += 1
         p, f32 = _hip.ptr, th.float32
         spec = agent._spec
-        _hip.check(_hip.lib().erl_sac_eval_synenv_f32(
+        entry = "erl_sac_eval_mod_synenv_f32" if spec.actor_variant else "erl_sac_eval_synenv_f32"        # (ActorFixSAC: AgentModSAC)
+        _hip.check(getattr(_hip.lib(), entry)(
             p(agent._actor_flat, f32), spec.S, spec.A, spec._c, len(spec.hidden), p(self.state, f32), p(self.Ws, f32), p(self.Wa, f32),
             p(self.step_count, th.int32), p(self.episode, th.int32), self.max_step, self.seed & (2 ** 64 - 1), self.num_envs, horizon_len,
-            p(workspace, th.uint8), workspace.numel(), _hip.stream_ptr()), "erl_sac_eval_synenv_f32")
+            p(workspace, th.uint8), workspace.numel(), _hip.stream_ptr()), entry)
 
 
 class PendulumVecEnv(_GpuVecEnv):
@@ -231,18 +235,19 @@ class PendulumVecEnv(_GpuVecEnv):
 
     def fused_rollout_offpolicy(self, agent, horizon_len: int, noise, bufs, last_state_out) -> None:
         """all `horizon_len` steps of the off-policy AgentBase._explore_vec_env in ONE launch (erl_sac_rollout_pendulum_f32); arguments as
-        SynVecEnv.fused_rollout_offpolicy."""
+        SynVecEnv.fused_rollout_offpolicy (AgentModSAC: erl_sac_rollout_mod_pendulum_f32)."""
         from .. import _hip
         self.state_epoch += 1
         p, f32 = _hip.ptr, th.float32
         states, actions, rewards, undones, unmasks = bufs
         spec = agent._spec
-        _hip.check(_hip.lib().erl_sac_rollout_pendulum_f32(
+        entry = "erl_sac_rollout_mod_pendulum_f32" if spec.actor_variant else "erl_sac_rollout_pendulum_f32"        # (ActorFixSAC: AgentModSAC)
+        _hip.check(getattr(_hip.lib(), entry)(
             p(agent._actor_flat, f32), spec._c, len(spec.hidden), p(self.phys, f32), p(self.state, f32), p(self.step_count, th.int32),
             p(self.episode, th.int32), self.max_step, self.seed & (2 ** 64 - 1), self.num_envs, horizon_len, p(noise, f32),
             agent.rng_seed & (2 ** 64 - 1), agent.rng_counter & (2 ** 64 - 1), float(agent.reward_scale), p(states, f32), p(actions, f32),
             p(rewards, f32), _hip.flag_ptr(undones), _hip.flag_ptr(unmasks), p(last_state_out, f32) if last_state_out is not None else None,
-            _hip.stream_ptr()), "erl_sac_rollout_pendulum_f32")
+            _hip.stream_ptr()), entry)
 
     def fused_rollout(self, agent, horizon_len: int, noise, bufs, values, next_value, epilogue=None) -> None:
         """all `horizon_len` steps of AgentPPO._explore_vec_env in ONE launch (erl_rollout_pendulum_f32); `epilogue` as
@@ -276,15 +281,17 @@ class PendulumVecEnv(_GpuVecEnv):
             p(workspace, th.uint8), workspace.numel(), _hip.stream_ptr()), "erl_eval_pendulum_f32")
 
     def fused_evaluate_offpolicy(self, agent, horizon_len: int, workspace) -> None:
-        """... of a fused-path AgentSAC (erl_sac_eval_pendulum_f32); arguments as SynVecEnv.fused_evaluate_offpolicy."""
+        """... of a fused-path AgentSAC (erl_sac_eval_pendulum_f32; AgentModSAC: erl_sac_eval_mod_pendulum_f32); arguments as
+        SynVecEnv.fused_evaluate_offpolicy."""
         from .. import _hip
         self.state_epoch += 1
         p, f32 = _hip.ptr, th.float32
         spec = agent._spec
-        _hip.check(_hip.lib().erl_sac_eval_pendulum_f32(
+        entry = "erl_sac_eval_mod_pendulum_f32" if spec.actor_variant else "erl_sac_eval_pendulum_f32"        # (ActorFixSAC: AgentModSAC)
+        _hip.check(getattr(_hip.lib(), entry)(
             p(agent._actor_flat, f32), spec._c, len(spec.hidden), p(self.phys, f32), p(self.state, f32), p(self.step_count, th.int32),
             p(self.episode, th.int32), self.max_step, self.seed & (2 ** 64 - 1), self.num_envs, horizon_len, p(workspace, th.uint8),
-            workspace.numel(), _hip.stream_ptr()), "erl_sac_eval_pendulum_f32")
+            workspace.numel(), _hip.stream_ptr()), entry)
 
 
 class _DiscreteGpuVecEnv(_GpuVecEnv):

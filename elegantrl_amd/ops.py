@@ -867,6 +867,11 @@ def sac_mod_fused_supported(spec: SacSpec, B: int) -> bool:
     return bool(lib().erl_sac_mod_fused_supported(spec.S, spec.A, spec._c, len(spec.hidden), spec.E, int(B)))
 
 
+def sac_rollout_mod_supported(spec: SacSpec, N: int) -> bool:
+    """ActorFixSAC's one-launch rollout / evaluation and the tile action cover this shape at N envs (erl_sac_rollout_mod_supported)"""
+    return bool(lib().erl_sac_rollout_mod_supported(spec.S, spec.A, spec._c, len(spec.hidden), int(N)))
+
+
 def sac_update_mod(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], batch: Sequence[TEN],
                    step: int, *, gamma: float, target_entropy: float, tau: float, lr: float, max_norm: float, objs_out: TEN,
                    update_actor: bool, actor_step: int, actor_target: Optional[TEN], noises: Optional[Tuple[TEN, TEN]] = None, seed: int = 0,
@@ -944,11 +949,20 @@ def sac_update_per_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alp
 
 
 def sac_explore_action(spec: SacSpec, actor: TEN, state: TEN, *, noise: Optional[TEN] = None, seed: int = 0, counter: int = 0,
-                       out: Optional[TEN] = None, out_state: Optional[TEN] = None) -> TEN:
-    """`out` (N, A): the action's destination (e.g. the rollout's row); `out_state` (N, S): a copy of `state` from the same launch."""
+                       out: Optional[TEN] = None, out_state: Optional[TEN] = None, tile: bool = False) -> TEN:
+    """`out` (N, A): the action's destination (e.g. the rollout's row); `out_state` (N, S): a copy of `state` from the same launch.
+    `tile`: the one-launch tile kernel for either actor variant (erl_sac_explore_action_tile_f32: the per-step twin of the one-launch
+    rollouts; refused outside `sac_rollout_mod_supported`)."""
     N = state.shape[0]
     out = th.empty((N, spec.A), dtype=th.float32, device=state.device) if out is None else out
     ws = _workspace(state.device, spec.workspace_bytes(N))
+    if tile:
+        check(lib().erl_sac_explore_action_tile_f32(ptr(actor, th.float32), spec.S, spec.A, spec._c, len(spec.hidden), ptr(state, th.float32), N,
+                                                    ptr(noise), seed & (2 ** 64 - 1), counter & (2 ** 64 - 1), ptr(out, th.float32),
+                                                    ptr(out_state, th.float32) if out_state is not None else None, ptr(ws), ws.numel(),
+                                                    spec.actor_variant, stream_ptr()),
+              "erl_sac_explore_action_tile_f32")
+        return out
     if spec.actor_variant:
         check(lib().erl_sac_explore_action_opt_f32(ptr(actor, th.float32), spec.S, spec.A, spec._c, len(spec.hidden), ptr(state, th.float32), N,
                                                    ptr(noise), seed & (2 ** 64 - 1), counter & (2 ** 64 - 1), ptr(out, th.float32),

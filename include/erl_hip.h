@@ -929,6 +929,37 @@ ERL_API int erl_sac_explore_action_opt_f32(const float *actor_params, int S, int
                                    float *action_out, float *state_out, void *workspace, int64_t workspace_bytes,
                                    int actor_variant, void *stream);
 
+/* AgentModSAC's rollout and evaluation in one launch (added within ABI 22: symbols added, none changed).  The four launches above and
+ * their erl_sac_eval_* forms with ActorFixSAC (AgentSAC.py:201-243) as a run-time variant of sac_rollout_synenv_kernel: the second
+ * hidden layer is raw, log_std is clamped to [-20, 2]; the evaluation's action is tanh of the first A head outputs, which is
+ * ActorFixSAC.forward (decoder_a_avg is the first row half of the head block).  Arguments, validation (with their own names in the
+ * messages) and outputs as their AgentSAC twins; erl_sac_rollout_mod_supported answers as erl_sac_rollout_synenv_supported.
+ * erl_sac_explore_action_tile_f32 is their per-step twin for either variant: the action of the fused step's actor kernel, one launch,
+ * the arithmetic of one step of the rollouts (bit-identical under the same Philox keys / noise); arguments of
+ * erl_sac_explore_action_opt_f32 (which keeps its own routes and bits).  It has no layered form: outside two hidden layers, widths in
+ * steps of 16 up to 256, S + A <= 64, A <= 8, N <= 4096, or under ERL_SAC_FUSED=0, the call is ERL_EINVAL before any launch. */
+ERL_API int erl_sac_rollout_mod_supported(int S, int A, const int *hidden, int n_hidden, int64_t N);
+ERL_API int erl_sac_rollout_mod_synenv_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state,
+                                   const float *Ws, const float *Wa, int32_t *step_count, int32_t *episode, int max_step,
+                                   uint64_t env_seed, int64_t N, int64_t H, const float *noise, uint64_t seed, uint64_t counter0,
+                                   float reward_scale, float *out_states, float *out_actions, float *out_rewards,
+                                   uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, void *stream);
+ERL_API int erl_sac_rollout_mod_pendulum_f32(const float *actor_params, const int *hidden, int n_hidden, float *phys, float *obs,
+                                     int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
+                                     const float *noise, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states,
+                                     float *out_actions, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks,
+                                     float *out_last_state, void *stream);
+ERL_API int erl_sac_eval_mod_synenv_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state,
+                                const float *Ws, const float *Wa, int32_t *step_count, int32_t *episode, int max_step,
+                                uint64_t env_seed, int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_sac_eval_mod_pendulum_f32(const float *actor_params, const int *hidden, int n_hidden, float *phys, float *obs,
+                                  int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
+                                  void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_sac_explore_action_tile_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden,
+                                    const float *state, int64_t N, const float *noise, uint64_t seed, uint64_t counter,
+                                    float *action_out, float *state_out, void *workspace, int64_t workspace_bytes,
+                                    int actor_variant, void *stream);
+
 /* measurement hook (bench.py's `roofline`; no reference counterpart): every_nth > 0 makes erl_ppo_step_f32 time every n-th K6
  * launch (1 = every launch, 0 = off) two ways -- a HIP-event bracket on the launch stream (contains the dispatch and completion
  * overhead of the bracket itself, 3-15 us depending on the box) and the kernel's own span, first workgroup in to last workgroup
