@@ -207,6 +207,9 @@ __global__ __launch_bounds__(NT) void reduce_exchange_kernel(const T *slabs, int
     erl_span_out(span, t_span);
 }
 
+// x / d for a divisor that is the same in every lane (d >= 1): a shift when d is a power of two
+__device__ __forceinline__ uint32_t tail_div_u32(uint32_t x, uint32_t d) { return (d & (d - 1)) ? x / d : x >> (__ffs((int)d) - 1); }
+
 // clip + Adam on ONE element (index ie of parameter group gi at `off`) + the refresh of the split-arithmetic minibatch kernels' weight
 // images that follow their fp32 weights (s3_image.h): the arithmetic of every tail of this file
 __device__ __forceinline__ void tail_adam_apply(float e_g, float e_m1, float e_m2, float e_p, float coef, float grad_scale, float beta1, float beta2,
@@ -220,8 +223,15 @@ __device__ __forceinline__ void tail_adam_apply(float e_g, float e_m1, float e_m
     if (gi < 2 && im.net[gi].img) {
         const int64_t e = ie - im.net[gi].w2_off;
         const int h1 = im.net[gi].h1, S = im.net[gi].S;
-        if (e >= 0 && e < (int64_t)h1 * im.net[gi].h2) s3_image_put_w2(im.net[gi].img, h1, im.net[gi].h2, (int)(e / h1), (int)(e % h1), e_p);
-        else if (im.net[gi].img1 && ie < (int64_t)h1 * S) s3_image_put(im.net[gi].img1, im.net[gi].K1, (int)(ie / S), (int)(ie % S), e_p);
+        // (inside a matrix the index fits 32 bits, and a power-of-two row length needs no division: the 64-bit quotients were ~0.17 us of
+        // the launch, whose 16 waves per CU pay for every instruction)
+        if (e >= 0 && e < (int64_t)h1 * im.net[gi].h2) {
+            const uint32_t eu = (uint32_t)e, row = tail_div_u32(eu, (uint32_t)h1);
+            s3_image_put_w2(im.net[gi].img, h1, im.net[gi].h2, (int)row, (int)(eu - row * (uint32_t)h1), e_p);
+        } else if (im.net[gi].img1 && ie < (int64_t)h1 * S) {
+            const uint32_t iu = (uint32_t)ie, row = tail_div_u32(iu, (uint32_t)S);
+            s3_image_put(im.net[gi].img1, im.net[gi].K1, (int)row, (int)(iu - row * (uint32_t)S), e_p);
+        }
     }
 }
 
@@ -236,6 +246,7 @@ __global__ __launch_bounds__(1024) void clip_adam_partials_kernel(float *__restr
                                                                   bool own_chunks_only = false)
 {
     __shared__ double scratch[16];
+    __shared__ float s_coef;
     const unsigned long long t_span = erl_span_in(span);
     // a gradient exchange of this update loop timed out (reduce_exchange_kernel): its sums are garbage -- touch nothing
     if (poison && __hip_atomic_load(poison, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
@@ -254,10 +265,20 @@ __global__ __launch_bounds__(1024) void clip_adam_partials_kernel(float *__restr
     } else {
         for (int b = threadIdx.x; b < nblk; b += 1024) ss += partials[(size_t)b * 4 + gi];
     }
-    ss = block_sum(ss, scratch);
-    const float total_norm = (float)sqrt(ss);
-    float coef = max_norm / (total_norm + 1e-6f);      // clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1)
-    coef = coef > 1.f ? 1.f : coef;
+    // block_sum's association (a butterfly per wave, then the 16 wave results in wave order), finished by ONE wave: the sum, the square
+    // root and the clamp are the same in every thread, and sixteen waves issuing them side by side stood in each other's way
+    ss = wave_sum(ss);
+    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = ss;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        double t = 0;
+        for (int w = 0; w < 16; ++w) t += scratch[w];
+        const float total_norm = (float)sqrt(t);
+        float c = max_norm / (total_norm + 1e-6f);     // clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1)
+        if (threadIdx.x == 0) s_coef = c > 1.f ? 1.f : c;
+    }
+    __syncthreads();
+    const float coef = s_coef;
     if (own) tail_adam_apply(e_g, e_m1, e_m2, e_p, coef, grad_scale, beta1, beta2, eps, step_size, bc2_sqrt, params, m1, m2, off, ie, gi, im);
     erl_span_out(span, t_span);
 }
