@@ -173,6 +173,12 @@ struct SpanT {
 struct SpanStamps {
     uint32_t *t;                  // LDS, kSpanPhases words
 };
+// The stamps are written and read through an LDS-typed pointer (ds_write_b32 / ds_read_b32).  Through the generic pointer hipcc issued
+// flat_store_dword wherever it could not prove the address space (the actor's path, whose `&sps` goes to span_exit), and a FLAT access
+// counts against BOTH the vector-memory and the LDS counter: as long as one is pending in hipcc's model -- and no later vmcnt wait of the
+// compiler's own retires it inside a phase -- every LDS wait it inserts is the full s_waitcnt lgkmcnt(0), never a partial one.
+typedef __attribute__((address_space(3))) uint32_t span_lds_u32;
+__device__ __forceinline__ span_lds_u32 *span_lds(const SpanStamps &st) { return (span_lds_u32 *)(uint32_t)(uintptr_t)st.t; }
 __device__ __forceinline__ unsigned long long erl_memtime()
 {
     unsigned long long t;
@@ -187,7 +193,7 @@ __device__ __forceinline__ SpanT span_enter(const Ppo2Args &g)
 }
 // a phase boundary (sampled launches only: a scalar branch otherwise)
 #ifndef ERL_NO_SPAN_STAMPS
-#define SPAN_STAMP(st, k) do { if (g.span) { const uint32_t t_ = (uint32_t)erl_memtime(); if (threadIdx.x == 0) (st).t[k] = t_; } } while (0)
+#define SPAN_STAMP(st, k) do { if (g.span) { const uint32_t t_ = (uint32_t)erl_memtime(); if (threadIdx.x == 0) span_lds(st)[k] = t_; } } while (0)
 #else      // A/B builds: the kernel without its phase stamps (what they cost the unsampled launches)
 #define SPAN_STAMP(st, k) do { } while (0)
 #endif
@@ -200,7 +206,7 @@ __device__ __forceinline__ void span_exit(const Ppo2Args &g, SpanT t0, const Spa
         unsigned long long ph[4] = {0ull, 0ull, 0ull, 0ull};
         if (st) {
 #pragma unroll
-            for (int k = 1; k < kSpanPhases; ++k) ph[(k - 1) >> 1] |= (unsigned long long)st->t[k] << (32 * ((k - 1) & 1));
+            for (int k = 1; k < kSpanPhases; ++k) ph[(k - 1) >> 1] |= (unsigned long long)span_lds(*st)[k] << (32 * ((k - 1) & 1));
         }
         uint32_t hw_id, xcc_id;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)\n\ts_getreg_b32 %1, hwreg(HW_REG_XCC_ID)" : "=s"(hw_id), "=s"(xcc_id));

@@ -229,12 +229,15 @@ __device__ __forceinline__ void fwd_s3(const u8 *img, const float *bias, Parts (
 #pragma unroll
     for (int To = 0; To < NO; ++To) {
         f32x16 acc = nb, acc1 = {0};
-        if (To + 1 < NO) load_bias(To + 1);
+        // The layer's FIRST k-step requests its successor's operand (and the next tile's bias) behind its first MFMA, not in front of it: a
+        // layer starts behind a barrier and a phase stamp, where hipcc reloads kernel arguments by scalar loads; those return out of
+        // order, and with one pending its next LDS wait is the full lgkmcnt(0), which would sit through the reads just issued as well.
+        if (To > 0 && To + 1 < NO) load_bias(To + 1);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ks = 0; ks < NK; ++ks) {
             const int c = To * NK + ks;
-            if (c + 1 < NC) issue(c + 1, aq[(c + 1) & 1]);
+            if (c > 0 && c + 1 < NC) issue(c + 1, aq[(c + 1) & 1]);
             const Parts &a = aq[c & 1], &b = inP[ks];
             auto fill = [&](int s) {
                 if (To > 0) stage(To - 1, ks, s);
@@ -243,6 +246,11 @@ __device__ __forceinline__ void fwd_s3(const u8 *img, const float *bias, Parts (
             };
             acc = mfma_bf(a.m, b.m, acc);
             __builtin_amdgcn_sched_barrier(0);
+            if (c == 0) {
+                if (c + 1 < NC) issue(c + 1, aq[(c + 1) & 1]);
+                if (To + 1 < NO) load_bias(To + 1);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             side(c);
             __builtin_amdgcn_sched_barrier(0);
             fill(0);
@@ -508,16 +516,28 @@ __device__ __forceinline__ void grad_tiles(const Parts (&A)[8], const u8 *SB, in
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) {
             const int c = 8 * k + ks;
-            if (c + 1 < 8 * NBW) tb.issue(jc + CS * ((c + 1) / 8), (c + 1) % 8, rq[(c + 1) & 1]);
             // the next k-step's reads go out BEFORE this k-step's MFMAs (192 cycles of cover): left in one scheduling region hipcc
             // lets the two operand buffers share registers and sinks the reads behind the fifth MFMA, one MFMA (32 cycles) before
-            // their use -- every k-step then waited for the LDS (round 3: 50-52 cycles per MFMA in dW1 / dW2, floor 32)
+            // their use -- every k-step then waited for the LDS (round 3: 50-52 cycles per MFMA in dW1 / dW2, floor 32).
+            // One k-step per tile is the exception: the one behind the finished tile's conditional store (below).  The store's addresses
+            // make hipcc reload kernel arguments by a scalar load in front of the branch, scalar loads return out of order, and with one
+            // pending hipcc's next LDS wait is the full lgkmcnt(0) -- behind reads issued here it would wait for them too.  There the
+            // reads go out behind the first MFMA, whose wait then covers this k-step's operand alone (160 cycles of cover).
+            const bool late = ks == 1 && k > 0;
+            auto refill = [&]() {
+                if (c + 1 < 8 * NBW) tb.issue(jc + CS * ((c + 1) / 8), (c + 1) % 8, rq[(c + 1) & 1]);
+            };
+            if (!late) refill();
             __builtin_amdgcn_sched_barrier(0);
             if constexpr (SIDE) {
                 const Parts &a = A[ks];
                 const Parts b = parts_of(rq[c & 1]);
                 acc = mfma_bf(a.m, b.m, acc);                 // (mma6's order: the same bits)
                 __builtin_amdgcn_sched_barrier(0);
+                if (late) {
+                    refill();
+                    __builtin_amdgcn_sched_barrier(0);
+                }
                 side(c, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 acc = mfma_bf(a.l, b.h, acc);
@@ -536,6 +556,18 @@ __device__ __forceinline__ void grad_tiles(const Parts (&A)[8], const u8 *SB, in
                 __builtin_amdgcn_sched_barrier(0);
                 side(c, 4);
                 __builtin_amdgcn_sched_barrier(0);
+                acc = mfma_bf(a.h, b.h, acc);
+            } else if (late) {
+                const Parts &a = A[ks];
+                const Parts b = parts_of(rq[c & 1]);
+                acc = mfma_bf(a.m, b.m, acc);                 // (mma6's order: the same bits)
+                __builtin_amdgcn_sched_barrier(0);
+                refill();
+                __builtin_amdgcn_sched_barrier(0);
+                acc = mfma_bf(a.l, b.h, acc);
+                acc = mfma_bf(a.h, b.l, acc);
+                acc = mfma_bf(a.m, b.h, acc);
+                acc = mfma_bf(a.h, b.m, acc);
                 acc = mfma_bf(a.h, b.h, acc);
             } else {
                 mma6(A[ks], parts_of(rq[c & 1]), acc);
@@ -1170,7 +1202,18 @@ __device__ __forceinline__ void ppo_block_s3(const Ppo2Args &g, u8 *smem, SpanSt
         // the logged sums' per-wave parts (block_sum's first half: the wave butterfly, one hop per k-step, behind MFMA 3 or 4; its scratch is
         // free until the kernel's end): the four parts are added at the end in block_sum's order -- the same bits -- without its two butterflies
         // and four barriers there, where every cycle is on the critical path (round 6: -1.9k cycles at the end)
-        float lw0 = loss0, lw1 = loss1;
+        // Beside the MFMAs a hop is CONSUMED ONE K-STEP AFTER ITS ds_bpermute (hop_issue behind MFMA 3 or 4 of k-step c, hop_take behind the
+        // first MFMA of k-step c + 1): added where it was issued, the bpermute -- the youngest LDS request -- put a full lgkmcnt(0) among the
+        // MFMAs six times, each a whole LDS round trip that also drained the dZ2 image's stores and the next operand's reads
+        float lw0 = loss0, lw1 = loss1, lh0 = 0.f, lh1 = 0.f;
+        auto hop_issue = [&](int hop) {
+            lh0 = __shfl_xor(lw0, 32 >> hop, 64);
+            lh1 = __shfl_xor(lw1, 32 >> hop, 64);
+        };
+        auto hop_take = [&]() {
+            lw0 += lh0;
+            lw1 += lh1;
+        };
         auto logs_hop = [&](int hop) {
             if (hop < 6) {
                 lw0 += __shfl_xor(lw0, 32 >> hop, 64);
@@ -1184,7 +1227,11 @@ __device__ __forceinline__ void ppo_block_s3(const Ppo2Args &g, u8 *smem, SpanSt
             auto side = [&](int c, int sl) {
                 if (sl < PPK && PPK * c + sl < NP) piece(PPK * c + sl);
                 if constexpr (ERL_K6_EARLY_LOGS) {
-                    if (sl == (PPK < 4 ? 3 : 4) && c < 7) logs_hop(c);
+                    if (sl == 0 && c >= 1 && c < 7) hop_take();                       // hop c - 1
+                    if (sl == (PPK < 4 ? 3 : 4)) {
+                        if (c < 6) hop_issue(c);
+                        else if (c == 6) logs_hop(6);                                 // (the store of the wave's parts)
+                    }
                 }
             };
             grad_tiles<CP1, NBW1, CS1, 0, 0>(A, SB, it, jc, 0, slab + d.oW1(), S, S, lane, side);
