@@ -22,7 +22,7 @@ GAE_VTRACE, GAE_MUTATE, GAE_STATS = 0x1, 0x2, 0x4
 GAE_ALGO_AUTO, GAE_ALGO_EXACT, GAE_ALGO_CHUNKED, GAE_ALGO_LOOKBACK = 0x00, 0x10, 0x20, 0x30
 MAX_STATE_DIM, MAX_HIDDEN, MAX_ACTION_DIM = 128, 128, 16
 MAX_LAYERS, MAXN_WIDTH = 6, 4096
-ABI_VERSION = 22
+ABI_VERSION = 23
 PPO_OBJ_REFERENCE, PPO_OBJ_CANONICAL, PPO_OBJ_A2C = 0, 1, 2      # include/erl_hip.h ERL_PPO_OBJ_*
 SAC_ACTOR_SAC, SAC_ACTOR_FIX = 0, 1                               # include/erl_hip.h ERL_SAC_ACTOR_*
 COMM_ID_BYTES = 128
@@ -92,11 +92,6 @@ _SIGNATURES = {
     "erl_grad_reduce_f32": (c_int, [_P, c_int, c_int64, _P, _P]),
     "erl_clip_adam_f32": (c_int, [_P, _P, _P, _P, POINTER(c_int64), POINTER(c_int64), c_int, _P, c_int32, c_float,
                                   c_float, c_float, c_float, c_float, c_float, _P]),
-    "erl_reduce_clip_adam_f32": (c_int, [_P, c_int, c_int64, _P, _P, _P, _P, POINTER(c_int64), POINTER(c_int64), c_int, c_int32, c_float,
-                                         c_float, c_float, c_float, c_float, c_float, _P]),
-    "erl_reduce_clip_adam_grid_f32": (c_int, [_P, c_int, c_int64, _P, _P, _P, _P, POINTER(c_int64), POINTER(c_int64), c_int, c_int32, c_float,
-                                              c_float, c_float, c_float, c_float, c_float, _P]),
-    "erl_reduce_clip_adam_grid_ok": (c_int, [c_int64]),
     "erl_tail_fused_ok": (c_int, [c_int64]),
     "erl_reduce_clip_adam_fused_f32": (c_int, [_P, c_int, c_int64, _P, _P, _P, _P, POINTER(c_int64), POINTER(c_int64), c_int, c_int32, c_float,
                                                c_float, c_float, c_float, c_float, c_float, _P]),
@@ -431,8 +426,8 @@ def ppo_wg_map_info(device: int = None, wide: bool = False) -> dict:
 
 
 def ppo_update_chains() -> int:
-    """the form the last PPO update loop of this process took: 1 = one chain of launches, 2 = one chain per network on two streams
-    (include/erl_hip.h erl_ppo_update_chains), 0 = none yet"""
+    """0 before any PPO update loop of this process has run, 1 after: the loop is one chain of launches (include/erl_hip.h
+    erl_ppo_update_chains)"""
     return int(lib().erl_ppo_update_chains())
 
 

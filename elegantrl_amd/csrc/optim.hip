@@ -80,175 +80,10 @@ __global__ __launch_bounds__(1024) void clip_adam_kernel(float *__restrict__ par
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Slab reduction + clip + Adam in ONE launch (single-process path: nothing sits between the reduction and the optimiser).
-// grid = ceil(stride / 256) workgroups of 1024 threads: element e of the flat gradient is summed by 4 threads in exactly
-// grad_reduce_kernel's association (bit-identical gradient), written out, and its square goes into the workgroup's
-// per-group partial sum (fp64).  Workgroups then ARRIVE on a monotonic device counter; the one that arrives last -- no
-// workgroup ever waits, so no co-residency is assumed and nothing can deadlock -- reads every partial in a fixed order,
-// derives the clip coefficients and applies Adam to all parameters (50k elements: 25 per thread and trip, two trips).
-// Visibility across CUs / XCDs (cdna_hip_programming.md Guideline 16, form R1): gradient and partials are stored
-// write-through (agent-scope relaxed atomic stores = sc1), every storing wave drains its stores before the workgroup's one
-// arrival, and the last workgroup makes ONE agent-scope acquire before it reads them back with plain loads.
-// MEASURED SLOWER than the two launches it replaces (34.9 vs 18.2 us at config 4, tools/tail_bench.py): the last workgroup's
-// Adam phase is one CU moving 1.4 MB (~75 GB/s per CU = ~19 us), which outweighs the saved launch; spreading that phase needs
-// every workgroup to WAIT for the norm (a grid barrier, i.e. co-residency assumptions).  Kept as an opt-in entry point
-// (ERL_FUSED_TAIL=1 in the update loop) and as the record of why the tail stays two launches.
-// ---------------------------------------------------------------------------------------------------------
-constexpr int RA_T = 1024, RA_E = 256;      // threads, elements per workgroup
-
-__device__ __forceinline__ void st_agent(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-template <bool GRID_WAIT>
-__global__ __launch_bounds__(RA_T) void reduce_clip_adam_kernel(const float *__restrict__ slabs, int n_slabs, int64_t stride,
-                                                                float *flat, float *__restrict__ params, float *__restrict__ m1,
-                                                                float *__restrict__ m2, AdamGroups gr, int n_groups, float lr,
-                                                                float beta1, float beta2, float eps, float max_norm, float grad_scale,
-                                                                float step_size, float bc2_sqrt, double *partials,
-                                                                unsigned *counter, unsigned target, uint32_t *fault)
-{
-    __shared__ float part[4][RA_E];
-    __shared__ double scratch[16];
-    __shared__ int s_last;
-    const int el = threadIdx.x & (RA_E - 1), p = threadIdx.x / RA_E;
-    const int64_t i = (int64_t)blockIdx.x * RA_E + el;
-    // (grid-wait form) the element's optimiser state rides the reduction's first round trip
-    int my_group = -1;
-    float e_m1 = 0.f, e_m2 = 0.f, e_p = 0.f;
-    if (GRID_WAIT && p == 0) {
-        for (int gi = 0; gi < n_groups; ++gi)
-            if (i >= gr.off[gi] && i < gr.off[gi] + gr.len[gi]) my_group = gi;
-        if (my_group >= 0) { e_m1 = m1[i]; e_m2 = m2[i]; e_p = params[i]; }
-    }
-    float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (i < stride) {                                  // (the loop nest of grad_reduce_kernel, mlp.hip: same association)
-        const float *src = slabs + i;
-        int k = p;
-        for (; k + 124 < n_slabs; k += 128) {
-            float x[32];
-#pragma unroll
-            for (int u = 0; u < 32; ++u) x[u] = __builtin_nontemporal_load(src + (size_t)(k + 4 * u) * stride);   // streamed once (see mlp.hip)
-#pragma unroll
-            for (int v = 0; v < 4; ++v)
-#pragma unroll
-                for (int u = 0; u < 8; ++u) s[u] += x[8 * v + u];
-        }
-        for (; k + 28 < n_slabs; k += 32) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s[u] += src[(size_t)(k + 4 * u) * stride];
-        }
-        for (; k < n_slabs; k += 4) s[0] += src[(size_t)k * stride];
-    }
-    part[p][el] = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
-    __syncthreads();
-    float gsum = 0.f;
-    if (p == 0 && i < stride) {
-        gsum = (part[0][el] + part[1][el]) + (part[2][el] + part[3][el]);
-        st_agent(flat + i, gsum);
-    }
-    for (int gi = 0; gi < n_groups; ++gi) {            // this workgroup's share of each group's squared norm
-        const bool in = p == 0 && i >= gr.off[gi] && i < gr.off[gi] + gr.len[gi];
-        const double xs = (double)(gsum * grad_scale);
-        const double t = block_sum(in ? xs * xs : 0.0, scratch);
-        if (threadIdx.x == 0) __hip_atomic_store(partials + (size_t)blockIdx.x * 4 + gi, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave drains its write-through stores ...
-    __syncthreads();
-    if (threadIdx.x == 0) {                            // ... before the workgroup's one arrival
-        const unsigned old = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = (old + 1u == target);
-    }
-    __syncthreads();
-    if (GRID_WAIT) {
-        // ---- every workgroup WAITS for the last arrival, then applies Adam to its own 256 elements from registers: the whole
-        // grid is resident (the host checked grid <= the device's capacity for this kernel and the stream is in order, so the
-        // workgroups not yet dispatched can only be waiting for unrelated kernels, which finish without us); the spin is
-        // bounded all the same and reports through the fault word instead of hanging
-        if (threadIdx.x == 0) {
-            unsigned spins = 0;
-            s_last = 0;                                // reused: 1 = the wait timed out
-            while ((int)(__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0) {
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > (1u << 24)) {
-                    if (fault) __hip_atomic_fetch_add(fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    s_last = 1;
-                    break;
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
-        __syncthreads();
-        if (s_last) return;                            // incomplete norm: the update is SKIPPED (and reported), never applied
-        const int nblk = gridDim.x;
-        float mul = 0.f;
-        for (int gi = 0; gi < n_groups; ++gi) {
-            double ss = 0.0;
-            for (int b = threadIdx.x; b < nblk; b += RA_T) ss += partials[(size_t)b * 4 + gi];
-            ss = block_sum(ss, scratch);
-            const float total_norm = (float)sqrt(ss);
-            float coef = max_norm / (total_norm + 1e-6f);  // clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1)
-            coef = coef > 1.f ? 1.f : coef;
-            if (gi == my_group) mul = grad_scale * coef;
-        }
-        if (my_group >= 0) {
-            erl_adam_update(erl_mul_rn(gsum, mul), e_m1, e_m2, e_p, beta1, beta2, eps, step_size, bc2_sqrt);
-            m1[i] = e_m1;
-            m2[i] = e_m2;
-            params[i] = e_p;
-        }
-        return;
-    }
-    if (!s_last) return;
-
-    // ---- the last workgroup: ONE agent-scope acquire (drops this CU's stale L1 lines), then plain loads -- the compiler
-    // serialises agent-scope atomic loads (52 dependent L2 trips per thread: 34 us for the launch, measured), plain ones it batches
-    if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    __syncthreads();
-    // norms in a fixed order, then clip + Adam for every group
-    const int nblk = gridDim.x;
-    float gmul[4];
-    for (int gi = 0; gi < n_groups; ++gi) {
-        double ss = 0.0;
-        for (int b = threadIdx.x; b < nblk; b += RA_T)
-            ss += partials[(size_t)b * 4 + gi];
-        ss = block_sum(ss, scratch);
-        const float total_norm = (float)sqrt(ss);
-        float coef = max_norm / (total_norm + 1e-6f);  // clip_grad_norm_: clamp(max_norm / (norm + 1e-6), max=1)
-        coef = coef > 1.f ? 1.f : coef;
-        gmul[gi] = grad_scale * coef;
-    }
-    for (int gi = 0; gi < n_groups; ++gi) {
-        const int64_t off = gr.off[gi], len = gr.len[gi];
-        constexpr int U = 13;                          // elements per thread and trip: 4 U loads in flight
-        for (int64_t i0 = threadIdx.x; i0 < len; i0 += (int64_t)U * RA_T) {
-            float xg[U], xm1[U], xm2[U], xp[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t e = i0 + (int64_t)u * RA_T, ec = e < len ? e : len - 1;
-                xg[u] = flat[off + ec];
-                xm1[u] = m1[off + ec];
-                xm2[u] = m2[off + ec];
-                xp[u] = params[off + ec];
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t e = i0 + (int64_t)u * RA_T;
-                if (e < len) {
-                    float a = xm1[u], b = xm2[u], pv = xp[u];
-                    erl_adam_update(erl_mul_rn(xg[u], gmul[gi]), a, b, pv, beta1, beta2, eps, step_size, bc2_sqrt);
-                    m1[off + e] = a;
-                    m2[off + e] = b;
-                    params[off + e] = pv;
-                }
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------
 // clip + Adam for LONG groups (more than 64 Ki elements: SAC's critic ensemble, 280k): clip_adam_kernel makes every
 // workgroup read the whole group for the norm, which at 274 workgroups x 1.1 MB is what the launch then costs (17-36 us
 // measured in the SAC step).  Here a workgroup squares only its own 1024 elements, publishes the fp64 partial, arrives on
-// the device counter and WAITS for the others (whole grid resident -- checked by the host, see reduce_clip_adam_kernel),
+// the device counter and WAITS for the others (whole grid resident -- checked by the host, see clip_adam_impl),
 // sums the group's partials in a fixed order and updates its elements from registers.  grid = (blocks, n_groups).
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(1024) void clip_adam_grid_kernel(float *__restrict__ params, const float *__restrict__ grads,
@@ -339,7 +174,7 @@ static RaScratch g_ra[32];
 
 }  // namespace
 
-// the per-device arrival counter and partial-norm table of the single-launch tails, and the counter value the launch that
+// the per-device arrival counter and partial-norm table of the grid-wait clip + Adam, and the counter value the launch that
 // is about to be enqueued completes at (`nblk` arrivals after everything enqueued before it).  One table per device: these
 // launches are meant for ONE stream per device (the update loop's); launches from concurrent streams would share the counter.
 static int ra_arrivals(const char *what, int64_t nblk, hipStream_t st, RaScratch **out, unsigned *target)
@@ -378,54 +213,6 @@ static int device_capacity(const void *kernel, int threads)
         return -1;
     }
     return per_cu * cus > 0 ? per_cu * cus : -1;
-}
-
-static int reduce_clip_adam_launch(bool grid_wait, const float *slabs, int n_slabs, int64_t stride, float *flat_grad, float *params,
-                                   float *exp_avg, float *exp_avg_sq, const int64_t *group_off, const int64_t *group_len,
-                                   int n_groups, int32_t step, float lr, float beta1, float beta2, float eps, float max_norm,
-                                   float grad_scale, void *stream)
-{
-    ERL_REQUIRE(slabs && flat_grad && params && exp_avg && exp_avg_sq && group_off && group_len, "erl_reduce_clip_adam_f32: NULL argument");
-    ERL_REQUIRE(n_slabs >= 1 && stride >= 1 && n_groups >= 1 && n_groups <= 4 && step >= 1, "erl_reduce_clip_adam_f32: bad argument");
-    AdamGroups gr;
-    for (int i = 0; i < 4; ++i) {
-        gr.off[i] = i < n_groups ? group_off[i] : 0;
-        gr.len[i] = i < n_groups ? group_len[i] : 0;
-        ERL_REQUIRE(gr.off[i] >= 0 && gr.len[i] >= 0 && gr.off[i] + gr.len[i] <= stride, "erl_reduce_clip_adam_f32: group outside the gradient row");
-    }
-    const int64_t nblk = erl_cdiv(stride, RA_E);
-    ERL_REQUIRE(nblk <= kRaMaxBlocks, "erl_reduce_clip_adam_f32: gradient row too long (%lld floats)", (long long)stride);
-    RaScratch *scp = nullptr;
-    unsigned target = 0;
-    hipStream_t st = (hipStream_t)stream;
-    {
-        int rc = ra_arrivals("erl_reduce_clip_adam_f32", nblk, st, &scp, &target);
-        if (rc) return rc;
-    }
-    RaScratch &sc = *scp;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    if (grid_wait)
-        hipLaunchKernelGGL(reduce_clip_adam_kernel<true>, dim3((unsigned)nblk), dim3(RA_T), 0, st, slabs, n_slabs, stride, flat_grad, params,
-                           exp_avg, exp_avg_sq, gr, n_groups, lr, beta1, beta2, eps, max_norm, grad_scale, (float)((double)lr / bc1),
-                           (float)sqrt(bc2), reinterpret_cast<double *>(sc.ptr + 256), reinterpret_cast<unsigned *>(sc.ptr), target,
-                           erl_fault_word(ERL_FAULT_ADAM_GRID_WAIT));
-    else
-        hipLaunchKernelGGL(reduce_clip_adam_kernel<false>, dim3((unsigned)nblk), dim3(RA_T), 0, st, slabs, n_slabs, stride, flat_grad, params,
-                           exp_avg, exp_avg_sq, gr, n_groups, lr, beta1, beta2, eps, max_norm, grad_scale, (float)((double)lr / bc1),
-                           (float)sqrt(bc2), reinterpret_cast<double *>(sc.ptr + 256), reinterpret_cast<unsigned *>(sc.ptr), target,
-                           (uint32_t *)nullptr);
-    ERL_LAUNCH_CHECK("erl_reduce_clip_adam_f32");
-}
-
-// 1 when the grid-wait form of erl_reduce_clip_adam_f32 may be used for a gradient row of `stride` floats on the current
-// device: every workgroup of the launch fits on the device at once (occupancy of the kernel x compute units)
-extern "C" int erl_reduce_clip_adam_grid_ok(int64_t stride)
-{
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) return 0;
-    static int capacity[32] = {0};
-    if (!capacity[dev]) capacity[dev] = device_capacity((const void *)reduce_clip_adam_kernel<true>, RA_T);
-    return capacity[dev] > 0 && erl_cdiv(stride, RA_E) <= capacity[dev];
 }
 
 static int clip_adam_impl(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, const int64_t *group_off,
@@ -508,26 +295,4 @@ int erl_clip_adam_parts_soft_f32(float *params, const float *grads, float *exp_a
     hipLaunchKernelGGL(clip_adam_parts_kernel, dim3((unsigned)erl_cdiv(len, 1024)), dim3(1024), 0, stream, params, grads, exp_avg, exp_avg_sq, len,
                        parts, nparts, beta1, beta2, eps, max_norm, (float)((double)lr / bc1), (float)sqrt(bc2), soft, tau);
     ERL_LAUNCH_CHECK("erl_clip_adam_parts_soft_f32");
-}
-
-extern "C" int erl_reduce_clip_adam_f32(const float *slabs, int n_slabs, int64_t stride, float *flat_grad, float *params,
-                                        float *exp_avg, float *exp_avg_sq, const int64_t *group_off, const int64_t *group_len,
-                                        int n_groups, int32_t step, float lr, float beta1, float beta2, float eps, float max_norm,
-                                        float grad_scale, void *stream)
-{
-    return reduce_clip_adam_launch(false, slabs, n_slabs, stride, flat_grad, params, exp_avg, exp_avg_sq, group_off, group_len, n_groups, step,
-                                   lr, beta1, beta2, eps, max_norm, grad_scale, stream);
-}
-
-// The same in the grid-wait form (every workgroup waits for the norm and updates its own elements); EINVAL when the launch
-// would not fit on the device at once (erl_reduce_clip_adam_grid_ok).
-extern "C" int erl_reduce_clip_adam_grid_f32(const float *slabs, int n_slabs, int64_t stride, float *flat_grad, float *params,
-                                             float *exp_avg, float *exp_avg_sq, const int64_t *group_off, const int64_t *group_len,
-                                             int n_groups, int32_t step, float lr, float beta1, float beta2, float eps, float max_norm,
-                                             float grad_scale, void *stream)
-{
-    ERL_REQUIRE(erl_reduce_clip_adam_grid_ok(stride), "erl_reduce_clip_adam_grid_f32: %lld-float row does not fit the device in one wave of workgroups",
-                (long long)stride);
-    return reduce_clip_adam_launch(true, slabs, n_slabs, stride, flat_grad, params, exp_avg, exp_avg_sq, group_off, group_len, n_groups, step,
-                                   lr, beta1, beta2, eps, max_norm, grad_scale, stream);
 }

@@ -36,9 +36,7 @@ struct Ppo2Args {
     const unsigned char *code_touch = nullptr;
     unsigned code_touch_bytes = 0;
     unsigned long long *pc_out = nullptr;
-    // >= 0: a HALF launch, grid (n_slabs, 1): every workgroup works on this network (0 actor, 1 critic) -- the two-chain update loop of
-    // comm.cpp runs the two networks' minibatch kernels as independent launches on two streams; -1: both networks, grid (n_slabs, 2)
-    int only_net = -1;
+    int only_net = -1;    // >= 0: a half launch, grid (n_slabs, 1), every workgroup on this network; the host leaves it at -1
     long long *prof;      // ERL_PROFILE builds only: [net][8 waves][32] s_memtime stamps of workgroup prof_block
     int prof_block;
 };

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ERL_ABI_VERSION 22
+#define ERL_ABI_VERSION 23
 #define ERL_API __attribute__((visibility("default")))
 #define ERL_OK 0
 #define ERL_EINVAL (-1)
@@ -481,12 +481,9 @@ ERL_API int erl_ppo_arith_in_use(int S, int h1, int h2, int A);   /* ERL_PPO_ARI
  * The (256, h2[, h3]) kernels decide for themselves (their code is 125 KB per network): device | ERL_PPO_WG_FAMILY_WIDE asks for theirs. */
 #define ERL_PPO_WG_FAMILY_WIDE 0x100
 ERL_API int erl_ppo_wg_map_info(int device, int *map, double *us_map0, double *us_map2);
-/* The form the last erl_ppo_update_f32 / erl_ppo_update_dp_f32 of this process took (ABI 19): 1 = one chain of launches per minibatch
- * (minibatch kernel over both networks, slab reduction, clip + Adam), 2 = TWO chains -- the actor's and the critic's minibatches share
- * nothing (own gradient, own clip norm, own Adam step: elegantrl/agents/AgentPPO.py:196-204, AgentBase.py:239-248), so each network runs
- * minibatch kernel -> slab reduction -> clip + Adam as its own chain of half-chip launches, the critic's on a library-owned second
- * stream forked from / joined into the caller's; 0 = no loop yet.  Bit-identical parameters either way.  Two chains are the default for
- * a single process on the split-arithmetic (128 | 64, h2) kernels where the device keeps workgroup map 0; ERL_PPO_CHAINS=1 forces one. */
+/* 0 before any erl_ppo_update_f32 / erl_ppo_update_dp_f32 of this process has run its loop, 1 after (ABI 19; measurement and logging).
+ * The loop is ONE chain of launches per minibatch on the caller's stream: minibatch kernel over both networks, slab reduction, clip +
+ * Adam.  (Up to ABI 22 it could also report 2, a two-chain form that was measured slower and deleted: DESIGN.md section 9.) */
 ERL_API int erl_ppo_update_chains(void);
 ERL_API int64_t erl_ppo_slab_stride(int S, int h1, int h2, int A);
 ERL_API int erl_ppo_num_slabs(int64_t B);
@@ -552,25 +549,6 @@ ERL_API int erl_ppo_finish_f32(const float *grad_rows, int64_t stride, int64_t o
                        float *rewards, uint8_t *undones, const uint8_t *unmasks, const float *values, int64_t total,
                        void *stream);
 
-/* erl_grad_reduce_f32 + erl_clip_adam_f32 in ONE launch (host step only), for loops with nothing between the two: the same
- * gradient bit for bit (same summation order), written to flat_grad; the workgroup that finishes last derives the clip
- * coefficients from per-workgroup fp64 partial norms (fixed order) and applies Adam.  No workgroup waits on another. */
-ERL_API int erl_reduce_clip_adam_f32(const float *slabs, int n_slabs, int64_t stride, float *flat_grad, float *params,
-                             float *exp_avg, float *exp_avg_sq, const int64_t *group_off, const int64_t *group_len,
-                             int n_groups, int32_t step, float lr, float beta1, float beta2, float eps, float max_norm,
-                             float grad_scale, void *stream);
-
-/* The same in the grid-wait form: every workgroup waits for the last partial norm (device counter) and updates its own
- * 256 elements from registers -- one launch, no single-workgroup Adam phase.  Valid only when the whole launch is resident
- * at once: erl_reduce_clip_adam_grid_ok(stride) (occupancy x compute units >= ceil(stride / 256)); EINVAL otherwise.  The
- * wait is bounded and reports through erl_async_fault_count.  Default optimiser tail of erl_ppo_update_f32 when it applies
- * (ERL_FUSED_TAIL=0 restores the two launches). */
-ERL_API int erl_reduce_clip_adam_grid_ok(int64_t stride);
-ERL_API int erl_reduce_clip_adam_grid_f32(const float *slabs, int n_slabs, int64_t stride, float *flat_grad, float *params,
-                             float *exp_avg, float *exp_avg_sq, const int64_t *group_off, const int64_t *group_len,
-                             int n_groups, int32_t step, float lr, float beta1, float beta2, float eps, float max_norm,
-                             float grad_scale, void *stream);
-
 /* The default two-launch tail (erl_grad_reduce_partials_f32 + erl_clip_adam_partials_f32) as ONE launch with the same bits (ABI 17,
  * csrc/grad_tail.hip tail_fused_kernel): the partial norms are published by agent-scope stores into a table double buffered by the
  * launch's parity and are their own flags (an unwritten entry holds a sentinel NaN); every workgroup polls them -- no arrival counter,
@@ -578,7 +556,7 @@ ERL_API int erl_reduce_clip_adam_grid_f32(const float *slabs, int n_slabs, int64
  * reduced, from registers.  Needs erl_tail_fused_ok(stride): rows up to 131 072 floats, every workgroup of the launch resident at once.
  * The wait is bounded; a workgroup whose wait times out SKIPS its 256 elements' update and reports through erl_async_fault_count -- the
  * others may already have stepped theirs: after such a fault the optimiser state is partially updated and must be restored, not used.  Single process only (a data-parallel
- * rank's exchange keeps the two launches).  erl_ppo_update_f32 uses it under ERL_FUSED_TAIL=3. */
+ * rank's exchange keeps the two launches).  A stand-alone entry: the update loops always take the two launches (measured faster). */
 ERL_API int erl_tail_fused_ok(int64_t stride);
 ERL_API int erl_reduce_clip_adam_fused_f32(const float *slabs, int n_slabs, int64_t stride, float *flat_grad, float *params,
                              float *exp_avg, float *exp_avg_sq, const int64_t *group_off, const int64_t *group_len,

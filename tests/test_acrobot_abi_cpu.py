@@ -14,7 +14,7 @@ UNSUPPORTED = ((4, 100, 32, 2), (65, 64, 32, 2), (4, 64, 32, 9), (4, 64, 32, 1),
 def test_abi_is_still_22_with_the_three_symbols():
     from elegantrl_amd import _hip
     txt = open(os.path.join(ROOT, "include", "erl_hip.h")).read()
-    assert int(re.search(r"#define ERL_ABI_VERSION (\d+)", txt).group(1)) == _hip.ABI_VERSION == _hip.lib().erl_abi_version() == 22
+    assert int(re.search(r"#define ERL_ABI_VERSION (\d+)", txt).group(1)) == _hip.ABI_VERSION == _hip.lib().erl_abi_version() == 23
     for name in NAMES:
         assert name in _hip.EXPORTED_SYMBOLS and re.search(r"ERL_API int " + name + r"\(", txt)
         assert getattr(_hip.lib(), name) is not None

@@ -13,7 +13,7 @@ NAMES = ("erl_rollout_discrete_supported", "erl_cartpole_step_f32", "erl_rollout
 def test_abi_22_and_the_four_symbols():
     from elegantrl_amd import _hip
     txt = open(os.path.join(ROOT, "include", "erl_hip.h")).read()
-    assert int(re.search(r"#define ERL_ABI_VERSION (\d+)", txt).group(1)) == _hip.ABI_VERSION == _hip.lib().erl_abi_version() == 22
+    assert int(re.search(r"#define ERL_ABI_VERSION (\d+)", txt).group(1)) == _hip.ABI_VERSION == _hip.lib().erl_abi_version() == 23
     for name in NAMES:
         assert name in _hip.EXPORTED_SYMBOLS and re.search(r"ERL_API int " + name + r"\(", txt)
         assert getattr(_hip.lib(), name) is not None

@@ -15,7 +15,7 @@ UNSUPPORTED_NETS = ((100, 32), (256, 64), (64, 160), (16, 32))
 def test_abi_is_still_22_with_the_four_symbols():
     from elegantrl_amd import _hip
     txt = open(os.path.join(ROOT, "include", "erl_hip.h")).read()
-    assert int(re.search(r"#define ERL_ABI_VERSION (\d+)", txt).group(1)) == _hip.ABI_VERSION == _hip.lib().erl_abi_version() == 22
+    assert int(re.search(r"#define ERL_ABI_VERSION (\d+)", txt).group(1)) == _hip.ABI_VERSION == _hip.lib().erl_abi_version() == 23
     for name in NAMES:
         proto = re.search(r"ERL_API (?:int|int64_t) " + name + r"\(([^;]*)\);", txt)
         assert proto is not None and name in _hip.EXPORTED_SYMBOLS, name

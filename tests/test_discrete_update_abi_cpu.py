@@ -16,7 +16,7 @@ BAD = ((4, 100, 32, 2), (65, 64, 32, 2), (4, 64, 32, 9), (4, 64, 32, 1), (4, 256
 def test_the_four_symbols_and_abi_22():
     from elegantrl_amd import _hip
     txt = open(os.path.join(ROOT, "include", "erl_hip.h")).read()
-    assert int(re.search(r"#define ERL_ABI_VERSION (\d+)", txt).group(1)) == _hip.ABI_VERSION == _hip.lib().erl_abi_version() == 22
+    assert int(re.search(r"#define ERL_ABI_VERSION (\d+)", txt).group(1)) == _hip.ABI_VERSION == _hip.lib().erl_abi_version() == 23
     for name in NAMES:
         assert name in _hip.EXPORTED_SYMBOLS and re.search(r"ERL_API (int|int64_t) " + name + r"\(", txt), name
         assert getattr(_hip.lib(), name) is not None

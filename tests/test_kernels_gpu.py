@@ -4,6 +4,10 @@ Bars (BASELINE.json north_star / SURVEY.md 8c): indices and gathered rows bit-ex
 returns within 1e-5 * max(1, |ref|) fp32 (bit-exact in ERL_GAE_ALGO_EXACT mode); MLP / loss / gradient
 math within rtol 1e-4 of the fp32 oracle (MFMA accumulation order differs from torch's GEMM).
 """
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 import torch as th
@@ -884,14 +888,21 @@ def test_update_loop_code_touch_changes_nothing(ops, dev, monkeypatch):
             assert np.array_equal(a, b), key
 
 
-@pytest.mark.parametrize("S,A,B,h1,h2,N", [(64, 8, 16384, 128, 128, 4000), (64, 8, 1000, 128, 128, 300), (17, 5, 300, 128, 128, 77), (3, 1, 4096, 128, 64, 500),
-                                            (32, 3, 260, 64, 128, 100), (20, 4, 129, 64, 64, 50)])
-def test_update_loop_two_chains_equal_one_chain(ops, dev, monkeypatch, S, A, B, h1, h2, N):
-    """csrc/comm.cpp, round 6: the actor's and the critic's minibatches share nothing (own gradient, own clip norm, own Adam step:
-    elegantrl/agents/AgentPPO.py:196-204), so the update loop runs them as TWO chains of half-chip launches on two streams
-    (ERL_PPO_CHAINS=2, the default where it applies; one-network minibatch kernel, one-group slab reduction, one-group clip + Adam).
-    Same kernels, same associations: weights, both moments and every gradient row (the logged sums included) BIT FOR BIT against the
-    one-chain loop, over two loops of three minibatches, full chip and ragged shapes, the actor | critic seam inside a 64-element chunk."""
+# (S, A, B, h1, h2, N, arithmetic): full chip, ragged slabs, the actor | critic seam inside a 64-element chunk; the last one is the loop
+# without weight images
+UPDATE_LOOP_CASES = [(64, 8, 16384, 128, 128, 4000, "split"), (64, 8, 1000, 128, 128, 300, "split"), (17, 5, 300, 128, 128, 77, "split"),
+                     (3, 1, 4096, 128, 64, 500, "split"), (32, 3, 260, 64, 128, 100, "split"), (20, 4, 129, 64, 64, 50, "split"),
+                     (64, 8, 1000, 128, 128, 300, "f32")]
+UPDATE_LOOP_DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ppo_update_loop_digests.json")
+
+
+def update_loop_case_key(S, A, B, h1, h2, N, arith):
+    return f"S{S}_A{A}_B{B}_net{h1}x{h2}_N{N}_{arith}"
+
+
+def run_update_loop_case(ops, dev, S, A, B, h1, h2, N, arith):
+    """two update loops of three minibatches from seeded inputs -> (sha256 of the raw bytes of weights, exp_avg, exp_avg_sq and all six
+    gradient rows; the largest move of a weight).  tools/record_update_loop_digests.py records the digests through this function."""
     H, T = 9, 3
     rng = np.random.default_rng(S * 1000 + B)
     buf = ppo_case(rng, H, N, S, A, B)[:6]
@@ -901,27 +912,43 @@ def test_update_loop_two_chains_equal_one_chain(ops, dev, monkeypatch, S, A, B, 
     P0 = cu(np.concatenate([flat_params(actor), flat_params(critic)]), dev)
     norm = [cu(actor.state_avg, dev), cu(actor.state_std, dev), cu(critic.state_avg, dev), cu(critic.state_std, dev)]
     tb = [cu(x, dev) for x in buf]
-    out, took = {}, {}
-    prev = ops.ppo_set_arith("split")
-    monkeypatch.setenv("ERL_K6_WG_MAP", "0")           # (a device that keeps map 2 stays on one chain: decided here, not measured)
+    prev_map = os.environ.get("ERL_K6_WG_MAP")
+    os.environ["ERL_K6_WG_MAP"] = "0"                  # (the workgroup map is decided here, not measured)
+    prev = ops.ppo_set_arith(arith)
     try:
-        for chains in ("1", "2"):
-            monkeypatch.setenv("ERL_PPO_CHAINS", chains)
-            P, M1, M2 = P0.clone(), th.zeros_like(P0), th.zeros_like(P0)
-            slabs, rows = th.full((n_slabs, stride), float("nan"), device=dev), th.full((2 * T, stride), float("nan"), device=dev)
-            for rep in range(2):
-                ops.ppo_update(P, M1, M2, *norm, S, h1, h2, A, *tb, ids, 0.25, 0.001, slabs, rows[T * rep:], 1 + T * rep, 1e-3, 3.0)
-            th.cuda.synchronize()
-            _hip.check_async_faults()
-            took[chains] = _hip.ppo_update_chains()
-            out[chains] = [x.cpu().numpy().view(np.uint32) for x in (P, M1, M2, rows)]
-            assert np.isfinite(out[chains][0].view(np.float32)).all() and np.isfinite(out[chains][3].view(np.float32)).all()
+        assert ops.ppo_arith_in_use(S, h1, h2, A) == arith
+        P, M1, M2 = P0.clone(), th.zeros_like(P0), th.zeros_like(P0)
+        slabs, rows = th.full((n_slabs, stride), float("nan"), device=dev), th.full((2 * T, stride), float("nan"), device=dev)
+        for rep in range(2):
+            ops.ppo_update(P, M1, M2, *norm, S, h1, h2, A, *tb, ids, 0.25, 0.001, slabs, rows[T * rep:], 1 + T * rep, 1e-3, 3.0)
+        th.cuda.synchronize()
+        _hip.check_async_faults()
     finally:
         ops.ppo_set_arith(prev)
-    assert took == {"1": 1, "2": 2}, took
-    for name, a, b in zip(("weights", "exp_avg", "exp_avg_sq", "gradient rows"), out["1"], out["2"]):
-        assert np.array_equal(a, b), name
-    assert np.abs(out["2"][0].view(np.float32) - P0.cpu().numpy()).max() > 1e-4
+        if prev_map is None:
+            del os.environ["ERL_K6_WG_MAP"]
+        else:
+            os.environ["ERL_K6_WG_MAP"] = prev_map
+    assert th.isfinite(P).all() and th.isfinite(rows).all()
+    digests = {name: hashlib.sha256(x.cpu().contiguous().numpy().tobytes()).hexdigest()
+               for name, x in (("weights", P), ("exp_avg", M1), ("exp_avg_sq", M2), ("gradient rows", rows))}
+    return digests, float((P - P0).abs().max())
+
+
+@pytest.mark.parametrize("S,A,B,h1,h2,N,arith", UPDATE_LOOP_CASES)
+def test_update_loop_matches_parent_digests(ops, dev, S, A, B, h1, h2, N, arith):
+    """csrc/comm.cpp: the update loop has one schedule (minibatch kernel -> slab reduction + partial norms -> clip + Adam, one stream); the
+    forms that were measured and rejected went, and the two tail kernels lost the arguments and branches that served them.  Weights, both
+    moments and every gradient row (the logged sums included) over two loops of three minibatches keep the BITS that the commit before
+    that change left: tests/golden/ppo_update_loop_digests.json, recorded there by tools/record_update_loop_digests.py, never from the
+    tree under test."""
+    with open(UPDATE_LOOP_DIGESTS) as f:
+        want = json.load(f)["digests"][update_loop_case_key(S, A, B, h1, h2, N, arith)]
+    got, moved = run_update_loop_case(ops, dev, S, A, B, h1, h2, N, arith)
+    assert _hip.ppo_update_chains() == 1
+    for name in ("weights", "exp_avg", "exp_avg_sq", "gradient rows"):
+        assert got[name] == want[name], name
+    assert moved > 1e-4
 
 
 def test_ppo_step_split_arith_at_benchmark_size(ops, dev):
@@ -1064,35 +1091,6 @@ def test_clip_adam_matches_oracle(ops, dev, n_a, n_c):
     _hip.check_async_faults()
 
 
-@pytest.mark.parametrize("grid_wait", [False, True])
-@pytest.mark.parametrize("n_slabs,Pa,Pc,max_norm", [(128, 25872, 24961, 3.0), (128, 25872, 24961, 1e9), (7, 1000, 37, 0.5), (1, 300, 200, 3.0)])
-def test_reduce_clip_adam_equals_the_two_kernel_tail(ops, dev, n_slabs, Pa, Pc, max_norm, grid_wait):
-    """erl_reduce_clip_adam_f32 (one launch, last-arriver) and erl_reduce_clip_adam_grid_f32 (one launch, every workgroup waits
-    for the norm) against erl_grad_reduce_f32 + erl_clip_adam_f32: the reduced gradient
-    bit for bit (same association), parameters and moments to fp32 round-off of the norm (fp64 partial sums in another order),
-    over several back-to-back steps (the arrival counter is monotonic across launches)."""
-    g = th.Generator(device=dev).manual_seed(n_slabs + Pa)
-    stride = Pa + Pc + 4
-    groups = [(0, Pa), (Pa, Pc)]
-    p0 = th.randn(Pa + Pc, device=dev, generator=g)
-    pa, ma, va = p0.clone(), th.zeros_like(p0), th.zeros_like(p0)
-    pb, mb, vb = p0.clone(), th.zeros_like(p0), th.zeros_like(p0)
-    fa, fb = th.empty(stride, device=dev), th.empty(stride, device=dev)
-    if grid_wait:
-        assert ops.reduce_clip_adam_grid_ok(stride)
-    for step in range(1, 6):
-        slabs = th.randn((n_slabs, stride), device=dev, generator=g) * (0.1 if step % 2 else 10.0)
-        ops.grad_reduce(slabs, n_slabs, stride, fa)
-        ops.clip_adam(pa, fa, ma, va, groups, step, 1e-3, max_norm)
-        ops.reduce_clip_adam(slabs, n_slabs, stride, fb, pb, mb, vb, groups, step, 1e-3, max_norm, grid_wait=grid_wait)
-        assert th.equal(fa, fb)
-        for x, y in ((pa, pb), (ma, mb), (va, vb)):
-            np.testing.assert_allclose(y.cpu().numpy(), x.cpu().numpy(), rtol=2e-6, atol=1e-9)
-    assert float((pa - p0).abs().max()) > 1e-4
-    th.cuda.synchronize()
-    _hip.check_async_faults()
-
-
 @pytest.mark.parametrize("n_slabs,Pa,Pc,max_norm,scale", [(128, 25872, 24961, 3.0, 1.0), (128, 25872, 24961, 1e9, 0.125), (7, 1000, 37, 0.5, 0.5),
                                                           (1, 300, 200, 3.0, 1.0), (37, 70000, 5, 3.0, 1.0)])
 def test_partials_tail_equals_the_two_kernel_tail(ops, dev, n_slabs, Pa, Pc, max_norm, scale):
@@ -1152,26 +1150,8 @@ def test_single_launch_tail_is_bit_identical_to_the_two_launch_tail(ops, dev, n_
     _hip.check_async_faults()
 
 
-def test_single_launch_tail_in_the_update_loop_and_its_timeout(ops, dev, monkeypatch):
-    """(i) erl_ppo_update_f32 under ERL_FUSED_TAIL=3 leaves exactly the weights, moments, gradient rows and -- for the split-arithmetic
-    minibatch kernel -- weight IMAGES (the next minibatch reads them) of the default two-launch loop: six minibatches on the reference
-    golden's shape; (ii) a row too long for the kernel is refused by erl_tail_fused_ok (the loop keeps the two launches)."""
-    g = load("ppo_c4shape.npz")
-    from tests.test_agent_gpu import make_agent
-    res = {}
-    for mode in ("0", "3"):
-        monkeypatch.setenv("ERL_FUSED_TAIL", mode)
-        agent, _ = make_agent(g)
-        agent.last_state = th.from_numpy(g["last_state"]).to(dev)
-        buf = [th.from_numpy(g[k]).to(dev) for k in ("states", "actions", "logprobs", "rewards", "undones", "unmasks")]
-        ids = th.from_numpy(np.concatenate([g["ids"]] * 3)).to(dev)
-        agent.repeat_times = ids.shape[0] * agent.batch_size / buf[0].shape[0]
-        objs = agent.update_net(buf, ids=ids)
-        res[mode] = (agent._flat.clone(), agent._exp_avg.clone(), agent._exp_avg_sq.clone(), agent._grads[:ids.shape[0]].clone(), objs)
-    monkeypatch.delenv("ERL_FUSED_TAIL")
-    for a, b in zip(res["0"][:4], res["3"][:4]):
-        assert th.equal(a, b)
-    assert res["0"][4] == res["3"][4]
+def test_single_launch_tail_refuses_a_row_too_long(ops):
+    """a row too long for tail_fused_kernel's two chunks per thread is refused by erl_tail_fused_ok"""
     assert not ops.tail_fused_ok(64 * 2049) and ops.tail_fused_ok(64 * 2048)
 
 

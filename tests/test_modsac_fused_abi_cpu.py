@@ -12,7 +12,7 @@ NAMES = ("erl_sac_mod_fused_supported", "erl_sac_update_mod_f32", "erl_sac_updat
 def test_the_four_symbols_and_abi_22():
     from elegantrl_amd import _hip
     txt = open(os.path.join(ROOT, "include", "erl_hip.h")).read()
-    assert int(re.search(r"#define ERL_ABI_VERSION (\d+)", txt).group(1)) == _hip.ABI_VERSION == _hip.lib().erl_abi_version() == 22
+    assert int(re.search(r"#define ERL_ABI_VERSION (\d+)", txt).group(1)) == _hip.ABI_VERSION == _hip.lib().erl_abi_version() == 23
     raw = ctypes.CDLL(_hip.LIB_PATH)
     for name in NAMES:
         assert name in _hip.EXPORTED_SYMBOLS and re.search(r"ERL_API int " + name + r"\(", txt), name

@@ -16,7 +16,7 @@ NAMES = ("erl_sac_rollout_mod_supported",) + ROLLOUTS + EVALS + (TILE,)
 def test_the_six_symbols_and_abi_22():
     from elegantrl_amd import _hip
     txt = open(os.path.join(ROOT, "include", "erl_hip.h")).read()
-    assert int(re.search(r"#define ERL_ABI_VERSION (\d+)", txt).group(1)) == _hip.ABI_VERSION == _hip.lib().erl_abi_version() == 22
+    assert int(re.search(r"#define ERL_ABI_VERSION (\d+)", txt).group(1)) == _hip.ABI_VERSION == _hip.lib().erl_abi_version() == 23
     raw = ctypes.CDLL(_hip.LIB_PATH)
     assert len(NAMES) == 6
     for name in NAMES:

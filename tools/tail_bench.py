@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""The optimiser tail at config 4 (128 slabs x 50 837 floats): erl_grad_reduce_f32 + erl_clip_adam_f32 against the one-launch
-erl_reduce_clip_adam_f32, HIP-event timed back to back (each variant also behind a K6-sized dirty-L2 producer is what bench.py sees)."""
+"""The optimiser tail at config 4 (128 slabs x 50 837 floats): erl_grad_reduce_f32 + erl_clip_adam_f32 against the partial-norm tail,
+HIP-event timed back to back (each variant also behind a K6-sized dirty-L2 producer is what bench.py sees).  The round-2 one-launch
+tails this file once timed next to them are deleted: profiles/r02_tail_bench.txt keeps their figures."""
 import os
 import sys
 
@@ -43,8 +44,6 @@ def two():
 print(f"grad_reduce            {timeit(lambda: ops.grad_reduce(slabs, n_slabs, stride, f)):7.2f} us")
 print(f"clip_adam              {timeit(lambda: ops.clip_adam(p, f, m, v, groups, 5, 1e-4, 3.0)):7.2f} us")
 print(f"grad_reduce+clip_adam  {timeit(two):7.2f} us")
-print(f"reduce_clip_adam       {timeit(lambda: ops.reduce_clip_adam(slabs, n_slabs, stride, f, p, m, v, groups, 5, 1e-4, 3.0)):7.2f} us")
-print(f"reduce_clip_adam(grid) {timeit(lambda: ops.reduce_clip_adam(slabs, n_slabs, stride, f, p, m, v, groups, 5, 1e-4, 3.0, grid_wait=True)):7.2f} us")
 
 
 def partials():
