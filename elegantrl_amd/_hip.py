@@ -144,6 +144,10 @@ _SIGNATURES = {
     "erl_sac_update_mod_ring_f32": (c_int, _SAC_HEAD + [_P] + _SAC_BATCH + [c_int64] + _SAC_NOISE + _SAC_HYPER + [c_int32] * 3 + [_P, _P] + _SAC_TAIL),
     "erl_sac_update_mod_ring_loop_f32": (c_int, _SAC_HEAD + [_P, _P, c_int64] + _SAC_BATCH + [c_int64] + _SAC_KEY + _SAC_HYPER +
                                                 [c_int32, c_int32, c_double, _P, _P, POINTER(c_int32)] + _SAC_TAIL),
+    "erl_sac_update_mod_per_loop_f32": (c_int, _SAC_HEAD + [_P, _P, c_int64] + _SAC_BATCH + [c_int64] + _SAC_KEY + _SAC_HYPER +
+                                               [c_int32, c_int32, c_double, _P, _P, POINTER(c_int32), c_int32] + _SAC_TAIL),
+    "erl_sac_update_per_draw_loop_f32": (c_int, _SAC_HEAD + [_P, _P, c_int64] + _SAC_BATCH + [c_int64] + _SAC_KEY + _SAC_HYPER + [c_int32, _P] +
+                                                _SAC_TAIL),
     "erl_sac_explore_action_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, c_int64, _P, c_uint64, c_uint64, _P, _P, _P,
                                            c_int64, _P]),
     "erl_sac_explore_action_opt_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, c_int64, _P, c_uint64, c_uint64, _P, _P, _P,

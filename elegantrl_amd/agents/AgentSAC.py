@@ -165,6 +165,11 @@ class AgentSAC(AgentBase):
         # step, bit-identical to the per-step calls on the same uniforms); `args.per_loop_in_c = False` / ERL_SAC_PER_LOOP_IN_C=0 keeps
         # _per_step's six host-driven calls per step
         self.per_loop_in_c = bool(getattr(args, "per_loop_in_c", os.environ.get("ERL_SAC_PER_LOOP_IN_C", "1") != "0"))
+        # the prioritised loop's draw + gather inside every step's first launch (erl_sac_update_per_draw_loop_f32, AgentModSAC:
+        # erl_sac_update_mod_per_loop_f32 with draw_in_step) instead of one erl_per_sample_rows_f32 launch per step: bit-identical, fused step
+        # only; opt-in -- args.per_draw_in_step = True or ERL_SAC_PER_DRAW_IN_STEP=1 -- until profiles/sac_per_loop_ab.txt shows the win
+        # DESIGN.md section 9 asks of a default
+        self.per_draw_in_step = bool(getattr(args, "per_draw_in_step", os.environ.get("ERL_SAC_PER_DRAW_IN_STEP", "0") != "0"))
         self.per_path = None                       # which route the last prioritised update_net took (None: none yet / not prioritised)
         self.update_path = None                    # which route the last update_net took: "one C call ..." / "per step: <reason>"
         self.rollout_path = None                   # which route the last _explore_vec_env took: "one launch ..." / "per-step loop ...: <reason>"
@@ -354,6 +359,10 @@ class AgentSAC(AgentBase):
         """`kernel_path` of an agent whose actor is not ActorSAC"""
         return self.kernel_path
 
+    def _variant_per_loop_reason(self) -> Optional[str]:
+        """why this agent class keeps a prioritised update_net on _per_step whatever the buffer offers (None: it does not)"""
+        return None
+
     def _ring_step_reason(self) -> Optional[str]:
         """None when this agent's step takes the replay sample inside its first launch (the ring forms), else why not"""
         return "ActorFixSAC / two-time-scale options take the layered step, which reads a finished batch" if self._actor_variant else None
@@ -378,17 +387,38 @@ class AgentSAC(AgentBase):
         from .. import ops
         p_ring, trees, cur_size, cursor, per_alpha, per_beta, stage, per_stage = per
         update_times = objs.shape[0]
-        shape = (update_times, buffer.num_seqs, self.batch_size // buffer.num_seqs)
-        if per_uniform is None:
-            per_uniform = th.rand(shape, dtype=th.float32, device=self.device)
-        assert per_uniform.shape == shape
-        ops.sac_update_per_loop(*self._nets(), p_ring, trees, per_uniform.contiguous(), cur_size, cursor, per_alpha, per_beta, stage, per_stage,
-                                self._step + 1, **self._hyper(), objs_all=objs, seed=self.rng_seed + 1, counter0=self._step + 1)
+        per_uniform = self._per_uniforms(buffer, update_times, per_uniform)
+        draw_why = self._per_draw_reason() if self.per_draw_in_step else "args.per_draw_in_step is off"
+        loop = ops.sac_update_per_loop if draw_why else ops.sac_update_per_draw_loop
+        loop(*self._nets(), p_ring, trees, per_uniform, cur_size, cursor, per_alpha, per_beta, stage, per_stage, self._step + 1, **self._hyper(),
+             objs_all=objs, seed=self.rng_seed + 1, counter0=self._step + 1)
         self._step += update_times
         buffer.ids0, buffer.ids1 = stage.ids
         self._td_error = per_stage.td_error
         self._set_step_counts()
-        return "prioritised update loop in one C call (erl_sac_update_per_loop_f32: draw + gather, step, tree update per step)"
+        if draw_why is None:
+            return ("prioritised update loop in one C call (erl_sac_update_per_draw_loop_f32: draw + gather inside the step's first launch, "
+                    "tree update behind every step)")
+        return ("prioritised update loop in one C call (erl_sac_update_per_loop_f32: draw + gather, step, tree update per step)" +
+                (f"; args.per_draw_in_step ignored: {draw_why}" if self.per_draw_in_step else ""))
+
+    def _per_uniforms(self, buffer, update_times: int, per_uniform: Optional[TEN]) -> TEN:
+        """the prioritised sampler's uniforms of a whole loop, (update_times, num_seqs, batch_size // num_seqs), drawn here unless injected"""
+        shape = (update_times, buffer.num_seqs, self.batch_size // buffer.num_seqs)
+        if per_uniform is None:
+            per_uniform = th.rand(shape, dtype=th.float32, device=self.device)
+        assert per_uniform.shape == shape
+        return per_uniform.contiguous()
+
+    def _per_draw_reason(self) -> Optional[str]:
+        """None when the prioritised loop's step is the fused one, whose first launch can draw and gather, else why it cannot"""
+        from .. import ops
+        if os.environ.get("ERL_SAC_FUSED", "1") == "0":
+            return "ERL_SAC_FUSED=0: the layered step reads a finished batch (the stand-alone draw runs)"
+        if not ops.sac_mod_fused_supported(self._spec, int(self.batch_size)):
+            return (f"net_dims {list(self.net_dims)}, batch {int(self.batch_size)} take the layered step, which reads a finished batch (the "
+                    "stand-alone draw runs)")
+        return None
 
     def _update_on_batch(self, batch, objs_out: TEN, noises=None, is_weight=None, td_error_out=None, buffer=None, update_t: int = 0):
         from .. import ops
@@ -433,8 +463,9 @@ class AgentSAC(AgentBase):
             return "args.update_loop_in_c is off"
         if self.lambda_fit_cum_r:
             return "lambda_fit_cum_r needs ids0 / ids1 on the host side of every step"
-        if self._actor_variant:
-            return "ActorFixSAC / two-time-scale options (AgentModSAC) are decided per step by the host"
+        why = self._variant_per_loop_reason()
+        if why is not None:
+            return why
         if not getattr(buffer, "per_for_fused_loop", None):
             return f"{type(buffer).__name__} has no per_for_fused_loop"
         return None
@@ -505,7 +536,9 @@ class AgentModSAC(AgentSAC):
     `critic_value` off 1.0, so this is 0.61: the actor skips roughly every third step).  The step is erl_sac_update_opt_f32 (csrc/sac.hip,
     layered path; ErlSacOptions carries what differs from AgentSAC) or, with `fused_step` on and inside the fused step's shapes,
     erl_sac_update_mod_f32 (csrc/sac_fused.hip: AgentSAC's tile kernels with ActorFixSAC as a run-time variant); update_net's loop on the
-    fused step is one erl_sac_update_mod_ring_loop_f32 call.  With `fused_mod_rollout` on and inside the same shapes, `explore_action` is the
+    fused step is one erl_sac_update_mod_ring_loop_f32 call; with prioritised replay (`if_use_per`, the reference's own PER demo) it is
+    AgentSAC._per_step per step unless `mod_per_loop_in_c` is on, then one erl_sac_update_mod_per_loop_f32 call (fused step only; with
+    `per_draw_in_step` the draw and the gather ride in every step's first launch); `per_path` names the route.  With `fused_mod_rollout` on and inside the same shapes, `explore_action` is the
     tile kernel (erl_sac_explore_action_tile_f32) and, on SynVecEnv / PendulumVecEnv with `fused_rollout`, `explore_env` and `evaluate_env` are
     one launch each (erl_sac_rollout_mod_*, erl_sac_eval_mod_*: csrc/sac_fused.hip sac_rollout_synenv_kernel<.., FIX>); `rollout_path` names
     the route the last rollout took."""
@@ -532,6 +565,10 @@ class AgentModSAC(AgentSAC):
         self.act_target = deepcopy(self._act)
         self._bind_at = FlatNet(self.act_target, _Slices(self._spec.actor_slices()), self._actor_target_flat)
         self._last_actor_updated = True
+        # a prioritised update_net as ONE C call (erl_sac_update_mod_per_loop_f32: the prioritised loop and the two-time-scale rule together,
+        # bit-identical to _per_step on the fused step): opt-in -- args.mod_per_loop_in_c = True or ERL_SAC_MOD_PER_LOOP_IN_C=1 -- until
+        # profiles/sac_per_loop_ab.txt shows the win DESIGN.md section 9 asks of a default; it needs the fused step (there is no layered form)
+        self.mod_per_loop_in_c = bool(getattr(args, "mod_per_loop_in_c", os.environ.get("ERL_SAC_MOD_PER_LOOP_IN_C", "0") != "0"))
 
     def _sync_modules(self):
         super()._sync_modules()
@@ -589,17 +626,49 @@ class AgentModSAC(AgentSAC):
         n_upd = ops.sac_update_mod_ring_loop(*self._nets(), arrays, id_all, sample_len, stage, self._step + 1, self._actor_step,
                                              float(self.critic_value), **self._hyper(), objs_all=objs, actor_target=self._actor_target_flat,
                                              seed=self.rng_seed + 1, counter0=self._step + 1)
+        self._count_loop(T, n_upd)
+        buffer.ids0, buffer.ids1 = stage.ids
+        self._set_step_counts()
+        return "one C call (erl_sac_update_mod_ring_loop_f32: the sample inside every step's first launch, the two-time-scale rule in C)"
+
+    def _count_loop(self, T: int, n_upd: int):
+        """the counters after a T-step loop in C that updated the actor n_upd times: the rule re-derived here as _step_options applies it
+        per step (the last step's flag; the count must be the library's)"""
         bound, ua, do = 1 / (2 - math.exp(-self.critic_value ** 2)), 0, True
-        for t in range(T):                                      # (the last step's flag; the count must be the library's)
+        for t in range(T):
             do = (ua / (t + 1)) < bound
             ua += do
         assert ua == n_upd, (ua, n_upd)
         self.update_a, self._last_actor_updated = n_upd, bool(do)
         self._actor_step += n_upd
         self._step += T
+
+    def _variant_per_loop_reason(self) -> Optional[str]:
+        if not self.mod_per_loop_in_c:
+            return ("ActorFixSAC / two-time-scale options (AgentModSAC) are decided per step by the host unless args.mod_per_loop_in_c is on "
+                    "(ERL_SAC_MOD_PER_LOOP_IN_C; profiles/sac_per_loop_ab.txt)")
+        why = self._fused_step_reason()
+        return None if why is None else "AgentModSAC's prioritised loop (erl_sac_update_mod_per_loop_f32) has no layered form: " + why
+
+    def _update_per_loop(self, buffer, per, objs: TEN, per_uniform: Optional[TEN]) -> str:
+        """the prioritised loop from ONE C call (erl_sac_update_mod_per_loop_f32): step t = what _per_step enqueues on uniforms[t] with
+        _step_options(t), the trees updated behind skipped actor steps too; afterwards the counters are what the per-step route leaves"""
+        from .. import ops
+        p_ring, trees, cur_size, cursor, per_alpha, per_beta, stage, per_stage = per
+        T = objs.shape[0]
+        per_uniform = self._per_uniforms(buffer, T, per_uniform)
+        draw = self.per_draw_in_step                            # (the step here is the fused one: _variant_per_loop_reason)
+        n_upd = ops.sac_update_mod_per_loop(*self._nets(), p_ring, trees, per_uniform, cur_size, cursor, per_alpha, per_beta, stage, per_stage,
+                                            self._step + 1, self._actor_step, float(self.critic_value), **self._hyper(), objs_all=objs,
+                                            actor_target=self._actor_target_flat, draw_in_step=draw, seed=self.rng_seed + 1,
+                                            counter0=self._step + 1)
+        self._count_loop(T, n_upd)
         buffer.ids0, buffer.ids1 = stage.ids
+        self._td_error = per_stage.td_error
         self._set_step_counts()
-        return "one C call (erl_sac_update_mod_ring_loop_f32: the sample inside every step's first launch, the two-time-scale rule in C)"
+        return ("prioritised update loop in one C call (erl_sac_update_mod_per_loop_f32: " +
+                ("draw + gather inside the step's first launch" if draw else "draw + gather, step") +
+                ", tree update behind every step, the two-time-scale rule in C)")
 
     def _update_from_ring(self, buffer, ring, ids: TEN, objs_out: TEN, noises=None, update_t: int = 0):
         from .. import ops

@@ -100,6 +100,17 @@ struct SacCall {
     float lambda_fit_cum_r;
     bool fused_only;                      // the erl_sac_update_mod_* entries: the fused step or a refusal
 };
+// prioritised replay's draw inside the fused step's first launch (sac_fused.hip ActorFwdArgs::per; per_draw.h): the trees with their leaf
+// count, the ring's fill state as erl_per_sample_rows_f32 derives it, this step's uniforms (num_seqs, n_per_seq), and where the draw's
+// indices and importance weights go.  The ring itself is SacStep::ring (interleaved; its ids and sample_len are not read).
+struct SacPerDraw {
+    const float *sum_tree, *min_tree;     // sum_tree NULL: no draw (the ring's ids name the rows)
+    int64_t leaves, n_per_seq, cur_size, newest;
+    float beta;
+    const float *uniform;
+    int64_t *is_index;
+    float *is_weight;
+};
 // what changes from step to step
 struct SacStep {
     const ErlRingSample *ring;            // not NULL: the replay sample is part of the step
@@ -111,6 +122,7 @@ struct SacStep {
     bool update_actor;                    // false: AgentModSAC's two-time-scale rule skips the actor this step
     int32_t actor_step;                   // the actor optimiser's own Adam step (read when update_actor)
     float *objs_out;
+    const SacPerDraw *per;                // not NULL (with `ring`, fused step only): the step's first launch draws its rows from the trees
 };
 int erl_sac_step_fused(const SacCall &c, const SacDims &d, const SacStep &st);
 

@@ -8,6 +8,7 @@
 // resolved deterministically (highest list index wins, as numpy's assignment in the oracle) -- bit-exact against
 // oracle/per_numpy.py, which also lists how this corrected restatement deviates from the reference's (non-working) SumTree.
 #include "erl_common.h"
+#include "per_draw.h"        // per_draw: the one arithmetic of a draw, shared with the fused SAC step
 
 namespace {
 
@@ -156,29 +157,6 @@ __global__ __launch_bounds__(256) void per_init_kernel(float *__restrict__ sum, 
         sum[i] = 0.f;
         mn[i] = __builtin_inff();
     }
-}
-
-// one stratified draw of sequence q (stratum j of n, `u` its uniform): proportional prioritisation (:285-298) by a full-depth descent,
-// then the two row moves; returns the time row and its importance weight.  Shared by both sampling kernels: one arithmetic.
-__device__ __forceinline__ int64_t per_draw(const float *__restrict__ sum, const float *__restrict__ mn, int64_t L, int64_t base, int64_t n,
-                                            int64_t j, float u, int64_t cur_size, int64_t newest, float beta, float &weight)
-{
-    const float total = sum[base + 1];
-    float v = ((float)j + u) * (total / (float)n);                      // (arange(n) + rand(n)) * (tree[0] / n)   (:287)
-    int64_t node = 1;
-    while (node < L) {
-        const float left = sum[base + 2 * node];
-        if (v <= left) node = 2 * node;
-        else {
-            v -= left;
-            node = 2 * node + 1;
-        }
-    }
-    int64_t row = node - L;
-    if (row > cur_size - 2) row = cur_size - 2;                        // the last filled position has no successor row (oracle D4)
-    if (row == newest) row = newest >= 1 ? newest - 1 : 1;             // full ring: the newest row's successor slot holds the OLDEST data (D6)
-    weight = powf(sum[base + L + row] / mn[base + 1], -beta);           // (prob / min prob)^(-beta)   (:296-297)
-    return row;
 }
 
 // one thread per sample
@@ -354,9 +332,7 @@ extern "C" int erl_per_sample_f32(const float *sum_tree, const float *min_tree, 
                 "erl_per_sample_f32: bad argument (cur_size=%lld max_size=%lld cursor=%lld)", (long long)cur_size, (long long)max_size,
                 (long long)cursor);
     const int64_t L = per_leaves(max_size);
-    // the ring's write cursor `p` when the ring is full (cursor < 0: not full / unknown): the newest row (p - 1) is followed in
-    // memory by the oldest one, so it has no valid successor either
-    const int64_t newest = (cursor >= 0 && cur_size == max_size && max_size >= 3) ? (cursor + max_size - 1) % max_size : -1;
+    const int64_t newest = per_newest(cursor, cur_size, max_size);
     hipLaunchKernelGGL(per_sample_kernel, dim3((unsigned)erl_cdiv(num_seqs * n_per_seq, 256)), dim3(256), 0, (hipStream_t)stream, sum_tree,
                        min_tree, L, (int)num_seqs, uniform, n_per_seq, cur_size, newest, per_beta, out_index, out_weight);
     ERL_LAUNCH_CHECK("erl_per_sample_f32");
@@ -378,7 +354,7 @@ extern "C" int erl_per_sample_rows_f32(const float *sum_tree, const float *min_t
                 "erl_per_sample_rows_f32: bad argument (cur_size=%lld max_size=%lld cursor=%lld num_seqs=%lld n_per_seq=%lld)", (long long)cur_size,
                 (long long)max_size, (long long)cursor, (long long)num_seqs, (long long)n_per_seq);
     const int64_t L = per_leaves(max_size), B = num_seqs * n_per_seq;
-    const int64_t newest = (cursor >= 0 && cur_size == max_size && max_size >= 3) ? (cursor + max_size - 1) % max_size : -1;   // (erl_per_sample_f32)
+    const int64_t newest = per_newest(cursor, cur_size, max_size);
     // draws per wave and trip: what fills the wave's 64 lanes with one 16-byte chunk each, so that a small batch (the SAC step's 256 rows)
     // is one round trip after its walks; more for large batches, up to one draw per lane
     const int RW = (int)row_floats, CW = RW / 4 + (S + 3) / 4;

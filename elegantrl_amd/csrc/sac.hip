@@ -16,6 +16,7 @@
 
 #include "mlpn_common.h"
 #include "eval_ws.h"
+#include "per_draw.h"        // per_newest: the fill state a draw inside the step needs, as erl_per_sample_rows_f32 derives it
 
 extern "C" int erl_clip_adam_f32(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, const int64_t *group_off,
                                  const int64_t *group_len, int n_groups, const int32_t *step_base, int32_t step_offset, float lr,
@@ -602,6 +603,7 @@ struct SacLoop {
     bool two_time_scale;                  // AgentModSAC: the rule decides update_actor per step, the actor's Adam count runs on from st.actor_step
     double critic_value;
     int32_t *actor_updates_out;
+    bool draw_in_step;                    // with `per`, fused step only: the draw + gather ride in the step's first launch (SacStep::per)
 };
 
 // AgentBase.update_net's loop (elegantrl/agents/AgentBase.py:172-189) from ONE call: validated before step 0, then step t counts as optimiser
@@ -620,7 +622,13 @@ int sac_loop(const char *what, const SacCall &c, SacStep st, const SacLoop &lp)
     // is evaluated here, in double precision as the interpreter does
     const double bound = 1.0 / (2.0 - exp(-(lp.critic_value * lp.critic_value)));
     const ErlPerSample *per = lp.per;
-    ErlRingSample r = st.ring ? *st.ring : ErlRingSample{};       // the loop's ring; a step sees it (with its ids) only when it samples by ids
+    ErlRingSample r = st.ring ? *st.ring : ErlRingSample{};       // the loop's ring; a step sees it only when it samples itself (by ids / by its own draw)
+    const bool draw = per && lp.draw_in_step;
+    ERL_REQUIRE(!draw || c.fused_only, "%s: the draw inside the step needs the fused step", what);
+    SacPerDraw pd{};
+    if (draw)
+        pd = SacPerDraw{per->sum_tree, per->min_tree, erl_per_tree_floats(per->max_size, 1) / 2, c.B / per->num_seqs, per->cur_size,
+                        per_newest(per->cursor, per->cur_size, per->max_size), per->per_beta, nullptr, per->is_index, per->is_weight};
     int32_t update_a = 0;
     for (int64_t t = 0; t < lp.n_steps; ++t) {
         if (lp.two_time_scale) {
@@ -629,8 +637,10 @@ int sac_loop(const char *what, const SacCall &c, SacStep st, const SacLoop &lp)
         }
         int rc;
         r.ids = lp.ids_all ? lp.ids_all + t * c.B : nullptr;
-        st.ring = lp.ids_all ? &r : nullptr;
-        if (per && (rc = erl_per_sample_rows_f32(per->sum_tree, per->min_tree, per->max_size, per->num_seqs, per->uniform_all + t * c.B, c.B / per->num_seqs,
+        st.ring = lp.ids_all || draw ? &r : nullptr;
+        pd.uniform = draw ? per->uniform_all + t * c.B : nullptr;
+        st.per = draw ? &pd : nullptr;
+        if (per && !draw && (rc = erl_per_sample_rows_f32(per->sum_tree, per->min_tree, per->max_size, per->num_seqs, per->uniform_all + t * c.B, c.B / per->num_seqs,
                                                  per->cur_size, per->cursor, per->per_beta, r.buf_states, c.S, c.A, r.row_floats, per->is_index,
                                                  per->is_weight, const_cast<float *>(c.state), const_cast<float *>(c.action),
                                                  const_cast<float *>(c.reward), const_cast<float *>(c.undone), const_cast<float *>(c.unmask),
@@ -646,6 +656,30 @@ int sac_loop(const char *what, const SacCall &c, SacStep st, const SacLoop &lp)
         if (!lp.two_time_scale) st.actor_step = st.step;
     }
     if (lp.actor_updates_out) *lp.actor_updates_out = update_a;
+    return ERL_OK;
+}
+
+// what every prioritised loop refuses about its ring, trees, fill state and batch, before its first launch, under the entry's own name
+int per_loop_refusals(const char *what, const ErlRingSample *ring, const ErlPerSample *per, const float *objs_all, int64_t n_steps, int32_t step0,
+                      int S, int A, int64_t B)
+{
+    ERL_REQUIRE(ring && per && objs_all, "%s: NULL argument", what);
+    ERL_REQUIRE(per->sum_tree && per->min_tree, "%s: NULL trees", what);
+    ERL_REQUIRE(ring->buf_states && per->uniform_all && per->is_index && per->is_weight && per->td_error,
+                "%s: NULL ring / sampler tensor", what);
+    ERL_REQUIRE(n_steps >= 1 && step0 >= 1, "%s: n_steps=%lld step0=%d", what, (long long)n_steps, (int)step0);
+    ERL_REQUIRE(ring->row_floats > 0 && ring->row_floats == erl_replay_row_floats(S, A) && (reinterpret_cast<uintptr_t>(ring->buf_states) & 15) == 0,
+                "%s: row_floats=%lld: the interleaved ring only (erl_replay_row_floats = %lld, 16-byte aligned)", what,
+                (long long)ring->row_floats, (long long)erl_replay_row_floats(S, A));
+    ERL_REQUIRE(per->max_size >= 2 && per->max_size <= (1LL << 30) && per->num_seqs >= 1 && per->num_seqs < (1 << 30) &&
+                    ring->max_size == per->max_size && ring->num_seqs == per->num_seqs,
+                "%s: ring (max_size=%lld num_seqs=%lld) and trees (max_size=%lld num_seqs=%lld) do not match", what,
+                (long long)ring->max_size, (long long)ring->num_seqs, (long long)per->max_size, (long long)per->num_seqs);
+    ERL_REQUIRE(per->cur_size >= 2 && per->cur_size <= per->max_size && per->cursor <= per->max_size,
+                "%s: cur_size=%lld cursor=%lld max_size=%lld", what, (long long)per->cur_size, (long long)per->cursor,
+                (long long)per->max_size);
+    ERL_REQUIRE(B >= 1 && B < (1LL << 24) && B % per->num_seqs == 0,
+                "%s: batch %lld must be num_seqs=%lld x n_per_seq, n_per_seq >= 1", what, (long long)B, (long long)per->num_seqs);
     return ERL_OK;
 }
 
@@ -736,23 +770,7 @@ extern "C" int erl_sac_update_per_loop_f32(float *actor_params, float *critic_pa
                                            float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step0,
                                            float *objs_all, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    ERL_REQUIRE(ring && per && objs_all, "erl_sac_update_per_loop_f32: NULL argument");
-    ERL_REQUIRE(per->sum_tree && per->min_tree, "erl_sac_update_per_loop_f32: NULL trees");
-    ERL_REQUIRE(ring->buf_states && per->uniform_all && per->is_index && per->is_weight && per->td_error,
-                "erl_sac_update_per_loop_f32: NULL ring / sampler tensor");
-    ERL_REQUIRE(n_steps >= 1 && step0 >= 1, "erl_sac_update_per_loop_f32: n_steps=%lld step0=%d", (long long)n_steps, (int)step0);
-    ERL_REQUIRE(ring->row_floats > 0 && ring->row_floats == erl_replay_row_floats(S, A) && (reinterpret_cast<uintptr_t>(ring->buf_states) & 15) == 0,
-                "erl_sac_update_per_loop_f32: row_floats=%lld: the interleaved ring only (erl_replay_row_floats = %lld, 16-byte aligned)",
-                (long long)ring->row_floats, (long long)erl_replay_row_floats(S, A));
-    ERL_REQUIRE(per->max_size >= 2 && per->max_size <= (1LL << 30) && per->num_seqs >= 1 && per->num_seqs < (1 << 30) &&
-                    ring->max_size == per->max_size && ring->num_seqs == per->num_seqs,
-                "erl_sac_update_per_loop_f32: ring (max_size=%lld num_seqs=%lld) and trees (max_size=%lld num_seqs=%lld) do not match",
-                (long long)ring->max_size, (long long)ring->num_seqs, (long long)per->max_size, (long long)per->num_seqs);
-    ERL_REQUIRE(per->cur_size >= 2 && per->cur_size <= per->max_size && per->cursor <= per->max_size,
-                "erl_sac_update_per_loop_f32: cur_size=%lld cursor=%lld max_size=%lld", (long long)per->cur_size, (long long)per->cursor,
-                (long long)per->max_size);
-    ERL_REQUIRE(B >= 1 && B < (1LL << 24) && B % per->num_seqs == 0,
-                "erl_sac_update_per_loop_f32: batch %lld must be num_seqs=%lld x n_per_seq, n_per_seq >= 1", (long long)B, (long long)per->num_seqs);
+    if (int rc = per_loop_refusals("erl_sac_update_per_loop_f32", ring, per, objs_all, n_steps, step0, S, A, B)) return rc;
     const SacCall c = SAC_CALL(ERL_SAC_ACTOR_SAC, nullptr, nullptr, 0.f, false);
     return sac_loop("erl_sac_update_per_loop_f32", c, SacStep{ring, per->is_weight, per->td_error, nullptr, nullptr, counter0, step0, true, step0, objs_all},
                     SacLoop{n_steps, nullptr, per, false, 0.0, nullptr});
@@ -807,6 +825,45 @@ extern "C" int erl_sac_update_mod_ring_loop_f32(float *actor_params, float *crit
     const SacCall c = SAC_CALL(ERL_SAC_ACTOR_FIX, actor_target_params, nullptr, 0.f, true);
     return sac_loop("erl_sac_update_mod_ring_loop_f32", c, SacStep{ring, nullptr, nullptr, nullptr, nullptr, counter0, step0, false, actor_step0, objs_all},
                     SacLoop{n_steps, ids_all, nullptr, true, critic_value, actor_updates_out});
+}
+
+// The prioritised loop for AgentModSAC (the reference's own PER demo trains it): sac_loop with both options -- erl_sac_update_per_loop_f32's
+// refusals and per-step order, erl_sac_update_mod_ring_loop_f32's two-time-scale rule and counts.  The tree update follows every step, a
+// skipped actor step included (its td errors come from the critic).  draw_in_step = 1: no erl_per_sample_rows_f32 launch, the step's first
+// launch draws and gathers (sac_fused.hip ActorFwdArgs::per).
+extern "C" int erl_sac_update_mod_per_loop_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
+                                               float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
+                                               const int *hidden, int n_hidden, int E, const ErlRingSample *ring, const ErlPerSample *per,
+                                               int64_t n_steps, float *state, float *action, float *reward, float *undone, float *unmask,
+                                               float *next_state, int64_t B, uint64_t seed, uint64_t counter0, float gamma, float target_entropy,
+                                               float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step0,
+                                               int32_t actor_step0, double critic_value, float *actor_target_params, float *objs_all,
+                                               int32_t *actor_updates_out, int32_t draw_in_step, void *workspace, int64_t workspace_bytes,
+                                               void *stream)
+{
+    const char *const what = "erl_sac_update_mod_per_loop_f32";
+    ERL_REQUIRE(draw_in_step == 0 || draw_in_step == 1, "%s: draw_in_step=%d (0: erl_per_sample_rows_f32 per step, 1: inside the step)", what,
+                (int)draw_in_step);
+    if (int rc = per_loop_refusals(what, ring, per, objs_all, n_steps, step0, S, A, B)) return rc;
+    const SacCall c = SAC_CALL(ERL_SAC_ACTOR_FIX, actor_target_params, nullptr, 0.f, true);
+    return sac_loop(what, c, SacStep{ring, per->is_weight, per->td_error, nullptr, nullptr, counter0, step0, false, actor_step0, objs_all},
+                    SacLoop{n_steps, nullptr, per, true, critic_value, actor_updates_out, draw_in_step != 0});
+}
+
+// erl_sac_update_per_loop_f32 with the draw + gather inside every step's first launch: fused step only (a shape outside it is refused)
+extern "C" int erl_sac_update_per_draw_loop_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
+                                                float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
+                                                const int *hidden, int n_hidden, int E, const ErlRingSample *ring, const ErlPerSample *per,
+                                                int64_t n_steps, float *state, float *action, float *reward, float *undone, float *unmask,
+                                                float *next_state, int64_t B, uint64_t seed, uint64_t counter0, float gamma, float target_entropy,
+                                                float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step0,
+                                                float *objs_all, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const char *const what = "erl_sac_update_per_draw_loop_f32";
+    if (int rc = per_loop_refusals(what, ring, per, objs_all, n_steps, step0, S, A, B)) return rc;
+    const SacCall c = SAC_CALL(ERL_SAC_ACTOR_SAC, nullptr, nullptr, 0.f, true);
+    return sac_loop(what, c, SacStep{ring, per->is_weight, per->td_error, nullptr, nullptr, counter0, step0, true, step0, objs_all},
+                    SacLoop{n_steps, nullptr, per, false, 0.0, nullptr, true});
 }
 #undef SAC_CALL
 

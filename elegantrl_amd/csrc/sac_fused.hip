@@ -41,6 +41,7 @@
 // rule skips -- one small launch (sac_skip_finish_kernel) in place of launches (7)-(10).  Its rollout and evaluation are the FIX forms of the
 // persistent rollout (a template parameter there: sac_rollout_synenv_kernel).
 #include "mlpn_common.h"
+#include "per_draw.h"
 
 #include <mutex>
 
@@ -422,9 +423,16 @@ struct ActorFwdArgs {
     // is clamped to [-20, 2], the log-prob is taken AT the sample with the tanh correction in its softplus form.  A run-time,
     // wavefront-uniform value: the kernels are not instantiated per variant.
     int variant;
+    // Prioritised replay: per.sum_tree != NULL (with rg the interleaved ring; rg.ids is not read) makes the tile DRAW its 16 rows from the
+    // trees (per_draw.h: the arithmetic of per_sample_rows_kernel) where it would decode them from rg.ids; the slice-0 workgroup that copies
+    // the batch out also writes is_index = q cur_size + row, is_weight, ids0, ids1.  Every other slice and the rg_self half repeat the same
+    // deterministic draws and write nothing.  The trees are read-only for the whole launch (the tree update of the step before sits earlier
+    // on the stream): no wait between workgroups is added.
+    // The form is a template parameter of the kernels (PER): the other instantiations are the code they were.
+    SacPerDraw per;
 };
 
-template <int C0, int C1>
+template <int C0, int C1, bool PER = false>
 __device__ __forceinline__ void actor_fwd_body(const ActorFwdArgs &g, TileLds &lds, const int bx, const int by)
 {
     const LaneId L = lane_id();
@@ -444,7 +452,23 @@ __device__ __forceinline__ void actor_fwd_body(const ActorFwdArgs &g, TileLds &l
     layer_small_load<false, true>(g.P + d.aWh + fo, d.h1, 2 * d.A, h1f, 0, L, wh);
     clear_images(lds.T0, lds.T1, L);
     __shared__ int64_t s_row[TS];
-    if (g.rg.ids && L.tid < TS) {                          // ids0 = ids % L, ids1 = ids // L  (replay_buffer.py:124-125)
+    const bool from_ring = PER || g.rg.ids;
+    if (PER) {
+        if (L.tid < TS) {                                  // sample_for_per's draw (replay_buffer.py:136-165), behind the weight requests
+            const int64_t b = row0 + L.tid;
+            const uint32_t i = (uint32_t)min(b, d.B - 1), n32 = (uint32_t)g.per.n_per_seq, q = i / n32, j = i - q * n32;   // (B <= 4096)
+            float w;
+            const int64_t t = per_draw(g.per.sum_tree, g.per.min_tree, g.per.leaves, (int64_t)q * 2 * g.per.leaves, g.per.n_per_seq, j,
+                                       g.per.uniform[i], g.per.cur_size, g.per.newest, g.per.beta, w);
+            s_row[L.tid] = (int64_t)q * g.rg.max_size + t;  // t <= cur_size - 2 <= max_size - 2: the row and its successor lie in sequence q
+            if (by == 0 && b < d.B && !g.rg_self) {
+                g.per.is_index[b] = (int64_t)q * g.per.cur_size + t;
+                g.per.is_weight[b] = w;
+                if (g.rg.out_ids0) g.rg.out_ids0[b] = t;
+                if (g.rg.out_ids1) g.rg.out_ids1[b] = q;
+            }
+        }
+    } else if (g.rg.ids && L.tid < TS) {                   // ids0 = ids % L, ids1 = ids // L  (replay_buffer.py:124-125)
         const int64_t b = row0 + L.tid, id = g.rg.ids[min(b, d.B - 1)];
         int64_t n, t;                                       // (a 64-bit divide is ~10x the instructions of a 32-bit one, on the tile's critical path)
         if ((uint64_t)id <= 0x7fffffffull && (uint64_t)g.rg.sample_len <= 0x7fffffffull) {
@@ -461,7 +485,7 @@ __device__ __forceinline__ void actor_fwd_body(const ActorFwdArgs &g, TileLds &l
     }
     lds_barrier();
     FPROF(0, 1);
-    if (g.rg.ids) {
+    if (from_ring) {
         const int S = d.S, A = d.A, CP = ((S + 15) >> 4) << 4;
         for (int e = L.tid; e < TS * CP; e += FT) {        // the next-state rows: the first layer's input image (+ the batch's copy)
             const int s_ = e / CP, c = e - s_ * CP;
@@ -592,21 +616,22 @@ __device__ __forceinline__ void actor_fwd_body(const ActorFwdArgs &g, TileLds &l
     FPROF(0, 8);
 }
 
-template <int C0, int C1>
+template <int C0, int C1, bool PER = false>
 __global__ __launch_bounds__(FT) void actor_fwd_kernel(ActorFwdArgs g)
 {
     __shared__ TileLds lds;
-    actor_fwd_body<C0, C1>(g, lds, (int)blockIdx.x, (int)blockIdx.y);
+    actor_fwd_body<C0, C1, PER>(g, lds, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // Launch (1) -- the actor on the next state -- and the policy-gradient sample's forward as ONE launch, the [256, 256] actor's second layer
 // split over `ay` workgroups per tile in both: rows y < ay of the grid run the first, the rest the second.  The two share nothing (the
 // sample's forward reads its state rows from the ring itself: ActorFwdArgs::rg_self).
+template <bool PER>
 __global__ __launch_bounds__(FT) void actor_fwd_pair_kernel(ActorFwdArgs ga, ActorFwdArgs gb, int ay)
 {
     __shared__ TileLds lds;
-    if ((int)blockIdx.y < ay) actor_fwd_body<2, 0>(ga, lds, (int)blockIdx.x, (int)blockIdx.y);
-    else actor_fwd_body<2, 0>(gb, lds, (int)blockIdx.x, (int)blockIdx.y - ay);
+    if ((int)blockIdx.y < ay) actor_fwd_body<2, 0, PER>(ga, lds, (int)blockIdx.x, (int)blockIdx.y);
+    else actor_fwd_body<2, 0, PER>(gb, lds, (int)blockIdx.x, (int)blockIdx.y - ay);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1705,6 +1730,8 @@ int erl_sac_step_fused(const SacCall &c, const SacDims &sd, const SacStep &st)
     const int32_t step = st.step;
     float *const td_error_out = st.td_error_out, *const objs_out = st.objs_out, *const workspace = (float *)c.workspace;
     const ErlRingSample *const ring = st.ring;
+    ERL_REQUIRE(!st.per || (ring && ring->row_floats > 0 && st.per->sum_tree && st.per->min_tree && st.per->uniform && st.per->is_index && st.per->is_weight),
+                "erl_sac_update_f32(fused): the draw inside the step needs the interleaved ring and the sampler's tensors");
     const hipStream_t s = (hipStream_t)c.stream;
     FusedDims d{};
     d.S = S; d.A = A; d.E = E; d.h0 = h0; d.h1 = h1; d.B = B;
@@ -1734,7 +1761,10 @@ int erl_sac_step_fused(const SacCall &c, const SacDims &sd, const SacStep &st)
     SacSlot *slot = sac_slot(s, nonce, nonce_y);
     auto actor_fwd = [&](const ActorFwdArgs &g, const dim3 &grid) {
 #define LAUNCH_ACTOR_FWD(K0, K1) hipLaunchKernelGGL((actor_fwd_kernel<K0, K1>), grid, blk, 0, s, g)
-        FUSED_KT_DISPATCH_D(g.d, LAUNCH_ACTOR_FWD)
+#define LAUNCH_ACTOR_FWD_PER(K0, K1) hipLaunchKernelGGL((actor_fwd_kernel<K0, K1, true>), grid, blk, 0, s, g)
+        if (g.per.sum_tree) { FUSED_KT_DISPATCH_D(g.d, LAUNCH_ACTOR_FWD_PER) }
+        else { FUSED_KT_DISPATCH_D(g.d, LAUNCH_ACTOR_FWD) }
+#undef LAUNCH_ACTOR_FWD_PER
 #undef LAUNCH_ACTOR_FWD
     };
 
@@ -1745,6 +1775,7 @@ int erl_sac_step_fused(const SacCall &c, const SacDims &sd, const SacStep &st)
     if (ring) {
         // the replay sample rides in this launch: the batch pointers are the staging block it fills (SacStep::ring)
         af.rg = *ring;
+        if (st.per) af.per = *st.per;                    // prioritised replay: the rows are drawn in the launch, not named by ring->ids
         af.o_state = const_cast<float *>(state); af.o_action = const_cast<float *>(action); af.o_reward = const_cast<float *>(reward);
         af.o_undone = const_cast<float *>(undone); af.o_unmask = const_cast<float *>(unmask); af.o_next = const_cast<float *>(next_state);
     }
@@ -1754,7 +1785,7 @@ int erl_sac_step_fused(const SacCall &c, const SacDims &sd, const SacStep &st)
     // the rows (1) staged.  The temperature's step (:76-79) rides the critic's weight-gradient launch (4).
     ActorFwdArgs pg = af;
     pg.X = state; pg.noise = st.eps_cur; pg.counter = 2 * st.counter + 1; pg.act_t = act_pg; pg.lp = lp_cur; pg.eps_out = eps_used; pg.Y = Y;
-    pg.H0 = H0; pg.G0 = G0; pg.H1 = H1; pg.G1 = G1; pg.alpha0 = nullptr; pg.rg = ErlRingSample{};
+    pg.H0 = H0; pg.G0 = G0; pg.H1 = H1; pg.G1 = G1; pg.alpha0 = nullptr; pg.rg = ErlRingSample{}; pg.per = SacPerDraw{};
     // (nothing of launch (1) is kept for a backward pass: a 256-wide second layer is split over kCritSplit workgroups per tile -- ActorFwdArgs::split)
     const bool a_split = slot && h1 == 64 * kCritSplit && tiles * kCritSplit <= 256;
     const bool pair = a_split && wclass(h0) == 2;
@@ -1766,12 +1797,14 @@ int erl_sac_step_fused(const SacCall &c, const SacDims &sd, const SacStep &st)
             ActorFwdArgs sp2 = pg;
             if (ring) {
                 sp2.rg = *ring;
+                sp2.per = af.per;
                 sp2.rg.out_ids0 = sp2.rg.out_ids1 = nullptr;
                 sp2.rg_self = 1;
             }
             sp2.split = kCritSplit; sp2.h1_full = h1; sp2.d.h1 = h1 / kCritSplit;
             sp2.yx = slot->yx + kYxPass; sp2.nonce = nonce_y; sp2.spin_limit = spin; sp2.fault = sp.fault;
-            hipLaunchKernelGGL(actor_fwd_pair_kernel, dim3(tiles, 2 * kCritSplit), blk, 0, s, sp, sp2, (int)kCritSplit);
+            if (sp.per.sum_tree) hipLaunchKernelGGL(actor_fwd_pair_kernel<true>, dim3(tiles, 2 * kCritSplit), blk, 0, s, sp, sp2, (int)kCritSplit);
+            else hipLaunchKernelGGL(actor_fwd_pair_kernel<false>, dim3(tiles, 2 * kCritSplit), blk, 0, s, sp, sp2, (int)kCritSplit);
         } else {
             actor_fwd(sp, dim3(tiles, kCritSplit));
         }

@@ -929,6 +929,55 @@ def sac_update_per_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alp
           "erl_sac_update_per_loop_f32")
 
 
+def _per_loop_structs(spec: SacSpec, ring: ReplayRing, trees: PerTrees, uniform_all: TEN, cur_size: int, cursor: int, per_alpha: float,
+                      per_beta: float, stage: ReplayStage, per_stage: PerStage, objs_all: TEN):
+    """(T, B, ErlRingSample, ErlPerSample, device) of a prioritised loop, checked as sac_update_per_loop checks them"""
+    T, Q, n = uniform_all.shape
+    B = Q * n
+    f32 = th.float32
+    assert isinstance(ring, ReplayRing) and Q == trees.num_seqs == ring.num_seqs and per_stage.B == B
+    assert uniform_all.is_contiguous() and objs_all.shape == (T, 2) and objs_all.is_contiguous()
+    rs, dev = _ring_sample(spec, ring, None, 0, stage, B)
+    pr = _PerSample(ptr(trees.sum, f32), ptr(trees.min, f32), trees.max_size, trees.num_seqs, int(cur_size), int(cursor), float(per_alpha),
+                    float(per_beta), ptr(uniform_all, f32), ptr(per_stage.is_index, th.int64), ptr(per_stage.is_weight, f32),
+                    ptr(per_stage.td_error, f32))
+    return T, B, rs, pr, dev
+
+
+def sac_update_mod_per_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring: ReplayRing,
+                            trees: PerTrees, uniform_all: TEN, cur_size: int, cursor: int, per_alpha: float, per_beta: float, stage: ReplayStage,
+                            per_stage: PerStage, step0: int, actor_step0: int, critic_value: float, *, gamma: float, target_entropy: float,
+                            tau: float, lr: float, max_norm: float, objs_all: TEN, actor_target: Optional[TEN], draw_in_step: bool = False,
+                            seed: int = 0, counter0: int = 0, betas=(0.9, 0.999), eps: float = 1e-8) -> int:
+    """AgentModSAC's whole prioritised update_net loop from ONE C call (erl_sac_update_mod_per_loop_f32): sac_update_per_loop's steps on the
+    fused ModSAC step, the two-time-scale rule evaluated in C and the actor's Adam count running on from `actor_step0` as in
+    sac_update_mod_ring_loop; the trees are updated behind every step, a skipped actor step included.  `draw_in_step`: the draw and the
+    gather ride in the step's first launch instead of a launch of their own.  Returns the number of actor updates."""
+    T, B, rs, pr, dev = _per_loop_structs(spec, ring, trees, uniform_all, cur_size, cursor, per_alpha, per_beta, stage, per_stage, objs_all)
+    updates = ctypes.c_int32(0)
+    check(lib().erl_sac_update_mod_per_loop_f32(*_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs),
+                                                ctypes.addressof(pr), T, *_sac_stage(stage), B,
+                                                *_sac_hyper(seed, counter0, gamma, target_entropy, tau, lr, betas, eps, max_norm), int(step0),
+                                                int(actor_step0), float(critic_value), ptr(actor_target, th.float32), ptr(objs_all, th.float32),
+                                                ctypes.byref(updates), int(bool(draw_in_step)), *_sac_tail(spec, dev, B)),
+          "erl_sac_update_mod_per_loop_f32")
+    return int(updates.value)
+
+
+def sac_update_per_draw_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring: ReplayRing,
+                             trees: PerTrees, uniform_all: TEN, cur_size: int, cursor: int, per_alpha: float, per_beta: float, stage: ReplayStage,
+                             per_stage: PerStage, step0: int, *, gamma: float, target_entropy: float, tau: float, lr: float, max_norm: float,
+                             objs_all: TEN, seed: int = 0, counter0: int = 0, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+    """sac_update_per_loop with the draw + gather inside every step's first launch (erl_sac_update_per_draw_loop_f32: the fused step only);
+    the same arguments, the same bits in everything it leaves"""
+    T, B, rs, pr, dev = _per_loop_structs(spec, ring, trees, uniform_all, cur_size, cursor, per_alpha, per_beta, stage, per_stage, objs_all)
+    check(lib().erl_sac_update_per_draw_loop_f32(*_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs),
+                                                 ctypes.addressof(pr), T, *_sac_stage(stage), B,
+                                                 *_sac_hyper(seed, counter0, gamma, target_entropy, tau, lr, betas, eps, max_norm), int(step0),
+                                                 ptr(objs_all, th.float32), *_sac_tail(spec, dev, B)),
+          "erl_sac_update_per_draw_loop_f32")
+
+
 def sac_explore_action(spec: SacSpec, actor: TEN, state: TEN, *, noise: Optional[TEN] = None, seed: int = 0, counter: int = 0,
                        out: Optional[TEN] = None, out_state: Optional[TEN] = None, tile: bool = False) -> TEN:
     """`out` (N, A): the action's destination (e.g. the rollout's row); `out_state` (N, S): a copy of `state` from the same launch.

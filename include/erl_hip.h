@@ -898,6 +898,38 @@ ERL_API int erl_sac_update_per_loop_f32(float *actor_params, float *critic_param
                                 float *unmask, float *next_state, int64_t B, uint64_t seed, uint64_t counter0, float gamma,
                                 float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm,
                                 int32_t step0, float *objs_all, void *workspace, int64_t workspace_bytes, void *stream);
+/* Two further prioritised loops (added within ABI 23: symbols added, none changed).  Both run erl_sac_update_per_loop_f32's refusals under
+ * their own names, are fused-only (a shape outside erl_sac_mod_fused_supported is refused: there is no layered form) and neither
+ * allocates nor synchronises the host.
+ *   erl_sac_update_mod_per_loop_f32    AgentModSAC with prioritised replay: erl_sac_update_per_loop_f32's arguments plus what
+ *                                      erl_sac_update_mod_ring_loop_f32 adds (actor_step0, critic_value, actor_target_params,
+ *                                      actor_updates_out: the two-time-scale rule evaluated on the host as there).  Per step: the draw +
+ *                                      gather, the step erl_sac_update_mod_f32 runs with is_weight / td_error_out, the tree update -- behind
+ *                                      a skipped actor step as well.  draw_in_step: 0 = erl_per_sample_rows_f32 per step; 1 = the draw and
+ *                                      the gather ride in the step's first launch (below); anything else is refused.
+ *   erl_sac_update_per_draw_loop_f32   erl_sac_update_per_loop_f32 for AgentSAC with the draw inside the step: no erl_per_sample_rows_f32
+ *                                      launch; every 16-row tile of the step's first launch draws its own rows from the trees (the
+ *                                      arithmetic of erl_per_sample_rows_f32, csrc/per_draw.h) behind its weight requests, and the tile's
+ *                                      first workgroup writes the staging block, ids0 / ids1, per->is_index and per->is_weight.
+ *                                      erl_per_update_index_f32 stays behind the step.  Bit-identical to erl_sac_update_per_loop_f32 on
+ *                                      the same uniforms. */
+ERL_API int erl_sac_update_mod_per_loop_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log,
+                                    float *actor_m, float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v,
+                                    int S, int A, const int *hidden, int n_hidden, int E, const ErlRingSample *ring,
+                                    const ErlPerSample *per, int64_t n_steps, float *state, float *action, float *reward,
+                                    float *undone, float *unmask, float *next_state, int64_t B, uint64_t seed, uint64_t counter0,
+                                    float gamma, float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam,
+                                    float max_norm, int32_t step0, int32_t actor_step0, double critic_value,
+                                    float *actor_target_params, float *objs_all, int32_t *actor_updates_out, int32_t draw_in_step,
+                                    void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_sac_update_per_draw_loop_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log,
+                                     float *actor_m, float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v,
+                                     int S, int A, const int *hidden, int n_hidden, int E, const ErlRingSample *ring,
+                                     const ErlPerSample *per, int64_t n_steps, float *state, float *action, float *reward,
+                                     float *undone, float *unmask, float *next_state, int64_t B, uint64_t seed, uint64_t counter0,
+                                     float gamma, float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam,
+                                     float max_norm, int32_t step0, float *objs_all, void *workspace, int64_t workspace_bytes,
+                                     void *stream);
 ERL_API int erl_sac_explore_action_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden,
                                const float *state, int64_t N, const float *noise, uint64_t seed, uint64_t counter,
                                float *action_out, float *state_out, void *workspace, int64_t workspace_bytes, void *stream);
