@@ -87,6 +87,7 @@ _SIGNATURES = {
     "erl_k6_timing_spans": (c_int, [c_int, POINTER(c_int64), POINTER(c_double), c_int]),
     "erl_ppo_wg_map_info": (c_int, [c_int, POINTER(c_int), POINTER(c_double), POINTER(c_double)]),
     "erl_ppo_update_chains": (c_int, []),
+    "erl_criterion_next_call": (c_int, [c_int32, c_float]),
     "erl_ppo_step_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P,
                                  c_int64, c_int64, _P, c_int64, c_float, c_float, c_float, c_int, _P, c_int, _P]),
     "erl_grad_reduce_f32": (c_int, [_P, c_int, c_int64, _P, _P]),
@@ -228,7 +229,11 @@ def lib() -> ctypes.CDLL:
                 "elegantrl_amd has no CPU/PyTorch fallback for its kernels.")
         handle = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError here = header/library mismatch
+            try:
+                fn = getattr(handle, name)
+            except AttributeError:      # header / library mismatch; symbols have been added WITHIN an ABI number (erl_criterion_next_call: 23)
+                raise HipExtensionError(f"{LIB_PATH} does not export {name}: it is older than this binding although both say ABI "
+                                        f"{ABI_VERSION}; rebuild it (`make -C elegantrl_amd/csrc`)") from None
             fn.restype = res
             fn.argtypes = args
         if handle.erl_abi_version() != ABI_VERSION:
@@ -241,6 +246,32 @@ def check(rc: int, what: str) -> None:
     if rc != 0:
         msg = lib().erl_last_error_string()
         raise HipExtensionError(f"{what} failed (rc={rc}): {msg.decode() if msg else '?'}")
+
+
+# the critic loss of an update call (include/erl_hip.h, ERL_CRIT_*): (kind, threshold); torch's defaults for beta / delta are 1.0
+CRIT_MSE, CRIT_SMOOTH_L1, CRIT_HUBER = 0, 1, 2
+CRITERION_MSE = (CRIT_MSE, 1.0)
+
+
+def next_call_criterion(criterion) -> None:
+    """Name the critic loss of the NEXT update entry this thread calls (erl_criterion_next_call: that entry takes it and validates it under
+    its own name; the thread is back at MSE afterwards).  MSE is what a call gets when nothing is said, so nothing is said for it."""
+    kind, beta = criterion
+    if kind != CRIT_MSE:
+        check(lib().erl_criterion_next_call(int(kind), float(beta)), "erl_criterion_next_call")
+
+
+def call_with_criterion(fn, criterion, *args) -> int:
+    """`fn(*args)` -- an update entry of the library -- under the critic loss `criterion`; returns the entry's code.  If the call never
+    reaches the entry (ctypes refuses an argument while it converts them), the thread's pending criterion is taken back: it must not fall to
+    the next, unrelated update call of this thread."""
+    next_call_criterion(criterion)
+    try:
+        return fn(*args)
+    except BaseException:
+        if criterion[0] != CRIT_MSE:
+            lib().erl_criterion_next_call(CRIT_MSE, 1.0)
+        raise
 
 
 def stream_ptr() -> int:

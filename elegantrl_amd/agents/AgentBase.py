@@ -82,6 +82,26 @@ class FlatNet:
         return p is not None and p.data_ptr() == self.flat.data_ptr() + 4 * probe[3]
 
 
+def criterion_code(criterion) -> Tuple[int, float]:
+    """`args.criterion` (elegantrl/agents/AgentBase.py:62) as the (kind, threshold) pair the update entries take (include/erl_hip.h,
+    ERL_CRIT_*; csrc/critic_loss.h).  The reference multiplies the element-wise loss by `unmask` (AgentPPO.py:190, AgentSAC.py:60), so only
+    reduction='none' makes sense there, and only the three modules whose loss the kernels hold are accepted: nothing is ignored."""
+    supported = "supported: torch.nn.MSELoss, torch.nn.SmoothL1Loss (beta > 0) and torch.nn.HuberLoss, each with reduction='none'"
+    for cls, kind, attr in ((nn.MSELoss, _hip.CRIT_MSE, None), (nn.SmoothL1Loss, _hip.CRIT_SMOOTH_L1, "beta"),
+                            (nn.HuberLoss, _hip.CRIT_HUBER, "delta")):
+        if type(criterion) is not cls:
+            continue
+        if criterion.reduction != "none":
+            raise ValueError(f"args.criterion = {criterion!r} has reduction={criterion.reduction!r}: the reference multiplies the element-wise "
+                             f"loss by `unmask` before it takes the mean, so the criterion must be built with reduction='none'")
+        beta = 1.0 if attr is None else float(getattr(criterion, attr))
+        if not (beta > 0.0 and beta < float("inf")):
+            why = "SmoothL1Loss(beta=0) is L1Loss, which the kernels do not hold" if cls is nn.SmoothL1Loss else "HuberLoss needs delta > 0"
+            raise NotImplementedError(f"args.criterion = {criterion!r} with {attr}={beta}: {why}; {supported}")
+        return kind, beta
+    raise NotImplementedError(f"args.criterion = {criterion!r} is not implemented by the HIP kernels; {supported}")
+
+
 class AgentBase:
     """Hyper-parameter capture + the generic pieces shared by the agents."""
 
@@ -117,7 +137,8 @@ class AgentBase:
         self.act_optimizer = None
         self.cri_optimizer = None
 
-        self.criterion = getattr(args, "criterion", th.nn.MSELoss(reduction="none"))
+        self.criterion = getattr(args, "criterion", th.nn.MSELoss(reduction="none"))     # the torch module, as the reference keeps it
+        self.criterion_code = criterion_code(self.criterion)       # (kind, threshold): what every update route hands to its entry
         self.if_vec_env = self.num_envs > 1
         self.if_use_per = getattr(args, "if_use_per", None)
         self.lambda_fit_cum_r = getattr(args, "lambda_fit_cum_r", 0.0)

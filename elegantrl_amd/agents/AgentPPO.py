@@ -683,7 +683,7 @@ class AgentPPO(AgentBase):
 
     def _layered_step(self, *args) -> None:
         from .. import ops
-        ops.mlpn_ppo_step(*args, objective=self._objective)
+        ops.mlpn_ppo_step(*args, objective=self._objective, criterion=self.criterion_code)
 
     def _loop_layered(self, batch, ids, comm, dp, norm):
         """generic-shape networks: one launch per dense layer, the summed gradient written directly; returns its own log means"""
@@ -717,7 +717,7 @@ class AgentPPO(AgentBase):
         h1, h2 = self.net_dims
         op(self._flat, self._exp_avg, self._exp_avg_sq, a.state_avg.data, a.state_std.data, c.state_avg.data, c.state_std.data,
            self.state_dim, h1, h2, self.action_dim, *batch, ids, float(self.ratio_clip), self.lambda_entropy_value, self._slabs,
-           self._grads, self._adam_step + 1, float(self.learning_rate), float(self.clip_grad_norm), **extra)
+           self._grads, self._adam_step + 1, float(self.learning_rate), float(self.clip_grad_norm), criterion=self.criterion_code, **extra)
         self._adam_step += ids.shape[0]
 
     def _loop_torch_dp(self, batch, ids, comm, dp, norm) -> None:
@@ -744,9 +744,10 @@ class AgentPPO(AgentBase):
         S_, A_, clip, lam_e = self.state_dim, self.action_dim, float(self.ratio_clip), self.lambda_entropy_value
         lr, max_norm, stride = float(self.learning_rate), float(self.clip_grad_norm), self._stride
         for k in range(update_times):
-            rc = L.erl_ppo_step_f32(pf, pf + 4 * self._Pa, p_avg_a, p_std_a, p_avg_c, p_std_c, S_, h1, h2, A_, p_s, p_ac, p_um,
-                                    p_lp, p_adv, p_rs, H, N, p_ids + 8 * k * B, B, clip, lam_e, inv_batch, mode, p_slabs,
-                                    n_slabs, sp)
+            # (args.criterion travels beside the call: include/erl_hip.h, ERL_CRIT_*)
+            rc = _hip.call_with_criterion(L.erl_ppo_step_f32, self.criterion_code, pf, pf + 4 * self._Pa, p_avg_a, p_std_a, p_avg_c, p_std_c,
+                                          S_, h1, h2, A_, p_s, p_ac, p_um, p_lp, p_adv, p_rs, H, N, p_ids + 8 * k * B, B, clip, lam_e,
+                                          inv_batch, mode, p_slabs, n_slabs, sp)
             rc = rc or L.erl_grad_reduce_f32(p_slabs, n_slabs, stride, p_g + 4 * k * stride, sp)
             if rc:
                 _hip.check(rc, "erl_ppo_step_f32 / erl_grad_reduce_f32")
@@ -920,7 +921,7 @@ class AgentDiscretePPO(AgentPPO):
 
     def _layered_step(self, *args) -> None:
         from .. import ops
-        ops.mlpn_ppo_step_discrete(*args)
+        ops.mlpn_ppo_step_discrete(*args, criterion=self.criterion_code)
 
     def _loop_discrete_fused(self, batch, ids, comm, dp, norm) -> None:
         """one C call enqueues, per minibatch, the fused kernel, the slab reduction into `_grads[k]` and the two-launch clip + Adam

@@ -335,7 +335,7 @@ class AgentSAC(AgentBase):
 
     def _hyper(self) -> dict:
         return dict(gamma=float(self.gamma), target_entropy=float(self.target_entropy), tau=float(self.soft_update_tau),
-                    lr=float(self.learning_rate), max_norm=float(self.clip_grad_norm))
+                    lr=float(self.learning_rate), max_norm=float(self.clip_grad_norm), criterion=self.criterion_code)
 
     def _set_step_counts(self):
         """the optimisers' `step_count` after a step (th.optim.Adam's own count, what a checkpoint stores)"""

@@ -18,6 +18,41 @@ extern "C" int erl_abi_version(void) { return ERL_ABI_VERSION; }
 
 extern "C" const char *erl_last_error_string(void) { return g_err; }
 
+// the critic loss of a call (erl_common.h): pending until an update entry takes it, the call's own while that entry runs
+static thread_local ErlCriterion g_crit_pending = {ERL_CRIT_MSE, 1.f};
+static thread_local ErlCriterion g_crit_call = {ERL_CRIT_MSE, 1.f};
+static thread_local int g_crit_depth = 0;
+
+extern "C" int erl_criterion_next_call(int32_t criterion, float criterion_beta)
+{
+    g_crit_pending = ErlCriterion{(int)criterion, criterion_beta};
+    return ERL_OK;
+}
+
+ErlCriterion erl_criterion_of_call() { return g_crit_call; }
+
+ErlCriterionScope::ErlCriterionScope()
+{
+    if (g_crit_depth++ == 0) {
+        g_crit_call = g_crit_pending;
+        g_crit_pending = ErlCriterion{ERL_CRIT_MSE, 1.f};
+    }
+}
+
+ErlCriterionScope::~ErlCriterionScope()
+{
+    if (--g_crit_depth == 0) g_crit_call = ErlCriterion{ERL_CRIT_MSE, 1.f};
+}
+
+int ErlCriterionScope::check(const char *entry) const
+{
+    const ErlCriterion c = g_crit_call;
+    ERL_REQUIRE(c.kind >= ERL_CRIT_MSE && c.kind <= ERL_CRIT_HUBER, "%s: unknown criterion %d (ERL_CRIT_MSE, _SMOOTH_L1, _HUBER)", entry, c.kind);
+    ERL_REQUIRE(c.beta - c.beta == 0.f, "%s: criterion_beta is not finite", entry);
+    ERL_REQUIRE(c.kind == ERL_CRIT_MSE || c.beta > 0.f, "%s: criterion_beta = %g must be > 0 for criterion %d", entry, (double)c.beta, c.kind);
+    return ERL_OK;
+}
+
 extern "C" int erl_device_info(int *num_cu, int *lds_bytes_per_block)
 {
     int dev = 0;
@@ -442,6 +477,7 @@ extern "C" int erl_ppo_update_f32(float *flat_params, float *exp_avg, float *exp
                                   int update_times, float ratio_clip, float lambda_entropy, int objective, float *slabs, float *grads,
                                   int32_t first_step, float lr, float beta1, float beta2, float eps, float max_norm, void *stream)
 {
+    ERL_CRITERION_ENTRY("erl_ppo_update_f32");
     return erl_ppo_update_dp_f32(flat_params, exp_avg, exp_avg_sq, act_avg, act_std, cri_avg, cri_std, S, h1, h2, A, states, actions,
                                  unmasks, logprobs, advantages, reward_sums, H, N, ids, B, update_times, ratio_clip, lambda_entropy,
                                  objective, slabs, grads, first_step, lr, beta1, beta2, eps, max_norm, /*adv_stats=*/nullptr,

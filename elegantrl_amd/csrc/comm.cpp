@@ -200,6 +200,7 @@ extern "C" int erl_ppo_update_dp_f32(float *flat_params, float *exp_avg, float *
                                      int32_t first_step, float lr, float beta1, float beta2, float eps, float max_norm, double *adv_stats,
                                      const double *adv_partials, int n_partials, void *comm, void *stream)
 {
+    ERL_CRITERION_ENTRY("erl_ppo_update_dp_f32");
     ERL_REQUIRE(flat_params && exp_avg && exp_avg_sq && ids && slabs && grads, "erl_ppo_update_dp_f32: NULL tensor");
     ERL_REQUIRE(update_times >= 1 && first_step >= 1 && B >= 1, "erl_ppo_update_dp_f32: bad argument");
     const int64_t Pa = erl_mlp_param_count(S, h1, h2, A, 1), Pc = erl_mlp_param_count(S, h1, h2, 1, 0);

@@ -15,6 +15,28 @@ void erl_set_error(const char *fmt, ...);
 enum ErlFaultSource { ERL_FAULT_GAE_LOOKBACK = 0, ERL_FAULT_P2P_EXCHANGE = 1, ERL_FAULT_ADAM_GRID_WAIT = 2, ERL_FAULT_SAC_Q_EXCHANGE = 3, ERL_FAULT_SOURCES = 4 };
 uint32_t *erl_fault_word(int source);
 
+// ---- the critic loss of a call (critic_loss.h; include/erl_hip.h, erl_criterion_next_call) ------------------------------------
+// The update entries' signatures are pinned by callers that predate the criterion, so it travels beside them: the thread's pending
+// {kind, threshold} is taken (and reset to MSE) by the first update entry the thread enters, checked under that entry's name, and is the
+// call's criterion until the entry returns -- an entry that forwards to another entry (erl_ppo_update_f32) keeps it.  The places that
+// fill the kernels' argument structs read erl_criterion_of_call().  Everything here is host code on the calling thread.
+struct ErlCriterion {
+    int kind;      // ERL_CRIT_*
+    float beta;    // SmoothL1Loss's beta / HuberLoss's delta (MSE: not read)
+};
+ErlCriterion erl_criterion_of_call();
+struct ErlCriterionScope {
+    ErlCriterionScope();
+    ~ErlCriterionScope();
+    ErlCriterionScope(const ErlCriterionScope &) = delete;
+    int check(const char *entry) const;        // ERL_OK, or ERL_EINVAL with the argument named in the error string
+};
+#define ERL_CRITERION_ENTRY(name)                          \
+    ErlCriterionScope erl_crit_scope_;                     \
+    do {                                                   \
+        if (erl_crit_scope_.check(name)) return ERL_EINVAL; \
+    } while (0)
+
 // ---- one-shot peer-to-peer exchange (p2p.hip owns the IPC-mapped stages, grad_tail.hip the kernels) ----------------------
 #define ERL_P2P_MAX_WORLD 8
 struct ErlExchange {
@@ -99,6 +121,8 @@ struct SacCall {
     const float *cum_reward;              // the lambda_fit_cum_r term (layered step only)
     float lambda_fit_cum_r;
     bool fused_only;                      // the erl_sac_update_mod_* entries: the fused step or a refusal
+    int crit_kind;                        // ERL_CRIT_* and its threshold: the call's critic loss (critic_loss.h; erl_criterion_of_call())
+    float crit_beta;
 };
 // prioritised replay's draw inside the fused step's first launch (sac_fused.hip ActorFwdArgs::per; per_draw.h): the trees with their leaf
 // count, the ring's fill state as erl_per_sample_rows_f32 derives it, this step's uniforms (num_seqs, n_per_seq), and where the draw's

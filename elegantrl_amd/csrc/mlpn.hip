@@ -220,6 +220,7 @@ int ppo_step_impl(const char *what, bool discrete, const float *actor_params, co
         float *dA, *dB, *dsl, *cs_scr, *part, *dw_scr;
     } st[2];
     const int nparts = (int)erl_cdiv(B, 256);
+    const ErlCriterion crit = erl_criterion_of_call();
     for (int net = 0; net < 2; ++net) {
         const NetDims &nd = net == 0 ? na : nc;
         NetState &q = st[net];
@@ -259,11 +260,11 @@ int ppo_step_impl(const char *what, bool discrete, const float *actor_params, co
                                        logprobs, advantages, ratio_clip, lambda_entropy, inv_batch, q.part);
                 else if (net == 0)
                     hipLaunchKernelGGL((objective_kernel<true>), dim3(nparts), dim3(256), 0, sn, Y, (float *)nullptr, ids, H, N, A, B, actions, unmasks,
-                                       logprobs, advantages, P + nd.oStd, ratio_clip, lambda_entropy, inv_batch, objective, q.part);
+                                       logprobs, advantages, P + nd.oStd, ratio_clip, lambda_entropy, inv_batch, objective, crit.kind, crit.beta, q.part);
                 else
                     hipLaunchKernelGGL((objective_kernel<false>), dim3(nparts), dim3(256), 0, sn, Y, (float *)nullptr, ids, H, N, 1, B, actions,
                                        unmasks, reward_sums, (const float *)nullptr, (const float *)nullptr, ratio_clip, lambda_entropy,
-                                       inv_batch, objective, q.part);
+                                       inv_batch, objective, crit.kind, crit.beta, q.part);
                 const bool gauss = net == 0 && !discrete;
                 hipLaunchKernelGGL(fold_logs_kernel, dim3(1), dim3(256), 0, sn, q.part, nparts, gauss ? 2 + A : 2, P + nd.oStd, A, inv_batch,
                                    net == 0 ? (discrete ? 2 : 1) : 0, logs, gauss ? G + nd.oStd : (float *)nullptr);   // + dL/dstd_log
@@ -289,6 +290,7 @@ extern "C" int erl_mlpn_ppo_step_f32(const float *actor_params, const float *cri
                                      int64_t B, float ratio_clip, float lambda_entropy, float inv_batch, int objective,
                                      float *flat_grad, void *workspace, int64_t workspace_bytes, void *stream)
 {
+    ERL_CRITERION_ENTRY("erl_mlpn_ppo_step_f32");
     ERL_REQUIRE(objective >= ERL_PPO_OBJ_REFERENCE && objective <= ERL_PPO_OBJ_A2C, "erl_mlpn_ppo_step_f32: unknown objective %d",
                 objective);
     // net_dims (256, 128, 64 | 128), the reference's BipedalWalker / Humanoid demo networks: one fused kernel (ppo_step_wd_impl.h)
@@ -308,6 +310,7 @@ extern "C" int erl_mlpn_ppo_step_discrete_f32(const float *actor_params, const f
                                               int64_t N, const int64_t *ids, int64_t B, float ratio_clip, float lambda_entropy,
                                               float inv_batch, float *flat_grad, void *workspace, int64_t workspace_bytes, void *stream)
 {
+    ERL_CRITERION_ENTRY("erl_mlpn_ppo_step_discrete_f32");
     return ppo_step_impl("erl_mlpn_ppo_step_discrete_f32", true, actor_params, critic_params, act_avg, act_std, cri_avg, cri_std,
                          actor_dims, n_dims, states, actions, unmasks, logprobs, advantages, reward_sums, H, N, ids, B, ratio_clip,
                          lambda_entropy, inv_batch, ERL_PPO_OBJ_REFERENCE, flat_grad, workspace, workspace_bytes, stream);

@@ -5,6 +5,7 @@
 #include "categorical.h"
 #include "gemm_tiles.h"
 #include "ppo_objective.h"
+#include "critic_loss.h"
 
 namespace {
 
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(256) void objective_kernel(float *__restrict__ Y, f
                                                         const uint8_t *__restrict__ unmasks, const float *__restrict__ xa_src,
                                                         const float *__restrict__ xb_src, const float *__restrict__ std_log,
                                                         float ratio_clip, float lambda_entropy, float inv_batch, int objective,
-                                                        float *__restrict__ part)
+                                                        int crit_kind, float crit_beta, float *__restrict__ part)
 {
     // part[block][2 (+ A)]: the block's sums of the two logged values and (actor) of dL/dstd_log per action -- folded in a
     // fixed order by fold_logs_kernel (the std_log gradient used to be a (B, A) tensor and two more launches)
@@ -190,8 +191,13 @@ __global__ __launch_bounds__(256) void objective_kernel(float *__restrict__ Y, f
         const int64_t row = t * N + n;
         const float um = unmasks[row] ? 1.f : 0.f;
         const float diff = Y[b] - xa_src[row];
-        l0 = diff * diff * um;
-        Y[b] = 2.f * diff * um * inv_batch;
+        if (crit_kind == ERL_CRIT_MSE) {
+            l0 = diff * diff * um;
+            Y[b] = 2.f * diff * um * inv_batch;
+        } else {                                           // args.criterion other than MSELoss (critic_loss.h)
+            l0 = critic_loss(crit_kind, crit_beta, diff) * um;
+            Y[b] = critic_loss_grad(crit_kind, crit_beta, diff) * um * inv_batch;
+        }
     }
     const float t0 = block_sum(l0, red), t1 = block_sum(l1, red);
     if (threadIdx.x == 0) {

@@ -7,6 +7,7 @@
 #include <functional>
 #include "mlp_chain.h"
 #include "ppo_objective.h"
+#include "critic_loss.h"
 
 struct Ppo2Args {
     const float *P[2];    // actor, critic flat params
@@ -35,8 +36,11 @@ struct Ppo2Args {
     // launch that only reports the kernel's program counter (how the host learns where the code lives; nullptr otherwise)
     const unsigned char *code_touch = nullptr;
     unsigned code_touch_bytes = 0;
+    int crit_kind = ERL_CRIT_MSE;   // the critic loss of this call (critic_loss.h; erl_criterion_of_call()) and, below, its threshold.  Both sit in what
+                                    // was padding in front of an 8-byte member: no other member moved and the struct kept its size (profiles/criterion_kernel_resources.txt)
     unsigned long long *pc_out = nullptr;
     int only_net = -1;    // >= 0: a half launch, grid (n_slabs, 1), every workgroup on this network; the host leaves it at -1
+    float crit_beta = 1.f;
     long long *prof;      // ERL_PROFILE builds only: [net][8 waves][32] s_memtime stamps of workgroup prof_block
     int prof_block;
 };

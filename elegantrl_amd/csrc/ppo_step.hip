@@ -191,8 +191,13 @@ __device__ __forceinline__ void ppo_block(const Ppo2Args &g, float *smem)
     if (!ACTOR) {
         const float diff = Y[0][0] - xa;                  // only (q = 0, r = 0) is the value head
         const bool head = q == 0;
-        loss0 = head ? diff * diff * um : 0.f;
-        dY[0] = f32x4{head ? 2.f * diff * um * g.inv_batch : 0.f, 0.f, 0.f, 0.f};
+        if (g.crit_kind == ERL_CRIT_MSE) {
+            loss0 = head ? diff * diff * um : 0.f;
+            dY[0] = f32x4{head ? 2.f * diff * um * g.inv_batch : 0.f, 0.f, 0.f, 0.f};
+        } else {                                           // args.criterion other than MSELoss (critic_loss.h)
+            loss0 = head ? critic_loss(g.crit_kind, g.crit_beta, diff) * um : 0.f;
+            dY[0] = f32x4{head ? critic_loss_grad(g.crit_kind, g.crit_beta, diff) * um * g.inv_batch : 0.f, 0.f, 0.f, 0.f};
+        }
     } else {
         float diffv[4], varv[4];
         float lp = 0.f;
@@ -573,6 +578,7 @@ int erl_ppo_step_images_f32(const float *actor_params, const float *critic_param
     g.S = S; g.h1 = h1; g.h2 = h2; g.A = A;
     g.ratio_clip = ratio_clip; g.lambda_entropy = lambda_entropy; g.inv_batch = inv_batch;
     g.objective = objective;
+    g.crit_kind = erl_criterion_of_call().kind; g.crit_beta = erl_criterion_of_call().beta;
     g.slabs = slabs;
     g.Pa = Dims{S, h1, h2, A}.count(true);
     g.Pc = Dims{S, h1, h2, 1}.count(false);
@@ -624,6 +630,7 @@ extern "C" int erl_ppo_step_f32(const float *actor_params, const float *critic_p
                                 const float *reward_sums, int64_t H, int64_t N, const int64_t *ids, int64_t B, float ratio_clip,
                                 float lambda_entropy, float inv_batch, int objective, float *slabs, int n_slabs, void *stream)
 {
+    ERL_CRITERION_ENTRY("erl_ppo_step_f32");
     return erl_ppo_step_images_f32(actor_params, critic_params, act_avg, act_std, cri_avg, cri_std, S, h1, h2, A, states, actions, unmasks,
                                    logprobs, advantages, reward_sums, H, N, ids, B, ratio_clip, lambda_entropy, inv_batch, objective, slabs,
                                    n_slabs, nullptr, nullptr, nullptr, stream);

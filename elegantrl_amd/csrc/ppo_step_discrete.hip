@@ -17,6 +17,7 @@
 // The critic's branch is ppo_step.hip's, statement for statement.
 #include "ppo_step_chain.h"
 #include "categorical.h"
+#include "critic_loss.h"
 
 namespace {
 
@@ -33,6 +34,8 @@ struct PpoDArgs {
     int64_t H, N, B;
     int S, h1, h2, A;
     float ratio_clip, lambda_entropy, inv_batch;
+    float crit_beta;      // the threshold of the call's critic loss (critic_loss.h; its kind is a template parameter).  In what was padding: no
+                          // member moved, the struct kept its size, and the MSE kernels their code
     float *slabs;
     int64_t stride, Pa, Pc;
 };
@@ -49,7 +52,10 @@ constexpr int kDBiasFloats = 128 + 128 + 16;
 constexpr size_t kPpoDLdsBytes = (size_t)(2 * kDRFloats + kDRCFloats + kDRW3Floats + kDBiasFloats + 16) * sizeof(float);
 static_assert(kPpoDLdsBytes <= 160 * 1024, "one workgroup per CU");
 
-template <bool ACTOR, int NS_, int N1_, int N2_, bool VEC>
+// CRIT: the critic loss, ERL_CRIT_* (critic_loss.h).  A template parameter in this family: as a run-time branch it cost the <1, 4, 2, .>
+// kernels 12-13 vector registers, from four waves a SIMD to three (profiles/criterion_kernel_resources.txt); the CRIT = ERL_CRIT_MSE kernels
+// are the parent's, byte for byte
+template <bool ACTOR, int NS_, int N1_, int N2_, bool VEC, int CRIT>
 __device__ __forceinline__ void ppo_discrete_block(const PpoDArgs &g, float *smem)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -151,8 +157,13 @@ __device__ __forceinline__ void ppo_discrete_block(const PpoDArgs &g, float *sme
     if (!ACTOR) {
         const float diff = Y[0][0] - xa;                  // only (q = 0, r = 0) is the value head
         const bool head = q == 0;
-        loss0 = head ? diff * diff * um : 0.f;
-        dY[0] = f32x4{head ? 2.f * diff * um * g.inv_batch : 0.f, 0.f, 0.f, 0.f};
+        if (CRIT == ERL_CRIT_MSE) {
+            loss0 = head ? diff * diff * um : 0.f;
+            dY[0] = f32x4{head ? 2.f * diff * um * g.inv_batch : 0.f, 0.f, 0.f, 0.f};
+        } else {                                           // args.criterion other than MSELoss (critic_loss.h)
+            loss0 = head ? critic_loss(CRIT, g.crit_beta, diff) * um : 0.f;
+            dY[0] = f32x4{head ? critic_loss_grad(CRIT, g.crit_beta, diff) * um * g.inv_batch : 0.f, 0.f, 0.f, 0.f};
+        }
     } else {
         const float z[4] = {Y[0][0], Y[0][1], Y[0][2], Y[0][3]};
         float dz[4];
@@ -232,12 +243,20 @@ __device__ __forceinline__ void ppo_discrete_block(const PpoDArgs &g, float *sme
     }
 }
 
+// the MSE kernel keeps its name and template list; the other criteria are a kernel of their own
 template <int NS_, int N1_, int N2_, bool VEC>
 __global__ __launch_bounds__(DNW * 64) void ppo_step_discrete_kernel(PpoDArgs g)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    if (blockIdx.y == 0) ppo_discrete_block<true, NS_, N1_, N2_, VEC>(g, smem);
-    else ppo_discrete_block<false, NS_, N1_, N2_, VEC>(g, smem);
+    if (blockIdx.y == 0) ppo_discrete_block<true, NS_, N1_, N2_, VEC, ERL_CRIT_MSE>(g, smem);
+    else ppo_discrete_block<false, NS_, N1_, N2_, VEC, ERL_CRIT_MSE>(g, smem);
+}
+template <int NS_, int N1_, int N2_, bool VEC, int CRIT>
+__global__ __launch_bounds__(DNW * 64) void ppo_step_discrete_crit_kernel(PpoDArgs g)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    if (blockIdx.y == 0) ppo_discrete_block<true, NS_, N1_, N2_, VEC, CRIT>(g, smem);
+    else ppo_discrete_block<false, NS_, N1_, N2_, VEC, CRIT>(g, smem);
 }
 
 // the shapes of the one-launch discrete rollout (rollout_discrete.hip, erl_rollout_discrete_supported), which this kernel completes
@@ -246,19 +265,35 @@ bool pd_dims_ok(int S, int h1, int h2, int A)
     return S >= 1 && S <= 64 && h1 >= 32 && h1 <= 128 && h1 % 32 == 0 && h2 >= 32 && h2 <= 128 && h2 % 32 == 0 && A >= 2 && A <= 8;
 }
 
-template <int NS_, int N1_, int N2_, bool VEC>
-int launch_discrete(const PpoDArgs &g, int n_slabs, hipStream_t stream)
+template <int NS_, int N1_, int N2_, bool VEC, int CRIT>
+constexpr auto discrete_kernel_of()
 {
+    if constexpr (CRIT == ERL_CRIT_MSE) return ppo_step_discrete_kernel<NS_, N1_, N2_, VEC>;       // (no crit kernel is instantiated for MSE)
+    else return ppo_step_discrete_crit_kernel<NS_, N1_, N2_, VEC, CRIT>;
+}
+
+template <int NS_, int N1_, int N2_, bool VEC, int CRIT>
+int launch_discrete_crit(const PpoDArgs &g, int n_slabs, hipStream_t stream)
+{
+    constexpr auto kernel = discrete_kernel_of<NS_, N1_, N2_, VEC, CRIT>();
     static bool attr_set = false;
     if (!attr_set) {
-        int rc = erl_hip_status(hipFuncSetAttribute((const void *)ppo_step_discrete_kernel<NS_, N1_, N2_, VEC>,
+        int rc = erl_hip_status(hipFuncSetAttribute((const void *)kernel,
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPpoDLdsBytes),
                                 "hipFuncSetAttribute(ppo_step_discrete_kernel)");
         if (rc) return rc;
         attr_set = true;
     }
-    hipLaunchKernelGGL((ppo_step_discrete_kernel<NS_, N1_, N2_, VEC>), dim3(n_slabs, 2), dim3(DNW * 64), kPpoDLdsBytes, stream, g);
+    hipLaunchKernelGGL(kernel, dim3(n_slabs, 2), dim3(DNW * 64), kPpoDLdsBytes, stream, g);
     return erl_hip_status(hipGetLastError(), "erl_ppo_step_discrete_f32");
+}
+
+template <int NS_, int N1_, int N2_, bool VEC>
+int launch_discrete(const PpoDArgs &g, int crit_kind, int n_slabs, hipStream_t stream)
+{
+    if (crit_kind == ERL_CRIT_SMOOTH_L1) return launch_discrete_crit<NS_, N1_, N2_, VEC, ERL_CRIT_SMOOTH_L1>(g, n_slabs, stream);
+    if (crit_kind == ERL_CRIT_HUBER) return launch_discrete_crit<NS_, N1_, N2_, VEC, ERL_CRIT_HUBER>(g, n_slabs, stream);
+    return launch_discrete_crit<NS_, N1_, N2_, VEC, ERL_CRIT_MSE>(g, n_slabs, stream);
 }
 
 // validation shared by the two entry points: everything that can be checked on the host, before any launch
@@ -289,6 +324,8 @@ int step_discrete(const float *actor_params, const float *critic_params, const f
     g.H = H; g.N = N; g.B = B;
     g.S = S; g.h1 = h1; g.h2 = h2; g.A = A;
     g.ratio_clip = ratio_clip; g.lambda_entropy = lambda_entropy; g.inv_batch = inv_batch;
+    const int crit = erl_criterion_of_call().kind;
+    g.crit_beta = erl_criterion_of_call().beta;
     g.slabs = slabs;
     g.Pa = Dims{S, h1, h2, A}.count(false);
     g.Pc = Dims{S, h1, h2, 1}.count(false);
@@ -299,8 +336,8 @@ int step_discrete(const float *actor_params, const float *critic_params, const f
     const bool vec = (S % 4 == 0) && al(actor_params) && al(critic_params) && al(states) && al(act_avg) && al(act_std) && al(cri_avg) &&
                      al(cri_std);
     const bool hot = S <= 16 && h1 == 64 && h2 == 32;      // CartPole's (64, 32): compile-time tile counts
-    if (hot) return vec ? launch_discrete<1, 4, 2, true>(g, n_slabs, st) : launch_discrete<1, 4, 2, false>(g, n_slabs, st);
-    return vec ? launch_discrete<0, 0, 0, true>(g, n_slabs, st) : launch_discrete<0, 0, 0, false>(g, n_slabs, st);
+    if (hot) return vec ? launch_discrete<1, 4, 2, true>(g, crit, n_slabs, st) : launch_discrete<1, 4, 2, false>(g, crit, n_slabs, st);
+    return vec ? launch_discrete<0, 0, 0, true>(g, crit, n_slabs, st) : launch_discrete<0, 0, 0, false>(g, crit, n_slabs, st);
 }
 
 }  // namespace
@@ -323,6 +360,7 @@ extern "C" int erl_ppo_step_discrete_f32(const float *actor_params, const float 
 {
     const void *const tensors[] = {actor_params, critic_params, act_avg, act_std, cri_avg, cri_std, states, actions,
                                    unmasks,      logprobs,      advantages, reward_sums, ids, slabs};
+    ERL_CRITERION_ENTRY("erl_ppo_step_discrete_f32");
     int rc = check_discrete("erl_ppo_step_discrete_f32", tensors, 14, S, h1, h2, A, H, N, B, n_slabs);
     if (rc) return rc;
     return step_discrete(actor_params, critic_params, act_avg, act_std, cri_avg, cri_std, S, h1, h2, A, states, actions, unmasks, logprobs,
@@ -340,6 +378,7 @@ extern "C" int erl_ppo_update_discrete_f32(float *flat_params, float *exp_avg, f
                                            float lr, float beta1, float beta2, float eps, float max_norm, void *stream)
 {
     const char *what = "erl_ppo_update_discrete_f32";
+    ERL_CRITERION_ENTRY(what);
     const void *const tensors[] = {flat_params, exp_avg, exp_avg_sq, act_avg, act_std, cri_avg, cri_std, states, actions,
                                    unmasks,     logprobs, advantages, reward_sums, ids, slabs, grads};
     int rc = check_discrete(what, tensors, 16, S, h1, h2, A, H, N, B, n_slabs);

@@ -596,7 +596,10 @@ static_assert(kS3LdsBytes <= 160 * 1024, "LDS budget");
 
 // PRE: the W2 image comes ready from memory (g.w2img: built by the update loop, refreshed by clip + Adam) by LDS-DMA under the
 // first layer; otherwise every workgroup splits W2 itself (stand-alone calls of erl_ppo_step_f32)
-template <bool ACTOR, int KXP, int N1, int N2, bool VEC, bool PRE>     // KXP: input tiles of 32 (1: S <= 32, 2: S <= 64); 0: S <= 8
+// CRIT: the critic loss is not MSE (critic_loss.h).  A template parameter in this family: as a run-time branch it cost <2, 4, 4, false, true>
+// two scalar-register spills it did not have (profiles/criterion_kernel_resources.txt); the CRIT = false kernels for S > 8 are the parent's,
+// byte for byte (the five S <= 8 ones moved a few vector registers within the rules: same file)
+template <bool ACTOR, int KXP, int N1, int N2, bool VEC, bool PRE, bool CRIT>     // KXP: input tiles of 32 (1: S <= 32, 2: S <= 64); 0: S <= 8
 __device__ __forceinline__ void ppo_block_s3(const Ppo2Args &g, u8 *smem, SpanStamps &sps, const int slab_ix)
 {
     constexpr bool TINY = KXP == 0;
@@ -979,8 +982,13 @@ __device__ __forceinline__ void ppo_block_s3(const Ppo2Args &g, u8 *smem, SpanSt
     if (!ACTOR) {
         const float diff = Y[0] - xa;
         const bool head = hi == 0;
-        loss0 = head ? diff * diff * um : 0.f;
-        dY[0] = head ? 2.f * diff * um * g.inv_batch : 0.f;
+        if (!CRIT) {
+            loss0 = head ? diff * diff * um : 0.f;
+            dY[0] = head ? 2.f * diff * um * g.inv_batch : 0.f;
+        } else {                                           // args.criterion other than MSELoss (critic_loss.h)
+            loss0 = head ? critic_loss(g.crit_kind, g.crit_beta, diff) * um : 0.f;
+            dY[0] = head ? critic_loss_grad(g.crit_kind, g.crit_beta, diff) * um * g.inv_batch : 0.f;
+        }
     } else {
         float diffv[4], ivar[4];
         float lp = 0.f;
@@ -1367,6 +1375,7 @@ __device__ __forceinline__ void ppo_block_s3(const Ppo2Args &g, u8 *smem, SpanSt
 #endif
 }
 
+// The MSE kernel keeps its name, template list and text (tools and build-time checks find it by them); the other criteria are a kernel of their own, ppo_step_s3_crit_kernel below: the same text around ppo_block_s3<..., true>.
 template <int KX, int N1, int N2, bool VEC, bool PRE>
 __global__ __launch_bounds__(QNT) void ppo_step_s3_kernel(Ppo2Args g)
 {
@@ -1381,17 +1390,37 @@ __global__ __launch_bounds__(QNT) void ppo_step_s3_kernel(Ppo2Args g)
 #else
     const bool as_actor = wg.actor;
 #endif
-    if (as_actor) ppo_block_s3<true, KX, N1, N2, VEC, PRE>(g, smem_s3, sps, wg.slab);
-    else ppo_block_s3<false, KX, N1, N2, VEC, PRE>(g, smem_s3, sps, wg.slab);
+    if (as_actor) ppo_block_s3<true, KX, N1, N2, VEC, PRE, false>(g, smem_s3, sps, wg.slab);
+    else ppo_block_s3<false, KX, N1, N2, VEC, PRE, false>(g, smem_s3, sps, wg.slab);
     span_exit(g, t_span, as_actor ? &sps : nullptr);
 }
 
 template <int KX, int N1, int N2, bool VEC, bool PRE>
+__global__ __launch_bounds__(QNT) void ppo_step_s3_crit_kernel(Ppo2Args g)
+{
+    extern __shared__ __attribute__((aligned(16))) u8 smem_s3[];
+    const SpanT t_span = span_enter(g);
+    if (k6_code_touch(g)) return;
+    SpanStamps sps{reinterpret_cast<uint32_t *>(smem_s3 + kS3LdsBytes - 32)};
+    const K6Wg wg = k6_wg_map(g);
+#if ERL_K6_EXP & 16
+    // (diagnostics) every workgroup on ONE network's code path: do two code paths of 55 KB each on a 64 KB instruction cache matter?
+    const bool as_actor = g.exp_net == 0 || (g.exp_net != 1 && wg.actor);
+#else
+    const bool as_actor = wg.actor;
+#endif
+    if (as_actor) ppo_block_s3<true, KX, N1, N2, VEC, PRE, true>(g, smem_s3, sps, wg.slab);
+    else ppo_block_s3<false, KX, N1, N2, VEC, PRE, true>(g, smem_s3, sps, wg.slab);
+    span_exit(g, t_span, as_actor ? &sps : nullptr);
+}
+
+template <int KX, int N1, int N2, bool VEC, bool PRE, bool CRIT>
 int launch_s3(const Ppo2Args &g, int n_slabs, hipStream_t stream)
 {
+    constexpr auto kernel = CRIT ? ppo_step_s3_crit_kernel<KX, N1, N2, VEC, PRE> : ppo_step_s3_kernel<KX, N1, N2, VEC, PRE>;
     static bool attr_set = false;
     if (!attr_set) {
-        int rc = erl_hip_status(hipFuncSetAttribute((const void *)ppo_step_s3_kernel<KX, N1, N2, VEC, PRE>,
+        int rc = erl_hip_status(hipFuncSetAttribute((const void *)kernel,
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)kS3LdsBytes),
                                 "hipFuncSetAttribute(ppo_step_s3_kernel)");
         if (rc) return rc;
@@ -1413,7 +1442,7 @@ int launch_s3(const Ppo2Args &g, int n_slabs, hipStream_t stream)
                 if (hipMalloc((void **)&d_pc, sizeof(pc)) == hipSuccess) {
                     Ppo2Args q = g;
                     q.code_touch_bytes = 0; q.span = nullptr; q.pc_out = d_pc;
-                    hipLaunchKernelGGL((ppo_step_s3_kernel<KX, N1, N2, VEC, PRE>), dim3(1, 1), dim3(QNT), kS3LdsBytes, stream, q);
+                    hipLaunchKernelGGL(kernel, dim3(1, 1), dim3(QNT), kS3LdsBytes, stream, q);
                     if (hipMemcpyAsync(&pc, d_pc, sizeof(pc), hipMemcpyDeviceToHost, stream) == hipSuccess && hipStreamSynchronize(stream) == hipSuccess && pc)
                         (void)erl_k6_code_range(pc, (size_t)128 << 10, &r.base, &r.bytes);
                     (void)hipFree(d_pc);
@@ -1422,19 +1451,26 @@ int launch_s3(const Ppo2Args &g, int n_slabs, hipStream_t stream)
             }
             t.code_touch = r.base; t.code_touch_bytes = r.base ? r.bytes : 0;
         }
-        hipLaunchKernelGGL((ppo_step_s3_kernel<KX, N1, N2, VEC, PRE>), dim3(n_slabs, g.only_net >= 0 ? 1 : 2), dim3(QNT), kS3LdsBytes, stream, t);
+        hipLaunchKernelGGL(kernel, dim3(n_slabs, g.only_net >= 0 ? 1 : 2), dim3(QNT), kS3LdsBytes, stream, t);
         return erl_hip_status(hipGetLastError(), "erl_ppo_step_f32");
     }
-    hipLaunchKernelGGL((ppo_step_s3_kernel<KX, N1, N2, VEC, PRE>), dim3(n_slabs, g.only_net >= 0 ? 1 : 2), dim3(QNT), kS3LdsBytes, stream, g);
+    hipLaunchKernelGGL(kernel, dim3(n_slabs, g.only_net >= 0 ? 1 : 2), dim3(QNT), kS3LdsBytes, stream, g);
     return erl_hip_status(hipGetLastError(), "erl_ppo_step_f32");
+}
+
+template <int N1, int N2, bool PRE, bool CRIT>
+int launch_s3_shape_crit(const Ppo2Args &g, int n_slabs, bool vec, hipStream_t stream)
+{
+    if (g.S <= 8) return launch_s3<0, N1, N2, false, PRE, CRIT>(g, n_slabs, stream);
+    if (vec) return g.S > 32 ? launch_s3<2, N1, N2, true, PRE, CRIT>(g, n_slabs, stream) : launch_s3<1, N1, N2, true, PRE, CRIT>(g, n_slabs, stream);
+    return g.S > 32 ? launch_s3<2, N1, N2, false, PRE, CRIT>(g, n_slabs, stream) : launch_s3<1, N1, N2, false, PRE, CRIT>(g, n_slabs, stream);
 }
 
 template <int N1, int N2, bool PRE>
 int launch_s3_shape(const Ppo2Args &g, int n_slabs, bool vec, hipStream_t stream)
 {
-    if (g.S <= 8) return launch_s3<0, N1, N2, false, PRE>(g, n_slabs, stream);
-    if (vec) return g.S > 32 ? launch_s3<2, N1, N2, true, PRE>(g, n_slabs, stream) : launch_s3<1, N1, N2, true, PRE>(g, n_slabs, stream);
-    return g.S > 32 ? launch_s3<2, N1, N2, false, PRE>(g, n_slabs, stream) : launch_s3<1, N1, N2, false, PRE>(g, n_slabs, stream);
+    return g.crit_kind == ERL_CRIT_MSE ? launch_s3_shape_crit<N1, N2, PRE, false>(g, n_slabs, vec, stream)
+                                       : launch_s3_shape_crit<N1, N2, PRE, true>(g, n_slabs, vec, stream);
 }
 
 }  // namespace

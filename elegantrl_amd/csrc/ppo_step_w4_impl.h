@@ -633,8 +633,13 @@ __device__ __forceinline__ void ppo_block_w4(const Ppo2Args &g, float *smem)
     if (!ACTOR) {
         const float diff = Y[0] - xa;                     // only (hi = 0, j = 0) is the value head
         const bool head = hi == 0;
-        loss0 = head ? diff * diff * um : 0.f;
-        dY[0] = head ? 2.f * diff * um * g.inv_batch : 0.f;
+        if (g.crit_kind == ERL_CRIT_MSE) {
+            loss0 = head ? diff * diff * um : 0.f;
+            dY[0] = head ? 2.f * diff * um * g.inv_batch : 0.f;
+        } else {                                           // args.criterion other than MSELoss (critic_loss.h)
+            loss0 = head ? critic_loss(g.crit_kind, g.crit_beta, diff) * um : 0.f;
+            dY[0] = head ? critic_loss_grad(g.crit_kind, g.crit_beta, diff) * um * g.inv_batch : 0.f;
+        }
     } else {
         // Normal(mean, exp(std_log)).log_prob(a) = -(a - mean)^2 / (2 var) - log(std) - log(sqrt(2 pi))  with log(std) = std_log
         // and 1 / var = exp(-2 std_log): hardware exp2 / no division (the library expf / logf / IEEE divisions of the

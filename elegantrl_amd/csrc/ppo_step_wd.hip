@@ -91,6 +91,7 @@ int erl_ppo_wd_step(const float *actor_params, const float *critic_params, const
     g.S = S; g.h1 = h1; g.h2 = h2; g.A = A;
     g.ratio_clip = ratio_clip; g.lambda_entropy = lambda_entropy; g.inv_batch = inv_batch;
     g.objective = objective;
+    g.crit_kind = erl_criterion_of_call().kind; g.crit_beta = erl_criterion_of_call().beta;
     g.slabs = slabs;
     g.Pa = Dims{S, h1, h2, A}.count(true);
     g.Pc = Dims{S, h1, h2, 1}.count(false);
@@ -223,6 +224,7 @@ int erl_ppo_wd3_step(const float *actor_params, const float *critic_params, cons
     g.S = S; g.h1 = 256; g.h2 = 128; g.A = A;
     g.ratio_clip = ratio_clip; g.lambda_entropy = lambda_entropy; g.inv_batch = inv_batch;
     g.objective = objective;
+    g.crit_kind = erl_criterion_of_call().kind; g.crit_beta = erl_criterion_of_call().beta;
     g.slabs = slabs;
     g.Pa = Pa; g.Pc = Pc; g.stride = stride;
     g.adv_stats = nullptr;

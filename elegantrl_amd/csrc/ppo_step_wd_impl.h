@@ -816,8 +816,13 @@ __device__ __forceinline__ void ppo_block_wd(const PpoWdArgs &args, u8 *smem, co
     if (!ACTOR) {
         const float diff = Y[0] - xa;
         const bool head = hi == 0;
-        loss0 = head ? diff * diff * um : 0.f;
-        dY[0] = head ? 2.f * diff * um * g.inv_batch : 0.f;
+        if (g.crit_kind == ERL_CRIT_MSE) {
+            loss0 = head ? diff * diff * um : 0.f;
+            dY[0] = head ? 2.f * diff * um * g.inv_batch : 0.f;
+        } else {                                           // args.criterion other than MSELoss (critic_loss.h)
+            loss0 = head ? critic_loss(g.crit_kind, g.crit_beta, diff) * um : 0.f;
+            dY[0] = head ? critic_loss_grad(g.crit_kind, g.crit_beta, diff) * um * g.inv_batch : 0.f;
+        }
     } else {
         float diffv[4], ivar[4];
         float lp = 0.f;

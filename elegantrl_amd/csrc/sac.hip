@@ -110,12 +110,12 @@ __global__ __launch_bounds__(256) void q_label_kernel(const float *__restrict__ 
     label[b] = reward[b] + (undone[b] * gamma) * (m - next_lp[b] * alpha);
 }
 
-// critic objective: td = mean_e (q - label)^2 * unmask; obj = mean_b (td w); dq[e][b] = 2 (q - label) unmask w / (E B), with the
+// critic objective (MSE; another args.criterion: critic_loss.h's l and l' for the square and 2 diff): td = mean_e (q - label)^2 * unmask; obj = mean_b (td w); dq[e][b] = 2 (q - label) unmask w / (E B), with the
 // importance-sampling weights w of prioritised replay (AgentSAC.py:60-62; w = 1 without) and td written out for the priorities
 __global__ __launch_bounds__(256) void critic_loss_kernel(const float *__restrict__ q, const float *__restrict__ label,
                                                           const float *__restrict__ unmask, const float *__restrict__ is_weight,
                                                           const float *__restrict__ fit, int E, int64_t B, float *__restrict__ dq,
-                                                          float *__restrict__ td_out, float *__restrict__ part)
+                                                          float *__restrict__ td_out, float *__restrict__ part, int crit_kind, float crit_beta)
 {
     __shared__ float red[4];
     const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -125,8 +125,14 @@ __global__ __launch_bounds__(256) void critic_loss_kernel(const float *__restric
         float s = 0.f;
         for (int e = 0; e < E; ++e) {
             const float diff = q[(size_t)e * B + b] - l;
-            s += diff * diff;
-            float d = 2.f * diff * um * w / ((float)E * (float)B);
+            float d;
+            if (crit_kind == ERL_CRIT_MSE) {
+                s += diff * diff;
+                d = 2.f * diff * um * w / ((float)E * (float)B);
+            } else {
+                s += critic_loss(crit_kind, crit_beta, diff);
+                d = critic_loss_grad(crit_kind, crit_beta, diff) * um * w / ((float)E * (float)B);
+            }
             if (fit) d += fit[e];                      // the lambda_fit_cum_r term's gradient (fit_cum_r_kernel)
             dq[(size_t)e * B + b] = d;
         }
@@ -139,10 +145,10 @@ __global__ __launch_bounds__(256) void critic_loss_kernel(const float *__restric
 }
 
 // `lambda_fit_cum_r` term of the critic objective (AgentSAC.py:66-68):
-//   obj += lambda * mean_e ( mean_b cum_reward[b] - mean_b q[e][b] )^2
+//   obj += lambda * mean_e ( mean_b cum_reward[b] - mean_b q[e][b] )^2        (the criterion of the call: MSE here, critic_loss.h otherwise)
 // One workgroup: the E + 1 batch means, then fit[e] = d term / d q[e][b] = 2 lambda (qbar_e - cbar) / (E B) and fit[E] = the term.
 __global__ __launch_bounds__(256) void fit_cum_r_kernel(const float *__restrict__ q, const float *__restrict__ cum_reward, int E, int64_t B,
-                                                        float lambda_fit, float *__restrict__ fit)
+                                                        float lambda_fit, float *__restrict__ fit, int crit_kind, float crit_beta)
 {
     __shared__ float red[4];
     float c = 0.f;
@@ -154,8 +160,13 @@ __global__ __launch_bounds__(256) void fit_cum_r_kernel(const float *__restrict_
         for (int64_t i = threadIdx.x; i < B; i += 256) s += q[(size_t)e * B + i];
         const float qbar = block_sum(s, red) / (float)B;
         const float diff = cbar - qbar;
-        term += diff * diff;
-        if (threadIdx.x == 0) fit[e] = 2.f * lambda_fit * (qbar - cbar) / ((float)E * (float)B);
+        if (crit_kind == ERL_CRIT_MSE) {
+            term += diff * diff;
+            if (threadIdx.x == 0) fit[e] = 2.f * lambda_fit * (qbar - cbar) / ((float)E * (float)B);
+        } else {                                       // d term / d q[e][b] = lambda l'(cbar - qbar) (-1 / B) / E
+            term += critic_loss(crit_kind, crit_beta, diff);
+            if (threadIdx.x == 0) fit[e] = -(lambda_fit * critic_loss_grad(crit_kind, crit_beta, diff)) / ((float)E * (float)B);
+        }
     }
     if (threadIdx.x == 0) fit[E] = lambda_fit * term / (float)E;
 }
@@ -473,9 +484,9 @@ int sac_step_layered(const SacCall &c, const SacDims &d, const SacStep &st)
     hipLaunchKernelGGL(concat_kernel, dim3(grid1d(B * (S + A))), blk, 0, s, c.state, c.action, S, A, B, xa);
     if ((rc = critic_forward(s, d, c.critic, B, xa, cw, true))) return rc;
     const bool fit_on = c.lambda_fit_cum_r != 0.f;                     // AgentSAC.py:66-68 (off by default: config.py:52)
-    if (fit_on) hipLaunchKernelGGL(fit_cum_r_kernel, dim3(1), blk, 0, s, cw.q, c.cum_reward, E, B, c.lambda_fit_cum_r, fit);
+    if (fit_on) hipLaunchKernelGGL(fit_cum_r_kernel, dim3(1), blk, 0, s, cw.q, c.cum_reward, E, B, c.lambda_fit_cum_r, fit, c.crit_kind, c.crit_beta);
     hipLaunchKernelGGL(critic_loss_kernel, rows_grid, blk, 0, s, cw.q, label, c.unmask, st.is_weight, fit_on ? fit : (const float *)nullptr, E, B, dq,
-                       st.td_error_out, part);
+                       st.td_error_out, part, c.crit_kind, c.crit_beta);
     hipLaunchKernelGGL(sum_kernel, dim3(1), blk, 0, s, part, (int64_t)nparts, 1.0f / (float)B, 0.f, st.objs_out,
                        fit_on ? fit + E : (const float *)nullptr);
     if (batched) {
@@ -697,7 +708,7 @@ int sac_single(const char *what, const SacCall &c, const SacStep &st, bool sampl
 #define SAC_CALL(...)                                                                                                                         \
     SacCall{actor_params, critic_params, target_params, alpha_log, actor_m, actor_v, critic_m, critic_v, alpha_m, alpha_v, S, A, hidden, n_hidden, E, \
             state, action, reward, undone, unmask, next_state, B, gamma, target_entropy, tau, lr, beta1, beta2, eps_adam, max_norm, seed, workspace,   \
-            workspace_bytes, stream, __VA_ARGS__}
+            workspace_bytes, stream, __VA_ARGS__, erl_criterion_of_call().kind, erl_criterion_of_call().beta}
 
 extern "C" int erl_sac_update_f32(float *actor_params, float *critic_params, float *target_params, float *alpha_log, float *actor_m,
                                   float *actor_v, float *critic_m, float *critic_v, float *alpha_m, float *alpha_v, int S, int A,
@@ -708,6 +719,7 @@ extern "C" int erl_sac_update_f32(float *actor_params, float *critic_params, flo
                                   float target_entropy, float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm,
                                   int32_t step, float *objs_out, void *workspace, int64_t workspace_bytes, void *stream)
 {
+    ERL_CRITERION_ENTRY("erl_sac_update_f32");
     const SacCall c = SAC_CALL(ERL_SAC_ACTOR_SAC, nullptr, cum_reward, lambda_fit_cum_r, false);
     return sac_single("erl_sac_update_f32", c, SacStep{nullptr, is_weight, td_error_out, eps_next, eps_cur, counter, step, true, step, objs_out}, false);
 }
@@ -724,6 +736,7 @@ extern "C" int erl_sac_update_opt_f32(float *actor_params, float *critic_params,
                                       int32_t step, float *objs_out, void *workspace, int64_t workspace_bytes, const ErlSacOptions *opt,
                                       void *stream)
 {
+    ERL_CRITERION_ENTRY("erl_sac_update_opt_f32");
     const SacCall c = SAC_CALL(opt ? opt->actor_variant : ERL_SAC_ACTOR_SAC, opt ? opt->actor_target_params : nullptr, cum_reward, lambda_fit_cum_r, false);
     const SacStep st{nullptr, is_weight, td_error_out, eps_next, eps_cur, counter, step, opt ? opt->update_actor != 0 : true,
                      opt && opt->actor_step > 0 ? opt->actor_step : step, objs_out};
@@ -739,6 +752,7 @@ extern "C" int erl_sac_update_ring_f32(float *actor_params, float *critic_params
                                        float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step, float *objs_out,
                                        void *workspace, int64_t workspace_bytes, void *stream)
 {
+    ERL_CRITERION_ENTRY("erl_sac_update_ring_f32");
     const SacCall c = SAC_CALL(ERL_SAC_ACTOR_SAC, nullptr, nullptr, 0.f, false);
     return sac_single("erl_sac_update_ring_f32", c, SacStep{ring, nullptr, nullptr, eps_next, eps_cur, counter, step, true, step, objs_out}, true);
 }
@@ -752,6 +766,7 @@ extern "C" int erl_sac_update_ring_loop_f32(float *actor_params, float *critic_p
                                             float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step0,
                                             float *objs_all, void *workspace, int64_t workspace_bytes, void *stream)
 {
+    ERL_CRITERION_ENTRY("erl_sac_update_ring_loop_f32");
     ERL_REQUIRE(ids_all, "erl_sac_update_ring_loop_f32: bad argument (NULL ids_all)");
     const SacCall c = SAC_CALL(ERL_SAC_ACTOR_SAC, nullptr, nullptr, 0.f, false);
     return sac_loop("erl_sac_update_ring_loop_f32", c, SacStep{ring, nullptr, nullptr, nullptr, nullptr, counter0, step0, true, step0, objs_all},
@@ -770,6 +785,7 @@ extern "C" int erl_sac_update_per_loop_f32(float *actor_params, float *critic_pa
                                            float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step0,
                                            float *objs_all, void *workspace, int64_t workspace_bytes, void *stream)
 {
+    ERL_CRITERION_ENTRY("erl_sac_update_per_loop_f32");
     if (int rc = per_loop_refusals("erl_sac_update_per_loop_f32", ring, per, objs_all, n_steps, step0, S, A, B)) return rc;
     const SacCall c = SAC_CALL(ERL_SAC_ACTOR_SAC, nullptr, nullptr, 0.f, false);
     return sac_loop("erl_sac_update_per_loop_f32", c, SacStep{ring, per->is_weight, per->td_error, nullptr, nullptr, counter0, step0, true, step0, objs_all},
@@ -792,6 +808,7 @@ extern "C" int erl_sac_update_mod_f32(float *actor_params, float *critic_params,
                                       float eps_adam, float max_norm, int32_t step, int32_t update_actor, int32_t actor_step,
                                       float *actor_target_params, float *objs_out, void *workspace, int64_t workspace_bytes, void *stream)
 {
+    ERL_CRITERION_ENTRY("erl_sac_update_mod_f32");
     const SacCall c = SAC_CALL(ERL_SAC_ACTOR_FIX, actor_target_params, nullptr, 0.f, true);
     const SacStep st{nullptr, is_weight, td_error_out, eps_next, eps_cur, counter, step, update_actor != 0, actor_step, objs_out};
     return sac_single("erl_sac_update_mod_f32", c, st, false);
@@ -806,6 +823,7 @@ extern "C" int erl_sac_update_mod_ring_f32(float *actor_params, float *critic_pa
                                            int32_t actor_step, float *actor_target_params, float *objs_out, void *workspace,
                                            int64_t workspace_bytes, void *stream)
 {
+    ERL_CRITERION_ENTRY("erl_sac_update_mod_ring_f32");
     const SacCall c = SAC_CALL(ERL_SAC_ACTOR_FIX, actor_target_params, nullptr, 0.f, true);
     const SacStep st{ring, nullptr, nullptr, eps_next, eps_cur, counter, step, update_actor != 0, actor_step, objs_out};
     return sac_single("erl_sac_update_mod_ring_f32", c, st, true);
@@ -821,6 +839,7 @@ extern "C" int erl_sac_update_mod_ring_loop_f32(float *actor_params, float *crit
                                                 int32_t actor_step0, double critic_value, float *actor_target_params, float *objs_all,
                                                 int32_t *actor_updates_out, void *workspace, int64_t workspace_bytes, void *stream)
 {
+    ERL_CRITERION_ENTRY("erl_sac_update_mod_ring_loop_f32");
     ERL_REQUIRE(ids_all, "erl_sac_update_mod_ring_loop_f32: NULL tensor");
     const SacCall c = SAC_CALL(ERL_SAC_ACTOR_FIX, actor_target_params, nullptr, 0.f, true);
     return sac_loop("erl_sac_update_mod_ring_loop_f32", c, SacStep{ring, nullptr, nullptr, nullptr, nullptr, counter0, step0, false, actor_step0, objs_all},
@@ -841,6 +860,7 @@ extern "C" int erl_sac_update_mod_per_loop_f32(float *actor_params, float *criti
                                                int32_t *actor_updates_out, int32_t draw_in_step, void *workspace, int64_t workspace_bytes,
                                                void *stream)
 {
+    ERL_CRITERION_ENTRY("erl_sac_update_mod_per_loop_f32");
     const char *const what = "erl_sac_update_mod_per_loop_f32";
     ERL_REQUIRE(draw_in_step == 0 || draw_in_step == 1, "%s: draw_in_step=%d (0: erl_per_sample_rows_f32 per step, 1: inside the step)", what,
                 (int)draw_in_step);
@@ -859,6 +879,7 @@ extern "C" int erl_sac_update_per_draw_loop_f32(float *actor_params, float *crit
                                                 float tau, float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step0,
                                                 float *objs_all, void *workspace, int64_t workspace_bytes, void *stream)
 {
+    ERL_CRITERION_ENTRY("erl_sac_update_per_draw_loop_f32");
     const char *const what = "erl_sac_update_per_draw_loop_f32";
     if (int rc = per_loop_refusals(what, ring, per, objs_all, n_steps, step0, S, A, B)) return rc;
     const SacCall c = SAC_CALL(ERL_SAC_ACTOR_SAC, nullptr, nullptr, 0.f, true);

@@ -648,6 +648,7 @@ struct CriticArgs {
     const float *qt;                         // [E][B] target q of the next state
     const float *reward, *undone, *unmask, *lp_next, *is_weight, *alpha0;
     float gamma;
+    int crit_kind;                           // ERL_CRIT_*: the call's critic loss (critic_loss.h; MODE 1's dq, MODE 2's td), read by the CRIT kernels only
     float *label, *dq;                       // (B,), [E][B]
     float *xa, *enc, *H1e, *dZ1e, *dEncE;    // (B, S+A), (B, h0), [E](B, h1), [E](B, h1), [E](B, h0)
     // MODE 2
@@ -670,6 +671,7 @@ struct CriticArgs {
     // goes to dEncP[E * split](B, h0) and the LAST of the four to arrive (arrive[tile * E + e], re-armed by it) adds the shares in slice
     // order into dEncE.  A workgroup streams 64 KB of the decoder (forward) + 64 KB (transposed) instead of 256 + 256 KB through one CU.
     int h1_full;                             // the decoder's hidden width when d.h1 is a slice's (0: d.h1)
+    float crit_beta;                         // crit_kind's threshold.  Both fields sit in what was padding: no member moved, the struct kept its size
     unsigned long long *qx;
     uint32_t nonce, spin_limit;
     float *dEncP;
@@ -679,7 +681,10 @@ struct CriticArgs {
 
 // (the training pass on decoder SLICES -- MODE 1, C1 = 0 -- capped at two workgroups per CU, 128 registers and 52 bytes of scratch, measured
 // slower than this build, one workgroup per CU without scratch: 22.0 against 20.7 us, profiles/r06_sac_train_split_ab.txt)
-template <int MODE, int C0, int C1>
+// CRIT: the critic loss is not MSE (critic_loss.h).  A template parameter in this family: as a run-time branch it cost the training and the
+// policy-gradient pass one to four more scalar-register spills and config 3 0.3 % of its step (profiles/criterion_default_route_ab.txt);
+// the CRIT = false kernels are the parent's code
+template <int MODE, int C0, int C1, bool CRIT = false>
 __global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(2))) void critic_tile_kernel(CriticArgs g)
 {
     __shared__ TileLds lds;
@@ -827,7 +832,8 @@ __global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(2))) void cr
                 if (first) g.label[b] = lab;
                 // td = mean_e (q - label)^2 * unmask; obj = mean_b (td w): dq = 2 (q - label) unmask w / (E B)   (:57-62)
                 const float w = g.is_weight ? p_w : 1.f;
-                dqv = 2.f * (qv - lab) * p_unm * w / ((float)E * (float)B);
+                if (!CRIT) dqv = 2.f * (qv - lab) * p_unm * w / ((float)E * (float)B);
+                else dqv = critic_loss_grad(g.crit_kind, g.crit_beta, qv - lab) * p_unm * w / ((float)E * (float)B);
                 if (fo == 0) g.dq[(size_t)e * B + b] = dqv;
             } else {
                 dqv = -1.0f / ((float)E * (float)B);               // L = -(mean_b mean_e q - alpha mean_b logprob)   (:82-84)
@@ -849,7 +855,8 @@ __global__ __launch_bounds__(FT) __attribute__((amdgpu_waves_per_eu(2))) void cr
                 for (int k = 0; k < FMAXE; ++k) {
                     if (k >= E) continue;
                     const float diff = p_qe[k] - lab;
-                    s2 += diff * diff;
+                    if (!CRIT) s2 += diff * diff;
+                    else s2 += critic_loss(g.crit_kind, g.crit_beta, diff);
                 }
                 td = (s2 / (float)E) * p_unm;
                 if (g.td_out) g.td_out[b] = td;
@@ -1099,6 +1106,8 @@ struct SkipFinishArgs {
     float *td_out, *objs_out, *alpha_log;               // (B,) or NULL, [2], [1]
     int E, ntiles;
     int64_t B;
+    int crit_kind;                                      // ERL_CRIT_* and its threshold (critic_loss.h)
+    float crit_beta;
 };
 __global__ __launch_bounds__(1024) void sac_skip_finish_kernel(SkipFinishArgs g)
 {
@@ -1112,7 +1121,8 @@ __global__ __launch_bounds__(1024) void sac_skip_finish_kernel(SkipFinishArgs g)
             float s2 = 0.f;
             for (int k = 0; k < g.E; ++k) {
                 const float diff = g.qc[(size_t)k * g.B + b] - lab;
-                s2 += diff * diff;
+                if (g.crit_kind == ERL_CRIT_MSE) s2 += diff * diff;
+                else s2 += critic_loss(g.crit_kind, g.crit_beta, diff);
             }
             td = (s2 / (float)g.E) * g.unmask[b];
             if (g.td_out) g.td_out[b] = td;
@@ -1826,6 +1836,9 @@ int erl_sac_step_fused(const SacCall &c, const SacDims &sd, const SacStep &st)
 #define LAUNCH_CRITIC0(K0, K1) LAUNCH_CRITIC(0, K0, K1)
 #define LAUNCH_CRITIC1(K0, K1) LAUNCH_CRITIC(1, K0, K1)
 #define LAUNCH_CRITIC2(K0, K1) LAUNCH_CRITIC(2, K0, K1)
+#define LAUNCH_CRITIC1C(K0, K1) hipLaunchKernelGGL((critic_tile_kernel<1, K0, K1, true>), cg, blk, 0, s, ca)
+#define LAUNCH_CRITIC2C(K0, K1) hipLaunchKernelGGL((critic_tile_kernel<2, K0, K1, true>), cg, blk, 0, s, ca)
+    const bool crit_mse = c.crit_kind == ERL_CRIT_MSE;
     FUSED_KT_DISPATCH_D(dsl, LAUNCH_CRITIC0)
     // ---- (3) critic training pass: labels, loss gradient, backward to the encoder output                      (:53-62)
     // (split like (2) whenever there is a slot: its workgroups exchange q inside the launch -- CriticArgs::qx; at config 3 22 us a launch
@@ -1840,9 +1853,10 @@ int erl_sac_step_fused(const SacCall &c, const SacDims &sd, const SacStep &st)
     }
     ca.P = critic_params; ca.Xs = state; ca.Xa = action; ca.q = qc;
     ca.qt = qt; ca.reward = reward; ca.undone = undone; ca.unmask = unmask; ca.lp_next = lp_next; ca.is_weight = is_weight; ca.alpha0 = alpha0;
-    ca.gamma = c.gamma; ca.label = label; ca.dq = dq; ca.xa = xa; ca.enc = enc; ca.H1e = H1e; ca.dZ1e = dZ1e; ca.dEncE = dEncE;
+    ca.gamma = c.gamma; ca.crit_kind = c.crit_kind; ca.crit_beta = c.crit_beta; ca.label = label; ca.dq = dq; ca.xa = xa; ca.enc = enc; ca.H1e = H1e; ca.dZ1e = dZ1e; ca.dEncE = dEncE;
     ca.span = erl_span_slot(ERL_SPAN_SAC_CRITIC_TRAIN, (int64_t)cg.x * cg.y);
-    FUSED_KT_DISPATCH_D(ca.d, LAUNCH_CRITIC1)
+    if (crit_mse) { FUSED_KT_DISPATCH_D(ca.d, LAUNCH_CRITIC1) }
+    else { FUSED_KT_DISPATCH_D(ca.d, LAUNCH_CRITIC1C) }
     ca.span = nullptr; ca.h1_full = 0;
     // ---- (4) every critic weight / bias gradient in one launch, and the temperature's step (workgroup 0)
     {
@@ -1870,7 +1884,7 @@ int erl_sac_step_fused(const SacCall &c, const SacDims &sd, const SacStep &st)
         // clip + Adam or actor-target update -- actor_params, its moments and the actor target are not touched
         SkipFinishArgs sf{};
         sf.qc = qc; sf.label = label; sf.unmask = unmask; sf.is_weight = is_weight; sf.td_out = td_error_out; sf.objs_out = objs_out;
-        sf.alpha_log = alpha_log; sf.E = E; sf.ntiles = tiles; sf.B = B;
+        sf.alpha_log = alpha_log; sf.E = E; sf.ntiles = tiles; sf.B = B; sf.crit_kind = c.crit_kind; sf.crit_beta = c.crit_beta;
         hipLaunchKernelGGL(sac_skip_finish_kernel, dim3(1), dim3(1024), 0, s, sf);
         return erl_hip_status(hipGetLastError(), "erl_sac_update_mod_f32(fused: skipped actor)");
     }
@@ -1879,7 +1893,8 @@ int erl_sac_step_fused(const SacCall &c, const SacDims &sd, const SacStep &st)
     ca.d = dsl; ca.split = split; ca.qt_split = 1;
     ca.P = target_params; ca.Xs = state; ca.Xa = act_pg; ca.q = q_pg;
     ca.dAct = dAct; ca.qpart = qpart; ca.qc = qc; ca.label_in = label; ca.td_out = td_error_out; ca.tdpart = tdpart;
-    FUSED_KT_DISPATCH_D(dsl, LAUNCH_CRITIC2)
+    if (crit_mse) { FUSED_KT_DISPATCH_D(dsl, LAUNCH_CRITIC2) }
+    else { FUSED_KT_DISPATCH_D(dsl, LAUNCH_CRITIC2C) }
     // ---- (8) actor backward, (9) its weight gradients, (10) clip + Adam, alpha clamp                            (:80-85)
     {
         ActorBwdArgs ab{};

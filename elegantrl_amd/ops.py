@@ -12,13 +12,20 @@ from typing import Optional, Sequence, Tuple
 import torch as th
 
 from . import _hip
-from ._hip import check, flag_ptr, lib, ptr, stream_ptr
+from ._hip import CRITERION_MSE, call_with_criterion, check, flag_ptr, lib, ptr, stream_ptr
 
 TEN = th.Tensor
 _ALGO = {"auto": _hip.GAE_ALGO_AUTO, "exact": _hip.GAE_ALGO_EXACT, "chunked": _hip.GAE_ALGO_CHUNKED,
          "lookback": _hip.GAE_ALGO_LOOKBACK}
 
 _workspaces = {}
+
+
+def _update_call(name: str, criterion, *args) -> None:
+    """an update entry under the critic loss `criterion` = (kind, threshold) (include/erl_hip.h, ERL_CRIT_*; AgentBase.criterion_code).  The
+    arguments are evaluated by the caller before this runs, and a call that ctypes refuses before it reaches the entry takes the pending
+    criterion back (_hip.call_with_criterion): it cannot fall to another call."""
+    check(call_with_criterion(getattr(lib(), name), criterion, *args), name)
 
 
 def _workspace(device: th.device, nbytes: int) -> TEN:
@@ -396,18 +403,17 @@ def ppo_arith_in_use(S: int, h1: int, h2: int, A: int) -> str:
 def ppo_step(actor_params: TEN, critic_params: TEN, act_avg: TEN, act_std: TEN, cri_avg: TEN, cri_std: TEN, S: int, h1: int,
              h2: int, A: int, states: TEN, actions: TEN, unmasks: TEN, logprobs: TEN, advantages: TEN, reward_sums: TEN,
              ids: TEN, ratio_clip: float, lambda_entropy: float, inv_batch: float, slabs: TEN, n_slabs: int,
-             objective: int = 0) -> None:
+             objective: int = 0, *, criterion=CRITERION_MSE) -> None:
     """`objective`: _hip.PPO_OBJ_REFERENCE (AgentPPO.py:199) / PPO_OBJ_CANONICAL (textbook clip) / PPO_OBJ_A2C (AgentPPO.py:296-303)"""
     H, N = states.shape[0], states.shape[1]
     need = n_slabs * lib().erl_ppo_slab_stride(S, h1, h2, A)
     if slabs.numel() < need:
         raise ValueError(f"slabs holds {slabs.numel()} floats, erl_ppo_step_f32 writes n_slabs x erl_ppo_slab_stride = {need}")
-    check(lib().erl_ppo_step_f32(ptr(actor_params, th.float32), ptr(critic_params, th.float32), ptr(act_avg), ptr(act_std),
+    _update_call("erl_ppo_step_f32", criterion, ptr(actor_params, th.float32), ptr(critic_params, th.float32), ptr(act_avg), ptr(act_std),
                                  ptr(cri_avg), ptr(cri_std), S, h1, h2, A, ptr(states, th.float32), ptr(actions, th.float32),
                                  flag_ptr(unmasks), ptr(logprobs, th.float32), ptr(advantages, th.float32),
                                  ptr(reward_sums, th.float32), H, N, ptr(ids, th.int64), ids.numel(), ratio_clip,
-                                 lambda_entropy, inv_batch, int(objective), ptr(slabs, th.float32), n_slabs, stream_ptr()),
-          "erl_ppo_step_f32")
+                                 lambda_entropy, inv_batch, int(objective), ptr(slabs, th.float32), n_slabs, stream_ptr())
 
 
 def grad_reduce(slabs: TEN, n_slabs: int, stride: int, flat_grad: TEN) -> None:
@@ -481,7 +487,7 @@ def ppo_update(flat_params: TEN, exp_avg: TEN, exp_avg_sq: TEN, act_avg: TEN, ac
                h1: int, h2: int, A: int, states: TEN, actions: TEN, unmasks: TEN, logprobs: TEN, advantages: TEN, reward_sums: TEN,
                ids: TEN, ratio_clip: float, lambda_entropy: float, slabs: TEN, grads: TEN, first_step: int, lr: float,
                max_norm: float, betas=(0.9, 0.999), eps: float = 1e-8, comm=None, objective: int = 0, adv_stats: Optional[TEN] = None,
-               adv_partials: Optional[TEN] = None, n_partials: int = 0) -> None:
+               adv_partials: Optional[TEN] = None, n_partials: int = 0, *, criterion=CRITERION_MSE) -> None:
     """the whole minibatch loop of AgentPPO.update_net in one C call; ids: (update_times, B).  `comm` (a
     parallel.RcclComm) puts the gradient all-reduce inside the loop, on the same stream (data-parallel ranks).
     `adv_stats` (8 float64: the raw sums left by gae_scan(stats=...) or the rollout's epilogue): `advantages` are then RAW
@@ -490,7 +496,7 @@ def ppo_update(flat_params: TEN, exp_avg: TEN, exp_avg_sq: TEN, act_avg: TEN, ac
     H, N = states.shape[0], states.shape[1]
     update_times, B = ids.shape
     assert grads.shape[0] >= update_times and slabs.shape[0] == ppo_num_slabs(B)
-    check(lib().erl_ppo_update_dp_f32(ptr(flat_params, th.float32), ptr(exp_avg, th.float32), ptr(exp_avg_sq, th.float32),
+    _update_call("erl_ppo_update_dp_f32", criterion, ptr(flat_params, th.float32), ptr(exp_avg, th.float32), ptr(exp_avg_sq, th.float32),
                                       ptr(act_avg), ptr(act_std), ptr(cri_avg), ptr(cri_std), S, h1, h2, A, ptr(states, th.float32),
                                       ptr(actions, th.float32), flag_ptr(unmasks), ptr(logprobs, th.float32),
                                       ptr(advantages, th.float32), ptr(reward_sums, th.float32), H, N, ptr(ids, th.int64), B,
@@ -499,8 +505,7 @@ def ppo_update(flat_params: TEN, exp_avg: TEN, exp_avg_sq: TEN, act_avg: TEN, ac
                                       first_step, lr, betas[0], betas[1], eps, max_norm,
                                       None if adv_stats is None else ptr(adv_stats, th.float64),
                                       None if adv_partials is None else ptr(adv_partials, th.float64), int(n_partials),
-                                      None if comm is None else comm.handle, stream_ptr()),
-          "erl_ppo_update_dp_f32")
+                                      None if comm is None else comm.handle, stream_ptr())
 
 
 # ------------------------------------------------------------------------------------------------
@@ -582,18 +587,17 @@ def mlpn_rollout_step(params: TEN, spec: MlpSpecN, state_avg: TEN, state_std: TE
 
 def mlpn_ppo_step(actor_params: TEN, critic_params: TEN, act_avg: TEN, act_std: TEN, cri_avg: TEN, cri_std: TEN, spec: MlpSpecN,
                   states: TEN, actions: TEN, unmasks: TEN, logprobs: TEN, advantages: TEN, reward_sums: TEN, ids: TEN,
-                  ratio_clip: float, lambda_entropy: float, inv_batch: float, flat_grad: TEN, objective: int = 0) -> None:
+                  ratio_clip: float, lambda_entropy: float, inv_batch: float, flat_grad: TEN, objective: int = 0, *, criterion=CRITERION_MSE) -> None:
     """one PPO minibatch for networks of any depth; `flat_grad` receives [actor | critic | 3 objectives, 0]."""
     H, N = states.shape[0], states.shape[1]
     B = ids.numel()
     ws = _workspace(states.device, spec.workspace_bytes(B, True))
     c, n = spec.cdims
-    check(lib().erl_mlpn_ppo_step_f32(ptr(actor_params, th.float32), ptr(critic_params, th.float32), ptr(act_avg), ptr(act_std),
+    _update_call("erl_mlpn_ppo_step_f32", criterion, ptr(actor_params, th.float32), ptr(critic_params, th.float32), ptr(act_avg), ptr(act_std),
                                       ptr(cri_avg), ptr(cri_std), c, n, ptr(states, th.float32), ptr(actions, th.float32),
                                       flag_ptr(unmasks), ptr(logprobs, th.float32), ptr(advantages, th.float32),
                                       ptr(reward_sums, th.float32), H, N, ptr(ids, th.int64), B, ratio_clip, lambda_entropy,
-                                      inv_batch, int(objective), ptr(flat_grad, th.float32), ptr(ws), ws.numel(), stream_ptr()),
-          "erl_mlpn_ppo_step_f32")
+                                      inv_batch, int(objective), ptr(flat_grad, th.float32), ptr(ws), ws.numel(), stream_ptr())
 
 
 def mlpn_rollout_step_discrete(params: TEN, spec: MlpSpecN, state_avg: TEN, state_std: TEN, state: TEN, *,
@@ -615,18 +619,17 @@ def mlpn_rollout_step_discrete(params: TEN, spec: MlpSpecN, state_avg: TEN, stat
 
 def mlpn_ppo_step_discrete(actor_params: TEN, critic_params: TEN, act_avg: TEN, act_std: TEN, cri_avg: TEN, cri_std: TEN,
                            spec: MlpSpecN, states: TEN, actions: TEN, unmasks: TEN, logprobs: TEN, advantages: TEN, reward_sums: TEN,
-                           ids: TEN, ratio_clip: float, lambda_entropy: float, inv_batch: float, flat_grad: TEN) -> None:
+                           ids: TEN, ratio_clip: float, lambda_entropy: float, inv_batch: float, flat_grad: TEN, *, criterion=CRITERION_MSE) -> None:
     """one PPO minibatch of the categorical policy; actions (H, N) int32."""
     H, N = states.shape[0], states.shape[1]
     B = ids.numel()
     ws = _workspace(states.device, spec.workspace_bytes(B, True))
     c, n = spec.cdims
-    check(lib().erl_mlpn_ppo_step_discrete_f32(ptr(actor_params, th.float32), ptr(critic_params, th.float32), ptr(act_avg), ptr(act_std),
+    _update_call("erl_mlpn_ppo_step_discrete_f32", criterion, ptr(actor_params, th.float32), ptr(critic_params, th.float32), ptr(act_avg), ptr(act_std),
                                                ptr(cri_avg), ptr(cri_std), c, n, ptr(states, th.float32), ptr(actions, th.int32),
                                                flag_ptr(unmasks), ptr(logprobs, th.float32), ptr(advantages, th.float32),
                                                ptr(reward_sums, th.float32), H, N, ptr(ids, th.int64), B, ratio_clip, lambda_entropy,
-                                               inv_batch, ptr(flat_grad, th.float32), ptr(ws), ws.numel(), stream_ptr()),
-          "erl_mlpn_ppo_step_discrete_f32")
+                                               inv_batch, ptr(flat_grad, th.float32), ptr(ws), ws.numel(), stream_ptr())
 
 
 def ppo_discrete_supported(S: int, h1: int, h2: int, A: int) -> bool:
@@ -641,25 +644,24 @@ def ppo_discrete_slab_stride(S: int, h1: int, h2: int, A: int) -> int:
 
 def ppo_step_discrete(actor_params: TEN, critic_params: TEN, act_avg: TEN, act_std: TEN, cri_avg: TEN, cri_std: TEN, S: int, h1: int,
                       h2: int, A: int, states: TEN, actions: TEN, unmasks: TEN, logprobs: TEN, advantages: TEN, reward_sums: TEN,
-                      ids: TEN, ratio_clip: float, lambda_entropy: float, inv_batch: float, slabs: TEN, n_slabs: int) -> None:
+                      ids: TEN, ratio_clip: float, lambda_entropy: float, inv_batch: float, slabs: TEN, n_slabs: int, *, criterion=CRITERION_MSE) -> None:
     """one PPO minibatch of the categorical policy in one launch, into `slabs` (n_slabs, ppo_discrete_slab_stride); actions (H, N)
     int32, `advantages` already normalised.  `grad_reduce(slabs, n_slabs, stride, row)` sums the slabs."""
     H, N = states.shape[0], states.shape[1]
     need = n_slabs * ppo_discrete_slab_stride(S, h1, h2, A)
     if need >= 0 and slabs.numel() < need:
         raise ValueError(f"slabs holds {slabs.numel()} floats, erl_ppo_step_discrete_f32 writes n_slabs x erl_ppo_discrete_slab_stride = {need}")
-    check(lib().erl_ppo_step_discrete_f32(ptr(actor_params, th.float32), ptr(critic_params, th.float32), ptr(act_avg), ptr(act_std),
+    _update_call("erl_ppo_step_discrete_f32", criterion, ptr(actor_params, th.float32), ptr(critic_params, th.float32), ptr(act_avg), ptr(act_std),
                                           ptr(cri_avg), ptr(cri_std), S, h1, h2, A, ptr(states, th.float32), ptr(actions, th.int32),
                                           flag_ptr(unmasks), ptr(logprobs, th.float32), ptr(advantages, th.float32),
                                           ptr(reward_sums, th.float32), H, N, ptr(ids, th.int64), ids.numel(), ratio_clip,
-                                          lambda_entropy, inv_batch, ptr(slabs, th.float32), n_slabs, stream_ptr()),
-          "erl_ppo_step_discrete_f32")
+                                          lambda_entropy, inv_batch, ptr(slabs, th.float32), n_slabs, stream_ptr())
 
 
 def ppo_update_discrete(flat_params: TEN, exp_avg: TEN, exp_avg_sq: TEN, act_avg: TEN, act_std: TEN, cri_avg: TEN, cri_std: TEN, S: int,
                         h1: int, h2: int, A: int, states: TEN, actions: TEN, unmasks: TEN, logprobs: TEN, advantages: TEN,
                         reward_sums: TEN, ids: TEN, ratio_clip: float, lambda_entropy: float, slabs: TEN, grads: TEN, first_step: int,
-                        lr: float, max_norm: float, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+                        lr: float, max_norm: float, betas=(0.9, 0.999), eps: float = 1e-8, *, criterion=CRITERION_MSE) -> None:
     """the whole minibatch loop of AgentDiscretePPO.update_net in one C call; ids: (update_times, B), `advantages` already normalised.
     Per minibatch: ppo_step_discrete, grad_reduce into grads[k], grad_sq_partials, clip_adam_partials at step first_step + k."""
     H, N = states.shape[0], states.shape[1]
@@ -669,13 +671,12 @@ def ppo_update_discrete(flat_params: TEN, exp_avg: TEN, exp_avg_sq: TEN, act_avg
     if stride >= 0 and (slabs.numel() < n_slabs * stride or grads.numel() < update_times * stride or grads.shape[-1] != stride):
         raise ValueError(f"slabs {tuple(slabs.shape)} / grads {tuple(grads.shape)}: erl_ppo_update_discrete_f32 needs rows of {stride} floats, "
                          f"{update_times} gradient rows")
-    check(lib().erl_ppo_update_discrete_f32(ptr(flat_params, th.float32), ptr(exp_avg, th.float32), ptr(exp_avg_sq, th.float32),
+    _update_call("erl_ppo_update_discrete_f32", criterion, ptr(flat_params, th.float32), ptr(exp_avg, th.float32), ptr(exp_avg_sq, th.float32),
                                             ptr(act_avg), ptr(act_std), ptr(cri_avg), ptr(cri_std), S, h1, h2, A,
                                             ptr(states, th.float32), ptr(actions, th.int32), flag_ptr(unmasks), ptr(logprobs, th.float32),
                                             ptr(advantages, th.float32), ptr(reward_sums, th.float32), H, N, ptr(ids, th.int64), B,
                                             update_times, ratio_clip, lambda_entropy, ptr(slabs, th.float32), n_slabs,
-                                            ptr(grads, th.float32), first_step, lr, betas[0], betas[1], eps, max_norm, stream_ptr()),
-          "erl_ppo_update_discrete_f32")
+                                            ptr(grads, th.float32), first_step, lr, betas[0], betas[1], eps, max_norm, stream_ptr())
 
 
 # ------------------------------------------------------------------------------------------------
@@ -794,7 +795,7 @@ def sac_update(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: T
                step: int, *, gamma: float, target_entropy: float, tau: float, lr: float, max_norm: float, objs_out: TEN,
                noises: Optional[Tuple[TEN, TEN]] = None, seed: int = 0, counter: int = 0, betas=(0.9, 0.999), eps: float = 1e-8,
                is_weight: Optional[TEN] = None, td_error_out: Optional[TEN] = None, cum_reward: Optional[TEN] = None,
-               lambda_fit_cum_r: float = 0.0, update_actor: bool = True, actor_step: int = 0, actor_target: Optional[TEN] = None) -> None:
+               lambda_fit_cum_r: float = 0.0, update_actor: bool = True, actor_step: int = 0, actor_target: Optional[TEN] = None, criterion=CRITERION_MSE) -> None:
     """one AgentSAC.update_objectives step after the sample; `moments` = (actor_m, actor_v, critic_m, critic_v, alpha_m,
     alpha_v); `batch` = (state, action, reward, undone, unmask, next_state); objs_out: float32[2] on the device.
     `cum_reward` (B,) + `lambda_fit_cum_r`: the critic's fit-the-batch's-mean-return term (AgentSAC.py:66-68)."""
@@ -808,39 +809,37 @@ def sac_update(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: T
         # AgentModSAC's step (include/erl_hip.h, ErlSacOptions): ActorFixSAC's head, the actor skipped by the two-time-scale rule, the
         # actor optimiser's own step count, the actor target's soft update
         opt = _SacOptions(spec.actor_variant, int(bool(update_actor)), int(actor_step), 0, ptr(actor_target, th.float32))
-        check(lib().erl_sac_update_opt_f32(*args, ws, ws_bytes, ctypes.byref(opt), stream), "erl_sac_update_opt_f32")
+        _update_call("erl_sac_update_opt_f32", criterion, *args, ws, ws_bytes, ctypes.byref(opt), stream)
         return
-    check(lib().erl_sac_update_f32(*args, ws, ws_bytes, stream), "erl_sac_update_f32")
+    _update_call("erl_sac_update_f32", criterion, *args, ws, ws_bytes, stream)
 
 
 def sac_update_from_ring(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring: Sequence[TEN],
                          ids: TEN, sample_len: int, stage: ReplayStage, step: int, *, gamma: float, target_entropy: float, tau: float, lr: float,
                          max_norm: float, objs_out: TEN, noises: Optional[Tuple[TEN, TEN]] = None, seed: int = 0, counter: int = 0,
-                         betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+                         betas=(0.9, 0.999), eps: float = 1e-8, criterion=CRITERION_MSE) -> None:
     """ReplayBuffer.sample(ids) + one AgentSAC.update_objectives step from ONE call (erl_sac_update_ring_f32): `ring` = the buffer's
     ReplayRing (interleaved block) or its five planar tensors (states, actions, rewards, undones, unmasks), `stage` receives the batch (stage.out / stage.ids: what replay_sample would have left)."""
     B = ids.numel()
     rs, dev = _ring_sample(spec, ring, ids, sample_len, stage, B)
     n_next, n_cur = (None, None) if noises is None else noises
-    check(lib().erl_sac_update_ring_f32(*_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs), *_sac_stage(stage), B,
+    _update_call("erl_sac_update_ring_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs), *_sac_stage(stage), B,
                                         ptr(n_next), ptr(n_cur), *_sac_hyper(seed, counter, gamma, target_entropy, tau, lr, betas, eps, max_norm),
-                                        step, ptr(objs_out, th.float32), *_sac_tail(spec, dev, B)),
-          "erl_sac_update_ring_f32")
+                                        step, ptr(objs_out, th.float32), *_sac_tail(spec, dev, B))
 
 
 def sac_update_ring_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring, ids_all: TEN,
                          sample_len: int, stage: ReplayStage, step0: int, *, gamma: float, target_entropy: float, tau: float, lr: float,
-                         max_norm: float, objs_all: TEN, seed: int = 0, counter0: int = 0, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+                         max_norm: float, objs_all: TEN, seed: int = 0, counter0: int = 0, betas=(0.9, 0.999), eps: float = 1e-8, criterion=CRITERION_MSE) -> None:
     """`ids_all.shape[0]` steps of sac_update_from_ring from ONE C call (erl_sac_update_ring_loop_f32): step t uses ids_all[t], optimiser
     step step0 + t, noise counter counter0 + t, and writes objs_all[t]; `stage` ends up holding the last step's batch and ids0 / ids1."""
     T, B = ids_all.shape
     assert ids_all.is_contiguous() and objs_all.shape == (T, 2) and objs_all.is_contiguous()
     rs, dev = _ring_sample(spec, ring, None, sample_len, stage, B)
-    check(lib().erl_sac_update_ring_loop_f32(*_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs),
+    _update_call("erl_sac_update_ring_loop_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs),
                                              ptr(ids_all, th.int64), T, *_sac_stage(stage), B,
                                              *_sac_hyper(seed, counter0, gamma, target_entropy, tau, lr, betas, eps, max_norm), int(step0),
-                                             ptr(objs_all, th.float32), *_sac_tail(spec, dev, B)),
-          "erl_sac_update_ring_loop_f32")
+                                             ptr(objs_all, th.float32), *_sac_tail(spec, dev, B))
 
 
 def sac_mod_fused_supported(spec: SacSpec, B: int) -> bool:
@@ -857,40 +856,38 @@ def sac_update_mod(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_lo
                    step: int, *, gamma: float, target_entropy: float, tau: float, lr: float, max_norm: float, objs_out: TEN,
                    update_actor: bool, actor_step: int, actor_target: Optional[TEN], noises: Optional[Tuple[TEN, TEN]] = None, seed: int = 0,
                    counter: int = 0, betas=(0.9, 0.999), eps: float = 1e-8, is_weight: Optional[TEN] = None,
-                   td_error_out: Optional[TEN] = None) -> None:
+                   td_error_out: Optional[TEN] = None, criterion=CRITERION_MSE) -> None:
     """one AgentModSAC.update_objectives step after the sample on the FUSED step (erl_sac_update_mod_f32): sac_update's arguments without
     the cum_reward term; `update_actor` False leaves the actor, its moments and `actor_target` untouched and writes nan to objs_out[1]"""
     B = batch[0].shape[0]
     n_next, n_cur = (None, None) if noises is None else noises
-    check(lib().erl_sac_update_mod_f32(*_sac_head(spec, actor, critic, target, alpha_log, moments), *_sac_batch(batch), ptr(is_weight),
+    _update_call("erl_sac_update_mod_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), *_sac_batch(batch), ptr(is_weight),
                                        ptr(td_error_out), B, ptr(n_next), ptr(n_cur),
                                        *_sac_hyper(seed, counter, gamma, target_entropy, tau, lr, betas, eps, max_norm), step,
                                        int(bool(update_actor)), int(actor_step), ptr(actor_target, th.float32), ptr(objs_out, th.float32),
-                                       *_sac_tail(spec, batch[0].device, B)),
-          "erl_sac_update_mod_f32")
+                                       *_sac_tail(spec, batch[0].device, B))
 
 
 def sac_update_mod_from_ring(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring, ids: TEN,
                              sample_len: int, stage: ReplayStage, step: int, *, gamma: float, target_entropy: float, tau: float, lr: float,
                              max_norm: float, objs_out: TEN, update_actor: bool, actor_step: int, actor_target: Optional[TEN],
                              noises: Optional[Tuple[TEN, TEN]] = None, seed: int = 0, counter: int = 0, betas=(0.9, 0.999),
-                             eps: float = 1e-8) -> None:
+                             eps: float = 1e-8, criterion=CRITERION_MSE) -> None:
     """sac_update_from_ring for AgentModSAC's fused step (erl_sac_update_mod_ring_f32): the sample rides in the step's first launch"""
     B = ids.numel()
     rs, dev = _ring_sample(spec, ring, ids, sample_len, stage, B)
     n_next, n_cur = (None, None) if noises is None else noises
-    check(lib().erl_sac_update_mod_ring_f32(*_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs), *_sac_stage(stage),
+    _update_call("erl_sac_update_mod_ring_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs), *_sac_stage(stage),
                                             B, ptr(n_next), ptr(n_cur),
                                             *_sac_hyper(seed, counter, gamma, target_entropy, tau, lr, betas, eps, max_norm), step,
                                             int(bool(update_actor)), int(actor_step), ptr(actor_target, th.float32), ptr(objs_out, th.float32),
-                                            *_sac_tail(spec, dev, B)),
-          "erl_sac_update_mod_ring_f32")
+                                            *_sac_tail(spec, dev, B))
 
 
 def sac_update_mod_ring_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring, ids_all: TEN,
                              sample_len: int, stage: ReplayStage, step0: int, actor_step0: int, critic_value: float, *, gamma: float,
                              target_entropy: float, tau: float, lr: float, max_norm: float, objs_all: TEN, actor_target: Optional[TEN],
-                             seed: int = 0, counter0: int = 0, betas=(0.9, 0.999), eps: float = 1e-8) -> int:
+                             seed: int = 0, counter0: int = 0, betas=(0.9, 0.999), eps: float = 1e-8, criterion=CRITERION_MSE) -> int:
     """AgentModSAC's whole update_net loop from ONE C call (erl_sac_update_mod_ring_loop_f32): step t = sac_update_mod_from_ring on
     ids_all[t], optimiser step step0 + t, noise counter counter0 + t, objs_all[t]; the two-time-scale rule is evaluated in C, the actor's
     Adam count runs on from `actor_step0`.  Returns the number of actor updates."""
@@ -898,19 +895,18 @@ def sac_update_mod_ring_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN
     assert ids_all.is_contiguous() and objs_all.shape == (T, 2) and objs_all.is_contiguous()
     rs, dev = _ring_sample(spec, ring, None, sample_len, stage, B)
     updates = ctypes.c_int32(0)
-    check(lib().erl_sac_update_mod_ring_loop_f32(*_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs),
+    _update_call("erl_sac_update_mod_ring_loop_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs),
                                                  ptr(ids_all, th.int64), T, *_sac_stage(stage), B,
                                                  *_sac_hyper(seed, counter0, gamma, target_entropy, tau, lr, betas, eps, max_norm), int(step0),
                                                  int(actor_step0), float(critic_value), ptr(actor_target, th.float32), ptr(objs_all, th.float32),
-                                                 ctypes.byref(updates), *_sac_tail(spec, dev, B)),
-          "erl_sac_update_mod_ring_loop_f32")
+                                                 ctypes.byref(updates), *_sac_tail(spec, dev, B))
     return int(updates.value)
 
 
 def sac_update_per_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring: ReplayRing,
                         trees: PerTrees, uniform_all: TEN, cur_size: int, cursor: int, per_alpha: float, per_beta: float, stage: ReplayStage,
                         per_stage: PerStage, step0: int, *, gamma: float, target_entropy: float, tau: float, lr: float, max_norm: float,
-                        objs_all: TEN, seed: int = 0, counter0: int = 0, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+                        objs_all: TEN, seed: int = 0, counter0: int = 0, betas=(0.9, 0.999), eps: float = 1e-8, criterion=CRITERION_MSE) -> None:
     """`uniform_all.shape[0]` prioritised steps from ONE C call (erl_sac_update_per_loop_f32): step t = per_sample_rows(uniform_all[t]), the
     step sac_update runs with is_weight / td_error_out, per_update_index; optimiser step step0 + t, noise counter counter0 + t,
     objs_all[t].  `stage` / `per_stage` end up holding the last step's batch, ids0 / ids1, indices, weights and td errors."""
@@ -923,10 +919,9 @@ def sac_update_per_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alp
     pr = _PerSample(ptr(trees.sum, f32), ptr(trees.min, f32), trees.max_size, trees.num_seqs, int(cur_size), int(cursor), float(per_alpha),
                     float(per_beta), ptr(uniform_all, f32), ptr(per_stage.is_index, th.int64), ptr(per_stage.is_weight, f32),
                     ptr(per_stage.td_error, f32))
-    check(lib().erl_sac_update_per_loop_f32(*_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs), ctypes.addressof(pr),
+    _update_call("erl_sac_update_per_loop_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs), ctypes.addressof(pr),
                                             T, *_sac_stage(stage), B, *_sac_hyper(seed, counter0, gamma, target_entropy, tau, lr, betas, eps, max_norm),
-                                            int(step0), ptr(objs_all, f32), *_sac_tail(spec, dev, B)),
-          "erl_sac_update_per_loop_f32")
+                                            int(step0), ptr(objs_all, f32), *_sac_tail(spec, dev, B))
 
 
 def _per_loop_structs(spec: SacSpec, ring: ReplayRing, trees: PerTrees, uniform_all: TEN, cur_size: int, cursor: int, per_alpha: float,
@@ -948,34 +943,32 @@ def sac_update_mod_per_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN,
                             trees: PerTrees, uniform_all: TEN, cur_size: int, cursor: int, per_alpha: float, per_beta: float, stage: ReplayStage,
                             per_stage: PerStage, step0: int, actor_step0: int, critic_value: float, *, gamma: float, target_entropy: float,
                             tau: float, lr: float, max_norm: float, objs_all: TEN, actor_target: Optional[TEN], draw_in_step: bool = False,
-                            seed: int = 0, counter0: int = 0, betas=(0.9, 0.999), eps: float = 1e-8) -> int:
+                            seed: int = 0, counter0: int = 0, betas=(0.9, 0.999), eps: float = 1e-8, criterion=CRITERION_MSE) -> int:
     """AgentModSAC's whole prioritised update_net loop from ONE C call (erl_sac_update_mod_per_loop_f32): sac_update_per_loop's steps on the
     fused ModSAC step, the two-time-scale rule evaluated in C and the actor's Adam count running on from `actor_step0` as in
     sac_update_mod_ring_loop; the trees are updated behind every step, a skipped actor step included.  `draw_in_step`: the draw and the
     gather ride in the step's first launch instead of a launch of their own.  Returns the number of actor updates."""
     T, B, rs, pr, dev = _per_loop_structs(spec, ring, trees, uniform_all, cur_size, cursor, per_alpha, per_beta, stage, per_stage, objs_all)
     updates = ctypes.c_int32(0)
-    check(lib().erl_sac_update_mod_per_loop_f32(*_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs),
+    _update_call("erl_sac_update_mod_per_loop_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs),
                                                 ctypes.addressof(pr), T, *_sac_stage(stage), B,
                                                 *_sac_hyper(seed, counter0, gamma, target_entropy, tau, lr, betas, eps, max_norm), int(step0),
                                                 int(actor_step0), float(critic_value), ptr(actor_target, th.float32), ptr(objs_all, th.float32),
-                                                ctypes.byref(updates), int(bool(draw_in_step)), *_sac_tail(spec, dev, B)),
-          "erl_sac_update_mod_per_loop_f32")
+                                                ctypes.byref(updates), int(bool(draw_in_step)), *_sac_tail(spec, dev, B))
     return int(updates.value)
 
 
 def sac_update_per_draw_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring: ReplayRing,
                              trees: PerTrees, uniform_all: TEN, cur_size: int, cursor: int, per_alpha: float, per_beta: float, stage: ReplayStage,
                              per_stage: PerStage, step0: int, *, gamma: float, target_entropy: float, tau: float, lr: float, max_norm: float,
-                             objs_all: TEN, seed: int = 0, counter0: int = 0, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+                             objs_all: TEN, seed: int = 0, counter0: int = 0, betas=(0.9, 0.999), eps: float = 1e-8, criterion=CRITERION_MSE) -> None:
     """sac_update_per_loop with the draw + gather inside every step's first launch (erl_sac_update_per_draw_loop_f32: the fused step only);
     the same arguments, the same bits in everything it leaves"""
     T, B, rs, pr, dev = _per_loop_structs(spec, ring, trees, uniform_all, cur_size, cursor, per_alpha, per_beta, stage, per_stage, objs_all)
-    check(lib().erl_sac_update_per_draw_loop_f32(*_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs),
+    _update_call("erl_sac_update_per_draw_loop_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs),
                                                  ctypes.addressof(pr), T, *_sac_stage(stage), B,
                                                  *_sac_hyper(seed, counter0, gamma, target_entropy, tau, lr, betas, eps, max_norm), int(step0),
-                                                 ptr(objs_all, th.float32), *_sac_tail(spec, dev, B)),
-          "erl_sac_update_per_draw_loop_f32")
+                                                 ptr(objs_all, th.float32), *_sac_tail(spec, dev, B))
 
 
 def sac_explore_action(spec: SacSpec, actor: TEN, state: TEN, *, noise: Optional[TEN] = None, seed: int = 0, counter: int = 0,

@@ -470,6 +470,24 @@ ERL_API int erl_rollout_discrete_acrobot_gae_f32(const float *actor_params, cons
 #define ERL_PPO_MODE(objective, arith) ((objective) | ((arith) << 8))
 ERL_API int erl_ppo_set_arith(int arith);
 ERL_API int erl_ppo_arith_in_use(int S, int h1, int h2, int A);   /* ERL_PPO_ARITH_F32 or _SPLIT for this shape under the current setting */
+/* The critic's loss, the reference's args.criterion (elegantrl/agents/AgentBase.py:62) with reduction = 'none' (csrc/critic_loss.h):
+ *   ERL_CRIT_MSE        torch.nn.MSELoss             l(d) = d d
+ *   ERL_CRIT_SMOOTH_L1  torch.nn.SmoothL1Loss(beta)  l(d) = |d| < beta ? 0.5 d d / beta : |d| - 0.5 beta
+ *   ERL_CRIT_HUBER      torch.nn.HuberLoss(delta)    l(d) = |d| <= delta ? 0.5 d d : delta (|d| - 0.5 delta)
+ * with d = prediction - target, in every critic objective of the library: erl_ppo_step_f32, erl_ppo_update_f32, erl_ppo_update_dp_f32,
+ * erl_mlpn_ppo_step_f32, erl_mlpn_ppo_step_discrete_f32, erl_ppo_step_discrete_f32, erl_ppo_update_discrete_f32 and the ten
+ * erl_sac_update*_f32 entries (the td term, td_error_out -- hence prioritised replay's priorities -- and the lambda_fit_cum_r term).
+ * PER CALL, like the arithmetic mode since ABI 17, but those entries' argument lists are pinned by their callers, so the two scalars
+ * travel beside the call: erl_criterion_next_call(criterion, criterion_beta) names the criterion of the NEXT of those entries that the
+ * calling thread enters; that entry takes it -- whether it then succeeds or not -- and the thread is back at MSE.  A call that nothing
+ * precedes is an MSE call: existing callers see no change.  The entry validates what it took and refuses, under its own name, an unknown
+ * criterion, a criterion_beta that is not finite, and a criterion_beta <= 0 for kinds 1 and 2.  State is per thread; nothing is
+ * process-wide.  (Added within ABI 23: symbols added, none changed -- so a library built before this entry existed passes the version check
+ * of a binding that knows it and fails at symbol lookup instead; elegantrl_amd/_hip.py says so by name.) */
+#define ERL_CRIT_MSE 0
+#define ERL_CRIT_SMOOTH_L1 1
+#define ERL_CRIT_HUBER 2
+ERL_API int erl_criterion_next_call(int32_t criterion, float criterion_beta);
 /* Where the split-arithmetic minibatch kernels' workgroups run (csrc/ppo_step.h, k6_wg_map).  Workgroups go to the 8 XCDs round-robin by
  * linear id and, inside an XCD, to its 4 shader engines round-robin: map 0 (network = blockIdx.y) puts both networks' workgroups -- two
  * ~55 KB code paths -- behind every 64 KB instruction cache; map 1 = the actor's workgroups on XCDs 0-3, the critic's on 4-7; map 2 = the

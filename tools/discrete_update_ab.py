@@ -33,6 +33,7 @@ ap.add_argument("--repeat", type=float, default=1024.0)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--regions", type=int, default=7)
 ap.add_argument("--calls", type=int, default=3)
+ap.add_argument("--criterion", choices=["mse", "smooth_l1", "huber"], default="mse", help="args.criterion of both arms (reduction='none', torch's default threshold)")
 opt = ap.parse_args()
 N, H, B = opt.envs, opt.horizon, opt.batch
 update_times = int(H * opt.repeat / B)              # AgentPPO.update_net's own count
@@ -55,6 +56,7 @@ def build(S, A, net, fused):
                                            "if_discrete": True})
     args.net_dims, args.fused_update, args.random_seed = net, fused, 0
     args.horizon_len, args.batch_size, args.repeat_times = H, B, opt.repeat
+    args.criterion = {"mse": th.nn.MSELoss, "smooth_l1": th.nn.SmoothL1Loss, "huber": th.nn.HuberLoss}[opt.criterion](reduction="none")
     th.manual_seed(0)
     return AgentDiscretePPO(args.net_dims, S, A, gpu_id=0, args=args)
 

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Registers, scratch, LDS and code bytes of the kernels in liberl_hip.so whose (demangled) name contains a pattern, read from the gfx950
 code objects' metadata notes and symbol tables; with --hash also a digest of each kernel's machine code (to tell whether a kernel
-came out unchanged between two builds of the library).
-    python tools/kernel_resources.py PATTERN [lib] [--hash]"""
+came out unchanged between two builds of the library), with --spills also the compiler's counts of spilled scalar and vector registers.
+    python tools/kernel_resources.py PATTERN [lib] [--hash] [--spills]"""
 import hashlib
 import os
 import re
@@ -25,6 +25,7 @@ def main():
     pattern = args[0] if args else "rollout"
     lib = args[1] if len(args) > 1 else os.path.join(ROOT, "elegantrl_amd", "lib", "liberl_hip.so")
     want_hash = "--hash" in sys.argv
+    want_spills = "--spills" in sys.argv
     data = open(lib, "rb").read()
 
 
@@ -68,14 +69,17 @@ def main():
                             start = text_off + addr - text_addr
                             digest = hashlib.sha1(blob[start:start + sz]).hexdigest()[:12]
                         rows.append((p[7], int(kv.get("vgpr_count", -1)), int(kv.get("agpr_count", -1)), int(kv.get("sgpr_count", -1)),
-                                     int(kv.get("private_segment_fixed_size", -1)), int(kv.get("group_segment_fixed_size", -1)), sz, digest))
+                                     int(kv.get("private_segment_fixed_size", -1)), int(kv.get("group_segment_fixed_size", -1)), sz, digest,
+                                     int(kv.get("sgpr_spill_count", -1)), int(kv.get("vgpr_spill_count", -1))))
             pos = data.find(MAGIC, pos + len(MAGIC))
     names = demangle([r[0] for r in rows])
-    print(f"{'vgpr':>5}{'agpr':>5}{'sgpr':>5}{'scratch':>8}{'lds':>7}{'code':>8}  kernel")
+    spill_head = f"{'s_spl':>6}{'v_spl':>6}" if want_spills else ""
+    print(f"{'vgpr':>5}{'agpr':>5}{'sgpr':>5}{'scratch':>8}{'lds':>7}{'code':>8}{spill_head}  kernel")
     for r, name in sorted(set(zip(rows, names)), key=lambda x: x[1]):
         name = name.replace("(anonymous namespace)::", "")
         if pattern in name:
-            print(f"{r[1]:5d}{r[2]:5d}{r[3]:5d}{r[4]:8d}{r[5]:7d}{r[6]:8d}  {name[:110]}" + (f"  {r[7]}" if r[7] else ""))
+            spills = f"{r[8]:6d}{r[9]:6d}" if want_spills else ""
+            print(f"{r[1]:5d}{r[2]:5d}{r[3]:5d}{r[4]:8d}{r[5]:7d}{r[6]:8d}{spills}  {name[:110]}" + (f"  {r[7]}" if r[7] else ""))
 
 
 if __name__ == "__main__":

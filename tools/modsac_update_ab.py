@@ -35,6 +35,7 @@ ap.add_argument("--steps", type=int, default=64)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--regions", type=int, default=7)
 ap.add_argument("--calls", type=int, default=3)
+ap.add_argument("--criterion", choices=["mse", "smooth_l1", "huber"], default="mse", help="args.criterion of both arms (reduction='none', torch's default threshold)")
 opt = ap.parse_args()
 N, ROWS, B = opt.envs, opt.rows, opt.batch
 if not th.cuda.is_available():
@@ -52,6 +53,7 @@ ROUTES = {"layered": dict(fused_step=False), "fused": dict(fused_step=True), "fu
 def build(S, A, net, items, **switches):
     args = Config(AgentModSAC, None, {"env_name": "ab", "num_envs": N, "max_step": 1000, "state_dim": S, "action_dim": A, "if_discrete": False})
     args.net_dims, args.batch_size, args.random_seed, args.num_ensembles = list(net), B, 0, 8
+    args.criterion = {"mse": th.nn.MSELoss, "smooth_l1": th.nn.SmoothL1Loss, "huber": th.nn.HuberLoss}[opt.criterion](reduction="none")
     for k, v in switches.items():
         setattr(args, k, v)
     th.manual_seed(0)
