@@ -202,6 +202,12 @@ _SIGNATURES = {
                                                       c_uint64, c_float] + [_P] * 8 + [_P] * 8 + [c_int64, c_float, c_float, c_int, _P]),
     "erl_rollout_discrete_acrobot_gae_f32": (c_int, [_P] * 3 + [c_int] * 4 + [_P] * 4 + [c_int, c_uint64, c_int64, c_int64, _P, c_uint64,
                                                      c_uint64, c_float] + [_P] * 8 + [_P] * 8 + [c_int64, c_float, c_float, c_int, _P]),
+    "erl_mountaincar_step_f32": (c_int, [_P] * 7 + [c_int64, c_int, c_uint64, _P]),
+    "erl_rollout_discrete_mountaincar_f32": (c_int, [_P] * 3 + [c_int] * 4 + [_P] * 3 + [c_int, c_uint64, c_int64, c_int64, _P, c_uint64,
+                                                     c_uint64, c_float] + [_P] * 9),
+    "erl_rollout_discrete_mountaincar_gae_f32": (c_int, [_P] * 3 + [c_int] * 4 + [_P] * 3 + [c_int, c_uint64, c_int64, c_int64, _P, c_uint64,
+                                                         c_uint64, c_float] + [_P] * 8 + [_P] * 8 + [c_int64, c_float, c_float, c_int, _P]),
+    "erl_eval_discrete_mountaincar_f32": (c_int, [_P] * 3 + [c_int] * 4 + [_P] * 3 + [c_int, c_uint64, c_int64, c_int64, _P, c_int64, _P]),
     "erl_ppo_discrete_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "erl_ppo_discrete_slab_stride": (c_int64, [c_int, c_int, c_int, c_int]),
     "erl_ppo_step_discrete_f32": (c_int, [_P] * 6 + [c_int] * 4 + [_P] * 6 + [c_int64, c_int64, _P, c_int64, c_float, c_float, c_float, _P,

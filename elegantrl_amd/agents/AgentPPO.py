@@ -830,12 +830,12 @@ class AgentDiscretePPO(AgentPPO):
     path: logits from the layered path's MFMA GEMMs, inverse-CDF sampling / log-prob and the clipped-scale objective
     with its state-dependent entropy in hand-written kernels (erl_mlpn_rollout_step_discrete_f32,
     erl_mlpn_ppo_step_discrete_f32).  Rollout dtypes as the reference: actions (H, N) int32, env receives int64.
-    On an env that offers `fused_rollout_discrete` / `fused_evaluate_discrete` (CartPoleGpuVecEnv, AcrobotGpuVecEnv) the whole rollout and the whole
+    On an env that offers `fused_rollout_discrete` / `fused_evaluate_discrete` (CartPoleGpuVecEnv, AcrobotGpuVecEnv, MountainCarGpuVecEnv) the whole rollout and the whole
     evaluation are one launch each (csrc/rollout_discrete.hip) for two hidden layers of 32..128 in steps of 32."""
     _discrete = True
     _actor_class = ActorDiscretePPO
     # the one-launch discrete rollout / evaluation is opt-in -- args.fused_rollout = True or ERL_FUSED_ROLLOUT=1 (DESIGN.md section 9);
-    # profiles/discrete_rollout_ab.txt holds its timing against the per-step loop on both envs, the default has not been flipped yet
+    # profiles/discrete_rollout_ab.txt holds its timing against the per-step loop on the three envs, the default has not been flipped yet
     _fused_rollout_default = "0"
     # the fused minibatch kernel + one-call update loop (csrc/ppo_step_discrete.hip): on by default, since profiles/discrete_update_ab.txt
     # has its median below the layered loop's at all three shapes of tools/discrete_update_ab.py (DESIGN.md section 9);
@@ -877,7 +877,7 @@ class AgentDiscretePPO(AgentPPO):
         dims, S, A = list(self.net_dims), self.state_dim, self.action_dim
         ok = self._one_launch_shape()
         if ok and self.fused_rollout:
-            route = "one-launch rollout and evaluation on envs that offer fused_rollout_discrete (CartPoleGpuVecEnv, AcrobotGpuVecEnv)"
+            route = "one-launch rollout and evaluation on envs that offer fused_rollout_discrete (CartPoleGpuVecEnv, AcrobotGpuVecEnv, MountainCarGpuVecEnv)"
         elif ok:
             route = "per-step rollout loop (args.fused_rollout is off, the default for discrete agents; the shape has the one-launch route)"
         else:

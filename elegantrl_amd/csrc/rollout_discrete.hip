@@ -1,20 +1,21 @@
-// Discrete PPO on the device: the per-step kernels of the discrete envs (CartPole-v1, Acrobot-v1), and the one-launch rollout /
-// evaluation of the categorical policy on either of them.
+// Discrete PPO on the device: the per-step kernels of the discrete envs (CartPole-v1, Acrobot-v1, MountainCar-v0), and the one-launch
+// rollout / evaluation of the categorical policy on any of them.
 //
-// Every extern "C" entry is one statement that forwards to the body of its form, templated on the env:
-//   erl_cartpole_step_f32 / erl_acrobot_step_f32    rd_step<Env>: env_step_kernel<Env>, one thread per env: cartpole_step.h /
-//                                                   acrobot_step.h on the live state, reward / flag rows out.
-//   erl_rollout_discrete_{cartpole,acrobot}_f32     rd_rollout<Env, false>: all H steps of AgentDiscretePPO._explore_vec_env in ONE launch
+// Every extern "C" entry is one statement that forwards to the body of its form, templated on the env (<env>: cartpole, acrobot,
+// mountaincar):
+//   erl_cartpole_step_f32 / erl_acrobot_step_f32 /  rd_step<Env>: env_step_kernel<Env>, one thread per env: cartpole_step.h /
+//   erl_mountaincar_step_f32                        acrobot_step.h / mountaincar_step.h on the live state, reward / flag rows out.
+//   erl_rollout_discrete_<env>_f32                  rd_rollout<Env, false>: all H steps of AgentDiscretePPO._explore_vec_env in ONE launch
 //                                                   (rollout_discrete_kernel<Env, false>).
-//   erl_rollout_discrete_{cartpole,acrobot}_gae_f32 rd_rollout<Env, true>: the rollout with a second phase in the same launch (GAE_): the
+//   erl_rollout_discrete_<env>_gae_f32              rd_rollout<Env, true>: the rollout with a second phase in the same launch (GAE_): the
 //                                                   critic's values of every visited state and of the final one, get_advantages, reward
 //                                                   sums and the partial sums of the advantage normalisation (below, "The GAE_ form").
-//   erl_eval_discrete_{cartpole,acrobot}_f32        rd_eval<Env>: the evaluation form (EV_): the greedy policy argmax(logits), per-episode
+//   erl_eval_discrete_<env>_f32                     rd_eval<Env>: the evaluation form (EV_): the greedy policy argmax(logits), per-episode
 //                                                   accounts (eval_ws.h) instead of buffer rows.
 // The arguments travel in three packs (RdHead: policy and env up to N, H; RdPlanes: the rollout's draws and planes; RdGaeTail: the GAE_
 // form's twelve); rd_fill checks the head for every form, and the kernel's argument is filled in one place per pack.
 //
-// The env behind the kernels is a trait (CartPoleEnv, AcrobotEnv below): P physical floats per env, an S-wide observation, how an env's
+// The env behind the kernels is a trait (CartPoleEnv, AcrobotEnv, MountainCarEnv below): P physical floats per env, an S-wide observation, how an env's
 // thread loads and stores both, how it forms the observation from the physical state, the action of an int64, and a step that returns
 // the reward.  A further env costs a header with its step, one such struct, its extern "C" forwards (include/erl_hip.h, _hip._SIGNATURES)
 // and one Python subclass of _DiscreteGpuVecEnv (envs/vec_envs.py).
@@ -55,6 +56,7 @@
 #include "eval_ws.h"
 #include "gae_step.h"
 #include "mlp_chain.h"
+#include "mountaincar_step.h"
 #include <type_traits>
 
 namespace {
@@ -175,6 +177,37 @@ struct AcrobotEnv {                         // the physical state (theta1, theta
                                                  bool &term, bool &trunc)
     {
         return acrobot_step(p, act, sc, ep, max_step, seed, env, term, trunc);
+    }
+};
+
+struct MountainCarEnv {                     // the observation IS the physical state (position, velocity); the reward is -1 on every step
+    static constexpr int P = 2, S = 2, A = 3;
+    static constexpr const char *kName = "MountainCar";
+    static __device__ __forceinline__ void load(const float *env_state, const float *, int64_t row, float (&p)[P], float (&ob)[S])
+    {
+        const float2 v = *reinterpret_cast<const float2 *>(env_state + 2 * row);
+        p[0] = ob[0] = v.x; p[1] = ob[1] = v.y;
+    }
+    static __device__ __forceinline__ int action(int64_t a) { return a == 0 ? 0 : (a == 2 ? 2 : 1); }
+    static __device__ __forceinline__ void observe(const float (&p)[P], float (&ob)[S]) { ob[0] = p[0]; ob[1] = p[1]; }
+    static __device__ __forceinline__ void store_obs(float *dst, const float (&ob)[S])
+    {
+        *reinterpret_cast<float2 *>(dst) = make_float2(ob[0], ob[1]);
+    }
+    static __device__ __forceinline__ void load_obs(const float *src, float (&ob)[S])          // what store_obs wrote (GAE_ form)
+    {
+        const float2 v = *reinterpret_cast<const float2 *>(src);
+        ob[0] = v.x; ob[1] = v.y;
+    }
+    static __device__ __forceinline__ void store(float *env_state, float *, int64_t row, const float (&p)[P], const float (&ob)[S])
+    {
+        *reinterpret_cast<float2 *>(env_state + 2 * row) = make_float2(p[0], p[1]);
+    }
+    static __device__ __forceinline__ float step(float (&p)[P], int act, int &sc, int &ep, int max_step, uint64_t seed, uint32_t env,
+                                                 bool &term, bool &trunc)
+    {
+        mountaincar_step(p, act, sc, ep, max_step, seed, env, term, trunc);
+        return -1.0f;
     }
 };
 
@@ -337,7 +370,7 @@ __device__ __forceinline__ void rd_values(const float *W1, const float *W2, cons
         for (int c = 0; c < S; ++c) xn[c] = (ob[u][c] - avg[c]) / den[c];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            float w = own ? xn[c] : 0.f;
+            float w = (own && c < S) ? xn[c < S ? c : 0] : 0.f;      // (S < 4: elements S .. 3 are zero operands)
 #pragma unroll
             for (int qq = 1; 4 * qq < S; ++qq) {
                 const float up = 4 * qq + c < S ? __shfl(xn[4 * qq + c < S ? 4 * qq + c : 0], l15, 64) : 0.f;
@@ -421,7 +454,7 @@ __global__ __launch_bounds__(256) void rollout_discrete_kernel(std::conditional_
         for (int c = 0; c < S; ++c) xn[c] = (ob[c] - avg[c]) / den[c];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            float v = own ? xn[c] : 0.f;
+            float v = (own && c < S) ? xn[c < S ? c : 0] : 0.f;      // (S < 4: elements S .. 3 are zero operands)
 #pragma unroll
             for (int qq = 1; 4 * qq < S; ++qq) {
                 const float up = 4 * qq + c < S ? __shfl(xn[4 * qq + c < S ? 4 * qq + c : 0], l15, 64) : 0.f;
@@ -804,4 +837,54 @@ extern "C" int erl_eval_discrete_acrobot_f32(const float *actor_params, const fl
     return rd_eval<AcrobotEnv>("erl_eval_discrete_acrobot_f32",
                                {actor_params, act_avg, act_std, S, h1, h2, A, phys, obs, step_count, episode, max_step, env_seed, N, H}, workspace,
                                workspace_bytes, stream);
+}
+
+// ---- MountainCar-v0: env_state (N, 2) = (position, velocity) is both live buffers
+extern "C" int erl_mountaincar_step_f32(float *state, const int64_t *action, int32_t *step_count, int32_t *episode, float *reward,
+                                        uint8_t *terminal, uint8_t *truncate, int64_t N, int max_step, uint64_t seed, void *stream)
+{
+    return rd_step<MountainCarEnv>("erl_mountaincar_step_f32", state, state, action, step_count, episode, reward, terminal, truncate, N, max_step,
+                                   seed, stream);
+}
+
+extern "C" int erl_rollout_discrete_mountaincar_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2,
+                                                    int A, float *env_state, int32_t *step_count, int32_t *episode, int max_step,
+                                                    uint64_t env_seed, int64_t N, int64_t H, const float *uniform, uint64_t seed,
+                                                    uint64_t counter0, float reward_scale, float *out_states, int32_t *out_actions,
+                                                    float *out_logprobs, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks,
+                                                    float *out_last_state, float *out_uniform, void *stream)
+{
+    return rd_rollout<MountainCarEnv, false>(
+        "erl_rollout_discrete_mountaincar_f32",
+        {actor_params, act_avg, act_std, S, h1, h2, A, env_state, env_state, step_count, episode, max_step, env_seed, N, H},
+        {uniform, seed, counter0, reward_scale, out_states, out_actions, out_logprobs, out_rewards, out_undones, out_unmasks, out_last_state,
+         out_uniform}, {}, stream);
+}
+
+extern "C" int erl_rollout_discrete_mountaincar_gae_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1,
+                                                        int h2, int A, float *env_state, int32_t *step_count, int32_t *episode, int max_step,
+                                                        uint64_t env_seed, int64_t N, int64_t H, const float *uniform, uint64_t seed,
+                                                        uint64_t counter0, float reward_scale, float *out_states, int32_t *out_actions,
+                                                        float *out_logprobs, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks,
+                                                        float *out_last_state, float *out_uniform, const float *critic_params,
+                                                        const float *cri_avg, const float *cri_std, float *out_values, float *out_next_value,
+                                                        float *out_advantages, float *out_reward_sums, void *gae_partials,
+                                                        int64_t gae_partials_bytes, float gamma, float lambda_gae, int use_v_trace, void *stream)
+{
+    return rd_rollout<MountainCarEnv, true>(
+        "erl_rollout_discrete_mountaincar_gae_f32",
+        {actor_params, act_avg, act_std, S, h1, h2, A, env_state, env_state, step_count, episode, max_step, env_seed, N, H},
+        {uniform, seed, counter0, reward_scale, out_states, out_actions, out_logprobs, out_rewards, out_undones, out_unmasks, out_last_state,
+         out_uniform},
+        {critic_params, cri_avg, cri_std, out_values, out_next_value, out_advantages, out_reward_sums, gae_partials, gae_partials_bytes, gamma,
+         lambda_gae, use_v_trace}, stream);
+}
+
+extern "C" int erl_eval_discrete_mountaincar_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2,
+                                                 int A, float *env_state, int32_t *step_count, int32_t *episode, int max_step,
+                                                 uint64_t env_seed, int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return rd_eval<MountainCarEnv>("erl_eval_discrete_mountaincar_f32",
+                                   {actor_params, act_avg, act_std, S, h1, h2, A, env_state, env_state, step_count, episode, max_step, env_seed, N, H},
+                                   workspace, workspace_bytes, stream);
 }

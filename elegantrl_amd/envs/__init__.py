@@ -1,1 +1,1 @@
-from .vec_envs import AcrobotGpuVecEnv, CartPoleGpuVecEnv, CartPoleVecEnv, PendulumVecEnv, SynVecEnv
+from .vec_envs import AcrobotGpuVecEnv, CartPoleGpuVecEnv, CartPoleVecEnv, MountainCarGpuVecEnv, PendulumVecEnv, SynVecEnv

@@ -6,7 +6,7 @@ elegantrl/envs/PointChasingEnv.py:84-182 as the in-tree exemplar).
 They additionally expose `step_into(action, reward_row, terminal_row, truncate_row) -> state`, which lets the
 rollout write step outputs straight into row t of its time-major buffers (no copies, no host sync).
 The dynamics run in erl_synenv_step_f32 / erl_pendulum_step_f32 (elegantrl_amd/csrc/envs.hip) and erl_cartpole_step_f32 /
-erl_acrobot_step_f32 (elegantrl_amd/csrc/rollout_discrete.hip).
+erl_acrobot_step_f32 / erl_mountaincar_step_f32 (elegantrl_amd/csrc/rollout_discrete.hip).
 """
 from __future__ import annotations
 
@@ -419,6 +419,42 @@ class AcrobotGpuVecEnv(_DiscreteGpuVecEnv):
         g = th.Generator(device=self.device).manual_seed(self.seed)
         self.phys = th.rand((self.num_envs, 4), device=self.device, generator=g) * 0.2 - 0.1
         self.state = self._observe(self.phys)
+        self.step_count.zero_()
+        self.episode.zero_()
+        return self.state.clone(), {}
+
+
+class MountainCarGpuVecEnv(_DiscreteGpuVecEnv):
+    """MountainCar-v0 for N envs on the device (erl_mountaincar_step_f32): gymnasium's dynamics -- `state` (N, 2) = (position, velocity)
+    is the observation; action 0 / 1 / 2 pushes left / nowhere / right (any other value: nowhere); velocity += (action - 1) * 0.001 +
+    cos(3 position) * (-0.0025), clipped to +-0.07; position += velocity, clipped to [-1.2, 0.6]; at position -1.2 a negative velocity
+    becomes 0; terminal when position >= 0.5 with velocity >= 0 on the new state; reward -1 on every step, the terminal one included;
+    truncation at max_step (200) -- in one launch per step, and behind `fused_rollout_discrete` / `fused_evaluate_discrete` the whole
+    horizon of a discrete agent in one launch.  A done row restarts at velocity 0 and a position U[-0.6, -0.4) from one Philox draw keyed
+    by (seed, env, episode, component).
+    No claim that PPO learns it from scratch is made or tested: a uniformly random policy ends no episode by `terminal` within 200 steps
+    (0 of 4096 gymnasium starts, in float64 and in float32), so every return such an agent sees is -200 and the reward carries no signal.
+    What is tested is the env, the one-launch routes on it and the update kernels at state_dim 2."""
+    env_name = "MountainCar-v0"
+    _rollout_entry, _gae_entry = "erl_rollout_discrete_mountaincar_f32", "erl_rollout_discrete_mountaincar_gae_f32"
+    _eval_entry = "erl_eval_discrete_mountaincar_f32"
+
+    def __init__(self, num_envs: int = 1024, max_step: int = 200, gpu_id: int = 0, seed: int = 0, **_):
+        super().__init__(num_envs, 2, 3, max_step, gpu_id, seed)
+        self.state = th.zeros((num_envs, 2), dtype=th.float32, device=self.device)
+
+    def _live(self):
+        return (self.state,)
+
+    def _step(self, *rows):
+        from .. import ops
+        ops.mountaincar_step(self.state, *rows)
+
+    def reset(self) -> Tuple[TEN, dict]:
+        self.state_epoch += 1
+        g = th.Generator(device=self.device).manual_seed(self.seed)
+        self.state = th.zeros((self.num_envs, 2), dtype=th.float32, device=self.device)
+        self.state[:, 0] = th.rand((self.num_envs,), device=self.device, generator=g) * 0.2 - 0.6
         self.step_count.zero_()
         self.episode.zero_()
         return self.state.clone(), {}

@@ -1041,6 +1041,15 @@ def acrobot_step(phys: TEN, obs: TEN, action: TEN, step_count: TEN, episode: TEN
           "erl_acrobot_step_f32")
 
 
+def mountaincar_step(state: TEN, action: TEN, step_count: TEN, episode: TEN, reward: TEN, terminal: TEN, truncate: TEN, max_step: int,
+                     seed: int) -> None:
+    """one MountainCar-v0 step of every env (erl_mountaincar_step_f32): state (N, 2) = (position, velocity) in place, action (N,) int64"""
+    check(lib().erl_mountaincar_step_f32(ptr(state, th.float32), ptr(action, th.int64), ptr(step_count, th.int32), ptr(episode, th.int32),
+                                         ptr(reward, th.float32), flag_ptr(terminal), flag_ptr(truncate), state.shape[0], max_step,
+                                         seed & (2 ** 64 - 1), stream_ptr()),
+          "erl_mountaincar_step_f32")
+
+
 def rollout_discrete_supported(S: int, h1: int, h2: int, A: int) -> bool:
     """the policy shapes of the one-launch discrete rollout / evaluation (erl_rollout_discrete_supported)"""
     return bool(lib().erl_rollout_discrete_supported(int(S), int(h1), int(h2), int(A)))

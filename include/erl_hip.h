@@ -362,7 +362,7 @@ ERL_API int erl_eval_episodes_compact_f32(const void *workspace, int64_t workspa
  * (erl_eval_workspace_bytes(N, H)), for erl_eval_episodes_compact_f32.
  *
  * erl_rollout_discrete_supported: the policy shapes of the two: S <= 64, two hidden layers of 32..128 in steps of 32, 2 <= A <= 8
- * (the CartPole entry points also need S = 4, the env's; the Acrobot ones S = 6 and A = 3).  Anything else is ERL_EINVAL ("unsupported dims") before any launch.
+ * (the CartPole entry points also need S = 4, the env's; the Acrobot ones S = 6 and A = 3, the MountainCar ones S = 2 and A = 3).  Anything else is ERL_EINVAL ("unsupported dims") before any launch.
  * No call allocates or synchronises; no workgroup waits for another. */
 ERL_API int erl_rollout_discrete_supported(int S, int h1, int h2, int A);
 ERL_API int erl_cartpole_step_f32(float *state, const int64_t *action, int32_t *step_count, int32_t *episode, float *reward,
@@ -437,6 +437,36 @@ ERL_API int erl_rollout_discrete_acrobot_gae_f32(const float *actor_params, cons
                           uint8_t *out_unmasks, float *out_last_state, float *out_uniform, const float *critic_params, const float *cri_avg,
                           const float *cri_std, float *out_values, float *out_next_value, float *out_advantages, float *out_reward_sums,
                           void *gae_partials, int64_t gae_partials_bytes, float gamma, float lambda_gae, int use_v_trace, void *stream);
+
+/* MountainCar-v0 behind the same kernels (additions to ABI 23; csrc/mountaincar_step.h, csrc/rollout_discrete.hip).
+ *
+ * erl_mountaincar_step_f32: one step of N envs.  state (N, 2) = (position, velocity) is the observation; action (N,) int64: 0 / 1 / 2
+ * pushes left / nowhere / right, any other value pushes nowhere.  gymnasium's MountainCar-v0 dynamics: velocity += (action - 1) * 0.001
+ * + cos(3 position) * (-0.0025), clipped to +-0.07; position += velocity, clipped to [-1.2, 0.6]; at position -1.2 a negative velocity
+ * becomes 0; terminal = position >= 0.5 and velocity >= 0 on the NEW state, truncate = step_count reached max_step and not terminal,
+ * reward = -1 on every step.  state / step_count / episode are updated in place; a done row restarts at velocity 0 and a position
+ * U[-0.6, -0.4) from one Philox draw keyed by (seed, env, episode, component).
+ *
+ * erl_rollout_discrete_mountaincar_f32 / erl_rollout_discrete_mountaincar_gae_f32 / erl_eval_discrete_mountaincar_f32: the CartPole
+ * entries above, argument for argument, with MountainCar behind the kernel: S must be 2 and A must be 3; out_states is (H, N, 2),
+ * out_last_state (N, 2).  The env rows are bit-identical to erl_mountaincar_step_f32 fed the recorded actions. */
+ERL_API int erl_mountaincar_step_f32(float *state, const int64_t *action, int32_t *step_count, int32_t *episode, float *reward,
+                          uint8_t *terminal, uint8_t *truncate, int64_t N, int max_step, uint64_t seed, void *stream);
+ERL_API int erl_rollout_discrete_mountaincar_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2,
+                          int A, float *env_state, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N,
+                          int64_t H, const float *uniform, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states,
+                          int32_t *out_actions, float *out_logprobs, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks,
+                          float *out_last_state, float *out_uniform, void *stream);
+ERL_API int erl_rollout_discrete_mountaincar_gae_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2,
+                          int A, float *env_state, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N,
+                          int64_t H, const float *uniform, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states,
+                          int32_t *out_actions, float *out_logprobs, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks,
+                          float *out_last_state, float *out_uniform, const float *critic_params, const float *cri_avg, const float *cri_std,
+                          float *out_values, float *out_next_value, float *out_advantages, float *out_reward_sums, void *gae_partials,
+                          int64_t gae_partials_bytes, float gamma, float lambda_gae, int use_v_trace, void *stream);
+ERL_API int erl_eval_discrete_mountaincar_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2, int A,
+                          float *env_state, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
+                          void *workspace, int64_t workspace_bytes, void *stream);
 
 /* K6  one PPO minibatch: gather (K5 indices) + critic fwd/bwd + actor fwd/bwd, both networks in one
  * launch.  Replaces AgentPPO.update_objectives up to (not including) the two optimizer steps

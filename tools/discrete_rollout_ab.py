@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""AgentDiscretePPO.explore_env on CartPole three ways (or, with --env acrobot, on Acrobot two ways), and one policy evaluation two ways
+"""AgentDiscretePPO.explore_env on CartPole three ways (or, with --env acrobot / --env mountaincar, on that env two ways), and one policy
+evaluation two ways
 (csrc/rollout_discrete.hip).
 
     (a) CartPoleVecEnv (torch ops) + the per-step loop            -- the only route before the device-resident env
     (b) CartPoleGpuVecEnv (erl_cartpole_step_f32) + the per-step loop (args.fused_rollout = False)
     (c) CartPoleGpuVecEnv + the one-launch rollout (erl_rollout_discrete_cartpole_f32)
 --env acrobot has no torch-ops env: (b) AcrobotGpuVecEnv (erl_acrobot_step_f32) + the per-step loop against (c) AcrobotGpuVecEnv + the
-one-launch rollout (erl_rollout_discrete_acrobot_f32).
+one-launch rollout (erl_rollout_discrete_acrobot_f32).  --env mountaincar likewise: MountainCarGpuVecEnv (erl_mountaincar_step_f32,
+erl_rollout_discrete_mountaincar_f32); its evaluation runs at max_step 500 like the others', not at the env's own 200.
 
 N = 4096 envs, H = 64 steps, net (64, 32).  Method: one agent + env per route in one process; a few warm-up calls of each, then
 REGIONS regions per route, the routes alternating, each region CALLS explore_env calls on the host clock between device
@@ -14,7 +16,8 @@ synchronisations.  Reported: milliseconds per explore_env -- median, min, max, i
 median lies below (a)'s and (b)'s by more than their own min .. max spread.  The evaluation (max_step 500: env.reset() + 500 steps of the
 greedy policy + the episode table on the host) is timed the same way through the Evaluator's loop and through agent.evaluate_env.
     python tools/discrete_rollout_ab.py > profiles/discrete_rollout_ab.txt
-    python tools/discrete_rollout_ab.py --env acrobot >> profiles/discrete_rollout_ab.txt"""
+    python tools/discrete_rollout_ab.py --env acrobot >> profiles/discrete_rollout_ab.txt
+    python tools/discrete_rollout_ab.py --env mountaincar >> profiles/discrete_rollout_ab.txt"""
 import argparse
 import os
 import statistics
@@ -27,7 +30,7 @@ os.environ.setdefault("ERL_QUIET", "1")
 import torch as th  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--env", choices=("cartpole", "acrobot"), default="cartpole")
+ap.add_argument("--env", choices=("cartpole", "acrobot", "mountaincar"), default="cartpole")
 ap.add_argument("--envs", type=int, default=4096)
 ap.add_argument("--horizon", type=int, default=64)
 ap.add_argument("--net", type=int, nargs=2, default=(64, 32))
@@ -41,14 +44,15 @@ if not th.cuda.is_available():
     sys.exit("discrete_rollout_ab: needs a GPU (there is no CPU path to time)")
 
 from elegantrl_amd.agents import AgentDiscretePPO  # noqa: E402
-from elegantrl_amd.envs import AcrobotGpuVecEnv, CartPoleGpuVecEnv, CartPoleVecEnv  # noqa: E402
+from elegantrl_amd.envs import AcrobotGpuVecEnv, CartPoleGpuVecEnv, CartPoleVecEnv, MountainCarGpuVecEnv  # noqa: E402
 from elegantrl_amd.train import Config  # noqa: E402
 from elegantrl_amd.train.evaluator import get_cumulative_rewards_and_step_from_vec_env  # noqa: E402
 
 N, H, NET = opt.envs, opt.horizon, list(opt.net)
 # env name, state_dim, action_dim, the torch-ops env (or None) and the device-resident env
-NAME, S, A, TORCH_ENV, GPU_ENV = (("CartPole-v1", 4, 2, CartPoleVecEnv, CartPoleGpuVecEnv) if opt.env == "cartpole" else
-                                  ("Acrobot-v1", 6, 3, None, AcrobotGpuVecEnv))
+NAME, S, A, TORCH_ENV, GPU_ENV = {"cartpole": ("CartPole-v1", 4, 2, CartPoleVecEnv, CartPoleGpuVecEnv),
+                                  "acrobot": ("Acrobot-v1", 6, 3, None, AcrobotGpuVecEnv),
+                                  "mountaincar": ("MountainCar-v0", 2, 3, None, MountainCarGpuVecEnv)}[opt.env]
 
 
 def build(env_cls, fused, max_step):
