@@ -36,6 +36,16 @@ _SAC_KEY = [c_uint64, c_uint64]                                          # seed,
 _SAC_NOISE = [_P, _P] + _SAC_KEY                                         # eps_next, eps_cur, seed, counter
 _SAC_HYPER = [c_float] * 8                                               # gamma, target_entropy, tau, lr, beta1, beta2, eps_adam, max_norm
 _SAC_TAIL = [_P, c_int64, _P]                                            # workspace, workspace_bytes, stream
+# what the one-launch entries of the continuous device envs share, in the order they name it
+_ENV_SYN = [_P] * 5 + [c_int, c_uint64]                                  # env_state, Ws, Wa, step_count, episode, max_step, env_seed
+_ENV_PEN = [_P] * 4 + [c_int, c_uint64]                                  # phys, obs, step_count, episode, max_step, env_seed
+_PPO_SYN, _PPO_PEN = [c_int] * 4 + _ENV_SYN, [c_int] * 2 + _ENV_PEN      # S, h1, h2, A | h1, h2 (S = 3, A = 1), then the env
+_SAC_SYN = [_P, c_int, c_int, POINTER(c_int), c_int] + _ENV_SYN          # actor_params, S, A, hidden, n_hidden, then the env
+_SAC_PEN = [_P, POINTER(c_int), c_int] + _ENV_PEN                        # actor_params, hidden, n_hidden, then the env
+_ROLL_DRAWS = [c_int64, c_int64, _P] + _SAC_KEY + [c_float]              # N, H, noise, seed, counter0, reward_scale
+_PPO_ROLL_TAIL = _ROLL_DRAWS + [_P] * 8 + [_P] * 5 + [c_int64, c_float, c_float, c_int, _P]   # six planes, values, next_value; the epilogue; stream
+_SAC_ROLL_TAIL = _ROLL_DRAWS + [_P] * 6 + [_P]                           # five planes, out_last_state; stream
+_EVAL_TAIL = [c_int64, c_int64] + _SAC_TAIL                              # N, H, workspace, workspace_bytes, stream
 _SIGNATURES = {
     # name: (restype, argtypes)
     "erl_abi_version": (c_int, []),
@@ -76,10 +86,8 @@ _SIGNATURES = {
                                      _P, _P, _P, _P, _P]),
     "erl_rollout_fused_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "erl_rollout_gae_workspace_bytes": (c_int64, [c_int64]),
-    "erl_rollout_synenv_f32": (c_int, [_P] * 6 + [c_int] * 4 + [_P] * 5 + [c_int, c_uint64, c_int64, c_int64, _P, c_uint64, c_uint64,
-                                       c_float] + [_P] * 8 + [_P] * 5 + [c_int64, c_float, c_float, c_int, _P]),
-    "erl_rollout_pendulum_f32": (c_int, [_P] * 6 + [c_int] * 2 + [_P] * 4 + [c_int, c_uint64, c_int64, c_int64, _P, c_uint64,
-                                         c_uint64, c_float] + [_P] * 8 + [_P] * 5 + [c_int64, c_float, c_float, c_int, _P]),
+    "erl_rollout_synenv_f32": (c_int, [_P] * 6 + _PPO_SYN + _PPO_ROLL_TAIL),
+    "erl_rollout_pendulum_f32": (c_int, [_P] * 6 + _PPO_PEN + _PPO_ROLL_TAIL),
     "erl_ppo_slab_stride": (c_int64, [c_int, c_int, c_int, c_int]),
     "erl_ppo_num_slabs": (c_int, [c_int64]),
     "erl_ppo_set_arith": (c_int, [c_int]),
@@ -154,27 +162,21 @@ _SIGNATURES = {
     "erl_sac_explore_action_opt_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, c_int64, _P, c_uint64, c_uint64, _P, _P, _P,
                                                c_int64, c_int, _P]),
     "erl_sac_rollout_synenv_supported": (c_int, [c_int, c_int, POINTER(c_int), c_int, c_int64]),
-    "erl_sac_rollout_synenv_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, _P, _P, _P, _P, c_int, c_uint64, c_int64, c_int64, _P,
-                                           c_uint64, c_uint64, c_float, _P, _P, _P, _P, _P, _P, _P]),
-    "erl_sac_rollout_pendulum_f32": (c_int, [_P, POINTER(c_int), c_int, _P, _P, _P, _P, c_int, c_uint64, c_int64, c_int64, _P, c_uint64, c_uint64,
-                                             c_float, _P, _P, _P, _P, _P, _P, _P]),
+    "erl_sac_rollout_synenv_f32": (c_int, _SAC_SYN + _SAC_ROLL_TAIL),
+    "erl_sac_rollout_pendulum_f32": (c_int, _SAC_PEN + _SAC_ROLL_TAIL),
     # AgentModSAC's one-launch rollout / evaluation (ActorFixSAC): the argument lists of their AgentSAC twins
     "erl_sac_rollout_mod_supported": (c_int, [c_int, c_int, POINTER(c_int), c_int, c_int64]),
-    "erl_sac_rollout_mod_synenv_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, _P, _P, _P, _P, c_int, c_uint64, c_int64, c_int64, _P,
-                                               c_uint64, c_uint64, c_float, _P, _P, _P, _P, _P, _P, _P]),
-    "erl_sac_rollout_mod_pendulum_f32": (c_int, [_P, POINTER(c_int), c_int, _P, _P, _P, _P, c_int, c_uint64, c_int64, c_int64, _P, c_uint64,
-                                                 c_uint64, c_float, _P, _P, _P, _P, _P, _P, _P]),
-    "erl_sac_eval_mod_synenv_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, _P, _P, _P, _P, c_int, c_uint64, c_int64, c_int64, _P,
-                                            c_int64, _P]),
-    "erl_sac_eval_mod_pendulum_f32": (c_int, [_P, POINTER(c_int), c_int, _P, _P, _P, _P, c_int, c_uint64, c_int64, c_int64, _P, c_int64, _P]),
+    "erl_sac_rollout_mod_synenv_f32": (c_int, _SAC_SYN + _SAC_ROLL_TAIL),
+    "erl_sac_rollout_mod_pendulum_f32": (c_int, _SAC_PEN + _SAC_ROLL_TAIL),
+    "erl_sac_eval_mod_synenv_f32": (c_int, _SAC_SYN + _EVAL_TAIL),
+    "erl_sac_eval_mod_pendulum_f32": (c_int, _SAC_PEN + _EVAL_TAIL),
     "erl_sac_explore_action_tile_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, c_int64, _P, c_uint64, c_uint64, _P, _P, _P,
                                                 c_int64, c_int, _P]),
     "erl_eval_workspace_bytes": (c_int64, [c_int64, c_int64]),
-    "erl_eval_synenv_f32": (c_int, [_P] * 3 + [c_int] * 4 + [_P] * 5 + [c_int, c_uint64, c_int64, c_int64, _P, c_int64, _P]),
-    "erl_eval_pendulum_f32": (c_int, [_P] * 3 + [c_int] * 2 + [_P] * 4 + [c_int, c_uint64, c_int64, c_int64, _P, c_int64, _P]),
-    "erl_sac_eval_synenv_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, _P, _P, _P, _P, c_int, c_uint64, c_int64, c_int64, _P,
-                                        c_int64, _P]),
-    "erl_sac_eval_pendulum_f32": (c_int, [_P, POINTER(c_int), c_int, _P, _P, _P, _P, c_int, c_uint64, c_int64, c_int64, _P, c_int64, _P]),
+    "erl_eval_synenv_f32": (c_int, [_P] * 3 + _PPO_SYN + _EVAL_TAIL),
+    "erl_eval_pendulum_f32": (c_int, [_P] * 3 + _PPO_PEN + _EVAL_TAIL),
+    "erl_sac_eval_synenv_f32": (c_int, _SAC_SYN + _EVAL_TAIL),
+    "erl_sac_eval_pendulum_f32": (c_int, _SAC_PEN + _EVAL_TAIL),
     "erl_eval_episodes_compact_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, c_int64, _P, _P]),
     "erl_k6_timing_enable": (None, [c_int]),
     "erl_k6_timing_read": (c_int, [POINTER(ctypes.c_double), POINTER(c_int)]),

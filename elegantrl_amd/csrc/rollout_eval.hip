@@ -37,35 +37,37 @@ int rf_eval_launch(RfArgs &g, int env_kind, hipStream_t stream)
         }                                                                                                                  \
         hipLaunchKernelGGL((rollout_fused_kernel<E, V, A_, B_, C_, false, true>), grid, block, lds_bytes, stream, g);      \
     } while (0)
-    const int ns = (g.S + 15) / 16;
-    if (env_kind == ENV_SYN) {
-        if (vec && ns == 4 && g.h1 == 128 && g.h2 == 128) RF_EVAL_LAUNCH(ENV_SYN, true, 4, 8, 8, 0);      // configs 4 / 5
-        else if (vec) RF_EVAL_LAUNCH(ENV_SYN, true, 0, 0, 0, 1);
-        else RF_EVAL_LAUNCH(ENV_SYN, false, 0, 0, 0, 2);
-    } else {
-        if (g.h1 == 128 && g.h2 == 64) RF_EVAL_LAUNCH(ENV_PENDULUM, false, 1, 8, 4, 3);                    // config 2
-        else RF_EVAL_LAUNCH(ENV_PENDULUM, false, 0, 0, 0, 4);
+    switch (rf_shape_class(env_kind, vec, g.S, g.h1, g.h2)) {       // the training launcher's classes (no role split here)
+    case RF_SYN_TUNED: RF_EVAL_LAUNCH(ENV_SYN, true, 4, 8, 8, 0); break;                                  // configs 4 / 5
+    case RF_SYN_VEC: RF_EVAL_LAUNCH(ENV_SYN, true, 0, 0, 0, 1); break;
+    case RF_SYN_SCALAR: RF_EVAL_LAUNCH(ENV_SYN, false, 0, 0, 0, 2); break;
+    case RF_PENDULUM_TUNED: RF_EVAL_LAUNCH(ENV_PENDULUM, false, 1, 8, 4, 3); break;                       // config 2
+    case RF_PENDULUM_ANY: RF_EVAL_LAUNCH(ENV_PENDULUM, false, 0, 0, 0, 4); break;
     }
 #undef RF_EVAL_LAUNCH
     return erl_hip_status(hipGetLastError(), "rollout_fused_kernel (evaluation form) launch");
 }
 
-int rf_eval_fill(RfArgs &g, const char *what, const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2,
-                 int A, int64_t N, int64_t H, void *workspace, int64_t workspace_bytes)
+// the evaluation entries' body (of RfNets the critic's three are not read)
+int rf_eval(const char *what, const RfNets &n, const ContEnv &e, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    ERL_REQUIRE(actor_params && act_avg && act_std, "%s: NULL network tensor", what);
+    ERL_REQUIRE(n.actor_params && n.act_avg && n.act_std, "%s: NULL network tensor", what);
     ERL_REQUIRE(workspace, "%s: NULL workspace", what);
-    ERL_REQUIRE(rf_dims_ok(S, h1, h2, A), "%s: unsupported dims S=%d net=[%d,%d] A=%d (fused rollout: state_dim <= %d, 2 hidden "
-                "layers of 32..128 in steps of 32, action_dim <= 16)", what, S, h1, h2, A, 16 * RF_NSM);
-    ERL_REQUIRE(N >= 1 && H >= 1 && H < (1LL << 30) && erl_eval_ws_bytes(N, H) > 0, "%s: bad shape N=%lld H=%lld", what, (long long)N, (long long)H);
-    ERL_REQUIRE(workspace_bytes >= erl_eval_ws_bytes(N, H), "%s: workspace of %lld bytes, erl_eval_workspace_bytes(N, H) = %lld", what,
-                (long long)workspace_bytes, (long long)erl_eval_ws_bytes(N, H));
-    g.Pa = actor_params; g.avg_a = act_avg; g.std_a = act_std;
-    g.S = S; g.h1 = h1; g.h2 = h2; g.A = A; g.N = N; g.H = (int)H;
+    ERL_REQUIRE(rf_dims_ok(n.S, n.h1, n.h2, n.A), "%s: unsupported dims S=%d net=[%d,%d] A=%d (fused rollout: state_dim <= %d, 2 hidden "
+                "layers of 32..128 in steps of 32, action_dim <= 16)", what, n.S, n.h1, n.h2, n.A, 16 * RF_NSM);
+    ERL_REQUIRE(n.N >= 1 && n.H >= 1 && n.H < (1LL << 30) && erl_eval_ws_bytes(n.N, n.H) > 0, "%s: bad shape N=%lld H=%lld", what, (long long)n.N,
+                (long long)n.H);
+    ERL_REQUIRE(workspace_bytes >= erl_eval_ws_bytes(n.N, n.H), "%s: workspace of %lld bytes, erl_eval_workspace_bytes(N, H) = %lld", what,
+                (long long)workspace_bytes, (long long)erl_eval_ws_bytes(n.N, n.H));
+    RfArgs g{};
+    g.Pa = n.actor_params; g.avg_a = n.act_avg; g.std_a = n.act_std;
+    g.S = n.S; g.h1 = n.h1; g.h2 = n.h2; g.A = n.A; g.N = n.N; g.H = (int)n.H;
     g.reward_scale = 1.0f;
-    const ErlEvalWs w = erl_eval_ws_layout(workspace, N, H);
+    const ErlEvalWs w = erl_eval_ws_layout(workspace, n.N, n.H);
     g.ev_rec = w.rec; g.ev_cnt = w.cnt;
-    return ERL_OK;
+    if (int rc = cont_env_check(what, e, true)) return rc;
+    rf_set_env(g, e);
+    return rf_eval_launch(g, e.kind, (hipStream_t)stream);
 }
 
 constexpr int EC_T = 256;      // threads = envs per workgroup of the compaction
@@ -121,26 +123,16 @@ extern "C" int erl_eval_synenv_f32(const float *actor_params, const float *act_a
                                    float *env_state, const float *Ws, const float *Wa, int32_t *step_count, int32_t *episode, int max_step,
                                    uint64_t env_seed, int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    RfArgs g{};
-    int rc = rf_eval_fill(g, "erl_eval_synenv_f32", actor_params, act_avg, act_std, S, h1, h2, A, N, H, workspace, workspace_bytes);
-    if (rc) return rc;
-    ERL_REQUIRE(env_state && Ws && Wa && step_count && episode && max_step >= 1, "erl_eval_synenv_f32: bad environment argument");
-    g.env_state = env_state; g.Ws = Ws; g.Wa = Wa; g.step_count = step_count; g.episode = episode;
-    g.max_step = max_step; g.env_seed = env_seed;
-    return rf_eval_launch(g, ENV_SYN, (hipStream_t)stream);
+    return rf_eval("erl_eval_synenv_f32", {actor_params, nullptr, act_avg, act_std, nullptr, nullptr, S, h1, h2, A, N, H},
+                   {ENV_SYN, env_state, nullptr, Ws, Wa, step_count, episode, max_step, env_seed}, workspace, workspace_bytes, stream);
 }
 
 extern "C" int erl_eval_pendulum_f32(const float *actor_params, const float *act_avg, const float *act_std, int h1, int h2, float *phys,
                                      float *obs, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
                                      void *workspace, int64_t workspace_bytes, void *stream)
 {
-    RfArgs g{};
-    int rc = rf_eval_fill(g, "erl_eval_pendulum_f32", actor_params, act_avg, act_std, 3, h1, h2, 1, N, H, workspace, workspace_bytes);
-    if (rc) return rc;
-    ERL_REQUIRE(phys && obs && step_count && episode && max_step >= 1, "erl_eval_pendulum_f32: bad environment argument");
-    g.env_state = obs; g.phys = phys; g.step_count = step_count; g.episode = episode;
-    g.max_step = max_step; g.env_seed = env_seed;
-    return rf_eval_launch(g, ENV_PENDULUM, (hipStream_t)stream);
+    return rf_eval("erl_eval_pendulum_f32", {actor_params, nullptr, act_avg, act_std, nullptr, nullptr, 3, h1, h2, 1, N, H},
+                   {ENV_PENDULUM, obs, phys, nullptr, nullptr, step_count, episode, max_step, env_seed}, workspace, workspace_bytes, stream);
 }
 
 extern "C" int erl_eval_episodes_compact_f32(const void *workspace, int64_t workspace_bytes, int64_t N, int64_t H, float *out_rows,

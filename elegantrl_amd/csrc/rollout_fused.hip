@@ -51,52 +51,64 @@ int rf_launch(RfArgs &g, int env_kind, hipStream_t stream)
         }                                                                                                                  \
         hipLaunchKernelGGL((rollout_fused_kernel<E, V, A_, B_, C_, (SLOT >= 6)>), grid, block, lds_bytes, stream, g);    \
     } while (0)
-    const int ns = (g.S + 15) / 16;
-    if (env_kind == ENV_SYN) {
-        if (vec && ns == 4 && g.h1 == 128 && g.h2 == 128 && rs) RF_LAUNCH(ENV_SYN, true, 4, 8, 8, 6);  // configs 4 / 5
-        else if (vec && ns == 4 && g.h1 == 128 && g.h2 == 128) RF_LAUNCH(ENV_SYN, true, 4, 8, 8, 0);
-        else if (vec) RF_LAUNCH(ENV_SYN, true, 0, 0, 0, 1);
-        else RF_LAUNCH(ENV_SYN, false, 0, 0, 0, 2);
-    } else {
-        if (g.h1 == 128 && g.h2 == 64 && rs) RF_LAUNCH(ENV_PENDULUM, false, 1, 8, 4, 7);              // config 2
-        else if (g.h1 == 128 && g.h2 == 64) RF_LAUNCH(ENV_PENDULUM, false, 1, 8, 4, 3);
-        else RF_LAUNCH(ENV_PENDULUM, false, 0, 0, 0, 4);
+    switch (rf_shape_class(env_kind, vec, g.S, g.h1, g.h2)) {
+    case RF_SYN_TUNED: if (rs) RF_LAUNCH(ENV_SYN, true, 4, 8, 8, 6); else RF_LAUNCH(ENV_SYN, true, 4, 8, 8, 0); break;                // configs 4 / 5
+    case RF_SYN_VEC: RF_LAUNCH(ENV_SYN, true, 0, 0, 0, 1); break;
+    case RF_SYN_SCALAR: RF_LAUNCH(ENV_SYN, false, 0, 0, 0, 2); break;
+    case RF_PENDULUM_TUNED: if (rs) RF_LAUNCH(ENV_PENDULUM, false, 1, 8, 4, 7); else RF_LAUNCH(ENV_PENDULUM, false, 1, 8, 4, 3); break;  // config 2
+    case RF_PENDULUM_ANY: RF_LAUNCH(ENV_PENDULUM, false, 0, 0, 0, 4); break;
     }
 #undef RF_LAUNCH
     return erl_hip_status(hipGetLastError(), "rollout_fused_kernel launch");
 }
 
-int rf_fill(RfArgs &g, const char *what, const float *actor_params, const float *critic_params, const float *act_avg,
-            const float *act_std, const float *cri_avg, const float *cri_std, int S, int h1, int h2, int A, int64_t N, int64_t H,
-            const float *noise, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states, float *out_actions,
-            float *out_logprobs, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_values,
-            float *out_next_value, float *out_last_state, float *out_adv, float *out_ret, double *gae_stats, double *gae_ws,
-            int64_t gae_ws_bytes, float gamma, float lam, int use_v_trace)
+// ---- the entries' arguments as the C ABI spells them (include/erl_hip.h), in its order: RfNets, the env (cont_env_args.h), and
+struct RfPlanes {                           // the rollout's draws and the planes it writes (out_values / out_next_value may be NULL)
+    const float *noise;
+    uint64_t seed, counter0;
+    float reward_scale;
+    float *out_states, *out_actions, *out_logprobs, *out_rewards;
+    uint8_t *out_undones, *out_unmasks;
+    float *out_values, *out_next_value;
+};
+struct RfEpilogue {                         // the kernel's optional tail: all may be NULL
+    float *out_last_state, *out_advantages, *out_reward_sums;
+    double *gae_stats, *gae_workspace;
+    int64_t gae_workspace_bytes;
+    float gamma, lambda_gae;
+    int use_v_trace;
+};
+
+// the rollout entries' body
+int rf_rollout(const char *what, const RfNets &n, const ContEnv &e, const RfPlanes &o, const RfEpilogue &c, void *stream)
 {
-    ERL_REQUIRE(actor_params && critic_params && act_avg && act_std && cri_avg && cri_std, "%s: NULL network tensor", what);
-    ERL_REQUIRE(out_states && out_actions && out_logprobs && out_rewards && out_undones && out_unmasks, "%s: NULL rollout buffer", what);
-    ERL_REQUIRE(rf_dims_ok(S, h1, h2, A), "%s: unsupported dims S=%d net=[%d,%d] A=%d (fused rollout: state_dim <= %d, 2 hidden "
-                "layers of 32..128 in steps of 32, action_dim <= 16)", what, S, h1, h2, A, 16 * RF_NSM);
-    ERL_REQUIRE(N >= 1 && H >= 1 && H < (1LL << 30), "%s: bad shape N=%lld H=%lld", what, (long long)N, (long long)H);
-    g.Pa = actor_params; g.Pc = critic_params;
-    g.avg_a = act_avg; g.std_a = act_std; g.avg_c = cri_avg; g.std_c = cri_std;
-    g.S = S; g.h1 = h1; g.h2 = h2; g.A = A; g.N = N; g.H = (int)H;
-    g.noise = noise; g.seed = seed; g.counter0 = counter0; g.reward_scale = reward_scale;
-    g.o_states = out_states; g.o_actions = out_actions; g.o_logprobs = out_logprobs; g.o_rewards = out_rewards;
-    g.o_undones = out_undones; g.o_unmasks = out_unmasks; g.o_values = out_values; g.o_next_value = out_next_value;
-    g.o_last_state = out_last_state;
-    if (out_adv || out_ret) {
-        ERL_REQUIRE(out_adv && out_ret && gae_ws && out_values && out_next_value,
+    ERL_REQUIRE(n.actor_params && n.critic_params && n.act_avg && n.act_std && n.cri_avg && n.cri_std, "%s: NULL network tensor", what);
+    ERL_REQUIRE(o.out_states && o.out_actions && o.out_logprobs && o.out_rewards && o.out_undones && o.out_unmasks, "%s: NULL rollout buffer", what);
+    ERL_REQUIRE(rf_dims_ok(n.S, n.h1, n.h2, n.A), "%s: unsupported dims S=%d net=[%d,%d] A=%d (fused rollout: state_dim <= %d, 2 hidden "
+                "layers of 32..128 in steps of 32, action_dim <= 16)", what, n.S, n.h1, n.h2, n.A, 16 * RF_NSM);
+    ERL_REQUIRE(n.N >= 1 && n.H >= 1 && n.H < (1LL << 30), "%s: bad shape N=%lld H=%lld", what, (long long)n.N, (long long)n.H);
+    RfArgs g{};
+    g.Pa = n.actor_params; g.Pc = n.critic_params;
+    g.avg_a = n.act_avg; g.std_a = n.act_std; g.avg_c = n.cri_avg; g.std_c = n.cri_std;
+    g.S = n.S; g.h1 = n.h1; g.h2 = n.h2; g.A = n.A; g.N = n.N; g.H = (int)n.H;
+    g.noise = o.noise; g.seed = o.seed; g.counter0 = o.counter0; g.reward_scale = o.reward_scale;
+    g.o_states = o.out_states; g.o_actions = o.out_actions; g.o_logprobs = o.out_logprobs; g.o_rewards = o.out_rewards;
+    g.o_undones = o.out_undones; g.o_unmasks = o.out_unmasks; g.o_values = o.out_values; g.o_next_value = o.out_next_value;
+    g.o_last_state = c.out_last_state;
+    if (c.out_advantages || c.out_reward_sums) {
+        ERL_REQUIRE(c.out_advantages && c.out_reward_sums && c.gae_workspace && o.out_values && o.out_next_value,
                     "%s: the advantage epilogue needs out_advantages, out_reward_sums, gae_workspace, out_values and out_next_value", what);
-        ERL_REQUIRE(gae_ws_bytes >= erl_rollout_gae_workspace_bytes(N), "%s: gae_workspace of %lld bytes, erl_rollout_gae_workspace_bytes(N) = %lld",
-                    what, (long long)gae_ws_bytes, (long long)erl_rollout_gae_workspace_bytes(N));
+        ERL_REQUIRE(c.gae_workspace_bytes >= erl_rollout_gae_workspace_bytes(n.N), "%s: gae_workspace of %lld bytes, erl_rollout_gae_workspace_bytes(N) = %lld",
+                    what, (long long)c.gae_workspace_bytes, (long long)erl_rollout_gae_workspace_bytes(n.N));
     }
-    g.o_adv = out_adv; g.o_ret = out_ret; g.gae_stats = gae_stats; g.gae_ws = gae_ws;
-    g.gamma = gamma; g.lam = lam; g.vtrace = use_v_trace ? 1 : 0;
+    g.o_adv = c.out_advantages; g.o_ret = c.out_reward_sums; g.gae_stats = c.gae_stats; g.gae_ws = c.gae_workspace;
+    g.gamma = c.gamma; g.lam = c.lambda_gae; g.vtrace = c.use_v_trace ? 1 : 0;
 #ifdef ERL_PROFILE
     g.prof = g_rf_prof;
 #endif
-    return ERL_OK;
+    if (int rc = cont_env_check(what, e, true)) return rc;
+    rf_set_env(g, e);
+    return rf_launch(g, e.kind, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -122,16 +134,12 @@ extern "C" int erl_rollout_synenv_f32(const float *actor_params, const float *cr
                                       double *gae_stats, double *gae_workspace, int64_t gae_workspace_bytes, float gamma,
                                       float lambda_gae, int use_v_trace, void *stream)
 {
-    RfArgs g{};
-    int rc = rf_fill(g, "erl_rollout_synenv_f32", actor_params, critic_params, act_avg, act_std, cri_avg, cri_std, S, h1, h2, A, N, H,
-                     noise, seed, counter0, reward_scale, out_states, out_actions, out_logprobs, out_rewards, out_undones, out_unmasks,
-                     out_values, out_next_value, out_last_state, out_advantages, out_reward_sums, gae_stats, gae_workspace,
-                     gae_workspace_bytes, gamma, lambda_gae, use_v_trace);
-    if (rc) return rc;
-    ERL_REQUIRE(env_state && Ws && Wa && step_count && episode && max_step >= 1, "erl_rollout_synenv_f32: bad environment argument");
-    g.env_state = env_state; g.Ws = Ws; g.Wa = Wa; g.step_count = step_count; g.episode = episode;
-    g.max_step = max_step; g.env_seed = env_seed;
-    return rf_launch(g, ENV_SYN, (hipStream_t)stream);
+    return rf_rollout("erl_rollout_synenv_f32", {actor_params, critic_params, act_avg, act_std, cri_avg, cri_std, S, h1, h2, A, N, H},
+                      {ENV_SYN, env_state, nullptr, Ws, Wa, step_count, episode, max_step, env_seed},
+                      {noise, seed, counter0, reward_scale, out_states, out_actions, out_logprobs, out_rewards, out_undones, out_unmasks,
+                       out_values, out_next_value},
+                      {out_last_state, out_advantages, out_reward_sums, gae_stats, gae_workspace, gae_workspace_bytes, gamma, lambda_gae,
+                       use_v_trace}, stream);
 }
 
 extern "C" int erl_rollout_pendulum_f32(const float *actor_params, const float *critic_params, const float *act_avg,
@@ -144,14 +152,10 @@ extern "C" int erl_rollout_pendulum_f32(const float *actor_params, const float *
                                         double *gae_workspace, int64_t gae_workspace_bytes, float gamma, float lambda_gae,
                                         int use_v_trace, void *stream)
 {
-    RfArgs g{};
-    int rc = rf_fill(g, "erl_rollout_pendulum_f32", actor_params, critic_params, act_avg, act_std, cri_avg, cri_std, 3, h1, h2, 1, N, H,
-                     noise, seed, counter0, reward_scale, out_states, out_actions, out_logprobs, out_rewards, out_undones, out_unmasks,
-                     out_values, out_next_value, out_last_state, out_advantages, out_reward_sums, gae_stats, gae_workspace,
-                     gae_workspace_bytes, gamma, lambda_gae, use_v_trace);
-    if (rc) return rc;
-    ERL_REQUIRE(phys && obs && step_count && episode && max_step >= 1, "erl_rollout_pendulum_f32: bad environment argument");
-    g.env_state = obs; g.phys = phys; g.step_count = step_count; g.episode = episode;
-    g.max_step = max_step; g.env_seed = env_seed;
-    return rf_launch(g, ENV_PENDULUM, (hipStream_t)stream);
+    return rf_rollout("erl_rollout_pendulum_f32", {actor_params, critic_params, act_avg, act_std, cri_avg, cri_std, 3, h1, h2, 1, N, H},
+                      {ENV_PENDULUM, obs, phys, nullptr, nullptr, step_count, episode, max_step, env_seed},
+                      {noise, seed, counter0, reward_scale, out_states, out_actions, out_logprobs, out_rewards, out_undones, out_unmasks,
+                       out_values, out_next_value},
+                      {out_last_state, out_advantages, out_reward_sums, gae_stats, gae_workspace, gae_workspace_bytes, gamma, lambda_gae,
+                       use_v_trace}, stream);
 }

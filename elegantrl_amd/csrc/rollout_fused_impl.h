@@ -4,6 +4,7 @@
 #pragma once
 #include <type_traits>
 
+#include "cont_env_args.h"
 #include "erl_common.h"
 #include "gae_step.h"
 #include "mlp_chain.h"
@@ -61,8 +62,6 @@ long long *g_rf_prof = nullptr;
 #else
 #define RFPROF(i) do { } while (0)
 #endif
-
-enum { ENV_SYN = 0, ENV_PENDULUM = 1 };
 
 constexpr int RF_WLD = 68;     // row stride of the LDS operand images (W1 rows, Ws^T rows): 16-byte rows, 4 banks apart
 // dynamic LDS layout (floats)
@@ -833,6 +832,32 @@ __global__ __launch_bounds__(512) void rollout_fused_kernel(RfArgs g)
 bool rf_dims_ok(int S, int h1, int h2, int A)
 {
     return mlp_dims_ok(S, h1, h2, A) && S <= 16 * RF_NSM;
+}
+
+// Which instantiation rollout_fused_kernel<E, V, A_, B_, C_, ..> a launch takes, for the training form (rollout_fused.hip) and the evaluation
+// form (rollout_eval.hip) alike: the evaluation is the training rollout under zero noise bit for bit only while both pick the same class.
+// TUNED: <ENV_SYN, true, 4, 8, 8> (configs 4 / 5: 49 <= S <= 64, net [128, 128]) and <ENV_PENDULUM, false, 1, 8, 4> (config 2: net [128, 64]);
+// the others run <E, V, 0, 0, 0>.  `vec`: the launcher's own finding that S % 4 == 0 and the pointers its form reads 16 bytes wide are aligned.
+enum RfShapeClass { RF_SYN_TUNED, RF_SYN_VEC, RF_SYN_SCALAR, RF_PENDULUM_TUNED, RF_PENDULUM_ANY };
+
+RfShapeClass rf_shape_class(int env_kind, bool vec, int S, int h1, int h2)
+{
+    if (env_kind == ENV_SYN) return !vec ? RF_SYN_SCALAR : ((S + 15) / 16 == 4 && h1 == 128 && h2 == 128) ? RF_SYN_TUNED : RF_SYN_VEC;
+    return (h1 == 128 && h2 == 64) ? RF_PENDULUM_TUNED : RF_PENDULUM_ANY;
+}
+
+// the policy and the shape as the entries of both forms are handed them (host side; the evaluation form reads the actor's three only)
+struct RfNets {
+    const float *actor_params, *critic_params, *act_avg, *act_std, *cri_avg, *cri_std;
+    int S, h1, h2, A;                       // Pendulum: S = 3, A = 1
+    int64_t N, H;
+};
+
+// the env pack into the kernel's argument (Pendulum: env_state is the live observation; fields the env does not have stay NULL)
+void rf_set_env(RfArgs &g, const ContEnv &e)
+{
+    g.env_state = e.env_state; g.phys = e.phys; g.Ws = e.Ws; g.Wa = e.Wa; g.step_count = e.step_count; g.episode = e.episode;
+    g.max_step = e.max_step; g.env_seed = e.env_seed;
 }
 
 }  // namespace

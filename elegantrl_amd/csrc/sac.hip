@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "mlpn_common.h"
+#include "cont_env_args.h"
 #include "eval_ws.h"
 #include "per_draw.h"        // per_newest: the fill state a draw inside the step needs, as erl_per_sample_rows_f32 derives it
 
@@ -888,42 +889,52 @@ extern "C" int erl_sac_update_per_draw_loop_f32(float *actor_params, float *crit
 }
 #undef SAC_CALL
 
-// The whole off-policy rollout of AgentBase._explore_vec_env (AgentBase.py:130-170) on a device-resident env as ONE launch
-// (sac_fused.hip sac_rollout_synenv_kernel); needs erl_sac_rollout_synenv_supported(...).  `what`: the entry's name; `phys` NULL: SynVecEnv,
-// else PendulumVecEnv (S = 3, A = 1; phys: (N, 2) theta, theta_dot; env_state: (N, 3) the live observation); `variant`:
-// ERL_SAC_ACTOR_FIX = ActorFixSAC.get_action (the erl_sac_rollout_mod_* entries, AgentModSAC)
-static int sac_rollout_impl(const char *what, int variant, const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state,
-                            const float *Ws, const float *Wa, float *phys, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
-                            int64_t N, int64_t H, const float *noise, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states,
-                            float *out_actions, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, void *stream)
+// What the one-launch rollout and its evaluation form share: the launch's shape class (erl_sac_rollout_synenv_supported) and the offsets of
+// the actor's layers in its parameter block.  `terse`: the refusal names N alone (the Pendulum rollout entries, whose S and A are fixed).
+static int sac_rollout_layout(const char *what, int variant, bool terse, int S, int A, const int *hidden, int n_hidden, int64_t N, int64_t (&aoff)[6])
 {
-    ERL_REQUIRE(actor_params && env_state && (phys || (Ws && Wa)) && step_count && episode && out_states && out_actions && out_rewards &&
-                out_undones && out_unmasks, "%s: NULL tensor", what);
-    if (phys)
-        ERL_REQUIRE(erl_sac_rollout_synenv_supported(S, A, hidden, n_hidden, N), "%s: unsupported dims N=%lld (two hidden "
-                    "layers <= 256 wide in steps of 16, N <= 4096; ERL_SAC_FUSED=0 turns it off)", what, (long long)N);
-    else
-        ERL_REQUIRE(erl_sac_rollout_synenv_supported(S, A, hidden, n_hidden, N), "%s: unsupported dims S=%d A=%d N=%lld (two "
-                    "hidden layers <= 256 wide in steps of 16, S + A <= 64, A <= 8, N <= 4096; ERL_SAC_FUSED=0 turns it off)", what, S, A, (long long)N);
-    ERL_REQUIRE(H >= 1 && H < (1LL << 30) && max_step >= 1, "%s: bad H=%lld max_step=%d", what, (long long)H, max_step);
+    if (!erl_sac_rollout_synenv_supported(S, A, hidden, n_hidden, N)) {
+        if (terse) erl_set_error("%s: unsupported dims N=%lld (two hidden layers <= 256 wide in steps of 16, N <= 4096; ERL_SAC_FUSED=0 turns it off)",
+                                 what, (long long)N);
+        else erl_set_error("%s: unsupported dims S=%d A=%d N=%lld (two hidden layers <= 256 wide in steps of 16, S + A <= 64, A <= 8, N <= 4096; "
+                           "ERL_SAC_FUSED=0 turns it off)", what, S, A, (long long)N);
+        return ERL_EINVAL;
+    }
     SacDims d;
     ERL_REQUIRE(make_sac_dims(S, A, hidden, n_hidden, 1, &d, variant), "%s: unsupported dims", what);
-    const int64_t aoff[6] = {d.actor.oW[0], d.actor.ob[0], d.actor.oW[1], d.actor.ob[1], d.actor.oW[2], d.actor.ob[2]};
-    return erl_sac_rollout_fused(actor_params, S, A, hidden[0], hidden[1], aoff, env_state, Ws, Wa, phys, step_count, episode, max_step, env_seed,
-                                 N, H, noise, seed, counter0, reward_scale, out_states, out_actions, out_rewards, out_undones, out_unmasks,
-                                 out_last_state, (hipStream_t)stream, nullptr, nullptr, variant);
+    for (int l = 0; l < 3; ++l) { aoff[2 * l] = d.actor.oW[l]; aoff[2 * l + 1] = d.actor.ob[l]; }
+    return ERL_OK;
 }
 
+// The whole off-policy rollout of AgentBase._explore_vec_env (AgentBase.py:130-170) on a device-resident env as ONE launch
+// (sac_fused.hip sac_rollout_synenv_kernel); needs erl_sac_rollout_synenv_supported(...).  `what`: the entry's name; `e`: the env
+// (cont_env_args.h; Pendulum: S = 3, A = 1, env_state the live observation); `variant`: ERL_SAC_ACTOR_FIX = ActorFixSAC.get_action (the
+// erl_sac_rollout_mod_* entries, AgentModSAC)
+static int sac_rollout_impl(const char *what, int variant, const float *actor_params, int S, int A, const int *hidden, int n_hidden,
+                            const ContEnv &e, int64_t N, int64_t H, const float *noise, uint64_t seed, uint64_t counter0, float reward_scale,
+                            float *out_states, float *out_actions, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks,
+                            float *out_last_state, void *stream)
+{
+    ERL_REQUIRE(actor_params && out_states && out_actions && out_rewards && out_undones && out_unmasks, "%s: NULL tensor", what);
+    if (int rc = cont_env_check(what, e, false)) return rc;
+    int64_t aoff[6];
+    if (int rc = sac_rollout_layout(what, variant, e.kind == ENV_PENDULUM, S, A, hidden, n_hidden, N, aoff)) return rc;
+    ERL_REQUIRE(H >= 1 && H < (1LL << 30) && e.max_step >= 1, "%s: bad H=%lld max_step=%d", what, (long long)H, e.max_step);
+    return erl_sac_rollout_fused(actor_params, S, A, hidden[0], hidden[1], aoff, e.env_state, e.Ws, e.Wa, e.phys, e.step_count, e.episode,
+                                 e.max_step, e.env_seed, N, H, noise, seed, counter0, reward_scale, out_states, out_actions, out_rewards,
+                                 out_undones, out_unmasks, out_last_state, (hipStream_t)stream, nullptr, nullptr, variant);
+}
+
+#define SAC_SYNENV {ENV_SYN, env_state, nullptr, Ws, Wa, step_count, episode, max_step, env_seed}
+#define SAC_PENDULUM {ENV_PENDULUM, obs, phys, nullptr, nullptr, step_count, episode, max_step, env_seed}
 #define SAC_ROLLOUT_SYNENV(NAME, VARIANT)                                                                                                    \
     extern "C" int NAME(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state, const float *Ws,         \
                         const float *Wa, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,       \
                         const float *noise, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states, float *out_actions,     \
                         float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, void *stream)                 \
     {                                                                                                                                        \
-        ERL_REQUIRE(Ws && Wa, #NAME ": NULL tensor");                                                                                        \
-        return sac_rollout_impl(#NAME, VARIANT, actor_params, S, A, hidden, n_hidden, env_state, Ws, Wa, nullptr, step_count, episode,       \
-                                max_step, env_seed, N, H, noise, seed, counter0, reward_scale, out_states, out_actions, out_rewards,         \
-                                out_undones, out_unmasks, out_last_state, stream);                                                           \
+        return sac_rollout_impl(#NAME, VARIANT, actor_params, S, A, hidden, n_hidden, SAC_SYNENV, N, H, noise, seed, counter0, reward_scale, \
+                                out_states, out_actions, out_rewards, out_undones, out_unmasks, out_last_state, stream);                     \
     }
 // the same loop on the device-resident PendulumVecEnv (S = 3, A = 1; phys: (N, 2) theta, theta_dot; obs: (N, 3) the live observation)
 #define SAC_ROLLOUT_PENDULUM(NAME, VARIANT)                                                                                                  \
@@ -932,10 +943,8 @@ static int sac_rollout_impl(const char *what, int variant, const float *actor_pa
                         uint64_t counter0, float reward_scale, float *out_states, float *out_actions, float *out_rewards,                    \
                         uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, void *stream)                                     \
     {                                                                                                                                        \
-        ERL_REQUIRE(phys, #NAME ": NULL tensor");                                                                                            \
-        return sac_rollout_impl(#NAME, VARIANT, actor_params, 3, 1, hidden, n_hidden, obs, nullptr, nullptr, phys, step_count, episode,      \
-                                max_step, env_seed, N, H, noise, seed, counter0, reward_scale, out_states, out_actions, out_rewards,         \
-                                out_undones, out_unmasks, out_last_state, stream);                                                           \
+        return sac_rollout_impl(#NAME, VARIANT, actor_params, 3, 1, hidden, n_hidden, SAC_PENDULUM, N, H, noise, seed, counter0,             \
+                                reward_scale, out_states, out_actions, out_rewards, out_undones, out_unmasks, out_last_state, stream);       \
     }
 SAC_ROLLOUT_SYNENV(erl_sac_rollout_synenv_f32, ERL_SAC_ACTOR_SAC)
 SAC_ROLLOUT_PENDULUM(erl_sac_rollout_pendulum_f32, ERL_SAC_ACTOR_SAC)
@@ -955,23 +964,21 @@ extern "C" int erl_sac_rollout_mod_supported(int S, int A, const int *hidden, in
 // ActorSAC.forward (variant ERL_SAC_ACTOR_FIX: ActorFixSAC.forward), per-episode (return, length) records and per-env episode counts into
 // `workspace` (erl_eval_workspace_bytes(N, H)); erl_eval_episodes_compact_f32 (rollout_eval.hip) turns them into the evaluator's table.
 // Support is that of the training twin.
-static int sac_eval_impl(const char *what, int variant, const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state,
-                         const float *Ws, const float *Wa, float *phys, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
+static int sac_eval_impl(const char *what, int variant, const float *actor_params, int S, int A, const int *hidden, int n_hidden, const ContEnv &e,
                          int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    ERL_REQUIRE(actor_params && env_state && (phys || (Ws && Wa)) && step_count && episode && workspace, "%s: NULL tensor", what);
-    ERL_REQUIRE(hidden && n_hidden >= 1 && erl_sac_rollout_synenv_supported(S, A, hidden, n_hidden, N), "%s: unsupported dims S=%d A=%d N=%lld (two "
-                "hidden layers <= 256 wide in steps of 16, S + A <= 64, A <= 8, N <= 4096; ERL_SAC_FUSED=0 turns it off)", what, S, A, (long long)N);
-    ERL_REQUIRE(H >= 1 && H < (1LL << 30) && max_step >= 1 && erl_eval_ws_bytes(N, H) > 0, "%s: bad H=%lld max_step=%d", what, (long long)H, max_step);
+    ERL_REQUIRE(actor_params && workspace, "%s: NULL tensor", what);
+    if (int rc = cont_env_check(what, e, false)) return rc;
+    int64_t aoff[6];
+    if (int rc = sac_rollout_layout(what, variant, false, S, A, hidden, n_hidden, N, aoff)) return rc;
+    ERL_REQUIRE(H >= 1 && H < (1LL << 30) && e.max_step >= 1 && erl_eval_ws_bytes(N, H) > 0, "%s: bad H=%lld max_step=%d", what, (long long)H,
+                e.max_step);
     ERL_REQUIRE(workspace_bytes >= erl_eval_ws_bytes(N, H), "%s: workspace of %lld bytes, erl_eval_workspace_bytes(N, H) = %lld", what,
                 (long long)workspace_bytes, (long long)erl_eval_ws_bytes(N, H));
-    SacDims d;
-    ERL_REQUIRE(make_sac_dims(S, A, hidden, n_hidden, 1, &d, variant), "%s: unsupported dims", what);
-    const int64_t aoff[6] = {d.actor.oW[0], d.actor.ob[0], d.actor.oW[1], d.actor.ob[1], d.actor.oW[2], d.actor.ob[2]};
     const ErlEvalWs w = erl_eval_ws_layout(workspace, N, H);
-    return erl_sac_rollout_fused(actor_params, S, A, hidden[0], hidden[1], aoff, env_state, Ws, Wa, phys, step_count, episode, max_step, env_seed,
-                                 N, H, nullptr, 0, 0, 1.0f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (hipStream_t)stream, w.rec, w.cnt,
-                                 variant);
+    return erl_sac_rollout_fused(actor_params, S, A, hidden[0], hidden[1], aoff, e.env_state, e.Ws, e.Wa, e.phys, e.step_count, e.episode,
+                                 e.max_step, e.env_seed, N, H, nullptr, 0, 0, 1.0f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                 (hipStream_t)stream, w.rec, w.cnt, variant);
 }
 
 #define SAC_EVAL_SYNENV(NAME, VARIANT)                                                                                                       \
@@ -979,18 +986,14 @@ static int sac_eval_impl(const char *what, int variant, const float *actor_param
                         const float *Wa, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,       \
                         void *workspace, int64_t workspace_bytes, void *stream)                                                              \
     {                                                                                                                                        \
-        ERL_REQUIRE(Ws && Wa, #NAME ": NULL tensor");                                                                                        \
-        return sac_eval_impl(#NAME, VARIANT, actor_params, S, A, hidden, n_hidden, env_state, Ws, Wa, nullptr, step_count, episode, max_step, \
-                             env_seed, N, H, workspace, workspace_bytes, stream);                                                            \
+        return sac_eval_impl(#NAME, VARIANT, actor_params, S, A, hidden, n_hidden, SAC_SYNENV, N, H, workspace, workspace_bytes, stream);    \
     }
 #define SAC_EVAL_PENDULUM(NAME, VARIANT)                                                                                                     \
     extern "C" int NAME(const float *actor_params, const int *hidden, int n_hidden, float *phys, float *obs, int32_t *step_count,            \
                         int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H, void *workspace, int64_t workspace_bytes,   \
                         void *stream)                                                                                                        \
     {                                                                                                                                        \
-        ERL_REQUIRE(phys, #NAME ": NULL tensor");                                                                                            \
-        return sac_eval_impl(#NAME, VARIANT, actor_params, 3, 1, hidden, n_hidden, obs, nullptr, nullptr, phys, step_count, episode, max_step, \
-                             env_seed, N, H, workspace, workspace_bytes, stream);                                                            \
+        return sac_eval_impl(#NAME, VARIANT, actor_params, 3, 1, hidden, n_hidden, SAC_PENDULUM, N, H, workspace, workspace_bytes, stream);  \
     }
 SAC_EVAL_SYNENV(erl_sac_eval_synenv_f32, ERL_SAC_ACTOR_SAC)
 SAC_EVAL_PENDULUM(erl_sac_eval_pendulum_f32, ERL_SAC_ACTOR_SAC)
@@ -998,6 +1001,8 @@ SAC_EVAL_SYNENV(erl_sac_eval_mod_synenv_f32, ERL_SAC_ACTOR_FIX)
 SAC_EVAL_PENDULUM(erl_sac_eval_mod_pendulum_f32, ERL_SAC_ACTOR_FIX)
 #undef SAC_EVAL_SYNENV
 #undef SAC_EVAL_PENDULUM
+#undef SAC_SYNENV
+#undef SAC_PENDULUM
 
 // ActorSAC.get_action for the off-policy rollout (AgentSAC.py:179-185): action = tanh(mean + std * eps); state_out (may be NULL):
 // the rollout's `states[t] = state` (AgentBase.py:145) written by the same launch.  With the actor variant named: ERL_SAC_ACTOR_FIX =

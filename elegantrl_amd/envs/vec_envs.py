@@ -7,6 +7,9 @@ They additionally expose `step_into(action, reward_row, terminal_row, truncate_r
 rollout write step outputs straight into row t of its time-major buffers (no copies, no host sync).
 The dynamics run in erl_synenv_step_f32 / erl_pendulum_step_f32 (elegantrl_amd/csrc/envs.hip) and erl_cartpole_step_f32 /
 erl_acrobot_step_f32 / erl_mountaincar_step_f32 (elegantrl_amd/csrc/rollout_discrete.hip).
+
+Each family's base class owns every launch and leaves an env its constructor, `reset`, its entries' names and its live buffers:
+_ContinuousGpuVecEnv (SynVecEnv, PendulumVecEnv) and _DiscreteGpuVecEnv (CartPole, Acrobot, MountainCar).
 """
 from __future__ import annotations
 
@@ -20,16 +23,20 @@ from .. import _hip
 TEN = th.Tensor
 
 
+def _u64(x: int) -> int:
+    """a Python int as the uint64 the C entries take (seeds and counters may be negative or beyond 64 bits)"""
+    return x & (2 ** 64 - 1)
+
+
 def _epilogue_args(epilogue):
     """the nine epilogue arguments of erl_rollout_*_f32 from (last_state_out, advantages, reward_sums, stats, workspace, gamma,
     lambda_gae, use_v_trace); all-NULL when there is none"""
     if epilogue is None:
         return None, None, None, None, None, 0, 0.0, 0.0, 0
     last, adv, ret, stats, ws, gamma, lam, vtrace = epilogue
-    p = _hip.ptr
-    return (None if last is None else p(last, th.float32), None if adv is None else p(adv, th.float32),
-            None if ret is None else p(ret, th.float32), None if stats is None else p(stats, th.float64),
-            None if ws is None else p(ws, th.float64), 0 if ws is None else ws.numel() * 8, float(gamma), float(lam), int(bool(vtrace)))
+    p, f32, f64 = _hip.ptr, th.float32, th.float64        # (None passes NULL)
+    return (p(last, f32), p(adv, f32), p(ret, f32), p(stats, f64), p(ws, f64), 0 if ws is None else ws.numel() * 8, float(gamma), float(lam),
+            int(bool(vtrace)))
 
 
 def _discrete_epilogue_args(agent, epilogue):
@@ -78,11 +85,112 @@ def compact_episodes(workspace: TEN, num_envs: int, horizon_len: int, rows: TEN,
         _hip.ptr(count, th.int32), _hip.stream_ptr()), "erl_eval_episodes_compact_f32")
 
 
-class SynVecEnv(_GpuVecEnv):
+class _ContinuousGpuVecEnv(_GpuVecEnv):
+    """what the device-resident continuous envs share: the per-step launch (erl_<stem>_step_f32, csrc/envs.hip) and the one-launch rollout /
+    evaluation of a PPO agent (erl_rollout_<stem>_f32, erl_eval_<stem>_f32) and of a SAC agent (erl_sac_rollout_[mod_]<stem>_f32,
+    erl_sac_eval_[mod_]<stem>_f32).  An env adds its constructor, `reset`, the three attributes below and `_live`."""
+    _stem = ""                              # "synenv" | "pendulum"
+    _action_at = 0                          # how many of the live buffers the per-step entry takes in front of the action
+    _takes_dims = False                     # the entries take state_dim and action_dim (else they fix them)
+
+    def _live(self) -> Tuple[TEN, ...]:
+        """the live buffers the C entries take, in their order (looked up per call: `reset` rebinds them)"""
+        raise NotImplementedError
+
+    def _dims(self, state_dim: int, action_dim: int) -> tuple:
+        return (state_dim, action_dim) if self._takes_dims else ()
+
+    def step_into(self, action: TEN, reward_row: TEN, terminal_row: TEN, truncate_row: TEN) -> TEN:
+        from .. import ops
+        self.state_epoch += 1
+        live, k = self._live(), self._action_at
+        getattr(ops, f"{self._stem}_step")(*live[:k], action, *live[k:], self.step_count, self.episode, reward_row, terminal_row, truncate_row,
+                                           self.max_step, self.seed)
+        return self.state
+
+    def raw_stepper(self):
+        """`step(action_ptr, reward_ptr, terminal_ptr, truncate_ptr, stream)` on raw device pointers (the rollout's per-step fast path: no
+        tensor views, no argument checks); the live buffers are bound here, once (fixed addresses until the next `reset`)."""
+        name = f"erl_{self._stem}_step_f32"
+        fn = getattr(_hip.lib(), name)
+        live = [t.data_ptr() for t in self._live()]
+        head, mid = tuple(live[:self._action_at]), (*live[self._action_at:], self.step_count.data_ptr(), self.episode.data_ptr())
+        tail = (self.num_envs, *self._dims(self.state_dim, self.action_dim), self.max_step, _u64(self.seed))
+
+        def step(action_ptr, reward_ptr, terminal_ptr, truncate_ptr, stream):
+            self.state_epoch += 1
+            rc = fn(*head, action_ptr, *mid, reward_ptr, terminal_ptr, truncate_ptr, *tail, stream)
+            if rc:
+                _hip.check(rc, name)
+        return step
+
+    def _env_args(self):
+        """the env block of the one-launch entries: live buffers, counters, max_step, env_seed, N"""
+        return (*[_hip.ptr(t, th.float32) for t in self._live()], _hip.ptr(self.step_count, th.int32), _hip.ptr(self.episode, th.int32),
+                self.max_step, _u64(self.seed), self.num_envs)
+
+    def _ppo_args(self, agent, critic: bool):
+        """a fused-path AgentPPO's networks (`critic`: both, as the rollout takes them; else the actor's three) and dims, then the env block"""
+        a, c = agent._act, agent.cri
+        nets = ((agent._flat_a.flat, agent._flat_c.flat, a.state_avg.data, a.state_std.data, c.state_avg.data, c.state_std.data) if critic else
+                (agent._flat_a.flat, a.state_avg.data, a.state_std.data))
+        dims, (h1, h2) = self._dims(self.state_dim, self.action_dim), agent.net_dims
+        return (*[_hip.ptr(t, th.float32) for t in nets], *dims[:1], h1, h2, *dims[1:], *self._env_args())
+
+    def _sac_call(self, form: str, agent, *rest) -> None:
+        """erl_sac_<form>_<stem>_f32 -- for an agent whose actor is ActorFixSAC (AgentModSAC, `agent._spec.actor_variant`) the launch's
+        ActorFixSAC form, erl_sac_<form>_mod_<stem>_f32 -- on the agent's actor, the env block and `rest`"""
+        self.state_epoch += 1
+        spec = agent._spec
+        entry = f"erl_sac_{form}_{'mod_' if spec.actor_variant else ''}{self._stem}_f32"
+        _hip.check(getattr(_hip.lib(), entry)(
+            _hip.ptr(agent._actor_flat, th.float32), *self._dims(spec.S, spec.A), spec._c, len(spec.hidden), *self._env_args(), *rest,
+            _hip.stream_ptr()), entry)
+
+    def fused_rollout(self, agent, horizon_len: int, noise, bufs, values, next_value, epilogue=None) -> None:
+        """all `horizon_len` steps of AgentPPO._explore_vec_env in ONE launch (erl_rollout_<stem>_f32); `bufs` = (states,
+        actions, logprobs, rewards, undones, unmasks) time-major, written in place; the env's state / counters advance.
+        `epilogue` = (last_state_out, advantages, reward_sums, stats, workspace, gamma, lambda_gae, use_v_trace) or None: the
+        kernel's optional tail (include/erl_hip.h): the agent's own copy of the final state, get_advantages + its statistics."""
+        self.state_epoch += 1
+        p, f32 = _hip.ptr, th.float32
+        states, actions, logprobs, rewards, undones, unmasks = bufs
+        entry = f"erl_rollout_{self._stem}_f32"
+        _hip.check(getattr(_hip.lib(), entry)(
+            *self._ppo_args(agent, True), horizon_len, p(noise, f32), _u64(agent.rng_seed), _u64(agent.rng_counter), float(agent.reward_scale),
+            p(states, f32), p(actions, f32), p(logprobs, f32), p(rewards, f32), _hip.flag_ptr(undones), _hip.flag_ptr(unmasks), p(values, f32),
+            p(next_value, f32), *_epilogue_args(epilogue), _hip.stream_ptr()), entry)
+
+    def fused_rollout_offpolicy(self, agent, horizon_len: int, noise, bufs, last_state_out) -> None:
+        """all `horizon_len` steps of the off-policy AgentBase._explore_vec_env in ONE launch (erl_sac_rollout_<stem>_f32; AgentModSAC:
+        erl_sac_rollout_mod_<stem>_f32): `bufs` = (states, actions, rewards, undones, unmasks) time-major, written in place (rewards scaled,
+        flags inverted); `last_state_out` (N, S) or None: the agent's own copy of the final state; the env's state / counters advance."""
+        p, f32 = _hip.ptr, th.float32
+        states, actions, rewards, undones, unmasks = bufs
+        self._sac_call("rollout", agent, horizon_len, p(noise, f32), _u64(agent.rng_seed), _u64(agent.rng_counter), float(agent.reward_scale),
+                       p(states, f32), p(actions, f32), p(rewards, f32), _hip.flag_ptr(undones), _hip.flag_ptr(unmasks), p(last_state_out, f32))
+
+    def fused_evaluate(self, agent, horizon_len: int, workspace) -> None:
+        """`horizon_len` steps of the deterministic policy tanh(mean) of a fused-path AgentPPO in ONE launch (erl_eval_<stem>_f32: the
+        evaluation form of `fused_rollout`); the per-episode records and per-env counts go to `workspace` (uint8, erl_eval_workspace_bytes);
+        the env's state / counters advance."""
+        self.state_epoch += 1
+        entry = f"erl_eval_{self._stem}_f32"
+        _hip.check(getattr(_hip.lib(), entry)(
+            *self._ppo_args(agent, False), horizon_len, _hip.ptr(workspace, th.uint8), workspace.numel(), _hip.stream_ptr()), entry)
+
+    def fused_evaluate_offpolicy(self, agent, horizon_len: int, workspace) -> None:
+        """... of the deterministic policy of a fused-path AgentSAC (erl_sac_eval_<stem>_f32: the evaluation form of
+        `fused_rollout_offpolicy`; AgentModSAC: erl_sac_eval_mod_<stem>_f32, ActorFixSAC.forward)"""
+        self._sac_call("eval", agent, horizon_len, _hip.ptr(workspace, th.uint8), workspace.numel())
+
+
+class SynVecEnv(_ContinuousGpuVecEnv):
     """Synthetic continuous-control workload of SURVEY.md 8d: s' = s Ws + a Wa with Ws = 0.9 I + 0.05 G1,
     Wa = 0.1 G2 (G ~ N(0,1), torch.Generator().manual_seed(0)); reward = -mean(s'^2) - 0.01 mean(a^2);
     terminal = max|s'| > 10; truncate at max_step; done rows reset to N(0,1)."""
     env_name = "SynVecEnv"
+    _stem, _action_at, _takes_dims = "synenv", 1, True
 
     def __init__(self, num_envs: int = 4096, state_dim: int = 64, action_dim: int = 8, max_step: int = 1000,
                  gpu_id: int = 0, seed: int = 0, **_):
@@ -92,6 +200,9 @@ class SynVecEnv(_GpuVecEnv):
         self.Wa = (0.1 * th.randn(action_dim, state_dim, generator=g)).to(self.device).contiguous()
         self.state = th.zeros((num_envs, state_dim), dtype=th.float32, device=self.device)
 
+    def _live(self):
+        return (self.state, self.Ws, self.Wa)
+
     def reset(self) -> Tuple[TEN, dict]:
         self.state_epoch += 1
         g = th.Generator(device=self.device).manual_seed(self.seed)
@@ -100,107 +211,21 @@ class SynVecEnv(_GpuVecEnv):
         self.episode.zero_()
         return self.state.clone(), {}
 
-    def step_into(self, action: TEN, reward_row: TEN, terminal_row: TEN, truncate_row: TEN) -> TEN:
-        from .. import ops
-        self.state_epoch += 1
-        ops.synenv_step(self.state, action, self.Ws, self.Wa, self.step_count, self.episode, reward_row, terminal_row,
-                        truncate_row, self.max_step, self.seed)
-        return self.state
 
-    def raw_stepper(self):
-        """`step(action_ptr, reward_ptr, terminal_ptr, truncate_ptr, stream)` on raw device pointers (the rollout's
-        per-step fast path: no tensor views, no argument checks); the state lives in `self.state` (fixed address)."""
-        from .. import _hip
-        fn = _hip.lib().erl_synenv_step_f32
-        st, ws, wa, sc, ep = (t.data_ptr() for t in (self.state, self.Ws, self.Wa, self.step_count, self.episode))
-        n, s, a, ms, seed = self.num_envs, self.state_dim, self.action_dim, self.max_step, self.seed & (2 ** 64 - 1)
-
-        def step(action_ptr, reward_ptr, terminal_ptr, truncate_ptr, stream):
-            self.state_epoch += 1
-            rc = fn(st, action_ptr, ws, wa, sc, ep, reward_ptr, terminal_ptr, truncate_ptr, n, s, a, ms, seed, stream)
-            if rc:
-                _hip.check(rc, "erl_synenv_step_f32")
-        return step
-
-
-    def fused_rollout(self, agent, horizon_len: int, noise, bufs, values, next_value, epilogue=None) -> None:
-        """all `horizon_len` steps of AgentPPO._explore_vec_env in ONE launch (erl_rollout_synenv_f32); `bufs` = (states,
-        actions, logprobs, rewards, undones, unmasks) time-major, written in place; the env's state / counters advance.
-        `epilogue` = (last_state_out, advantages, reward_sums, stats, workspace, gamma, lambda_gae, use_v_trace) or None: the
-        kernel's optional tail (include/erl_hip.h): the agent's own copy of the final state, get_advantages + its statistics."""
-        from .. import _hip
-        self.state_epoch += 1
-        p, f32 = _hip.ptr, th.float32
-        a, c = agent._act, agent.cri
-        states, actions, logprobs, rewards, undones, unmasks = bufs
-        h1, h2 = agent.net_dims
-        _hip.check(_hip.lib().erl_rollout_synenv_f32(
-            p(agent._flat_a.flat, f32), p(agent._flat_c.flat, f32), p(a.state_avg.data, f32), p(a.state_std.data, f32),
-            p(c.state_avg.data, f32), p(c.state_std.data, f32), self.state_dim, h1, h2, self.action_dim, p(self.state, f32),
-            p(self.Ws, f32), p(self.Wa, f32), p(self.step_count, th.int32), p(self.episode, th.int32), self.max_step,
-            self.seed & (2 ** 64 - 1), self.num_envs, horizon_len, p(noise, f32), agent.rng_seed & (2 ** 64 - 1),
-            agent.rng_counter & (2 ** 64 - 1), float(agent.reward_scale), p(states, f32), p(actions, f32), p(logprobs, f32),
-            p(rewards, f32), _hip.flag_ptr(undones), _hip.flag_ptr(unmasks), p(values, f32), p(next_value, f32),
-            *_epilogue_args(epilogue), _hip.stream_ptr()), "erl_rollout_synenv_f32")
-
-
-    def fused_rollout_offpolicy(self, agent, horizon_len: int, noise, bufs, last_state_out) -> None:
-        """all `horizon_len` steps of the off-policy AgentBase._explore_vec_env in ONE launch (erl_sac_rollout_synenv_f32): `bufs` = (states,
-        actions, rewards, undones, unmasks) time-major, written in place (rewards scaled, flags inverted); `last_state_out` (N, S) or None:
-        the agent's own copy of the final state; the env's state / counters advance.  An agent whose actor is ActorFixSAC (AgentModSAC,
-        `agent._spec.actor_variant`) takes the launch's ActorFixSAC form, erl_sac_rollout_mod_synenv_f32."""
-        from .. import _hip
-        self.state_epoch += 1
-        p, f32 = _hip.ptr, th.float32
-        states, actions, rewards, undones, unmasks = bufs
-        spec = agent._spec
-        entry = "erl_sac_rollout_mod_synenv_f32" if spec.actor_variant else "erl_sac_rollout_synenv_f32"        # (ActorFixSAC: AgentModSAC)
-        _hip.check(getattr(_hip.lib(), entry)(
-            p(agent._actor_flat, f32), spec.S, spec.A, spec._c, len(spec.hidden), p(self.state, f32), p(self.Ws, f32), p(self.Wa, f32),
-            p(self.step_count, th.int32), p(self.episode, th.int32), self.max_step, self.seed & (2 ** 64 - 1), self.num_envs, horizon_len,
-            p(noise, f32), agent.rng_seed & (2 ** 64 - 1), agent.rng_counter & (2 ** 64 - 1), float(agent.reward_scale), p(states, f32),
-            p(actions, f32), p(rewards, f32), _hip.flag_ptr(undones), _hip.flag_ptr(unmasks),
-            p(last_state_out, f32) if last_state_out is not None else None, _hip.stream_ptr()), entry)
-
-
-    def fused_evaluate(self, agent, horizon_len: int, workspace) -> None:
-        """`horizon_len` steps of the deterministic policy tanh(mean) of a fused-path AgentPPO in ONE launch (erl_eval_synenv_f32: the
-        evaluation form of `fused_rollout`); the per-episode records and per-env counts go to `workspace` (uint8, erl_eval_workspace_bytes);
-        the env's state / counters advance."""
-        from .. import _hip
-        self.state_epoch += 1
-        p, f32 = _hip.ptr, th.float32
-        a = agent._act
-        h1, h2 = agent.net_dims
-        _hip.check(_hip.lib().erl_eval_synenv_f32(
-            p(agent._flat_a.flat, f32), p(a.state_avg.data, f32), p(a.state_std.data, f32), self.state_dim, h1, h2, self.action_dim,
-            p(self.state, f32), p(self.Ws, f32), p(self.Wa, f32), p(self.step_count, th.int32), p(self.episode, th.int32), self.max_step,
-            self.seed & (2 ** 64 - 1), self.num_envs, horizon_len, p(workspace, th.uint8), workspace.numel(), _hip.stream_ptr()),
-            "erl_eval_synenv_f32")
-
-    def fused_evaluate_offpolicy(self, agent, horizon_len: int, workspace) -> None:
-        """... of the deterministic policy of a fused-path AgentSAC (erl_sac_eval_synenv_f32: the evaluation form of `fused_rollout_offpolicy`;
-        AgentModSAC: erl_sac_eval_mod_synenv_f32, ActorFixSAC.forward)"""
-        from .. import _hip
-        self.state_epoch += 1
-        p, f32 = _hip.ptr, th.float32
-        spec = agent._spec
-        entry = "erl_sac_eval_mod_synenv_f32" if spec.actor_variant else "erl_sac_eval_synenv_f32"        # (ActorFixSAC: AgentModSAC)
-        _hip.check(getattr(_hip.lib(), entry)(
-            p(agent._actor_flat, f32), spec.S, spec.A, spec._c, len(spec.hidden), p(self.state, f32), p(self.Ws, f32), p(self.Wa, f32),
-            p(self.step_count, th.int32), p(self.episode, th.int32), self.max_step, self.seed & (2 ** 64 - 1), self.num_envs, horizon_len,
-            p(workspace, th.uint8), workspace.numel(), _hip.stream_ptr()), entry)
-
-
-class PendulumVecEnv(_GpuVecEnv):
+class PendulumVecEnv(_ContinuousGpuVecEnv):
     """Pendulum-v1 (g=10, m=l=1, dt=0.05, 200-step truncation) behind the reference wrapper's scaling
-    (elegantrl/envs/CustomGymEnv.py:42-44: torque = 2*action, reward = 0.5*gym reward)."""
+    (elegantrl/envs/CustomGymEnv.py:42-44: torque = 2*action, reward = 0.5*gym reward).  `phys` (N, 2) = (theta, theta_dot) is the state
+    of record, `state` (N, 3) the live observation; the entries fix state_dim 3 and action_dim 1."""
     env_name = "Pendulum-v1"
+    _stem, _action_at = "pendulum", 2
 
     def __init__(self, num_envs: int = 4096, max_step: int = 200, gpu_id: int = 0, seed: int = 0, **_):
         super().__init__(num_envs, 3, 1, max_step, gpu_id, seed)
         self.phys = th.zeros((num_envs, 2), dtype=th.float32, device=self.device)
         self.state = th.zeros((num_envs, 3), dtype=th.float32, device=self.device)
+
+    def _live(self):
+        return (self.phys, self.state)
 
     def reset(self) -> Tuple[TEN, dict]:
         self.state_epoch += 1
@@ -211,87 +236,6 @@ class PendulumVecEnv(_GpuVecEnv):
         self.step_count.zero_()
         self.episode.zero_()
         return self.state.clone(), {}
-
-    def step_into(self, action: TEN, reward_row: TEN, terminal_row: TEN, truncate_row: TEN) -> TEN:
-        from .. import ops
-        self.state_epoch += 1
-        ops.pendulum_step(self.phys, self.state, action, self.step_count, self.episode, reward_row, terminal_row,
-                          truncate_row, self.max_step, self.seed)
-        return self.state
-
-    def raw_stepper(self):
-        from .. import _hip
-        fn = _hip.lib().erl_pendulum_step_f32
-        ph, ob, sc, ep = (t.data_ptr() for t in (self.phys, self.state, self.step_count, self.episode))
-        n, ms, seed = self.num_envs, self.max_step, self.seed & (2 ** 64 - 1)
-
-        def step(action_ptr, reward_ptr, terminal_ptr, truncate_ptr, stream):
-            self.state_epoch += 1
-            rc = fn(ph, ob, action_ptr, sc, ep, reward_ptr, terminal_ptr, truncate_ptr, n, ms, seed, stream)
-            if rc:
-                _hip.check(rc, "erl_pendulum_step_f32")
-        return step
-
-
-    def fused_rollout_offpolicy(self, agent, horizon_len: int, noise, bufs, last_state_out) -> None:
-        """all `horizon_len` steps of the off-policy AgentBase._explore_vec_env in ONE launch (erl_sac_rollout_pendulum_f32); arguments as
-        SynVecEnv.fused_rollout_offpolicy (AgentModSAC: erl_sac_rollout_mod_pendulum_f32)."""
-        from .. import _hip
-        self.state_epoch += 1
-        p, f32 = _hip.ptr, th.float32
-        states, actions, rewards, undones, unmasks = bufs
-        spec = agent._spec
-        entry = "erl_sac_rollout_mod_pendulum_f32" if spec.actor_variant else "erl_sac_rollout_pendulum_f32"        # (ActorFixSAC: AgentModSAC)
-        _hip.check(getattr(_hip.lib(), entry)(
-            p(agent._actor_flat, f32), spec._c, len(spec.hidden), p(self.phys, f32), p(self.state, f32), p(self.step_count, th.int32),
-            p(self.episode, th.int32), self.max_step, self.seed & (2 ** 64 - 1), self.num_envs, horizon_len, p(noise, f32),
-            agent.rng_seed & (2 ** 64 - 1), agent.rng_counter & (2 ** 64 - 1), float(agent.reward_scale), p(states, f32), p(actions, f32),
-            p(rewards, f32), _hip.flag_ptr(undones), _hip.flag_ptr(unmasks), p(last_state_out, f32) if last_state_out is not None else None,
-            _hip.stream_ptr()), entry)
-
-    def fused_rollout(self, agent, horizon_len: int, noise, bufs, values, next_value, epilogue=None) -> None:
-        """all `horizon_len` steps of AgentPPO._explore_vec_env in ONE launch (erl_rollout_pendulum_f32); `epilogue` as
-        SynVecEnv.fused_rollout."""
-        from .. import _hip
-        self.state_epoch += 1
-        p, f32 = _hip.ptr, th.float32
-        a, c = agent._act, agent.cri
-        states, actions, logprobs, rewards, undones, unmasks = bufs
-        h1, h2 = agent.net_dims
-        _hip.check(_hip.lib().erl_rollout_pendulum_f32(
-            p(agent._flat_a.flat, f32), p(agent._flat_c.flat, f32), p(a.state_avg.data, f32), p(a.state_std.data, f32),
-            p(c.state_avg.data, f32), p(c.state_std.data, f32), h1, h2, p(self.phys, f32), p(self.state, f32),
-            p(self.step_count, th.int32), p(self.episode, th.int32), self.max_step, self.seed & (2 ** 64 - 1), self.num_envs,
-            horizon_len, p(noise, f32), agent.rng_seed & (2 ** 64 - 1), agent.rng_counter & (2 ** 64 - 1),
-            float(agent.reward_scale), p(states, f32), p(actions, f32), p(logprobs, f32), p(rewards, f32),
-            _hip.flag_ptr(undones), _hip.flag_ptr(unmasks), p(values, f32), p(next_value, f32), *_epilogue_args(epilogue),
-            _hip.stream_ptr()), "erl_rollout_pendulum_f32")
-
-
-    def fused_evaluate(self, agent, horizon_len: int, workspace) -> None:
-        """`horizon_len` steps of the deterministic policy in ONE launch (erl_eval_pendulum_f32); arguments as SynVecEnv.fused_evaluate."""
-        from .. import _hip
-        self.state_epoch += 1
-        p, f32 = _hip.ptr, th.float32
-        a = agent._act
-        h1, h2 = agent.net_dims
-        _hip.check(_hip.lib().erl_eval_pendulum_f32(
-            p(agent._flat_a.flat, f32), p(a.state_avg.data, f32), p(a.state_std.data, f32), h1, h2, p(self.phys, f32), p(self.state, f32),
-            p(self.step_count, th.int32), p(self.episode, th.int32), self.max_step, self.seed & (2 ** 64 - 1), self.num_envs, horizon_len,
-            p(workspace, th.uint8), workspace.numel(), _hip.stream_ptr()), "erl_eval_pendulum_f32")
-
-    def fused_evaluate_offpolicy(self, agent, horizon_len: int, workspace) -> None:
-        """... of a fused-path AgentSAC (erl_sac_eval_pendulum_f32; AgentModSAC: erl_sac_eval_mod_pendulum_f32); arguments as
-        SynVecEnv.fused_evaluate_offpolicy."""
-        from .. import _hip
-        self.state_epoch += 1
-        p, f32 = _hip.ptr, th.float32
-        spec = agent._spec
-        entry = "erl_sac_eval_mod_pendulum_f32" if spec.actor_variant else "erl_sac_eval_pendulum_f32"        # (ActorFixSAC: AgentModSAC)
-        _hip.check(getattr(_hip.lib(), entry)(
-            p(agent._actor_flat, f32), spec._c, len(spec.hidden), p(self.phys, f32), p(self.state, f32), p(self.step_count, th.int32),
-            p(self.episode, th.int32), self.max_step, self.seed & (2 ** 64 - 1), self.num_envs, horizon_len, p(workspace, th.uint8),
-            workspace.numel(), _hip.stream_ptr()), entry)
 
 
 class _DiscreteGpuVecEnv(_GpuVecEnv):

@@ -7,8 +7,9 @@ the same machine, and diff the outputs:
     python tools/agent_route_digest.py --tree ../before  > before.txt      # imports elegantrl_amd from another checkout (built)
 
 Per route: ITERS iterations of explore_env + update_net; hashed are the rollout tensors of the last iteration (as update_net left
-them), the flat weights and Adam moments, `_grads[:update_times]` and the logs every update_net returned.  The SAC route hashes
-its rollout tensors and the rows of evaluate_env.  Shapes: 48 envs x 10 steps (H * N = 480 is no multiple of 256: the plane pitch
+them), the flat weights and Adam moments, `_grads[:update_times]` and the logs every update_net returned.  The SAC routes hash
+their rollout tensors and the rows of evaluate_env.  The PendulumVecEnv routes and the AgentModSAC route run max_step 4: truncation and
+auto-reset fall inside the horizon.  Shapes: 48 envs x 10 steps (H * N = 480 is no multiple of 256: the plane pitch
 is padded), batch 256 = two slabs, two minibatches per update; one env x 10 steps, batch 4 for the single-env rollout."""
 import argparse
 import hashlib
@@ -27,8 +28,8 @@ import torch as th  # noqa: E402
 if not th.cuda.is_available():
     sys.exit("agent_route_digest: needs a GPU")
 
-from elegantrl_amd.agents import AgentA2C, AgentDiscretePPO, AgentPPO, AgentSAC  # noqa: E402
-from elegantrl_amd.envs import CartPoleGpuVecEnv, SynVecEnv  # noqa: E402
+from elegantrl_amd.agents import AgentA2C, AgentDiscretePPO, AgentModSAC, AgentPPO, AgentSAC  # noqa: E402
+from elegantrl_amd.envs import CartPoleGpuVecEnv, PendulumVecEnv, SynVecEnv  # noqa: E402
 from elegantrl_amd.train import Config  # noqa: E402
 
 ITERS, N, H, B, S, A = 3, 48, 10, 256, 17, 3
@@ -112,12 +113,37 @@ on_policy("AgentDiscretePPO (64,32) CartPole fused_update off", AgentDiscretePPO
 on_policy("AgentA2C (64,32) one numpy env", AgentA2C, StubEnv(5), 5, 2, (64, 32), n_envs=1, batch=4, repeat=1.0)
 on_policy("AgentDiscretePPO (64,32) one numpy env", AgentDiscretePPO, StubEnv(5), 5, 3, (64, 32), n_envs=1, batch=4, repeat=1.0, discrete=True)
 
-# AgentSAC: the one-launch off-policy rollout and the evaluation that goes with it
-env = SynVecEnv(N, S, A, max_step=6, gpu_id=0, seed=5)
-agent = make(AgentSAC, env, S, A, (64, 64), N, B, 1.0, False, fused_rollout=True)
-for _ in range(ITERS):
-    items = agent.explore_env(env, H)
-assert agent._last_state_token is not None, agent.kernel_path
-rows = agent.evaluate_env(env)
-assert rows is not None, agent._fused_eval_reason(env)
-print(f"{sha([*items, agent.last_state, rows], [])}  AgentSAC (64,64) one-launch rollout + evaluate_env", flush=True)
+
+
+def pendulum():
+    return PendulumVecEnv(N, max_step=4, gpu_id=0, seed=5)
+
+
+for net, name in (((128, 64), "tuned class"), ((64, 64), "general class")):
+    on_policy(f"AgentPPO {net} Pendulum one-launch rollout ({name})", AgentPPO, pendulum(), 3, 1, net, rollout="one-launch", fused_rollout=True,
+              fused_gae=True)
+on_policy("AgentPPO (128,64) Pendulum raw-stepper loop", AgentPPO, pendulum(), 3, 1, (128, 64), rollout="loop", fused_rollout=False)
+# the evaluation form of the PPO rollout on both envs
+for name, env, S_, A_, net in (("SynVecEnv", syn(), S, A, (128, 128)), ("Pendulum", pendulum(), 3, 1, (128, 64))):
+    agent = make(AgentPPO, env, S_, A_, net, N, B, 52.0, False, fused_rollout=True)
+    agent.explore_env(env, H)
+    rows = agent.evaluate_env(env)
+    assert rows is not None, agent._fused_eval_reason(env)
+    print(f"{sha([rows, env.state, env.step_count, env.episode], [])}  AgentPPO {net} {name} evaluate_env", flush=True)
+
+
+def off_policy(name, cls, env, S_, A_, net=(64, 64)):
+    """the one-launch off-policy rollout and the evaluation that goes with it (AgentModSAC: both are opt-in, fused_mod_rollout)"""
+    agent = make(cls, env, S_, A_, net, N, B, 1.0, False, fused_rollout=True, fused_mod_rollout=True)
+    for _ in range(ITERS):
+        items = agent.explore_env(env, H)
+    assert agent._last_state_token is not None, agent.kernel_path
+    rows = agent.evaluate_env(env)
+    assert rows is not None, agent._fused_eval_reason(env)
+    print(f"{sha([*items, agent.last_state, rows], [])}  {name} one-launch rollout + evaluate_env", flush=True)
+
+
+off_policy("AgentSAC (64,64)", AgentSAC, SynVecEnv(N, S, A, max_step=6, gpu_id=0, seed=5), S, A)
+off_policy("AgentSAC (64,64) Pendulum", AgentSAC, pendulum(), 3, 1)
+off_policy("AgentModSAC (64,64)", AgentModSAC, SynVecEnv(N, S, A, max_step=4, gpu_id=0, seed=5), S, A)
+off_policy("AgentModSAC (64,64) Pendulum", AgentModSAC, pendulum(), 3, 1)
