@@ -24,8 +24,7 @@
 // ready", so nothing has to be cleared between launches (a memset + its launch gap cost ~25 % at 151 MB).  Problems
 // whose table exceeds that buffer, or calls on a second stream, use the caller's workspace with a memset instead.
 #include "erl_common.h"
-
-#include <mutex>
+#include "stream_slots.h"
 
 namespace {
 
@@ -575,21 +574,15 @@ bool erl_gae_lookback_usable(const float *rewards, const uint8_t *undones, const
     return (N % 4 == 0) && (f % 16 == 0) && (b % 4 == 0);
 }
 
-// Library-owned look-back tables, one per (device, stream) that has launched the scan: [ticket counter: 256 B][granules].  Only
-// gae_lookback_kernel writes them; stale granules carry older nonces, and launches that share a table are ordered by its stream
-// (two agents on two streams of one device each get their own: round 4 kept ONE table per device and sent the second stream to
-// the memset path).  Allocated (and zeroed) on first use; beyond kLbMaxTables the caller's workspace + a memset serve.
+// Look-back tables (library-owned: stream_slots.h): [ticket counter: 256 B][granules].  Only gae_lookback_kernel writes them; stale
+// granules carry older nonces, and launches that share a table are ordered by its stream.  Allocated (and zeroed) on first use; when
+// all 16 entries are taken the caller's workspace + a memset serve.
 constexpr size_t kLbTableBytes = 256 + ((size_t)8 << 20);   // 8 MiB of granules: K * N <= 1M (e.g. 2048 x 65536 at T = 128)
-constexpr int kLbMaxTables = 16;
 struct LbTable {
     char *ptr = nullptr;
     uint32_t nonce = 1, ticket_base = 0;
-    int dev = -1;
-    hipStream_t stream = nullptr;
 };
-static LbTable g_lb_table[kLbMaxTables];
-static int g_lb_tables = 0;
-static std::mutex g_lb_mutex;      // table lookup / creation / nonce hand-out (agents on several devices or streams launch from their own threads)
+static StreamSlots<LbTable, 16> g_lb_table;
 
 // Enqueues [memset +] kernel.  workspace layout (fallback path): [ticket: 256 B][slots: K*N*8 B][partials: nblk*24 B].
 // Returns the number of statistics partials (blocks) through *nparts and their location through *partials.
@@ -664,23 +657,20 @@ int erl_gae_lookback_launch(float *rewards, uint8_t *undones, const uint8_t *unm
     // fast path: the library-owned table (no clearing); fallback: the caller's workspace, cleared by a memset
     LbTable *tab = nullptr;
     int dev = -1;
-    std::lock_guard<std::mutex> lock(g_lb_mutex);
+    auto lock = g_lb_table.lock();      // look-up, creation, nonce and ticket-base hand-out, up to the launch
     if (!getenv("ERL_GAE_LB_NO_TABLE") && hipGetDevice(&dev) == hipSuccess && dev >= 0 && 256 + slot_bytes <= kLbTableBytes) {
-        for (int i = 0; i < g_lb_tables && !tab; ++i)
-            if (g_lb_table[i].dev == dev && g_lb_table[i].stream == stream) tab = &g_lb_table[i];
-        if (!tab && g_lb_tables < kLbMaxTables) {
+        tab = g_lb_table.find_or_claim(dev, stream);
+        if (tab && !tab->ptr) {
             void *p = nullptr;
-            if (hipMalloc(&p, kLbTableBytes) == hipSuccess) {
-                // zeroed ON THE LAUNCH STREAM: torch's side streams are non-blocking, i.e. not ordered behind the legacy stream a plain
-                // hipMemset runs on -- the scan could start while its ticket counter and granules were still being cleared (round 6: an
-                // intermittent memory fault in tests/test_kernels_gpu.py::test_gae_lookback_tables_are_per_stream; latent since round 5)
-                if (hipMemsetAsync(p, 0, kLbTableBytes, stream) == hipSuccess) {
-                    LbTable &t = g_lb_table[g_lb_tables++];
-                    t.ptr = (char *)p; t.dev = dev; t.stream = stream;
-                    tab = &t;
-                } else {
-                    (void)hipFree(p);
-                }
+            // zeroed ON THE LAUNCH STREAM: torch's side streams are non-blocking, i.e. not ordered behind the legacy stream a plain
+            // hipMemset runs on -- the scan could start while its ticket counter and granules were still being cleared (round 6: an
+            // intermittent memory fault in tests/test_kernels_gpu.py::test_gae_lookback_tables_are_per_stream; latent since round 5)
+            if (hipMalloc(&p, kLbTableBytes) == hipSuccess && hipMemsetAsync(p, 0, kLbTableBytes, stream) == hipSuccess) {
+                tab->ptr = (char *)p;
+            } else {
+                if (p) (void)hipFree(p);
+                g_lb_table.release(tab);
+                tab = nullptr;
             }
             (void)hipGetLastError();
         }

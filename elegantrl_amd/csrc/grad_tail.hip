@@ -21,6 +21,7 @@
 #include "erl_common.h"
 #include "s3_image.h"
 #include "ppo_step_wd.h"
+#include "stream_slots.h"
 
 namespace {
 
@@ -454,14 +455,12 @@ __global__ __launch_bounds__(192) void logs_mean_kernel(const float *__restrict_
     }
 }
 
-// the partial-norm table of an optimiser tail: library-owned, one per (device, stream) that ran one -- written by launch 1 and
-// read by launch 2 of the SAME stream, so two update loops on different streams of a device never share a table
+// the partial-norm table of an optimiser tail (library-owned: stream_slots.h) -- written by launch 1 and read by launch 2 of the
+// SAME stream, so two update loops on different streams of a device never share a table
 struct PartialsSlot {
-    int device = -1;
-    hipStream_t stream = nullptr;
     double *buf = nullptr;
 };
-PartialsSlot g_partials[32];
+StreamSlots<PartialsSlot, 32> g_partials;
 
 int fill_groups(const char *what, const int64_t *off, const int64_t *len, int n_groups, int64_t stride, TailGroups *gr)
 {
@@ -476,16 +475,13 @@ int fill_groups(const char *what, const int64_t *off, const int64_t *len, int n_
 
 
 // ---- the single-launch tail (tail_fused_kernel): per (device, stream, row length) a double-buffered partial-norm table, blank at first
+// (library-owned: stream_slots.h, the row length as the key's extra word)
 struct FusedSlot {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    int64_t stride = 0;
     double *buf = nullptr;        // [2 parities][nchunks_alloc][4]
     int64_t nchunks_alloc = 0;
     unsigned parity = 0;
-    int capacity = -1;            // workgroups of tail_fused_kernel the device holds at once
 };
-FusedSlot g_fused[32];
+StreamSlots<FusedSlot, 32> g_fused;
 
 __global__ __launch_bounds__(256) void fill_u64_kernel(unsigned long long *p, unsigned long long v, int64_t n)
 {
@@ -523,28 +519,30 @@ static int erl_tail_fused_f32(const float *slabs, int n_slabs, int64_t stride, f
     ERL_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0, "single-launch tail: no device");
     const int64_t nchunks = erl_cdiv(stride, 64);
     ERL_REQUIRE(nchunks <= 2048, "single-launch tail: row too long (%lld floats)", (long long)stride);
-    FusedSlot *slot = nullptr;
-    for (auto &f : g_fused)
-        if (f.buf && f.device == dev && f.stream == stream && f.stride == stride) { slot = &f; break; }
-    if (!slot) {
-        for (auto &f : g_fused)
-            if (!f.buf) { slot = &f; break; }
-        ERL_REQUIRE(slot, "single-launch tail: more than 32 (device, stream, row length) triples");
-        const int64_t alloc = erl_cdiv(stride, 256) * 4;              // whole workgroups: 4 chunks each
-        void *pbuf = nullptr;
-        if ((rc = erl_hip_status(hipMalloc(&pbuf, (size_t)2 * alloc * 4 * sizeof(double)), "hipMalloc(single-launch tail table)"))) return rc;
-        hipLaunchKernelGGL(fill_u64_kernel, dim3(64), dim3(256), 0, stream, (unsigned long long *)pbuf, kTailBlank, 2 * alloc * 4);
-        slot->buf = (double *)pbuf;
-        slot->device = dev; slot->stream = stream; slot->stride = stride; slot->nchunks_alloc = alloc; slot->parity = 0;
-    }
     FusedTail ft{};
+    {
+        auto lock = g_fused.lock();         // the parity is handed out under the look-up's lock
+        FusedSlot *slot = g_fused.find_or_claim(dev, stream, stride);
+        ERL_REQUIRE(slot, "single-launch tail: more than 32 (device, stream, row length) triples");
+        if (!slot->buf) {
+            const int64_t alloc = erl_cdiv(stride, 256) * 4;              // whole workgroups: 4 chunks each
+            void *pbuf = nullptr;
+            if ((rc = erl_hip_status(hipMalloc(&pbuf, (size_t)2 * alloc * 4 * sizeof(double)), "hipMalloc(single-launch tail table)"))) {
+                g_fused.release(slot);
+                return rc;
+            }
+            hipLaunchKernelGGL(fill_u64_kernel, dim3(64), dim3(256), 0, stream, (unsigned long long *)pbuf, kTailBlank, 2 * alloc * 4);
+            slot->buf = (double *)pbuf;
+            slot->nchunks_alloc = alloc;
+        }
+        ft.cur = slot->buf + (size_t)(slot->parity & 1u) * slot->nchunks_alloc * 4;
+        ft.other = slot->buf + (size_t)((slot->parity & 1u) ^ 1u) * slot->nchunks_alloc * 4;
+        slot->parity++;
+    }
     ft.params = params; ft.m1 = exp_avg; ft.m2 = exp_avg_sq;
     const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
     ft.beta1 = beta1; ft.beta2 = beta2; ft.eps = eps; ft.max_norm = max_norm;
     ft.step_size = (float)((double)lr / bc1); ft.bc2_sqrt = (float)sqrt(bc2);
-    ft.cur = slot->buf + (size_t)(slot->parity & 1u) * slot->nchunks_alloc * 4;
-    ft.other = slot->buf + (size_t)((slot->parity & 1u) ^ 1u) * slot->nchunks_alloc * 4;
-    slot->parity++;
     ft.nchunks = (int)nchunks;
     static const uint32_t spin = [] { const char *e = getenv("ERL_TAIL_SPIN"); return e && atol(e) > 0 ? (uint32_t)atol(e) : (1u << 22); }();
     ft.spin_limit = spin;
@@ -569,19 +567,17 @@ int erl_tail_partials(double **out, hipStream_t stream)
 {
     int dev = -1;
     ERL_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0, "gradient tail: no device");
-    PartialsSlot *slot = nullptr;
-    for (auto &s : g_partials)
-        if (s.buf && s.device == dev && s.stream == stream) { slot = &s; break; }
-    if (!slot) {
-        for (auto &s : g_partials)
-            if (!s.buf) { slot = &s; break; }
-        ERL_REQUIRE(slot, "gradient tail: more than 32 (device, stream) pairs ran an optimiser tail");
+    auto lock = g_partials.lock();
+    PartialsSlot *slot = g_partials.find_or_claim(dev, stream);
+    ERL_REQUIRE(slot, "gradient tail: more than 32 (device, stream) pairs ran an optimiser tail");
+    if (!slot->buf) {
         void *p = nullptr;
         int rc = erl_hip_status(hipMalloc(&p, (size_t)kMaxPartialChunks * 4 * sizeof(double)), "hipMalloc(partial norms)");
-        if (rc) return rc;
+        if (rc) {
+            g_partials.release(slot);
+            return rc;
+        }
         slot->buf = (double *)p;
-        slot->device = dev;
-        slot->stream = stream;
     }
     *out = slot->buf;
     return ERL_OK;
@@ -732,18 +728,16 @@ extern "C" int erl_comm_clip_adam_partials_f32(void *comm, float *params, const 
                                              eps, max_norm, grad_scale, nullptr, erl_comm_poison_word(comm), stream);
 }
 
-// Image buffers: library-owned, one pair per (device, stream) that ran an update loop (a handful in any process); rebuilt from
-// the fp32 parameters at the start of every loop, so nothing has to be kept coherent across calls.
+// Image buffers (library-owned: stream_slots.h): rebuilt from the fp32 parameters at the start of every loop, so nothing has to be kept
+// coherent across calls.
 namespace {
 struct S3Slot {
-    int device = -1;
-    hipStream_t stream = nullptr;
     unsigned char *buf = nullptr;
     size_t bytes = 0;
-    float *aux = nullptr;         // per-sample records (s3_image.h), grown on demand
+    float *aux = nullptr;         // per-sample records (s3_image.h)
     size_t aux_bytes = 0;
 };
-S3Slot g_s3_slots[16];
+StreamSlots<S3Slot, 16> g_s3_slots;
 constexpr size_t kS3AuxMaxBytes = (size_t)256 << 20;     // beyond it (H x N > 4 Mi rows) the minibatch kernels keep gathering from the buffers
 }  // namespace
 
@@ -755,24 +749,10 @@ int erl_s3_images_build(const float *flat_params, int S, int h1, int h2, int A, 
     if (rc) return rc;
     const size_t two = (s3_image_bytes(h1, h2) + 1023) / 1024 * 1024, first = (s3_image1_bytes(h1, S) + 1023) / 1024 * 1024;
     const size_t one = two + first, need = 2 * one;
-    S3Slot *slot = nullptr;
-    for (auto &s : g_s3_slots)
-        if (s.buf && s.device == dev && s.stream == stream) slot = &s;
-    if (!slot)
-        for (auto &s : g_s3_slots)
-            if (!s.buf) { slot = &s; break; }
+    auto lock = g_s3_slots.lock();
+    S3Slot *slot = g_s3_slots.find_or_claim(dev, stream);
     ERL_REQUIRE(slot, "erl_s3_images_build: more than 16 (device, stream) pairs ran a split-arithmetic update loop");
-    if (slot->bytes < need) {
-        if (slot->buf) {
-            if ((rc = erl_hip_status(hipStreamSynchronize(slot->stream), "hipStreamSynchronize"))) return rc;
-            if ((rc = erl_hip_status(hipFree(slot->buf), "hipFree"))) return rc;
-            slot->buf = nullptr;
-        }
-        if ((rc = erl_hip_status(hipMalloc((void **)&slot->buf, need), "hipMalloc(weight images)"))) return rc;
-        slot->bytes = need;
-    }
-    slot->device = dev;
-    slot->stream = stream;
+    if ((rc = erl_slot_grow((void **)&slot->buf, &slot->bytes, need, stream, "hipMalloc(weight images)"))) return rc;
     const int64_t Pa = (int64_t)h1 * S + h1 + (int64_t)h2 * h1 + h2 + (int64_t)A * h2 + A + A;     // actor block incl. action_std_log
     for (int gi = 0; gi < 2; ++gi) {
         out->net[gi].img = slot->buf + gi * one;
@@ -791,16 +771,7 @@ int erl_s3_images_build(const float *flat_params, int S, int h1, int h2, int A, 
     if (aux_on && aux_src && aux_src->actions && aux_src->logprobs && aux_src->advantages && aux_src->reward_sums && aux_src->unmasks &&
         aux_src->A >= 1 && aux_src->A <= 8 && aux_src->rows >= 1 && (size_t)aux_src->rows * kS3AuxFloats * sizeof(float) <= kS3AuxMaxBytes) {
         const size_t want = (size_t)aux_src->rows * kS3AuxFloats * sizeof(float);
-        if (slot->aux_bytes < want) {
-            if (slot->aux) {
-                if ((rc = erl_hip_status(hipStreamSynchronize(slot->stream), "hipStreamSynchronize"))) return rc;
-                if ((rc = erl_hip_status(hipFree(slot->aux), "hipFree"))) return rc;
-                slot->aux = nullptr;
-                slot->aux_bytes = 0;
-            }
-            if ((rc = erl_hip_status(hipMalloc((void **)&slot->aux, want), "hipMalloc(per-sample records)"))) return rc;
-            slot->aux_bytes = want;
-        }
+        if ((rc = erl_slot_grow((void **)&slot->aux, &slot->aux_bytes, want, stream, "hipMalloc(per-sample records)"))) return rc;
         ax = *aux_src;
         out->aux = slot->aux;
     }

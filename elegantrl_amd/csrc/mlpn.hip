@@ -13,6 +13,7 @@
 //   W1[d1][d0] b1[d1] ... WL[dL][dL-1] bL[dL] Wout[out][dL] bout[out] (+ action_std_log[out] for the actor)
 #include "mlpn_common.h"
 #include "ppo_step_wd.h"
+#include "stream_slots.h"
 
 extern "C" int64_t erl_mlpn_param_count(const int *dims, int n_dims, int with_std_log)
 {
@@ -127,37 +128,31 @@ extern "C" int erl_mlpn_rollout_step_discrete_f32(const float *actor_params, con
 // One PPO minibatch for networks of any depth: writes the summed gradient [actor | critic | logs(4)] to flat_grad.
 namespace {
 
-// a library-owned second stream per (device, caller stream) (non-blocking) with the two events that fork it from / join it into
-// the caller's stream; NULL when ERL_MLPN_STREAMS=1 or the runtime refuses (then everything stays on the caller's stream)
+// a second stream (non-blocking) of the caller's stream (library-owned: stream_slots.h) with the two events that fork it from / join
+// it into the caller's stream; NULL when ERL_MLPN_STREAMS=1, all entries are taken or the runtime refuses (then everything stays on
+// the caller's stream)
 struct SideStream {
-    int device = -1;
-    hipStream_t owner = nullptr;
     hipStream_t stream = nullptr;
     hipEvent_t fork = nullptr, join = nullptr;
 };
-static SideStream g_side[16];
+static StreamSlots<SideStream, 16> g_side;
 
 SideStream *side_stream(hipStream_t owner)
 {
     static const bool off = [] { const char *e = getenv("ERL_MLPN_STREAMS"); return e && atoi(e) == 1; }();
     int dev = -1;
     if (off || hipGetDevice(&dev) != hipSuccess || dev < 0) return nullptr;
-    for (auto &q : g_side)
-        if (q.stream && q.device == dev && q.owner == owner) return &q;
-    for (auto &q : g_side) {
-        if (q.stream) continue;
-        if (hipStreamCreateWithFlags(&q.stream, hipStreamNonBlocking) != hipSuccess ||
-            hipEventCreateWithFlags(&q.fork, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&q.join, hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            q.stream = nullptr;
-            return nullptr;
-        }
-        q.device = dev;
-        q.owner = owner;
-        return &q;
+    auto lock = g_side.lock();
+    SideStream *q = g_side.find_or_claim(dev, owner);
+    if (q && !q->stream &&
+        (hipStreamCreateWithFlags(&q->stream, hipStreamNonBlocking) != hipSuccess ||
+         hipEventCreateWithFlags(&q->fork, hipEventDisableTiming) != hipSuccess ||
+         hipEventCreateWithFlags(&q->join, hipEventDisableTiming) != hipSuccess)) {
+        (void)hipGetLastError();
+        g_side.release(q);
+        return nullptr;
     }
-    return nullptr;
+    return q;
 }
 
 // every exit path after the fork joins the side stream back into the caller's

@@ -3,6 +3,7 @@
 #include "ppo_step_wd_args.h"
 #include "ppo_step_wd.h"
 #include "erl_common.h"
+#include "stream_slots.h"
 #include "../../include/erl_hip.h"
 #include <cstdlib>
 
@@ -22,39 +23,22 @@ void erl_ppo_wd_set_prof(long long *dev_buf, int block) { g_wd_prof = dev_buf; g
 
 namespace {
 
-// GELU'(z1) and H2 of every workgroup between the forward and the backward pass: library-owned, one block per (device, stream)
+// GELU'(z1) and H2 of every workgroup between the forward and the backward pass (library-owned: stream_slots.h)
 struct WdScratch {
-    int device = -1;
-    hipStream_t stream = nullptr;
     float *buf = nullptr;
-    size_t floats = 0;
+    size_t bytes = 0;
 };
-WdScratch g_wd_scratch[16];
+StreamSlots<WdScratch, 16> g_wd_scratch;
 
 int wd_scratch(size_t floats, hipStream_t stream, float **out)
 {
     int dev = 0;
     int rc = erl_hip_status(hipGetDevice(&dev), "hipGetDevice");
     if (rc) return rc;
-    WdScratch *slot = nullptr;
-    for (auto &s : g_wd_scratch)
-        if (s.buf && s.device == dev && s.stream == stream) slot = &s;
-    if (!slot)
-        for (auto &s : g_wd_scratch)
-            if (!s.buf) { slot = &s; break; }
+    auto lock = g_wd_scratch.lock();
+    WdScratch *slot = g_wd_scratch.find_or_claim(dev, stream);
     ERL_REQUIRE(slot, "erl_ppo_step_f32 (wide): more than 16 (device, stream) pairs");
-    if (slot->floats < floats) {
-        if (slot->buf) {
-            if ((rc = erl_hip_status(hipStreamSynchronize(slot->stream), "hipStreamSynchronize"))) return rc;
-            if ((rc = erl_hip_status(hipFree(slot->buf), "hipFree"))) return rc;
-            slot->buf = nullptr;
-            slot->floats = 0;
-        }
-        if ((rc = erl_hip_status(hipMalloc((void **)&slot->buf, floats * sizeof(float)), "hipMalloc(wide-net scratch)"))) return rc;
-        slot->floats = floats;
-    }
-    slot->device = dev;
-    slot->stream = stream;
+    if ((rc = erl_slot_grow((void **)&slot->buf, &slot->bytes, floats * sizeof(float), stream, "hipMalloc(wide-net scratch)"))) return rc;
     *out = slot->buf;
     return ERL_OK;
 }
@@ -158,13 +142,11 @@ __global__ __launch_bounds__(256) void wd3_images_kernel(const float *__restrict
     }
 }
 
-struct Wd3Bufs {
-    int device = -1;
-    hipStream_t stream = nullptr;
+struct Wd3Bufs {         // images, slabs and scratch in one block (library-owned: stream_slots.h)
     unsigned char *buf = nullptr;
     size_t bytes = 0;
 };
-Wd3Bufs g_wd3[16];
+StreamSlots<Wd3Bufs, 16> g_wd3;
 
 }  // namespace
 
@@ -187,24 +169,12 @@ int erl_ppo_wd3_step(const float *actor_params, const float *critic_params, cons
     int rc = erl_hip_status(hipGetDevice(&dev), "hipGetDevice");
     if (rc) return rc;
     Wd3Bufs *slot = nullptr;
-    for (auto &s : g_wd3)
-        if (s.buf && s.device == dev && s.stream == st) slot = &s;
-    if (!slot)
-        for (auto &s : g_wd3)
-            if (!s.buf) { slot = &s; break; }
-    ERL_REQUIRE(slot, "erl_mlpn_ppo_step_f32 (256,128,h3): more than 16 (device, stream) pairs");
-    if (slot->bytes < need) {
-        if (slot->buf) {
-            if ((rc = erl_hip_status(hipStreamSynchronize(slot->stream), "hipStreamSynchronize"))) return rc;
-            if ((rc = erl_hip_status(hipFree(slot->buf), "hipFree"))) return rc;
-            slot->buf = nullptr;
-            slot->bytes = 0;
-        }
-        if ((rc = erl_hip_status(hipMalloc((void **)&slot->buf, need), "hipMalloc(wide-net buffers)"))) return rc;
-        slot->bytes = need;
+    {
+        auto lock = g_wd3.lock();
+        slot = g_wd3.find_or_claim(dev, st);
+        ERL_REQUIRE(slot, "erl_mlpn_ppo_step_f32 (256,128,h3): more than 16 (device, stream) pairs");
+        if ((rc = erl_slot_grow((void **)&slot->buf, &slot->bytes, need, st, "hipMalloc(wide-net buffers)"))) return rc;
     }
-    slot->device = dev;
-    slot->stream = st;
     Wd3Imgs im;
     unsigned char *p = slot->buf;
     for (int n = 0; n < 2; ++n) { im.w1[n] = p; p += b1; im.w2[n] = p; p += b2; im.w3[n] = p; p += b3; }

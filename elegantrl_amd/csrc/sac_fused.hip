@@ -42,8 +42,7 @@
 // persistent rollout (a template parameter there: sac_rollout_synenv_kernel).
 #include "mlpn_common.h"
 #include "per_draw.h"
-
-#include <mutex>
+#include "stream_slots.h"
 
 namespace {
 
@@ -1315,13 +1314,10 @@ int dw_launch(const DwArgs &a, hipStream_t s)
 
 int wclass(int width) { return width <= 64 ? 0 : (width <= 128 ? 1 : 2); }
 
-// The library-owned state of the in-launch exchanges, one slot per (device, caller stream): two agents on different streams of one device
-// never share granules or counters.  One allocation, zeroed on the caller's stream behind whatever it already holds (nothing synchronises
-// the host).  Without a slot -- the allocation failed, or all are taken -- the step runs the unsplit forms of the actor's forward and of the
-// critic's training pass.
+// The state of the in-launch exchanges (library-owned: stream_slots.h).  One allocation, zeroed on the caller's stream behind whatever
+// it already holds (nothing synchronises the host).  Without a slot -- the allocation failed, or all are taken -- the step runs the
+// unsplit forms of the actor's forward and of the critic's training pass.
 struct SacSlot {
-    int device = -1;
-    hipStream_t owner = nullptr;
     unsigned long long *qx = nullptr;     // [FMAXE * kQxSplit * 4096] granules {share of q, nonce} (CriticArgs::qx)
     unsigned long long *yx = nullptr;     // [2 passes][kQxSplit][4096][16] granules {share of the actor's head output, nonce} (ActorFwdArgs::yx)
     unsigned *arrive = nullptr;           // [256] arrival counters of the training pass's dEnc shares (zero between launches)
@@ -1330,34 +1326,28 @@ struct SacSlot {
 constexpr size_t kQxGranules = (size_t)FMAXE * kQxSplit * 4096;
 constexpr size_t kYxPass = (size_t)kQxSplit * 4096 * 16;      // granules of one pass
 constexpr size_t kSlotBytes = (kQxGranules + 2 * kYxPass) * sizeof(unsigned long long) + 256 * sizeof(unsigned);
-SacSlot g_sac_slot[16];
-std::mutex g_sac_slot_mutex;          // slot lookup / creation / nonce hand-out (agents on several devices or streams step from their own threads)
+StreamSlots<SacSlot, 16> g_sac_slot;
 
-// the slot of (the current device, `owner`), created on first use, and this step's two nonces; nullptr: no slot
+// the slot of (the current device, `owner`), created on first use, and this step's two nonces (handed out under the look-up's lock);
+// nullptr: no slot
 SacSlot *sac_slot(hipStream_t owner, uint32_t &nonce, uint32_t &nonce_y)
 {
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0) return nullptr;
-    std::lock_guard<std::mutex> lock(g_sac_slot_mutex);
-    SacSlot *q = nullptr, *free_slot = nullptr;
-    for (auto &t : g_sac_slot) {
-        if (t.qx && t.device == dev && t.owner == owner) q = &t;
-        if (!t.qx && !free_slot) free_slot = &t;
-    }
-    if (!q) {
+    auto lock = g_sac_slot.lock();
+    SacSlot *q = g_sac_slot.find_or_claim(dev, owner);
+    if (!q) return nullptr;
+    if (!q->qx) {
         void *p = nullptr;
-        if (!free_slot) return nullptr;
         if (hipMalloc(&p, kSlotBytes) != hipSuccess || hipMemsetAsync(p, 0, kSlotBytes, owner) != hipSuccess) {
             if (p) (void)hipFree(p);
             (void)hipGetLastError();
+            g_sac_slot.release(q);
             return nullptr;
         }
-        q = free_slot;
         q->qx = (unsigned long long *)p;
         q->yx = q->qx + kQxGranules;
         q->arrive = (unsigned *)(q->yx + 2 * kYxPass);
-        q->device = dev;
-        q->owner = owner;
     }
     if (++q->nonce == 0) q->nonce = 1;        // (0 is what the cleared granules carry)
     if (++q->nonce_y == 0) q->nonce_y = 1;
