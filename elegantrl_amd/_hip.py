@@ -39,6 +39,9 @@ _SAC_TAIL = [_P, c_int64, _P]                                            # works
 # what the one-launch entries of the continuous device envs share, in the order they name it
 _ENV_SYN = [_P] * 5 + [c_int, c_uint64]                                  # env_state, Ws, Wa, step_count, episode, max_step, env_seed
 _ENV_PEN = [_P] * 4 + [c_int, c_uint64]                                  # phys, obs, step_count, episode, max_step, env_seed
+_ENV_PNT = _ENV_PEN                                                      # state, distance, step_count, episode, max_step, env_seed
+_PPO_PNT = [c_int] * 4 + _ENV_PNT                                        # S, h1, h2, A, then the env
+_SAC_PNT = [_P, c_int, c_int, POINTER(c_int), c_int] + _ENV_PNT          # actor_params, S, A, hidden, n_hidden, then the env
 _PPO_SYN, _PPO_PEN = [c_int] * 4 + _ENV_SYN, [c_int] * 2 + _ENV_PEN      # S, h1, h2, A | h1, h2 (S = 3, A = 1), then the env
 _SAC_SYN = [_P, c_int, c_int, POINTER(c_int), c_int] + _ENV_SYN          # actor_params, S, A, hidden, n_hidden, then the env
 _SAC_PEN = [_P, POINTER(c_int), c_int] + _ENV_PEN                        # actor_params, hidden, n_hidden, then the env
@@ -88,6 +91,7 @@ _SIGNATURES = {
     "erl_rollout_gae_workspace_bytes": (c_int64, [c_int64]),
     "erl_rollout_synenv_f32": (c_int, [_P] * 6 + _PPO_SYN + _PPO_ROLL_TAIL),
     "erl_rollout_pendulum_f32": (c_int, [_P] * 6 + _PPO_PEN + _PPO_ROLL_TAIL),
+    "erl_rollout_pointchasing_f32": (c_int, [_P] * 6 + _PPO_PNT + _PPO_ROLL_TAIL),
     "erl_ppo_slab_stride": (c_int64, [c_int, c_int, c_int, c_int]),
     "erl_ppo_num_slabs": (c_int, [c_int64]),
     "erl_ppo_set_arith": (c_int, [c_int]),
@@ -164,12 +168,15 @@ _SIGNATURES = {
     "erl_sac_rollout_synenv_supported": (c_int, [c_int, c_int, POINTER(c_int), c_int, c_int64]),
     "erl_sac_rollout_synenv_f32": (c_int, _SAC_SYN + _SAC_ROLL_TAIL),
     "erl_sac_rollout_pendulum_f32": (c_int, _SAC_PEN + _SAC_ROLL_TAIL),
+    "erl_sac_rollout_pointchasing_f32": (c_int, _SAC_PNT + _SAC_ROLL_TAIL),
     # AgentModSAC's one-launch rollout / evaluation (ActorFixSAC): the argument lists of their AgentSAC twins
     "erl_sac_rollout_mod_supported": (c_int, [c_int, c_int, POINTER(c_int), c_int, c_int64]),
     "erl_sac_rollout_mod_synenv_f32": (c_int, _SAC_SYN + _SAC_ROLL_TAIL),
     "erl_sac_rollout_mod_pendulum_f32": (c_int, _SAC_PEN + _SAC_ROLL_TAIL),
     "erl_sac_eval_mod_synenv_f32": (c_int, _SAC_SYN + _EVAL_TAIL),
     "erl_sac_eval_mod_pendulum_f32": (c_int, _SAC_PEN + _EVAL_TAIL),
+    "erl_sac_rollout_mod_pointchasing_f32": (c_int, _SAC_PNT + _SAC_ROLL_TAIL),
+    "erl_sac_eval_mod_pointchasing_f32": (c_int, _SAC_PNT + _EVAL_TAIL),
     "erl_sac_explore_action_tile_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, c_int64, _P, c_uint64, c_uint64, _P, _P, _P,
                                                 c_int64, c_int, _P]),
     "erl_eval_workspace_bytes": (c_int64, [c_int64, c_int64]),
@@ -177,6 +184,8 @@ _SIGNATURES = {
     "erl_eval_pendulum_f32": (c_int, [_P] * 3 + _PPO_PEN + _EVAL_TAIL),
     "erl_sac_eval_synenv_f32": (c_int, _SAC_SYN + _EVAL_TAIL),
     "erl_sac_eval_pendulum_f32": (c_int, _SAC_PEN + _EVAL_TAIL),
+    "erl_eval_pointchasing_f32": (c_int, [_P] * 3 + _PPO_PNT + _EVAL_TAIL),
+    "erl_sac_eval_pointchasing_f32": (c_int, _SAC_PNT + _EVAL_TAIL),
     "erl_eval_episodes_compact_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, c_int64, _P, _P]),
     "erl_k6_timing_enable": (None, [c_int]),
     "erl_k6_timing_read": (c_int, [POINTER(ctypes.c_double), POINTER(c_int)]),
@@ -189,6 +198,7 @@ _SIGNATURES = {
                                      POINTER(ctypes.c_double), c_int, POINTER(c_int), POINTER(c_int)]),
     "erl_synenv_step_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_int, c_int, c_uint64, _P]),
     "erl_pendulum_step_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int, c_uint64, _P]),
+    "erl_pointchasing_step_f32": (c_int, [_P] * 8 + [c_int64, c_int, c_int, c_int, c_uint64, _P]),
     "erl_rollout_discrete_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "erl_cartpole_step_f32": (c_int, [_P] * 7 + [c_int64, c_int, c_uint64, _P]),
     "erl_rollout_discrete_cartpole_f32": (c_int, [_P] * 3 + [c_int] * 4 + [_P] * 3 + [c_int, c_uint64, c_int64, c_int64, _P, c_uint64, c_uint64,

@@ -5,6 +5,7 @@
 // maps staged in LDS for action_dim > 16 (synenv_step_kernel).
 #include "erl_common.h"
 #include "mlp_chain.h"
+#include "pointchasing_step.h"
 
 namespace {
 
@@ -231,6 +232,31 @@ __global__ __launch_bounds__(256) void pendulum_step_kernel(float *__restrict__ 
     step_count[n] = trunc ? 0 : sc;
 }
 
+// PointChasingVecEnv (pointchasing_step.h): one lane per env; state (N, 4 dim) = (p0, v0, p1, v1) in place, distance (N,) the carried
+// |p0 - p1|; done rows return the post-reset state and its recomputed distance
+__global__ __launch_bounds__(256) void pointchasing_step_kernel(float *__restrict__ state, const float *__restrict__ action,
+                                                                float *__restrict__ distance, int32_t *__restrict__ step_count,
+                                                                int32_t *__restrict__ episode, float *__restrict__ reward,
+                                                                uint8_t *__restrict__ terminal, uint8_t *__restrict__ truncate, int64_t N,
+                                                                int dim, int max_step, uint64_t seed)
+{
+    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    float a[kPointChasingMaxDim];
+#pragma unroll
+    for (int k = 0; k < kPointChasingMaxDim; ++k) a[k] = k < dim ? action[n * dim + k] : 0.f;
+    float dist = distance[n], rew;
+    int sc = step_count[n], ep = episode[n];
+    bool term, trunc;
+    pointchasing_step(state + n * 4 * dim, a, dim, dist, sc, ep, max_step, seed, (uint32_t)n, rew, term, trunc);
+    distance[n] = dist;
+    reward[n] = rew;
+    terminal[n] = term;
+    truncate[n] = trunc;
+    step_count[n] = sc;
+    episode[n] = ep;
+}
+
 }  // namespace
 
 extern "C" int erl_synenv_step_f32(float *state, const float *action, const float *Ws, const float *Wa, int32_t *step_count,
@@ -278,4 +304,16 @@ extern "C" int erl_pendulum_step_f32(float *phys, float *obs, const float *actio
     hipLaunchKernelGGL(pendulum_step_kernel, dim3((unsigned)erl_cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, phys, obs, action,
                        step_count, episode, reward, terminal, truncate, N, max_step, seed);
     ERL_LAUNCH_CHECK("erl_pendulum_step_f32");
+}
+
+extern "C" int erl_pointchasing_step_f32(float *state, const float *action, float *distance, int32_t *step_count, int32_t *episode,
+                                         float *reward, uint8_t *terminal, uint8_t *truncate, int64_t N, int S, int A, int max_step,
+                                         uint64_t seed, void *stream)
+{
+    ERL_REQUIRE(state && action && distance && step_count && episode && reward && terminal && truncate,
+                "erl_pointchasing_step_f32: NULL tensor");
+    ERL_REQUIRE(N >= 1 && max_step >= 1 && A >= 1 && A <= kPointChasingMaxDim && S == 4 * A, "erl_pointchasing_step_f32: bad shape");
+    hipLaunchKernelGGL(pointchasing_step_kernel, dim3((unsigned)erl_cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, state, action,
+                       distance, step_count, episode, reward, terminal, truncate, N, A, max_step, seed);
+    ERL_LAUNCH_CHECK("erl_pointchasing_step_f32");
 }

@@ -84,7 +84,8 @@ int erl_sac_rollout_fused(const float *actor_params, int S, int A, int h0, int h
                           const float *noise, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states, float *out_actions,
                           float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, hipStream_t stream,
                           float2 *ev_rec = nullptr, int32_t *ev_cnt = nullptr,        // ev_*: the evaluation form (eval_ws.h)
-                          int variant = 0);                                           // ERL_SAC_ACTOR_FIX: ActorFixSAC (AgentModSAC)
+                          int variant = 0,                                            // ERL_SAC_ACTOR_FIX: ActorFixSAC (AgentModSAC)
+                          int env_kind = 0);                                          // ContEnv::kind (cont_env_args.h): whose `phys` this is
 int64_t erl_sac_fused_ws_floats(int S, int A, int h0, int h1, int E, int64_t B, int64_t Pa, int64_t Pc);
 int erl_sac_explore_fused(const float *actor_params, int S, int A, int h0, int h1, const int64_t *aoff, const float *state, int64_t N,
                           const float *noise, uint64_t seed, uint64_t counter, float *action_out, float *state_out, float *lp_scratch,

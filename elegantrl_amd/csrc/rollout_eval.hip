@@ -25,7 +25,7 @@ int rf_eval_launch(RfArgs &g, int env_kind, hipStream_t stream)
     const bool vec = (g.S % 4 == 0) && al(g.Pa);
     const dim3 grid((unsigned)erl_cdiv(g.N, 16)), block(512);
     const size_t lds_bytes = kRfLdsBytes;
-    static bool attr[5] = {false, false, false, false, false};
+    static bool attr[6] = {false, false, false, false, false, false};
 #define RF_EVAL_LAUNCH(E, V, A_, B_, C_, SLOT)                                                                             \
     do {                                                                                                                   \
         if (!attr[SLOT]) {                                                                                                 \
@@ -43,6 +43,7 @@ int rf_eval_launch(RfArgs &g, int env_kind, hipStream_t stream)
     case RF_SYN_SCALAR: RF_EVAL_LAUNCH(ENV_SYN, false, 0, 0, 0, 2); break;
     case RF_PENDULUM_TUNED: RF_EVAL_LAUNCH(ENV_PENDULUM, false, 1, 8, 4, 3); break;                       // config 2
     case RF_PENDULUM_ANY: RF_EVAL_LAUNCH(ENV_PENDULUM, false, 0, 0, 0, 4); break;
+    case RF_POINT_ANY: RF_EVAL_LAUNCH(ENV_POINT, false, 0, 0, 0, 5); break;
     }
 #undef RF_EVAL_LAUNCH
     return erl_hip_status(hipGetLastError(), "rollout_fused_kernel (evaluation form) launch");
@@ -133,6 +134,15 @@ extern "C" int erl_eval_pendulum_f32(const float *actor_params, const float *act
 {
     return rf_eval("erl_eval_pendulum_f32", {actor_params, nullptr, act_avg, act_std, nullptr, nullptr, 3, h1, h2, 1, N, H},
                    {ENV_PENDULUM, obs, phys, nullptr, nullptr, step_count, episode, max_step, env_seed}, workspace, workspace_bytes, stream);
+}
+
+extern "C" int erl_eval_pointchasing_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2, int A,
+                                         float *state, float *distance, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
+                                         int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (int rc = cont_env_point_dims("erl_eval_pointchasing_f32", S, A)) return rc;
+    return rf_eval("erl_eval_pointchasing_f32", {actor_params, nullptr, act_avg, act_std, nullptr, nullptr, S, h1, h2, A, N, H},
+                   {ENV_POINT, state, distance, nullptr, nullptr, step_count, episode, max_step, env_seed}, workspace, workspace_bytes, stream);
 }
 
 extern "C" int erl_eval_episodes_compact_f32(const void *workspace, int64_t workspace_bytes, int64_t N, int64_t H, float *out_rows,

@@ -57,6 +57,7 @@ int rf_launch(RfArgs &g, int env_kind, hipStream_t stream)
     case RF_SYN_SCALAR: RF_LAUNCH(ENV_SYN, false, 0, 0, 0, 2); break;
     case RF_PENDULUM_TUNED: if (rs) RF_LAUNCH(ENV_PENDULUM, false, 1, 8, 4, 7); else RF_LAUNCH(ENV_PENDULUM, false, 1, 8, 4, 3); break;  // config 2
     case RF_PENDULUM_ANY: RF_LAUNCH(ENV_PENDULUM, false, 0, 0, 0, 4); break;
+    case RF_POINT_ANY: RF_LAUNCH(ENV_POINT, false, 0, 0, 0, 5); break;
     }
 #undef RF_LAUNCH
     return erl_hip_status(hipGetLastError(), "rollout_fused_kernel launch");
@@ -154,6 +155,27 @@ extern "C" int erl_rollout_pendulum_f32(const float *actor_params, const float *
 {
     return rf_rollout("erl_rollout_pendulum_f32", {actor_params, critic_params, act_avg, act_std, cri_avg, cri_std, 3, h1, h2, 1, N, H},
                       {ENV_PENDULUM, obs, phys, nullptr, nullptr, step_count, episode, max_step, env_seed},
+                      {noise, seed, counter0, reward_scale, out_states, out_actions, out_logprobs, out_rewards, out_undones, out_unmasks,
+                       out_values, out_next_value},
+                      {out_last_state, out_advantages, out_reward_sums, gae_stats, gae_workspace, gae_workspace_bytes, gamma, lambda_gae,
+                       use_v_trace}, stream);
+}
+
+// ... on the device-resident PointChasingVecEnv (S = 4 A, A = dim in 1..4; state: (N, S) the live observation; distance: (N,) the carried
+// |p0 - p1|; pointchasing_step.h's dynamics, operation for operation)
+extern "C" int erl_rollout_pointchasing_f32(const float *actor_params, const float *critic_params, const float *act_avg,
+                                            const float *act_std, const float *cri_avg, const float *cri_std, int S, int h1, int h2, int A,
+                                            float *state, float *distance, int32_t *step_count, int32_t *episode, int max_step,
+                                            uint64_t env_seed, int64_t N, int64_t H, const float *noise, uint64_t seed, uint64_t counter0,
+                                            float reward_scale, float *out_states, float *out_actions, float *out_logprobs,
+                                            float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_values,
+                                            float *out_next_value, float *out_last_state, float *out_advantages, float *out_reward_sums,
+                                            double *gae_stats, double *gae_workspace, int64_t gae_workspace_bytes, float gamma,
+                                            float lambda_gae, int use_v_trace, void *stream)
+{
+    if (int rc = cont_env_point_dims("erl_rollout_pointchasing_f32", S, A)) return rc;
+    return rf_rollout("erl_rollout_pointchasing_f32", {actor_params, critic_params, act_avg, act_std, cri_avg, cri_std, S, h1, h2, A, N, H},
+                      {ENV_POINT, state, distance, nullptr, nullptr, step_count, episode, max_step, env_seed},
                       {noise, seed, counter0, reward_scale, out_states, out_actions, out_logprobs, out_rewards, out_undones, out_unmasks,
                        out_values, out_next_value},
                       {out_last_state, out_advantages, out_reward_sums, gae_stats, gae_workspace, gae_workspace_bytes, gamma, lambda_gae,

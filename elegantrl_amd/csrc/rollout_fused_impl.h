@@ -8,6 +8,7 @@
 #include "erl_common.h"
 #include "gae_step.h"
 #include "mlp_chain.h"
+#include "pointchasing_step.h"
 #include "rollout_bf16.h"
 
 namespace {
@@ -36,8 +37,8 @@ struct RfArgs {
     int vtrace;
     int gae_lds;                                   // 1: the epilogue's inputs are kept in LDS during the rollout (H <= kRfGaeLdsSteps)
     // environment
-    float *env_state;                              // (N, S) live state (SynVecEnv.state / PendulumVecEnv.state = obs)
-    float *phys;                                   // Pendulum: (N, 2) theta, theta_dot
+    float *env_state;                              // (N, S) live state (SynVecEnv.state / PendulumVecEnv.state = obs / PointChasingVecEnv.state)
+    float *phys;                                   // Pendulum: (N, 2) theta, theta_dot; PointChasing: (N,) distance
     const float *Ws, *Wa;                          // SynVecEnv
     int32_t *step_count, *episode;
     int max_step;
@@ -284,6 +285,8 @@ __global__ __launch_bounds__(512) void rollout_fused_kernel(RfArgs g)
     int sc = g.step_count[row], ep = g.episode[row];
     float th = 0.f, thdot = 0.f;
     if (ENV == ENV_PENDULUM) { th = g.phys[2 * row]; thdot = g.phys[2 * row + 1]; }
+    float dist = 0.f;                                        // PointChasing: the env's carried |p0 - p1|
+    if (ENV == ENV_POINT) dist = g.phys[row];
 
     // The N(0,1) draws of step t are produced one step ahead by waves 4..7 (idle while waves < nt step the environment):
     // wave 4 + r, lane (m, q) owns eps[m][4 q + r] -- injected noise[t] or Philox4x32-10 + Box-Muller keyed by
@@ -622,7 +625,7 @@ __global__ __launch_bounds__(512) void rollout_fused_kernel(RfArgs g)
                     a2 += a2y; sq += sqy; mx = fmaxf(mx, mxy);
                 }
                 if (q == 0) { RED[(wave * 16 + l15) * 2] = sq; RED[(wave * 16 + l15) * 2 + 1] = mx; }
-            } else {
+            } else if (ENV == ENV_PENDULUM) {
                 // Pendulum-v1 behind the reference wrapper's scaling (envs.hip pendulum_step_kernel); lanes q > 0 mirror q = 0
                 const float PI = 3.14159265358979323846f;
                 const float a_env = __shfl(te[0], l15, 64);              // action 0 lives in lane group q = 0
@@ -637,10 +640,14 @@ __global__ __launch_bounds__(512) void rollout_fused_kernel(RfArgs g)
                 nthdot = fminf(fmaxf(nthdot, -8.f), 8.f);
                 out[0] = th + nthdot * 0.05f;                              // new theta
                 out[1] = nthdot;
+            } else {
+                // PointChasingVecEnv: the action's (up to four) components live in lane group q = 0, which steps the env below
+#pragma unroll
+                for (int r = 0; r < 4; ++r) out[r] = te[r];
             }
         }
         RFPROF(5);
-        // (3) the env's cross-wave reductions (SynVecEnv: S features over nt waves).  Pendulum is stepped by wave 0 alone, which goes straight
+        // (3) the env's cross-wave reductions (SynVecEnv: S features over nt waves).  Pendulum and PointChasing are stepped by wave 0 alone, which goes straight
         // on: nothing it reads below was written by another wave since barrier (2), and what it writes is read after barrier (4)
         if (ENV == ENV_SYN || RS_) lds_barrier();
         RFPROF(6);
@@ -688,7 +695,7 @@ __global__ __launch_bounds__(512) void rollout_fused_kernel(RfArgs g)
                 }
                 sc = done ? 0 : sc1;
                 if (done) ep = ep + 1;
-            } else {
+            } else if (ENV == ENV_PENDULUM) {
                 const float PI = 3.14159265358979323846f;
                 float nth = out[0], nthdot = out[1];
                 const int sc1 = sc + 1;
@@ -726,6 +733,40 @@ __global__ __launch_bounds__(512) void rollout_fused_kernel(RfArgs g)
                     }
                     }
                 }
+            } else {
+                // PointChasingVecEnv (pointchasing_step.h, the statements of envs.hip pointchasing_step_kernel) in place on this env's row
+                // of the state tile: lane group q = 0 alone (its sc / ep / dist are the ones handed back)
+                if (q == 0) {
+                    float rew;
+                    bool term, trunc;
+                    pointchasing_step(XS + l15 * RF_XLD, out, A, dist, sc, ep, g.max_step, g.env_seed, (uint32_t)row, rew, term, trunc);
+                    // the normalised tiles from the row just written (S = 4 A <= 16 columns, four at a time)
+#pragma unroll
+                    for (int jc = 0; jc < 4 * kPointChasingMaxDim; jc += 4) {
+                        if (jc < S) {
+                            const float4 x = *reinterpret_cast<const float4 *>(XS + l15 * RF_XLD + jc);
+                            const float4 aa = *reinterpret_cast<const float4 *>(NRM + jc), ad = *reinterpret_cast<const float4 *>(NRM + 64 + jc);
+                            rb_tile_put(XA, RB_XLD, l15, jc, (x.x - aa.x) / ad.x, (x.y - aa.y) / ad.y, (x.z - aa.z) / ad.z, (x.w - aa.w) / ad.w);
+                            if constexpr (!EV_) {
+                                const float4 ca = *reinterpret_cast<const float4 *>(NRM + 128 + jc), cd = *reinterpret_cast<const float4 *>(NRM + 192 + jc);
+                                rb_tile_put(XC, RB_XLD, l15, jc, (x.x - ca.x) / cd.x, (x.y - ca.y) / cd.y, (x.z - ca.z) / cd.z, (x.w - ca.w) / cd.w);
+                            }
+                        }
+                    }
+                    if constexpr (EV_) ev_account(t, rew, term || trunc);
+                    else {
+                    const float rws = g.reward_scale == 1.0f ? rew : rew * g.reward_scale;
+                    if (valid) {
+                        g.o_rewards[(size_t)t * N + row] = rws;
+                        g.o_undones[(size_t)t * N + row] = term ? 0 : 1;
+                        g.o_unmasks[(size_t)t * N + row] = trunc ? 0 : 1;
+                    }
+                    if (g.gae_lds) {
+                        GAE[(t * 3 + 0) * 16 + l15] = rws;
+                        GAE[(t * 3 + 2) * 16 + l15] = __int_as_float((term ? 0 : 1) | (trunc ? 0 : 2));
+                    }
+                    }
+                }
             }
         }
         RFPROF(7);
@@ -749,6 +790,7 @@ __global__ __launch_bounds__(512) void rollout_fused_kernel(RfArgs g)
         g.step_count[row] = sc;
         g.episode[row] = ep;
         if (ENV == ENV_PENDULUM) { g.phys[2 * row] = th; g.phys[2 * row + 1] = thdot; }
+        if (ENV == ENV_POINT) g.phys[row] = dist;
         if constexpr (EV_) g.ev_cnt[row] = ev_n;
     }
     if constexpr (EV_) return;
@@ -837,23 +879,26 @@ bool rf_dims_ok(int S, int h1, int h2, int A)
 // Which instantiation rollout_fused_kernel<E, V, A_, B_, C_, ..> a launch takes, for the training form (rollout_fused.hip) and the evaluation
 // form (rollout_eval.hip) alike: the evaluation is the training rollout under zero noise bit for bit only while both pick the same class.
 // TUNED: <ENV_SYN, true, 4, 8, 8> (configs 4 / 5: 49 <= S <= 64, net [128, 128]) and <ENV_PENDULUM, false, 1, 8, 4> (config 2: net [128, 64]);
-// the others run <E, V, 0, 0, 0>.  `vec`: the launcher's own finding that S % 4 == 0 and the pointers its form reads 16 bytes wide are aligned.
-enum RfShapeClass { RF_SYN_TUNED, RF_SYN_VEC, RF_SYN_SCALAR, RF_PENDULUM_TUNED, RF_PENDULUM_ANY };
+// the others run <E, V, 0, 0, 0> (PointChasing: <ENV_POINT, false, 0, 0, 0> alone).  `vec`: the launcher's own finding that S % 4 == 0 and the
+// pointers its form reads 16 bytes wide are aligned.
+enum RfShapeClass { RF_SYN_TUNED, RF_SYN_VEC, RF_SYN_SCALAR, RF_PENDULUM_TUNED, RF_PENDULUM_ANY, RF_POINT_ANY };
 
 RfShapeClass rf_shape_class(int env_kind, bool vec, int S, int h1, int h2)
 {
     if (env_kind == ENV_SYN) return !vec ? RF_SYN_SCALAR : ((S + 15) / 16 == 4 && h1 == 128 && h2 == 128) ? RF_SYN_TUNED : RF_SYN_VEC;
+    if (env_kind == ENV_POINT) return RF_POINT_ANY;
     return (h1 == 128 && h2 == 64) ? RF_PENDULUM_TUNED : RF_PENDULUM_ANY;
 }
 
 // the policy and the shape as the entries of both forms are handed them (host side; the evaluation form reads the actor's three only)
 struct RfNets {
     const float *actor_params, *critic_params, *act_avg, *act_std, *cri_avg, *cri_std;
-    int S, h1, h2, A;                       // Pendulum: S = 3, A = 1
+    int S, h1, h2, A;                       // Pendulum: S = 3, A = 1; PointChasing: S = 4 A
     int64_t N, H;
 };
 
-// the env pack into the kernel's argument (Pendulum: env_state is the live observation; fields the env does not have stay NULL)
+// the env pack into the kernel's argument (Pendulum: env_state is the live observation; PointChasing: phys is the (N,) distance; fields
+// the env does not have stay NULL)
 void rf_set_env(RfArgs &g, const ContEnv &e)
 {
     g.env_state = e.env_state; g.phys = e.phys; g.Ws = e.Ws; g.Wa = e.Wa; g.step_count = e.step_count; g.episode = e.episode;

@@ -908,7 +908,7 @@ static int sac_rollout_layout(const char *what, int variant, bool terse, int S, 
 
 // The whole off-policy rollout of AgentBase._explore_vec_env (AgentBase.py:130-170) on a device-resident env as ONE launch
 // (sac_fused.hip sac_rollout_synenv_kernel); needs erl_sac_rollout_synenv_supported(...).  `what`: the entry's name; `e`: the env
-// (cont_env_args.h; Pendulum: S = 3, A = 1, env_state the live observation); `variant`: ERL_SAC_ACTOR_FIX = ActorFixSAC.get_action (the
+// (cont_env_args.h; Pendulum: S = 3, A = 1, env_state the live observation; PointChasing: S = 4 A, phys the (N,) distance); `variant`: ERL_SAC_ACTOR_FIX = ActorFixSAC.get_action (the
 // erl_sac_rollout_mod_* entries, AgentModSAC)
 static int sac_rollout_impl(const char *what, int variant, const float *actor_params, int S, int A, const int *hidden, int n_hidden,
                             const ContEnv &e, int64_t N, int64_t H, const float *noise, uint64_t seed, uint64_t counter0, float reward_scale,
@@ -922,11 +922,12 @@ static int sac_rollout_impl(const char *what, int variant, const float *actor_pa
     ERL_REQUIRE(H >= 1 && H < (1LL << 30) && e.max_step >= 1, "%s: bad H=%lld max_step=%d", what, (long long)H, e.max_step);
     return erl_sac_rollout_fused(actor_params, S, A, hidden[0], hidden[1], aoff, e.env_state, e.Ws, e.Wa, e.phys, e.step_count, e.episode,
                                  e.max_step, e.env_seed, N, H, noise, seed, counter0, reward_scale, out_states, out_actions, out_rewards,
-                                 out_undones, out_unmasks, out_last_state, (hipStream_t)stream, nullptr, nullptr, variant);
+                                 out_undones, out_unmasks, out_last_state, (hipStream_t)stream, nullptr, nullptr, variant, e.kind);
 }
 
 #define SAC_SYNENV {ENV_SYN, env_state, nullptr, Ws, Wa, step_count, episode, max_step, env_seed}
 #define SAC_PENDULUM {ENV_PENDULUM, obs, phys, nullptr, nullptr, step_count, episode, max_step, env_seed}
+#define SAC_POINT {ENV_POINT, state, distance, nullptr, nullptr, step_count, episode, max_step, env_seed}
 #define SAC_ROLLOUT_SYNENV(NAME, VARIANT)                                                                                                    \
     extern "C" int NAME(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state, const float *Ws,         \
                         const float *Wa, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,       \
@@ -946,13 +947,27 @@ static int sac_rollout_impl(const char *what, int variant, const float *actor_pa
         return sac_rollout_impl(#NAME, VARIANT, actor_params, 3, 1, hidden, n_hidden, SAC_PENDULUM, N, H, noise, seed, counter0,             \
                                 reward_scale, out_states, out_actions, out_rewards, out_undones, out_unmasks, out_last_state, stream);       \
     }
+// ... on the device-resident PointChasingVecEnv (S = 4 A, A = dim in 1..4; state: (N, S) the live observation; distance: (N,) the carried |p0 - p1|)
+#define SAC_ROLLOUT_POINT(NAME, VARIANT)                                                                                                     \
+    extern "C" int NAME(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *state, float *distance,             \
+                        int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H, const float *noise,    \
+                        uint64_t seed, uint64_t counter0, float reward_scale, float *out_states, float *out_actions, float *out_rewards,     \
+                        uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, void *stream)                                     \
+    {                                                                                                                                        \
+        if (int rc = cont_env_point_dims(#NAME, S, A)) return rc;                                                                            \
+        return sac_rollout_impl(#NAME, VARIANT, actor_params, S, A, hidden, n_hidden, SAC_POINT, N, H, noise, seed, counter0, reward_scale,  \
+                                out_states, out_actions, out_rewards, out_undones, out_unmasks, out_last_state, stream);                     \
+    }
 SAC_ROLLOUT_SYNENV(erl_sac_rollout_synenv_f32, ERL_SAC_ACTOR_SAC)
 SAC_ROLLOUT_PENDULUM(erl_sac_rollout_pendulum_f32, ERL_SAC_ACTOR_SAC)
 // ActorFixSAC.get_action (AgentSAC.py:217-224) in the same launches: AgentModSAC's rollout
 SAC_ROLLOUT_SYNENV(erl_sac_rollout_mod_synenv_f32, ERL_SAC_ACTOR_FIX)
 SAC_ROLLOUT_PENDULUM(erl_sac_rollout_mod_pendulum_f32, ERL_SAC_ACTOR_FIX)
+SAC_ROLLOUT_POINT(erl_sac_rollout_pointchasing_f32, ERL_SAC_ACTOR_SAC)
+SAC_ROLLOUT_POINT(erl_sac_rollout_mod_pointchasing_f32, ERL_SAC_ACTOR_FIX)
 #undef SAC_ROLLOUT_SYNENV
 #undef SAC_ROLLOUT_PENDULUM
+#undef SAC_ROLLOUT_POINT
 
 // the ActorFixSAC launches cover the shapes of their AgentSAC twins
 extern "C" int erl_sac_rollout_mod_supported(int S, int A, const int *hidden, int n_hidden, int64_t N)
@@ -978,7 +993,7 @@ static int sac_eval_impl(const char *what, int variant, const float *actor_param
     const ErlEvalWs w = erl_eval_ws_layout(workspace, N, H);
     return erl_sac_rollout_fused(actor_params, S, A, hidden[0], hidden[1], aoff, e.env_state, e.Ws, e.Wa, e.phys, e.step_count, e.episode,
                                  e.max_step, e.env_seed, N, H, nullptr, 0, 0, 1.0f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                 (hipStream_t)stream, w.rec, w.cnt, variant);
+                                 (hipStream_t)stream, w.rec, w.cnt, variant, e.kind);
 }
 
 #define SAC_EVAL_SYNENV(NAME, VARIANT)                                                                                                       \
@@ -995,14 +1010,26 @@ static int sac_eval_impl(const char *what, int variant, const float *actor_param
     {                                                                                                                                        \
         return sac_eval_impl(#NAME, VARIANT, actor_params, 3, 1, hidden, n_hidden, SAC_PENDULUM, N, H, workspace, workspace_bytes, stream);  \
     }
+#define SAC_EVAL_POINT(NAME, VARIANT)                                                                                                        \
+    extern "C" int NAME(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *state, float *distance,             \
+                        int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H, void *workspace,       \
+                        int64_t workspace_bytes, void *stream)                                                                               \
+    {                                                                                                                                        \
+        if (int rc = cont_env_point_dims(#NAME, S, A)) return rc;                                                                            \
+        return sac_eval_impl(#NAME, VARIANT, actor_params, S, A, hidden, n_hidden, SAC_POINT, N, H, workspace, workspace_bytes, stream);     \
+    }
 SAC_EVAL_SYNENV(erl_sac_eval_synenv_f32, ERL_SAC_ACTOR_SAC)
 SAC_EVAL_PENDULUM(erl_sac_eval_pendulum_f32, ERL_SAC_ACTOR_SAC)
 SAC_EVAL_SYNENV(erl_sac_eval_mod_synenv_f32, ERL_SAC_ACTOR_FIX)
 SAC_EVAL_PENDULUM(erl_sac_eval_mod_pendulum_f32, ERL_SAC_ACTOR_FIX)
+SAC_EVAL_POINT(erl_sac_eval_pointchasing_f32, ERL_SAC_ACTOR_SAC)
+SAC_EVAL_POINT(erl_sac_eval_mod_pointchasing_f32, ERL_SAC_ACTOR_FIX)
 #undef SAC_EVAL_SYNENV
 #undef SAC_EVAL_PENDULUM
+#undef SAC_EVAL_POINT
 #undef SAC_SYNENV
 #undef SAC_PENDULUM
+#undef SAC_POINT
 
 // ActorSAC.get_action for the off-policy rollout (AgentSAC.py:179-185): action = tanh(mean + std * eps); state_out (may be NULL):
 // the rollout's `states[t] = state` (AgentBase.py:145) written by the same launch.  With the actor variant named: ERL_SAC_ACTOR_FIX =

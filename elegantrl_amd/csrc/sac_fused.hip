@@ -40,8 +40,10 @@
 // and its options (SacCall / SacStep): the actor's own Adam count, its target's soft update behind that step, and -- on the steps its two-time-scale
 // rule skips -- one small launch (sac_skip_finish_kernel) in place of launches (7)-(10).  Its rollout and evaluation are the FIX forms of the
 // persistent rollout (a template parameter there: sac_rollout_synenv_kernel).
+#include "cont_env_args.h"
 #include "mlpn_common.h"
 #include "per_draw.h"
+#include "pointchasing_step.h"
 #include "stream_slots.h"
 
 namespace {
@@ -1381,7 +1383,7 @@ struct SacRolloutArgs {
     float *o_last_state;                           // (N, S) or NULL
     float *env_state;                              // (N, S) live state (PendulumVecEnv: the observation cos, sin, theta_dot)
     const float *Ws, *Wa;                          // SynVecEnv
-    float *phys;                                   // PendulumVecEnv: (N, 2) theta, theta_dot
+    float *phys;                                   // PendulumVecEnv: (N, 2) theta, theta_dot; PointChasingVecEnv: (N,) distance
     int32_t *step_count, *episode;
     int max_step;
     uint64_t env_seed;
@@ -1396,7 +1398,8 @@ constexpr int SR_XLD = 68, SR_WLD = 68;
 constexpr int SR_O_XS = 0, SR_O_WST = SR_O_XS + 16 * SR_XLD, SR_O_WAT = SR_O_WST + 64 * SR_WLD, SR_O_ACT = SR_O_WAT + 64 * 16;
 constexpr int SR_O_RED = SR_O_ACT + 16 * 16, SR_O_W1L = SR_O_RED + 8 * 16 * 2, SR_O_BIA = SR_O_W1L + FMAXW * SR_WLD, SR_FLOATS = SR_O_BIA + 3 * FMAXW;
 
-enum { SR_ENV_SYN = 0, SR_ENV_PENDULUM = 1 };
+enum { SR_ENV_SYN = 0, SR_ENV_PENDULUM = 1, SR_ENV_POINT = 2 };
+static_assert(SR_ENV_SYN == ENV_SYN && SR_ENV_PENDULUM == ENV_PENDULUM && SR_ENV_POINT == ENV_POINT, "the launcher is handed ContEnv::kind");
 
 // EV (the evaluation form, behind erl_sac_eval_*_f32): the deterministic policy -- the action is tanh of the first A head outputs,
 // ActorSAC.forward -- without the draws, the states / actions / rewards / flags rows and the reward scale.  The layers and the env
@@ -1456,11 +1459,13 @@ __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g
     }
     const float *wst_row = WST + ((16 * L.wave + L.l15) & 63) * SR_WLD + 4 * L.q, *wat_row = WAT + ((16 * L.wave + L.l15) & 63) * 16 + 4 * L.q;
     int sc = g.step_count[row], ep = g.episode[row];
-    // Pendulum: thread s < 16 steps env row0 + s by itself (no matrix product, no cross-wave reduction)
+    // Pendulum, PointChasing: thread s < 16 steps env row0 + s by itself (no matrix product, no cross-wave reduction)
     const int64_t prow = min(row0 + (int64_t)min(L.tid, TS - 1), N - 1);
     float th = 0.f, thdot = 0.f;
     int psc = 0, pep = 0;
     if (ENV == SR_ENV_PENDULUM) { th = g.phys[2 * prow]; thdot = g.phys[2 * prow + 1]; psc = g.step_count[prow]; pep = g.episode[prow]; }
+    float pdist = 0.f;                                     // PointChasing: the env's carried |p0 - p1|
+    if (ENV == SR_ENV_POINT) { pdist = g.phys[prow]; psc = g.step_count[prow]; pep = g.episode[prow]; }
     // (evaluation form) the open episode of the env whose reward this thread computes, and the episodes it has finished
     double ev_ret = 0.0;
     int ev_len = 0, ev_n = 0;
@@ -1558,9 +1563,34 @@ __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g
                     g.o_unmasks[(size_t)t * N + b] = trunc ? 0 : 1;
                 }
             }
+            if (ENV == SR_ENV_POINT) {
+                // PointChasingVecEnv (pointchasing_step.h, the statements of envs.hip pointchasing_step_kernel) in place on this env's row of the state tile
+                const float4 a4 = *reinterpret_cast<const float4 *>(ACT + L.tid * 16);      // (columns >= A are zero and not read)
+                const float av[kPointChasingMaxDim] = {a4.x, a4.y, a4.z, a4.w};
+                float rew;
+                bool term, trunc;
+                pointchasing_step(XS + L.tid * SR_XLD, av, A, pdist, psc, pep, g.max_step, g.env_seed, (uint32_t)bc, rew, term, trunc);
+                const bool done = term || trunc;
+                if constexpr (EV) {
+                    // the env's account waits in its thread's own row of ACT, columns 8..11, as Pendulum's does (A <= 4 uses columns 0..3)
+                    double *acc = reinterpret_cast<double *>(ACT + L.tid * 16 + 8);
+                    int *cnt = reinterpret_cast<int *>(ACT + L.tid * 16 + 10);      // [length of the open episode, episodes finished]
+                    const double ret = *acc + (double)rew;
+                    const int len = cnt[0] + 1;
+                    if (b < N) g.ev_rec[(size_t)t * N + b] = done ? make_float2((float)ret, (float)len) : make_float2(0.f, 0.f);
+                    *acc = done ? 0.0 : ret;
+                    cnt[0] = done ? 0 : len;
+                    if (done) cnt[1] += 1;
+                }
+                if (!EV && b < N) {
+                    g.o_rewards[(size_t)t * N + b] = g.reward_scale == 1.0f ? rew : rew * g.reward_scale;
+                    g.o_undones[(size_t)t * N + b] = term ? 0 : 1;
+                    g.o_unmasks[(size_t)t * N + b] = trunc ? 0 : 1;
+                }
+            }
         }
         lds_barrier();
-        if (ENV == SR_ENV_PENDULUM) continue;              // (the new state tile is in place: the barrier above publishes it)
+        if (ENV != SR_ENV_SYN) continue;                   // (the new state tile is in place: the barrier above publishes it)
         // ---- env.step on the matrix cores: s' = s Ws + a Wa, wave w < ns owns features 16 w .. 16 w + 15 (envs.hip synenv_tile_kernel)
         float out[4] = {0.f, 0.f, 0.f, 0.f}, a2 = 0.f;
         const int j0 = 16 * L.wave + 4 * L.q;
@@ -1647,8 +1677,10 @@ __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g
         if constexpr (EV) g.ev_cnt[prow] = reinterpret_cast<const int *>(ACT + L.tid * 16 + 10)[1];
         g.step_count[prow] = psc;
         g.episode[prow] = pep;
-        g.phys[2 * prow] = th;
-        g.phys[2 * prow + 1] = thdot;
+        if (ENV == SR_ENV_PENDULUM) {
+            g.phys[2 * prow] = th;
+            g.phys[2 * prow + 1] = thdot;
+        } else g.phys[prow] = pdist;
     }
 }
 
@@ -1924,7 +1956,7 @@ int erl_sac_rollout_fused(const float *actor_params, int S, int A, int h0, int h
                           const float *Wa, float *phys, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
                           const float *noise, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states, float *out_actions,
                           float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, hipStream_t stream,
-                          float2 *ev_rec, int32_t *ev_cnt, int variant)
+                          float2 *ev_rec, int32_t *ev_cnt, int variant, int env_kind)
 {
     FusedDims d{};
     d.S = S; d.A = A; d.E = 1; d.h0 = h0; d.h1 = h1; d.B = N;
@@ -1937,7 +1969,7 @@ int erl_sac_rollout_fused(const float *actor_params, int S, int A, int h0, int h
     g.ev_rec = ev_rec; g.ev_cnt = ev_cnt;
     const dim3 grid((unsigned)((N + TS - 1) / TS)), blk(FT);
     const size_t lds_bytes = (size_t)SR_FLOATS * sizeof(float);
-    static bool attr[2][2][2][9] = {};                   // (the dynamic part alone is beyond 64 KB)
+    static bool attr[2][2][3][9] = {};                   // (the dynamic part alone is beyond 64 KB)
 #define LAUNCH_SAC_ROLLOUT_E(K0, K1, ENV_, EVAL_, FIX_)                                                                         \
     do {                                                                                                                        \
         if (!attr[FIX_][EVAL_][ENV_][K0 * 3 + K1]) {                                                                            \
@@ -1957,13 +1989,26 @@ int erl_sac_rollout_fused(const float *actor_params, int S, int A, int h0, int h
 #define LAUNCH_MOD_ROLLOUT_PEN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_PENDULUM, false, true)
 #define LAUNCH_MOD_EVAL_SYN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_SYN, true, true)
 #define LAUNCH_MOD_EVAL_PEN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_PENDULUM, true, true)
+#define LAUNCH_SAC_ROLLOUT_PNT(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_POINT, false, false)
+#define LAUNCH_SAC_EVAL_PNT(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_POINT, true, false)
+#define LAUNCH_MOD_ROLLOUT_PNT(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_POINT, false, true)
+#define LAUNCH_MOD_EVAL_PNT(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_POINT, true, true)
     const bool fix = variant == ERL_SAC_ACTOR_FIX;
-    if (ev_rec) {                                        // the evaluation form (erl_sac_eval_*_f32, erl_sac_eval_mod_*_f32)
-        if (phys) { if (fix) { FUSED_KT_DISPATCH(LAUNCH_MOD_EVAL_PEN) } else { FUSED_KT_DISPATCH(LAUNCH_SAC_EVAL_PEN) } }
+    const bool pen = env_kind == SR_ENV_PENDULUM;
+    if (env_kind == SR_ENV_POINT) {
+        if (ev_rec) { if (fix) { FUSED_KT_DISPATCH(LAUNCH_MOD_EVAL_PNT) } else { FUSED_KT_DISPATCH(LAUNCH_SAC_EVAL_PNT) } }
+        else { if (fix) { FUSED_KT_DISPATCH(LAUNCH_MOD_ROLLOUT_PNT) } else { FUSED_KT_DISPATCH(LAUNCH_SAC_ROLLOUT_PNT) } }
+    }
+    else if (ev_rec) {                                   // the evaluation form (erl_sac_eval_*_f32, erl_sac_eval_mod_*_f32)
+        if (pen) { if (fix) { FUSED_KT_DISPATCH(LAUNCH_MOD_EVAL_PEN) } else { FUSED_KT_DISPATCH(LAUNCH_SAC_EVAL_PEN) } }
         else { if (fix) { FUSED_KT_DISPATCH(LAUNCH_MOD_EVAL_SYN) } else { FUSED_KT_DISPATCH(LAUNCH_SAC_EVAL_SYN) } }
     }
-    else if (phys) { if (fix) { FUSED_KT_DISPATCH(LAUNCH_MOD_ROLLOUT_PEN) } else { FUSED_KT_DISPATCH(LAUNCH_SAC_ROLLOUT_PEN) } }
+    else if (pen) { if (fix) { FUSED_KT_DISPATCH(LAUNCH_MOD_ROLLOUT_PEN) } else { FUSED_KT_DISPATCH(LAUNCH_SAC_ROLLOUT_PEN) } }
     else { if (fix) { FUSED_KT_DISPATCH(LAUNCH_MOD_ROLLOUT_SYN) } else { FUSED_KT_DISPATCH(LAUNCH_SAC_ROLLOUT_SYN) } }
+#undef LAUNCH_MOD_EVAL_PNT
+#undef LAUNCH_MOD_ROLLOUT_PNT
+#undef LAUNCH_SAC_EVAL_PNT
+#undef LAUNCH_SAC_ROLLOUT_PNT
 #undef LAUNCH_MOD_EVAL_SYN
 #undef LAUNCH_MOD_EVAL_PEN
 #undef LAUNCH_MOD_ROLLOUT_SYN

@@ -1,1 +1,2 @@
-from .vec_envs import AcrobotGpuVecEnv, CartPoleGpuVecEnv, CartPoleVecEnv, MountainCarGpuVecEnv, PendulumVecEnv, SynVecEnv
+from .vec_envs import (AcrobotGpuVecEnv, CartPoleGpuVecEnv, CartPoleVecEnv, MountainCarGpuVecEnv, PendulumVecEnv, PointChasingVecEnv,
+                       SynVecEnv)

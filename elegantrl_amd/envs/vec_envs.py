@@ -5,16 +5,16 @@ elegantrl/envs/PointChasingEnv.py:84-182 as the in-tree exemplar).
 
 They additionally expose `step_into(action, reward_row, terminal_row, truncate_row) -> state`, which lets the
 rollout write step outputs straight into row t of its time-major buffers (no copies, no host sync).
-The dynamics run in erl_synenv_step_f32 / erl_pendulum_step_f32 (elegantrl_amd/csrc/envs.hip) and erl_cartpole_step_f32 /
+The dynamics run in erl_synenv_step_f32 / erl_pendulum_step_f32 / erl_pointchasing_step_f32 (elegantrl_amd/csrc/envs.hip) and erl_cartpole_step_f32 /
 erl_acrobot_step_f32 / erl_mountaincar_step_f32 (elegantrl_amd/csrc/rollout_discrete.hip).
 
 Each family's base class owns every launch and leaves an env its constructor, `reset`, its entries' names and its live buffers:
-_ContinuousGpuVecEnv (SynVecEnv, PendulumVecEnv) and _DiscreteGpuVecEnv (CartPole, Acrobot, MountainCar).
+_ContinuousGpuVecEnv (SynVecEnv, PendulumVecEnv, PointChasingVecEnv) and _DiscreteGpuVecEnv (CartPole, Acrobot, MountainCar).
 """
 from __future__ import annotations
 
 import math
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch as th
 
@@ -89,7 +89,7 @@ class _ContinuousGpuVecEnv(_GpuVecEnv):
     """what the device-resident continuous envs share: the per-step launch (erl_<stem>_step_f32, csrc/envs.hip) and the one-launch rollout /
     evaluation of a PPO agent (erl_rollout_<stem>_f32, erl_eval_<stem>_f32) and of a SAC agent (erl_sac_rollout_[mod_]<stem>_f32,
     erl_sac_eval_[mod_]<stem>_f32).  An env adds its constructor, `reset`, the three attributes below and `_live`."""
-    _stem = ""                              # "synenv" | "pendulum"
+    _stem = ""                              # "synenv" | "pendulum" | "pointchasing"
     _action_at = 0                          # how many of the live buffers the per-step entry takes in front of the action
     _takes_dims = False                     # the entries take state_dim and action_dim (else they fix them)
 
@@ -236,6 +236,65 @@ class PendulumVecEnv(_ContinuousGpuVecEnv):
         self.step_count.zero_()
         self.episode.zero_()
         return self.state.clone(), {}
+
+
+class PointChasingVecEnv(_ContinuousGpuVecEnv):
+    """The reference's PointChasingVecEnv (elegantrl/envs/PointChasingEnv.py:84-182) on the device: a chaser p1, steered by the action
+    (scaled down to unit length where longer), runs after a target p0 that drifts by `dim` uniform draws per step; reward = the distance
+    closed minus 0.02 max(|action|, 1); the episode ends when the distance falls below `dim` or at `max_step`.  `state` (N, 4 dim) =
+    (p0, v0, p1, v1) is the observation and the state of record, `distance` (N,) the carried |p0 - p1|; the entries take state_dim = 4 dim
+    and action_dim = dim (1..4).  csrc/pointchasing_step.h states the step, operation for operation, and the three deviations from the
+    reference's vec env: `distance` is recomputed after a reset (the reference leaves it stale), terminal = caught and truncate = time limit
+    (the reference raises terminal for both), draws are Philox4x32-10 keyed by (seed, env, episode, step).
+    The reference's KEYWORD spellings `env_num` and `sim_gpu_id` are accepted; its positional order (dim, env_num, sim_gpu_id) is not this
+    constructor's (dim, num_envs, max_step, ...), so a positional third argument is a max_step here and one below 1 is refused."""
+    env_name = "PointChasingVecEnv"
+    _stem, _action_at, _takes_dims = "pointchasing", 1, True
+    init_distance = 8.0
+
+    def __init__(self, dim: int = 2, num_envs: int = 4096, max_step: int = 1024, gpu_id: int = 0, seed: int = 0, env_num: Optional[int] = None,
+                 sim_gpu_id: Optional[int] = None, **_):
+        num_envs, gpu_id = self._aliases(num_envs, gpu_id, env_num, sim_gpu_id)
+        if not 1 <= int(dim) <= 4:
+            raise ValueError(f"PointChasingVecEnv: dim = {dim}, the device env covers 1..4")
+        if int(max_step) < 1 or int(num_envs) < 1:
+            raise ValueError(f"PointChasingVecEnv: num_envs = {num_envs}, max_step = {max_step}; both must be at least 1 (the arguments are "
+                             "(dim, num_envs, max_step, gpu_id, seed): pass the reference's env_num / sim_gpu_id by keyword)")
+        self.dim = int(dim)
+        super().__init__(num_envs, 4 * self.dim, self.dim, max_step, gpu_id, seed)
+        self.state = th.zeros((num_envs, 4 * self.dim), dtype=th.float32, device=self.device)
+        self.distance = th.zeros(num_envs, dtype=th.float32, device=self.device)
+
+    @staticmethod
+    def _aliases(num_envs: int, gpu_id: int, env_num, sim_gpu_id) -> Tuple[int, int]:
+        """the reference's spellings (`env_num`, `sim_gpu_id`; -1 there means the CPU) win where they are given"""
+        return (num_envs if env_num is None else int(env_num)), (gpu_id if sim_gpu_id is None else int(sim_gpu_id))
+
+    def _live(self):
+        return (self.state, self.distance)
+
+    def reset(self, **_) -> Tuple[TEN, dict]:
+        self.state_epoch += 1
+        d = self.dim
+        g = th.Generator(device=self.device).manual_seed(self.seed)
+        draws = th.randn((self.num_envs, 2 * d), device=self.device, generator=g)
+        zeros = th.zeros((self.num_envs, d), dtype=th.float32, device=self.device)
+        p0, p1 = draws[:, :d], draws[:, d:] - self.init_distance
+        self.state = th.cat((p0, zeros, p1, zeros), dim=1).contiguous()
+        sq = (p0 - p1) ** 2
+        total = sq[:, 0]
+        for k in range(1, d):                  # (index order, as the step sums it)
+            total = total + sq[:, k]
+        self.distance = total.sqrt().contiguous()
+        self.step_count.zero_()
+        self.episode.zero_()
+        return self.state.clone(), {}
+
+    @staticmethod
+    def get_action(states: TEN) -> TEN:
+        """the reference's chase heuristic: head for the target (p0 - p1)"""
+        rows = states.reshape((states.shape[0], 4, -1))
+        return rows[:, 0] - rows[:, 2]
 
 
 class _DiscreteGpuVecEnv(_GpuVecEnv):

@@ -1023,6 +1023,18 @@ def pendulum_step(phys: TEN, obs: TEN, action: TEN, step_count: TEN, episode: TE
           "erl_pendulum_step_f32")
 
 
+def pointchasing_step(state: TEN, action: TEN, distance: TEN, step_count: TEN, episode: TEN, reward: TEN, terminal: TEN, truncate: TEN,
+                      max_step: int, seed: int) -> None:
+    """one PointChasingVecEnv step of every env (erl_pointchasing_step_f32): state (N, 4 dim) = (p0, v0, p1, v1) and distance (N,) in place,
+    action (N, dim)"""
+    N, S = state.shape
+    A = action.shape[1]
+    check(lib().erl_pointchasing_step_f32(ptr(state, th.float32), ptr(action, th.float32), ptr(distance, th.float32),
+                                          ptr(step_count, th.int32), ptr(episode, th.int32), ptr(reward, th.float32),
+                                          flag_ptr(terminal), flag_ptr(truncate), N, S, A, max_step, seed & (2 ** 64 - 1), stream_ptr()),
+          "erl_pointchasing_step_f32")
+
+
 def cartpole_step(state: TEN, action: TEN, step_count: TEN, episode: TEN, reward: TEN, terminal: TEN, truncate: TEN, max_step: int,
                   seed: int) -> None:
     """one CartPole-v1 step of every env (erl_cartpole_step_f32): state (N, 4) in place, action (N,) int64"""

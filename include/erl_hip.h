@@ -297,6 +297,18 @@ ERL_API int erl_rollout_pendulum_f32(const float *actor_params, const float *cri
                              float *out_last_state, float *out_advantages, float *out_reward_sums, double *gae_stats,
                              double *gae_workspace, int64_t gae_workspace_bytes, float gamma, float lambda_gae,
                              int use_v_trace, void *stream);
+/* ... on the device-resident PointChasingVecEnv (erl_pointchasing_step_f32 below: S = 4 A, A = dim in 1..4; state (N, S) the live
+ * observation, distance (N,) the carried |p0 - p1|, both advanced in place).  Terminal steps (the chaser catches the target) clear
+ * out_undones, time limits out_unmasks; the epilogue is the one above. */
+ERL_API int erl_rollout_pointchasing_f32(const float *actor_params, const float *critic_params, const float *act_avg,
+                                 const float *act_std, const float *cri_avg, const float *cri_std, int S, int h1, int h2, int A,
+                                 float *state, float *distance, int32_t *step_count, int32_t *episode, int max_step,
+                                 uint64_t env_seed, int64_t N, int64_t H, const float *noise, uint64_t seed, uint64_t counter0,
+                                 float reward_scale, float *out_states, float *out_actions, float *out_logprobs,
+                                 float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_values,
+                                 float *out_next_value, float *out_last_state, float *out_advantages, float *out_reward_sums,
+                                 double *gae_stats, double *gae_workspace, int64_t gae_workspace_bytes, float gamma,
+                                 float lambda_gae, int use_v_trace, void *stream);
 
 /* Policy evaluation on the device (ABI 20): the Evaluator's episodes (elegantrl/train/evaluator.py:201-238) in two launches.
  *
@@ -337,6 +349,13 @@ ERL_API int erl_sac_eval_synenv_f32(const float *actor_params, int S, int A, con
 ERL_API int erl_sac_eval_pendulum_f32(const float *actor_params, const int *hidden, int n_hidden, float *phys, float *obs,
                               int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
                               void *workspace, int64_t workspace_bytes, void *stream);
+/* the evaluation forms of erl_rollout_pointchasing_f32 and erl_sac_rollout_pointchasing_f32 */
+ERL_API int erl_eval_pointchasing_f32(const float *actor_params, const float *act_avg, const float *act_std, int S, int h1, int h2, int A,
+                              float *state, float *distance, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
+                              int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_sac_eval_pointchasing_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *state,
+                                  float *distance, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
+                                  int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream);
 ERL_API int erl_eval_episodes_compact_f32(const void *workspace, int64_t workspace_bytes, int64_t N, int64_t H, float *out_rows,
                                   int64_t out_capacity, int32_t *out_count, void *stream);
 
@@ -912,6 +931,13 @@ ERL_API int erl_sac_rollout_pendulum_f32(const float *actor_params, const int *h
                                  const float *noise, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states,
                                  float *out_actions, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks,
                                  float *out_last_state, void *stream);
+/* ... on the device-resident PointChasingVecEnv (S = 4 A, A = dim in 1..4; erl_pointchasing_step_f32's dynamics, operation for operation;
+ * state (N, S) the live observation, distance (N,) the carried |p0 - p1|) */
+ERL_API int erl_sac_rollout_pointchasing_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *state,
+                                     float *distance, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
+                                     int64_t N, int64_t H, const float *noise, uint64_t seed, uint64_t counter0, float reward_scale,
+                                     float *out_states, float *out_actions, float *out_rewards, uint8_t *out_undones,
+                                     uint8_t *out_unmasks, float *out_last_state, void *stream);
 /* erl_sac_update_f32 with ReplayBuffer.sample in front of it, from ONE call: state / action / reward / undone / unmask / next_state are
  * the (B, .) staging block the sample is written to (what erl_replay_sample_f32 would have produced: bit-identical), everything else
  * as erl_sac_update_f32.  In the fused step the gather rides in the step's first launch (under its weight loads: one launch and one
@@ -1013,6 +1039,14 @@ ERL_API int erl_sac_eval_mod_synenv_f32(const float *actor_params, int S, int A,
 ERL_API int erl_sac_eval_mod_pendulum_f32(const float *actor_params, const int *hidden, int n_hidden, float *phys, float *obs,
                                   int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
                                   void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_sac_rollout_mod_pointchasing_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *state,
+                                         float *distance, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
+                                         int64_t N, int64_t H, const float *noise, uint64_t seed, uint64_t counter0,
+                                         float reward_scale, float *out_states, float *out_actions, float *out_rewards,
+                                         uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, void *stream);
+ERL_API int erl_sac_eval_mod_pointchasing_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *state,
+                                      float *distance, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
+                                      int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream);
 ERL_API int erl_sac_explore_action_tile_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden,
                                     const float *state, int64_t N, const float *noise, uint64_t seed, uint64_t counter,
                                     float *action_out, float *state_out, void *workspace, int64_t workspace_bytes,
@@ -1080,6 +1114,13 @@ ERL_API int erl_synenv_step_f32(float *state, const float *action, const float *
 ERL_API int erl_pendulum_step_f32(float *phys, float *obs, const float *action, int32_t *step_count, int32_t *episode,
                           float *reward, uint8_t *terminal, uint8_t *truncate, int64_t N, int max_step,
                           uint64_t seed, void *stream);
+/* PointChasingVecEnv (the reference's elegantrl/envs/PointChasingEnv.py:84-182; csrc/pointchasing_step.h states the step and its three
+ * deviations: distance recomputed after a reset, terminal = caught / truncate = time limit, Philox draws).  state: (N, S) =
+ * (p0, v0, p1, v1), dim = A floats each, in place; distance: (N,) the carried |p0 - p1|, in place; action: (N, A).  A in 1..4, S = 4 A,
+ * N >= 1, max_step >= 1, else "bad shape".  Done rows return the post-reset state. */
+ERL_API int erl_pointchasing_step_f32(float *state, const float *action, float *distance, int32_t *step_count, int32_t *episode,
+                              float *reward, uint8_t *terminal, uint8_t *truncate, int64_t N, int S, int A, int max_step,
+                              uint64_t seed, void *stream);
 
 /* self-test of the MFMA tile helpers against scalar code; returns 0 and writes max |err| to *max_err
  * (host pointer).  Needs a GPU. */
