@@ -36,6 +36,9 @@ _SAC_KEY = [c_uint64, c_uint64]                                          # seed,
 _SAC_NOISE = [_P, _P] + _SAC_KEY                                         # eps_next, eps_cur, seed, counter
 _SAC_HYPER = [c_float] * 8                                               # gamma, target_entropy, tau, lr, beta1, beta2, eps_adam, max_norm
 _SAC_TAIL = [_P, c_int64, _P]                                            # workspace, workspace_bytes, stream
+# what the erl_td3_update_* prototypes share
+_TD3_HEAD = [_P] * 8 + [c_int, c_int, POINTER(c_int), c_int, c_int]      # actor, critic, their targets, four moments, S, A, hidden, n_hidden, E
+_TD3_HYPER = [c_float] * 8                                               # policy_noise_std, gamma, tau, lr, beta1, beta2, eps_adam, max_norm
 # what the one-launch entries of the continuous device envs share, in the order they name it
 _ENV_SYN = [_P] * 5 + [c_int, c_uint64]                                  # env_state, Ws, Wa, step_count, episode, max_step, env_seed
 _ENV_PEN = [_P] * 4 + [c_int, c_uint64]                                  # phys, obs, step_count, episode, max_step, env_seed
@@ -179,6 +182,14 @@ _SIGNATURES = {
     "erl_sac_eval_mod_pointchasing_f32": (c_int, _SAC_PNT + _EVAL_TAIL),
     "erl_sac_explore_action_tile_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, c_int64, _P, c_uint64, c_uint64, _P, _P, _P,
                                                 c_int64, c_int, _P]),
+    # TD3 / DDPG (csrc/td3.hip)
+    "erl_td3_param_counts": (c_int, [c_int, c_int, POINTER(c_int), c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    "erl_td3_workspace_bytes": (c_int64, [c_int, c_int, POINTER(c_int), c_int, c_int, c_int64]),
+    "erl_td3_explore_action_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, c_int64, _P] + _SAC_KEY + [c_float, _P, _P] + _SAC_TAIL),
+    "erl_td3_update_f32": (c_int, _TD3_HEAD + _SAC_BATCH + [_P, _P, c_int64, _P] + _SAC_KEY + _TD3_HYPER + [c_int32] * 3 + [_P] + _SAC_TAIL),
+    "erl_td3_update_ring_f32": (c_int, _TD3_HEAD + [_P] + _SAC_BATCH + [c_int64, _P] + _SAC_KEY + _TD3_HYPER + [c_int32] * 3 + [_P] + _SAC_TAIL),
+    "erl_td3_update_ring_loop_f32": (c_int, _TD3_HEAD + [_P, _P, c_int64] + _SAC_BATCH + [c_int64] + _SAC_KEY + _TD3_HYPER + [c_int32] * 4 +
+                                            [_P, POINTER(c_int32)] + _SAC_TAIL),
     "erl_eval_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "erl_eval_synenv_f32": (c_int, [_P] * 3 + _PPO_SYN + _EVAL_TAIL),
     "erl_eval_pendulum_f32": (c_int, [_P] * 3 + _PPO_PEN + _EVAL_TAIL),

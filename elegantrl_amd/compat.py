@@ -4,8 +4,9 @@ under elegantrl/agents and elegantrl/train") is the reference's class protocol, 
 train_agent`, `from elegantrl.train.replay_buffer import ReplayBuffer`, `from elegantrl import train_agent` ... -- should run
 unmodified.  `install()` puts an import hook at the front of `sys.meta_path` that resolves `elegantrl` and every
 `elegantrl.<x>` to the very module object of `elegantrl_amd` / `elegantrl_amd.<x>` (no second copy of any module, so
-`elegantrl.agents.AgentPPO is elegantrl_amd.agents.AgentPPO`).  Names the reference has and this package does not (the DQN /
-TD3 families, gym wrappers: outside SURVEY.md 8) fail with the ordinary ImportError / AttributeError.
+`elegantrl.agents.AgentPPO is elegantrl_amd.agents.AgentPPO`).  Names the reference has and this package does not (the DQN
+family, gym wrappers: outside SURVEY.md 8) fail with the ordinary ImportError / AttributeError.  `AgentTD3` and `AgentDDPG` are exported
+from `elegantrl.agents` (they live in elegantrl_amd/agents/AgentDDPG.py); `from elegantrl.agents.AgentTD3 import ...` remains unsupported.
 
 Two ways in: `import elegantrl_amd.compat; elegantrl_amd.compat.install()` before the script's imports, or simply keep the
 repository root on `sys.path`: the `elegantrl/` directory there is a three-line package that calls `install()` and hands

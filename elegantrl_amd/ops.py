@@ -1001,6 +1001,111 @@ def sac_explore_action(spec: SacSpec, actor: TEN, state: TEN, *, noise: Optional
 
 
 # ------------------------------------------------------------------------------------------------
+# TD3 / DDPG (csrc/td3.hip)
+# ------------------------------------------------------------------------------------------------
+class Td3Spec:
+    """shapes of Actor / CriticTwin (Critic: E = 1) of elegantrl/agents/AgentTD3.py as flat fp32 blocks (include/erl_hip.h)."""
+
+    def __init__(self, S: int, A: int, hidden: Sequence[int], num_ensembles: int):
+        self.S, self.A, self.hidden, self.E = int(S), int(A), [int(h) for h in hidden], int(num_ensembles)
+        self._c = (ctypes.c_int * len(self.hidden))(*self.hidden)
+        pa, pc = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(lib().erl_td3_param_counts(self.S, self.A, self._c, len(self.hidden), self.E, ctypes.byref(pa), ctypes.byref(pc)),
+              "erl_td3_param_counts")
+        self.actor_count, self.critic_count = pa.value, pc.value
+
+    @staticmethod
+    def _slices(dims):
+        out, o = [], 0
+        for i, (d_in, d_out) in enumerate(zip(dims[:-1], dims[1:])):
+            out += [(f"net.{2 * i}.weight", o, (d_out, d_in)), (f"net.{2 * i}.bias", o + d_out * d_in, (d_out,))]
+            o += d_out * d_in + d_out
+        return out
+
+    def actor_slices(self):
+        """(parameter name in Actor, offset, shape) in flat order: the reference's state_dict order"""
+        return self._slices([self.S, *self.hidden, self.A])
+
+    def critic_slices(self):
+        return self._slices([self.S + self.A, *self.hidden, self.E])
+
+    def workspace_bytes(self, B: int) -> int:
+        return lib().erl_td3_workspace_bytes(self.S, self.A, self._c, len(self.hidden), self.E, B)
+
+
+def _td3_head(spec: Td3Spec, nets: Sequence[TEN], moments: Sequence[TEN]) -> tuple:
+    """actor, critic, actor target, critic target, the four moments, S, A, hidden, n_hidden, E"""
+    f32 = th.float32
+    assert len(nets) == 4 and len(moments) == 4
+    return (*[ptr(t, f32) for t in nets], *[ptr(m, f32) for m in moments], spec.S, spec.A, spec._c, len(spec.hidden), spec.E)
+
+
+def _td3_hyper(seed: int, counter: int, policy_noise_std, gamma, tau, lr, betas, eps, max_norm) -> tuple:
+    return (seed & _U64, counter & _U64, float(policy_noise_std), float(gamma), float(tau), float(lr), betas[0], betas[1], eps,
+            float(max_norm))
+
+
+def td3_update(spec: Td3Spec, nets: Sequence[TEN], moments: Sequence[TEN], batch: Sequence[TEN], step: int, *, policy_noise_std: float,
+               gamma: float, tau: float, lr: float, max_norm: float, objs_out: TEN, update_actor: bool, actor_step: int,
+               noise: Optional[TEN] = None, seed: int = 0, counter: int = 0, betas=(0.9, 0.999), eps: float = 1e-8,
+               is_weight: Optional[TEN] = None, td_error_out: Optional[TEN] = None, criterion=CRITERION_MSE) -> None:
+    """one AgentTD3 / AgentDDPG.update_objectives step after the sample (erl_td3_update_f32); `nets` = (actor, critic, actor target,
+    critic target), `moments` = (actor_m, actor_v, critic_m, critic_v), `batch` = (state, action, reward, undone, unmask, next_state);
+    objs_out: float32[2] on the device; `noise` (B, A) injects the target-policy draw"""
+    B = batch[0].shape[0]
+    ws = _workspace(batch[0].device, spec.workspace_bytes(B))
+    _update_call("erl_td3_update_f32", criterion, *_td3_head(spec, nets, moments), *_sac_batch(batch), ptr(is_weight), ptr(td_error_out), B,
+                 ptr(noise), *_td3_hyper(seed, counter, policy_noise_std, gamma, tau, lr, betas, eps, max_norm), int(step),
+                 int(bool(update_actor)), int(actor_step), ptr(objs_out, th.float32), ptr(ws), ws.numel(), stream_ptr())
+
+
+def td3_update_from_ring(spec: Td3Spec, nets: Sequence[TEN], moments: Sequence[TEN], ring, ids: TEN, sample_len: int, stage: ReplayStage,
+                         step: int, *, policy_noise_std: float, gamma: float, tau: float, lr: float, max_norm: float, objs_out: TEN,
+                         update_actor: bool, actor_step: int, noise: Optional[TEN] = None, seed: int = 0, counter: int = 0,
+                         betas=(0.9, 0.999), eps: float = 1e-8, criterion=CRITERION_MSE) -> None:
+    """ReplayBuffer.sample(ids) + one step from ONE call (erl_td3_update_ring_f32); `ring` / `stage` as in sac_update_from_ring"""
+    B = ids.numel()
+    rs, dev = _ring_sample(spec, ring, ids, sample_len, stage, B)
+    ws = _workspace(dev, spec.workspace_bytes(B))
+    _update_call("erl_td3_update_ring_f32", criterion, *_td3_head(spec, nets, moments), ctypes.addressof(rs), *_sac_stage(stage), B, ptr(noise),
+                 *_td3_hyper(seed, counter, policy_noise_std, gamma, tau, lr, betas, eps, max_norm), int(step), int(bool(update_actor)),
+                 int(actor_step), ptr(objs_out, th.float32), ptr(ws), ws.numel(), stream_ptr())
+
+
+def td3_update_ring_loop(spec: Td3Spec, nets: Sequence[TEN], moments: Sequence[TEN], ring, ids_all: TEN, sample_len: int, stage: ReplayStage,
+                         step0: int, actor_step0: int, update_freq: int, actor_gate: bool, *, policy_noise_std: float, gamma: float,
+                         tau: float, lr: float, max_norm: float, objs_all: TEN, seed: int = 0, counter0: int = 0, betas=(0.9, 0.999),
+                         eps: float = 1e-8, criterion=CRITERION_MSE) -> int:
+    """`ids_all.shape[0]` steps of td3_update_from_ring from ONE C call (erl_td3_update_ring_loop_f32): step t uses ids_all[t], critic
+    optimiser step step0 + t, noise counter counter0 + t, writes objs_all[t] and updates the actor when `actor_gate` and
+    t % update_freq == 0; returns how many steps did"""
+    T, B = ids_all.shape
+    assert ids_all.is_contiguous() and objs_all.shape == (T, 2) and objs_all.is_contiguous()
+    rs, dev = _ring_sample(spec, ring, None, sample_len, stage, B)
+    ws = _workspace(dev, spec.workspace_bytes(B))
+    n_upd = ctypes.c_int32(-1)
+    _update_call("erl_td3_update_ring_loop_f32", criterion, *_td3_head(spec, nets, moments), ctypes.addressof(rs), ptr(ids_all, th.int64), T,
+                 *_sac_stage(stage), B, *_td3_hyper(seed, counter0, policy_noise_std, gamma, tau, lr, betas, eps, max_norm), int(step0),
+                 int(actor_step0), int(update_freq), int(bool(actor_gate)), ptr(objs_all, th.float32), ctypes.byref(n_upd), ptr(ws),
+                 ws.numel(), stream_ptr())
+    return int(n_upd.value)
+
+
+def td3_explore_action(spec: Td3Spec, actor: TEN, state: TEN, action_std: float, *, noise: Optional[TEN] = None, seed: int = 0,
+                       counter: int = 0, out: Optional[TEN] = None, out_state: Optional[TEN] = None) -> TEN:
+    """Actor.get_action(state, action_std) (erl_td3_explore_action_f32); `out` (N, A): the action's destination (e.g. the rollout's row);
+    `out_state` (N, S): a copy of `state` from the same launch"""
+    N = state.shape[0]
+    out = th.empty((N, spec.A), dtype=th.float32, device=state.device) if out is None else out
+    ws = _workspace(state.device, lib().erl_td3_workspace_bytes(spec.S, spec.A, spec._c, len(spec.hidden), 1, N))
+    check(lib().erl_td3_explore_action_f32(ptr(actor, th.float32), spec.S, spec.A, spec._c, len(spec.hidden), ptr(state, th.float32), N,
+                                           ptr(noise), seed & _U64, counter & _U64, float(action_std), ptr(out, th.float32),
+                                           ptr(out_state, th.float32) if out_state is not None else None, ptr(ws), ws.numel(), stream_ptr()),
+          "erl_td3_explore_action_f32")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # environments
 # ------------------------------------------------------------------------------------------------
 def synenv_step(state: TEN, action: TEN, Ws: TEN, Wa: TEN, step_count: TEN, episode: TEN, reward: TEN, terminal: TEN,

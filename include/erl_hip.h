@@ -1101,6 +1101,56 @@ ERL_API int erl_k6_timing_clocks(int bracketed, double *span_ms, int *launches, 
                          double *phase_cycles, int max_phases, int *n_phases, int *phase_workgroups);
 
 /* ---------------------------------------------------------------------------------------------
+ * TD3 / DDPG (elegantrl/agents/AgentTD3.py:15-87, AgentBase.py:191-224; csrc/td3.hip): the update step after ReplayBuffer.sample, the
+ * loop of AgentBase.update_net from one call, and Actor.get_action for the per-step rollout.  hidden = net_dims (n_hidden <=
+ * ERL_MAX_LAYERS); E = num_ensembles in 1..8 (AgentDDPG: 1).  Parameter blocks: actor = build_mlp([S, *hidden, A]) (tanh on top),
+ * critic = build_mlp([S + A, *hidden, E]), each W0 b0 W1 b1 ...; the two targets have their shapes.  The step:
+ *   next action = clip(tanh(actor(next_state)) + policy_noise_std * eps, -1, 1)   (0: plain tanh, AgentDDPG); eps = noise (B, A) or,
+ *   NULL, Philox keyed by (seed, counter, row, component); label = reward + undone gamma min_e target(next_state, next action);
+ *   td = mean_e criterion(q_e, label) unmask (the call's criterion, erl_criterion_next_call); objs_out[0] = mean(td [is_weight]);
+ *   td_error_out (B), may be NULL, receives td; critic clip + Adam at Adam step `step`, soft update of critic_target;
+ *   update_actor != 0: objs_out[1] = mean q(state, tanh(actor(state))) on the critic just stepped, actor clip + Adam at `actor_step`
+ *   (its own 1-based count), soft update of actor_target;  update_actor == 0: objs_out[1] = nan, nothing of the actor is written.
+ * For E = 1 the critic objective is the per-sample one, criterion(q_i, label_i) unmask_i, not the reference's
+ * (B, B) broadcast.  The ring entries gather the batch by ring->ids into the staging pointers first (ErlRingSample above);
+ * erl_td3_update_ring_loop_f32 runs n_steps of them: step t uses ids_all[t B ..], Adam step step0 + t, noise counter counter0 + t,
+ * objs_all[2 t ..], and updates the actor when actor_gate != 0 and t % update_freq == 0 (the actor's Adam count runs on from
+ * actor_step0; *actor_updates_out, may be NULL, receives the number of such steps).  Every entry validates everything before its first
+ * launch and refuses under its own name: NULL tensors, E outside 1..8, update_freq < 1, unsupported dims, a workspace below
+ * erl_td3_workspace_bytes, a bad ring.  No allocation, no host synchronisation.  erl_td3_explore_action_f32: action_out (N, A) =
+ * clip(tanh(actor(state)) + action_std * eps, -1, 1); state_out (N, S), may be NULL, receives `state`; workspace:
+ * erl_td3_workspace_bytes(S, A, hidden, n_hidden, 1, N) covers it.
+ * ------------------------------------------------------------------------------------------- */
+ERL_API int erl_td3_param_counts(int S, int A, const int *hidden, int n_hidden, int E, int64_t *actor_count, int64_t *critic_count);
+ERL_API int64_t erl_td3_workspace_bytes(int S, int A, const int *hidden, int n_hidden, int E, int64_t B);
+ERL_API int erl_td3_explore_action_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, const float *state,
+                               int64_t N, const float *noise, uint64_t seed, uint64_t counter, float action_std,
+                               float *action_out, float *state_out, void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_td3_update_f32(float *actor_params, float *critic_params, float *actor_target_params, float *critic_target_params,
+                       float *actor_m, float *actor_v, float *critic_m, float *critic_v, int S, int A, const int *hidden,
+                       int n_hidden, int E, const float *state, const float *action, const float *reward, const float *undone,
+                       const float *unmask, const float *next_state, const float *is_weight, float *td_error_out, int64_t B,
+                       const float *noise, uint64_t seed, uint64_t counter, float policy_noise_std, float gamma, float tau,
+                       float lr, float beta1, float beta2, float eps_adam, float max_norm, int32_t step, int32_t update_actor,
+                       int32_t actor_step, float *objs_out, void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_td3_update_ring_f32(float *actor_params, float *critic_params, float *actor_target_params, float *critic_target_params,
+                            float *actor_m, float *actor_v, float *critic_m, float *critic_v, int S, int A, const int *hidden,
+                            int n_hidden, int E, const ErlRingSample *ring, float *state, float *action, float *reward,
+                            float *undone, float *unmask, float *next_state, int64_t B, const float *noise, uint64_t seed,
+                            uint64_t counter, float policy_noise_std, float gamma, float tau, float lr, float beta1, float beta2,
+                            float eps_adam, float max_norm, int32_t step, int32_t update_actor, int32_t actor_step,
+                            float *objs_out, void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_td3_update_ring_loop_f32(float *actor_params, float *critic_params, float *actor_target_params,
+                                 float *critic_target_params, float *actor_m, float *actor_v, float *critic_m, float *critic_v,
+                                 int S, int A, const int *hidden, int n_hidden, int E, const ErlRingSample *ring,
+                                 const int64_t *ids_all, int64_t n_steps, float *state, float *action, float *reward,
+                                 float *undone, float *unmask, float *next_state, int64_t B, uint64_t seed, uint64_t counter0,
+                                 float policy_noise_std, float gamma, float tau, float lr, float beta1, float beta2,
+                                 float eps_adam, float max_norm, int32_t step0, int32_t actor_step0, int32_t update_freq,
+                                 int32_t actor_gate, float *objs_all, int32_t *actor_updates_out, void *workspace,
+                                 int64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * GPU-resident synthetic environments for measurement; they implement the
  * env protocol of elegantrl (step -> state, reward, terminal, truncate; auto-reset).
  * ------------------------------------------------------------------------------------------- */
