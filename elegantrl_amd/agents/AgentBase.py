@@ -9,13 +9,14 @@ builders `build_mlp` / `layer_init_with_orthogonal` (:345-365).
 
 What is new: `FlatNet` makes an actor/critic's trainable parameters views into one flat fp32 buffer laid
 out as include/erl_hip.h describes, so kernels read/write weights in place while the objects stay
-ordinary picklable `nn.Module`s.
+ordinary picklable `nn.Module`s; `_OffPolicyFlatAgent` is what AgentSAC / AgentModSAC / AgentTD3 / AgentDDPG share on top of it.
 """
 from __future__ import annotations
 
 import os
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
+import numpy as np
 import torch as th
 from torch import nn
 
@@ -376,3 +377,191 @@ class AgentBase:
                     th.save(obj, path)
             elif os.path.isfile(path):
                 setattr(self, attr_name, th.load(path, map_location=self.device, weights_only=False))
+
+
+class _Slices:
+    def __init__(self, slices):
+        self._s = slices
+
+    def slices(self):
+        return self._s
+
+
+class _FlatAdamState:
+    """Adam moments of one parameter block as flat tensors (what `save_or_load_agent` stores for the optimisers)."""
+
+    def __init__(self, numel: int, lr: float, device):
+        self.exp_avg = th.zeros(numel, dtype=th.float32, device=device)
+        self.exp_avg_sq = th.zeros(numel, dtype=th.float32, device=device)
+        self.step_count = 0
+        self.param_groups = [{"lr": lr, "betas": (0.9, 0.999), "eps": 1e-8}]
+
+
+class UpdateRoute(NamedTuple):
+    """what `_OffPolicyFlatAgent._update_net_route` decides"""
+    route: str                       # "ring_loop" | "per_loop" | "ring_step" | "batch_step" | "per_step"
+    update_path: str                 # what `update_path` reads after the call
+    per_path: Optional[str]          # what `per_path` reads after it (None: the agent names no prioritised route; left as it is)
+    source: object = None            # what the buffer handed over for the route: ring_for_fused_sample's / per_for_fused_loop's tuple
+
+
+class _OffPolicyFlatAgent(AgentBase):
+    """What the off-policy agents on the HIP steps share (AgentSAC / AgentModSAC, AgentTD3 / AgentDDPG): networks as `nn.Module`s bound
+    to flat fp32 blocks (the bind table), optimisers as `_FlatAdamState`s, the checkpoint round trip, and `update_net` -- a decision that
+    launches nothing (`_update_net_route`) and one executor.  A subclass builds its nets with `_bind`, names its optimisers
+    (`_optimizers`; `_set_step_counts` writes their `step_count`s, what a checkpoint stores) and provides the calls into ops
+    (`_update_on_batch`, `_update_from_ring`, `_update_ring_loop`, `_update_per_loop`), `_step_kwargs(buffer, update_t, noise=None)` (the
+    keyword arguments of the three per-step calls for step `update_t`) and its own reasons for leaving the one-call routes:
+    `_ring_step_reason()`, and `_ring_loop_reason(buffer, ring)` on what the buffer's ring_for_fused_sample returned (maybe None)."""
+    sample_ids_ahead = True          # update_net draws the sample ids of all its steps with one th.randint (AgentSAC reads args)
+    _ring_loop_path = ""             # `update_path` of update_net's loop as one C call
+    _per_why = ""                    # `update_path` behind "per step: " under prioritised replay
+
+    def __init__(self, net_dims: List[int], state_dim: int, action_dim: int, gpu_id: int = 0, args: Config = None):
+        super().__init__(net_dims, state_dim, action_dim, gpu_id, args)
+        self.if_off_policy = True
+        self._binds = {}                           # attribute name of a module -> the FlatNet that ties it to its flat block
+        self.update_path = None                    # which route the last update_net took: "one C call ..." / "per step: <reason>"
+        self.per_path = None                       # which route the last prioritised update_net took (None: none yet / not named)
+        self.rollout_path = None                   # which route the last rollout took
+        self._step = 0                             # the critic optimiser's Adam step = update steps taken
+        self._objs = th.zeros(2, dtype=th.float32, device=self.device)
+        self.objs_all = None                       # (update_times, 2) device tensor: the last update_net's (obj_critic, obj_actor) per step
+        self._td_error = None                      # per-sample td errors of a prioritised step
+
+    # ---- modules <-> flat blocks ------------------------------------------------------------------------
+    def _bind(self, name: str, module: nn.Module, slices, flat: TEN) -> None:
+        """`module` becomes the attribute `name`, its parameters views into `flat` in the order of `slices`"""
+        self._binds[name] = FlatNet(module, _Slices(slices), flat)
+        setattr(self, name, module)
+
+    def _on_act_replaced(self):
+        bind = getattr(self, "_binds", {}).get("_act")
+        if bind is not None and self._act is not None and not bind.is_bound(self._act):
+            self._act = self._act.to(self.device)
+            bind.bind(self._act)
+
+    def _sync_modules(self):
+        for name, bind in self._binds.items():
+            mod = getattr(self, name)
+            if not bind.is_bound(mod):
+                bind.bind(mod)
+
+    # ---- checkpoints ------------------------------------------------------------------------------------
+    def _optimizers(self) -> tuple:
+        return self.act_optimizer, self.cri_optimizer
+
+    def _checkpoint_extras(self, if_save: bool):
+        """what a subclass stamps onto its optimisers before a save / reads back after a load beyond `_step` and `rng_counter`"""
+
+    def save_or_load_agent(self, cwd: str, if_save: bool):
+        """AgentBase.save_or_load_agent; the optimisers carry their Adam step counts and the Philox counter, so a resumed agent
+        continues bit for bit"""
+        if if_save:
+            self._set_step_counts()
+            for opt in self._optimizers():
+                opt.rng_counter = self.rng_counter
+            self._checkpoint_extras(True)
+        super().save_or_load_agent(cwd, if_save)
+        if not if_save:
+            for opt in self._optimizers():
+                opt.exp_avg = opt.exp_avg.to(self.device, th.float32).contiguous()
+                opt.exp_avg_sq = opt.exp_avg_sq.to(self.device, th.float32).contiguous()
+            self._step = int(self.cri_optimizer.step_count)
+            self.rng_counter = int(getattr(self.act_optimizer, "rng_counter", self.rng_counter))
+            self._checkpoint_extras(False)
+            for name in self._binds:
+                if name != "_act" and getattr(self, name, None) is not None:
+                    setattr(self, name, getattr(self, name).to(self.device))
+            self._on_act_replaced()
+            self._sync_modules()
+
+    # ---- one step -----------------------------------------------------------------------------------------
+    def _per_step(self, buffer, objs_out: TEN, *args, uniform: Optional[TEN] = None, **kwargs):
+        """one step on a prioritised sample: importance weights into the critic objective, td errors back into the trees"""
+        *batch, is_weight, is_index = buffer.sample_for_per(self.batch_size) if uniform is None else buffer.sample_for_per(self.batch_size, uniform)
+        if self._td_error is None or self._td_error.numel() != is_weight.numel():
+            self._td_error = th.empty_like(is_weight)
+        self._update_on_batch(batch, objs_out, *args, is_weight=is_weight, td_error_out=self._td_error, buffer=buffer, **kwargs)
+        buffer.td_error_update_for_per(is_index, self._td_error)
+
+    @_hip.on_device
+    def update_objectives(self, buffer, update_t: int, ids: Optional[TEN] = None, noises=None) -> Tuple[float, float]:
+        """one step of the reference's `update_objectives`.  `ids` / `noises` inject the random draws."""
+        assert isinstance(update_t, int)
+        self._sync_modules()
+        kw = self._step_kwargs(buffer, update_t, noises)
+        if self.if_use_per:
+            self._per_step(buffer, self._objs, **kw)
+        else:
+            self._update_on_batch(buffer.sample(self.batch_size, ids=ids), self._objs, buffer=buffer, **kw)       # HIP K9
+        oc, oa = self._objs.cpu().tolist()
+        _hip.check_async_faults()          # the stream is drained: a skipped optimiser step (grid-wait timeout) raises here
+        return oc, oa
+
+    # ---- update_net: the decision ... ---------------------------------------------------------------------
+    def _ring_step_reason(self) -> Optional[str]:
+        """None when this agent's step can take the replay sample itself from the ring and the ids, else why it reads a finished batch"""
+        return None
+
+    def _per_route(self, buffer) -> tuple:
+        """(`per_path`, per_for_fused_loop's tuple or None) of a prioritised update_net; the default names no route and steps"""
+        return None, None
+
+    def _update_net_route(self, buffer) -> UpdateRoute:
+        """Which route `update_net(buffer)` takes and what `update_path` / `per_path` say about it.  Launches nothing: it reads the
+        agent's switches and asks the buffer what it offers (ring_for_fused_sample, per_for_fused_loop)."""
+        if self.if_use_per:
+            per_path, per = self._per_route(buffer)
+            return UpdateRoute("per_loop" if per else "per_step", "per step: " + self._per_why, per_path, per or None)
+        ring, why = None, self._ring_step_reason()
+        if why is None:
+            ring = (getattr(buffer, "ring_for_fused_sample", None) and buffer.ring_for_fused_sample(self.batch_size)) or None
+            why = self._ring_loop_reason(buffer, ring)
+        if why is None:
+            return UpdateRoute("ring_loop", self._ring_loop_path, None, ring)
+        return UpdateRoute("ring_step" if ring else "batch_step", "per step: " + why, None, ring)
+
+    # ---- ... and its execution ----------------------------------------------------------------------------
+    def _before_update_net(self, buffer):
+        """what a subclass does to the buffer ahead of the loop"""
+
+    @_hip.on_device
+    def update_net(self, buffer, per_uniform: Optional[TEN] = None) -> Tuple[float, float]:
+        """AgentBase.update_net (:172-189) with ONE host sync: the per-step objectives stay on the device until the end.  The route is
+        `_update_net_route`'s; `update_path` / `per_path` name it.
+        `per_uniform` (update_times, num_seqs, batch_size // num_seqs) in [0, 1) injects the prioritised sampler's random numbers (tests)."""
+        self._before_update_net(buffer)
+        self._sync_modules()
+        update_times = int(buffer.cur_size * self.repeat_times / self.batch_size)
+        if update_times < 1:
+            return 0.0, 0.0
+        objs = self.objs_all = th.zeros((update_times, 2), dtype=th.float32, device=self.device)
+        id_all = id_rows = None
+        if not self.if_use_per and self.sample_ids_ahead:
+            # the sample ids of ALL the steps in one th.randint (the reference draws batch_size of them per step, replay_buffer.py:121-122:
+            # same distribution, same generator, one launch instead of `update_times`; nothing is written to the buffer inside this loop)
+            id_all = th.randint((buffer.cur_size - 1) * buffer.num_seqs, size=(update_times, self.batch_size), requires_grad=False,
+                                device=self.device)
+            id_rows = id_all.unbind(0)
+        route, self.update_path, per_path, src = self._update_net_route(buffer)
+        if per_path is not None:
+            self.per_path = per_path
+        if route == "ring_loop":
+            self._update_ring_loop(buffer, src, id_all, objs)
+        elif route == "per_loop":
+            self._update_per_loop(buffer, src, objs, per_uniform)
+        else:
+            for t in range(update_times):
+                kw = self._step_kwargs(buffer, t)
+                if route == "per_step":
+                    self._per_step(buffer, objs[t], uniform=None if per_uniform is None else per_uniform[t], **kw)
+                elif route == "ring_step":
+                    self._update_from_ring(buffer, src, id_rows[t], objs[t], **kw)
+                else:       # (the batch is consumed before the next draw)
+                    self._update_on_batch(buffer.sample(self.batch_size, ids=None if id_rows is None else id_rows[t], reuse=True), objs[t],
+                                          buffer=buffer, **kw)
+        o = objs.cpu().numpy()
+        _hip.check_async_faults()          # the stream is drained: a skipped optimiser step (grid-wait timeout) raises here
+        oa = o[:, 1][~np.isnan(o[:, 1])]   # (steps whose actor update was skipped log nan, AgentBase.py:186-188)
+        return float(np.nanmean(o[:, 0])), float(oa.mean()) if oa.size else 0.0

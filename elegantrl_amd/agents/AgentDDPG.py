@@ -21,14 +21,12 @@ import os
 from copy import deepcopy
 from typing import List, Optional, Tuple
 
-import numpy as np
 import torch as th
 from torch import nn
 
 from .. import _hip
 from ..train.config import Config
-from .AgentBase import AgentBase, FlatNet, build_mlp, layer_init_with_orthogonal
-from .AgentSAC import _FlatAdamState, _Slices
+from .AgentBase import _FlatAdamState, _OffPolicyFlatAgent, build_mlp, layer_init_with_orthogonal
 
 TEN = th.Tensor
 
@@ -75,7 +73,7 @@ class Critic(CriticTwin):
         super().__init__(net_dims, state_dim, action_dim, num_ensembles=1)
 
 
-class AgentTD3(AgentBase):
+class AgentTD3(_OffPolicyFlatAgent):
     """Twin Delayed DDPG (AgentTD3.py:15-70): `num_ensembles` (8) heads on one critic trunk, target-policy smoothing with
     `policy_noise_std` (0.10), the actor and its target updated every `update_freq`-th (2) step, exploration noise `explore_noise_std`
     (0.05).  `update_path` / `rollout_path` name the route the last `update_net` / rollout took and, for a fallback, why."""
@@ -83,11 +81,12 @@ class AgentTD3(AgentBase):
     # default follows the A/B record (tools/td3_update_ab.py -> profiles/td3_update_ab.txt);
     # args.td3_loop_in_c / ERL_TD3_LOOP_IN_C override it
     _loop_in_c_default = "0"
+    _ring_loop_path = "one C call (erl_td3_update_ring_loop_f32: sample, step and the actor's delay rule per step inside the call)"
+    _per_why = "prioritised replay (a prioritised one-call loop is out of scope): sample_for_per, erl_td3_update_f32, tree update per step"
 
     def __init__(self, net_dims: List[int], state_dim: int, action_dim: int, gpu_id: int = 0, args: Config = None):
         args = Config() if args is None else args
         super().__init__(net_dims, state_dim, action_dim, gpu_id, args)
-        self.if_off_policy = True
         if self.if_discrete:
             raise NotImplementedError(f"{type(self).__name__} is a continuous-action agent")
         if self.lambda_fit_cum_r != 0:
@@ -96,8 +95,6 @@ class AgentTD3(AgentBase):
         from .. import ops
         self._read_args(args)
         self.td3_loop_in_c = bool(getattr(args, "td3_loop_in_c", os.environ.get("ERL_TD3_LOOP_IN_C", self._loop_in_c_default) != "0"))
-        self.update_path = None                    # which route the last update_net took: "one C call ..." / "per step: <reason>"
-        self.rollout_path = None                   # which route the last rollout took
         self._spec = ops.Td3Spec(state_dim, action_dim, net_dims, self.num_ensembles)
         dev, f32 = self.device, th.float32
         sp = self._spec
@@ -105,21 +102,15 @@ class AgentTD3(AgentBase):
         self._critic_flat = th.zeros(sp.critic_count, dtype=f32, device=dev)
         act = Actor(net_dims, state_dim, action_dim).to(dev)
         cri = self._make_critic(net_dims, state_dim, action_dim).to(dev)
-        self._bind_a = FlatNet(act, _Slices(sp.actor_slices()), self._actor_flat)
-        self._bind_c = FlatNet(cri, _Slices(sp.critic_slices()), self._critic_flat)
+        self._bind("_act", act, sp.actor_slices(), self._actor_flat)
+        self._bind("cri", cri, sp.critic_slices(), self._critic_flat)
         self._actor_target_flat = self._actor_flat.clone()
         self._critic_target_flat = self._critic_flat.clone()
-        act_target, cri_target = deepcopy(act), deepcopy(cri)
-        self._bind_at = FlatNet(act_target, _Slices(sp.actor_slices()), self._actor_target_flat)
-        self._bind_ct = FlatNet(cri_target, _Slices(sp.critic_slices()), self._critic_target_flat)
-        self._act, self.cri, self.act_target, self.cri_target = act, cri, act_target, cri_target
+        self._bind("act_target", deepcopy(act), sp.actor_slices(), self._actor_target_flat)
+        self._bind("cri_target", deepcopy(cri), sp.critic_slices(), self._critic_target_flat)
         self.act_optimizer = _FlatAdamState(sp.actor_count, self.learning_rate, dev)
         self.cri_optimizer = _FlatAdamState(sp.critic_count, self.learning_rate, dev)
-        self._step = 0                             # the critic optimiser's Adam step = update steps taken
-        self._actor_step = 0                       # the actor optimiser's own (it steps only when the actor is updated)
-        self._objs = th.zeros(2, dtype=f32, device=dev)
-        self.objs_all = None                       # (update_times, 2) device tensor: the last update_net's (obj_critic, obj_actor) per step
-        self._td_error = None
+        self._actor_step = 0                       # the actor optimiser's own Adam step (it steps only when the actor is updated)
         L = len(net_dims)
         self.kernel_path = (f"layered TD3 step (csrc/td3.hip: one MFMA GEMM launch per dense layer, {10 * L + 20} launches with the actor's "
                             f"update, {5 * L + 11} without)")
@@ -145,38 +136,10 @@ class AgentTD3(AgentBase):
     def _update_actor(self, buffer, update_t: int) -> bool:
         return self._actor_gate(buffer) and update_t % self.update_freq == 0              # AgentTD3.py:63
 
-    # ---- modules <-> flat blocks ------------------------------------------------------------------------
-    def _on_act_replaced(self):
-        if getattr(self, "_bind_a", None) is not None and self._act is not None and not self._bind_a.is_bound(self._act):
-            self._act = self._act.to(self.device)
-            self._bind_a.bind(self._act)
-
-    def _sync_modules(self):
-        for bind, mod in ((self._bind_a, self._act), (self._bind_c, self.cri), (self._bind_at, self.act_target),
-                          (self._bind_ct, self.cri_target)):
-            if not bind.is_bound(mod):
-                bind.bind(mod)
-
-    def save_or_load_agent(self, cwd: str, if_save: bool):
-        """AgentBase.save_or_load_agent (the reference's file set: act, act_target, act_optimizer, cri, cri_target, cri_optimizer); the
-        optimisers carry their Adam step counts and the Philox counter, so a resumed agent continues bit for bit"""
-        if if_save:
-            self._set_step_counts()
-            for opt in (self.act_optimizer, self.cri_optimizer):
-                opt.rng_counter = self.rng_counter
-        super().save_or_load_agent(cwd, if_save)
+    # ---- checkpoints (the reference's file set: act, act_target, act_optimizer, cri, cri_target, cri_optimizer) ---------------------
+    def _checkpoint_extras(self, if_save: bool):
         if not if_save:
-            for opt in (self.act_optimizer, self.cri_optimizer):
-                opt.exp_avg = opt.exp_avg.to(self.device, th.float32).contiguous()
-                opt.exp_avg_sq = opt.exp_avg_sq.to(self.device, th.float32).contiguous()
-            self._step = int(self.cri_optimizer.step_count)
             self._actor_step = int(self.act_optimizer.step_count)
-            self.rng_counter = int(getattr(self.act_optimizer, "rng_counter", self.rng_counter))
-            for name in ("cri", "cri_target", "act_target"):
-                if getattr(self, name, None) is not None:
-                    setattr(self, name, getattr(self, name).to(self.device))
-            self._on_act_replaced()
-            self._sync_modules()
 
     def _set_step_counts(self):
         """the optimisers' `step_count` (th.optim.Adam's own count, what a checkpoint stores)"""
@@ -228,7 +191,8 @@ class AgentTD3(AgentBase):
             self._actor_step += 1
         return dict(update_actor=update_actor, actor_step=self._actor_step, seed=self.rng_seed + 1, counter=self._step)
 
-    def _update_on_batch(self, batch, objs_out: TEN, update_actor: bool, noise=None, is_weight=None, td_error_out=None):
+    def _update_on_batch(self, batch, objs_out: TEN, update_actor: bool, noise=None, is_weight=None, td_error_out=None, buffer=None):
+        # (`buffer`: what the shared loop hands every step; nothing here reads it)
         from .. import ops
         kw = self._count_step(update_actor)
         ops.td3_update(*self._nets(), batch, self._step, **self._hyper(), objs_out=objs_out, noise=noise, is_weight=is_weight,
@@ -244,20 +208,12 @@ class AgentTD3(AgentBase):
         buffer.ids0, buffer.ids1 = stage.ids
         self._set_step_counts()
 
-    def _per_step(self, buffer, objs_out: TEN, update_actor: bool, noise=None, uniform: Optional[TEN] = None):
-        """one step on a prioritised sample: importance weights into the critic objective, td errors back into the trees"""
-        *batch, is_weight, is_index = buffer.sample_for_per(self.batch_size) if uniform is None else buffer.sample_for_per(self.batch_size, uniform)
-        if self._td_error is None or self._td_error.numel() != is_weight.numel():
-            self._td_error = th.empty_like(is_weight)
-        self._update_on_batch(batch, objs_out, update_actor, noise, is_weight=is_weight, td_error_out=self._td_error)
-        buffer.td_error_update_for_per(is_index, self._td_error)
-
-    def _update_ring_loop(self, buffer, ring, id_all: TEN, objs: TEN, gate: bool) -> str:
+    def _update_ring_loop(self, buffer, ring, id_all: TEN, objs: TEN):
         """update_net's whole loop from ONE C call: step t = what _update_from_ring(id_all[t]) enqueues, the delay rule decided on the
         host side of the loop in C; afterwards the counters are what the per-step route leaves"""
         from .. import ops
         arrays, sample_len, stage = ring
-        T = id_all.shape[0]
+        T, gate = id_all.shape[0], self._actor_gate(buffer)
         n_upd = ops.td3_update_ring_loop(*self._nets(), arrays, id_all, sample_len, stage, self._step + 1, self._actor_step, self.update_freq,
                                          gate, **self._hyper(), objs_all=objs, seed=self.rng_seed + 1, counter0=self._step + 1)
         assert n_upd == (len(range(0, T, self.update_freq)) if gate else 0), n_upd
@@ -265,66 +221,22 @@ class AgentTD3(AgentBase):
         self._actor_step += n_upd
         buffer.ids0, buffer.ids1 = stage.ids
         self._set_step_counts()
-        return "one C call (erl_td3_update_ring_loop_f32: sample, step and the actor's delay rule per step inside the call)"
+
+    def _step_kwargs(self, buffer, update_t: int, noise=None) -> dict:
+        return dict(update_actor=self._update_actor(buffer, update_t), noise=noise)
 
     @_hip.on_device
     def update_objectives(self, buffer, update_t: int, ids: Optional[TEN] = None, noise: Optional[TEN] = None) -> Tuple[float, float]:
         """one step (AgentTD3.py:34-70 / AgentBase.py:191-224).  `ids` / `noise` (batch_size, action_dim) inject the random draws."""
-        assert isinstance(update_t, int)
-        self._sync_modules()
-        upd = self._update_actor(buffer, update_t)
-        if self.if_use_per:
-            self._per_step(buffer, self._objs, upd, noise)
-        else:
-            self._update_on_batch(buffer.sample(self.batch_size, ids=ids), self._objs, upd, noise)
-        oc, oa = self._objs.cpu().tolist()
-        _hip.check_async_faults()
-        return oc, oa
+        return super().update_objectives(buffer, update_t, ids, noise)
 
-    @_hip.on_device
-    def update_net(self, buffer, per_uniform: Optional[TEN] = None) -> Tuple[float, float]:
-        """AgentBase.update_net (:172-189) with ONE host sync: the per-step objectives stay on the device until the end.  On the
-        interleaved ring with uniform sampling the whole loop is one C call when `td3_loop_in_c` is on, else one
-        erl_td3_update_ring_f32 call per step; prioritised replay samples first and runs erl_td3_update_f32 per step.
-        `per_uniform` (update_times, num_seqs, batch_size // num_seqs) in [0, 1) injects the prioritised sampler's draws (tests)."""
-        self._sync_modules()
-        update_times = int(buffer.cur_size * self.repeat_times / self.batch_size)
-        if update_times < 1:
-            return 0.0, 0.0
-        objs = self.objs_all = th.zeros((update_times, 2), dtype=th.float32, device=self.device)
-        gate = self._actor_gate(buffer)
-        ring, id_rows = None, None
-        if self.if_use_per:
-            why = "prioritised replay (a prioritised one-call loop is out of scope): sample_for_per, erl_td3_update_f32, tree update per step"
-        else:
-            # the sample ids of ALL the steps in one th.randint (the reference draws batch_size of them per step, replay_buffer.py:121-123:
-            # same distribution, same generator; nothing is written to the buffer inside this loop)
-            id_all = th.randint((buffer.cur_size - 1) * buffer.num_seqs, size=(update_times, self.batch_size), requires_grad=False,
-                                device=self.device)
-            id_rows = id_all.unbind(0)
-            ring = getattr(buffer, "ring_for_fused_sample", None) and buffer.ring_for_fused_sample(self.batch_size)
-            from ..ops import ReplayRing
-            why = (f"{type(buffer).__name__} offers no continuous-action ring of >= 2 rows" if not ring else
-                   "planar replay ring (args.replay_interleaved is off): erl_td3_update_ring_f32 per step" if not isinstance(ring[0], ReplayRing) else
-                   "args.td3_loop_in_c is off (ERL_TD3_LOOP_IN_C; profiles/td3_update_ab.txt): erl_td3_update_ring_f32 per step"
-                   if not self.td3_loop_in_c else None)
-        if why is None:
-            self.update_path = self._update_ring_loop(buffer, ring, id_all, objs, gate)
-            update_times = 0
-        else:
-            self.update_path = "per step: " + why
-        for t in range(update_times):
-            upd = self._update_actor(buffer, t)
-            if self.if_use_per:
-                self._per_step(buffer, objs[t], upd, uniform=None if per_uniform is None else per_uniform[t])
-            elif ring:
-                self._update_from_ring(buffer, ring, id_rows[t], objs[t], upd)
-            else:       # (the batch is consumed before the next draw)
-                self._update_on_batch(buffer.sample(self.batch_size, ids=id_rows[t], reuse=True), objs[t], upd)
-        o = objs.cpu().numpy()
-        _hip.check_async_faults()
-        oa = o[:, 1][~np.isnan(o[:, 1])]           # (steps whose actor update was skipped log nan, AgentBase.py:186-188)
-        return float(np.nanmean(o[:, 0])), float(oa.mean()) if oa.size else 0.0
+    def _ring_loop_reason(self, buffer, ring) -> Optional[str]:
+        """on the interleaved ring the whole loop is one C call when `td3_loop_in_c` is on, else one erl_td3_update_ring_f32 call per step"""
+        from ..ops import ReplayRing
+        return (f"{type(buffer).__name__} offers no continuous-action ring of >= 2 rows" if not ring else
+                "planar replay ring (args.replay_interleaved is off): erl_td3_update_ring_f32 per step" if not isinstance(ring[0], ReplayRing) else
+                "args.td3_loop_in_c is off (ERL_TD3_LOOP_IN_C; profiles/td3_update_ab.txt): erl_td3_update_ring_f32 per step"
+                if not self.td3_loop_in_c else None)
 
 
 class AgentDDPG(AgentTD3):

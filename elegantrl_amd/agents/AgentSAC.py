@@ -19,13 +19,13 @@ import os
 from copy import deepcopy
 from typing import List, Optional, Tuple
 
-import numpy as np
 import torch as th
 from torch import nn
 
 from .. import _hip
 from ..train.config import Config
-from .AgentBase import AgentBase, FlatNet, build_mlp, layer_init_with_orthogonal
+# (_FlatAdamState: checkpoints written before it moved pickle it under this module's path)
+from .AgentBase import _FlatAdamState, _OffPolicyFlatAgent, build_mlp, layer_init_with_orthogonal
 
 TEN = th.Tensor
 
@@ -118,34 +118,16 @@ class CriticEnsemble(nn.Module):
         return self.get_q_values(state, action).mean(dim=-1, keepdim=True)
 
 
-
-class _Slices:
-    def __init__(self, slices):
-        self._s = slices
-
-    def slices(self):
-        return self._s
-
-
-class _FlatAdamState:
-    """Adam moments of one parameter block as flat tensors (what `save_or_load_agent` stores for the optimisers)."""
-
-    def __init__(self, numel: int, lr: float, device):
-        self.exp_avg = th.zeros(numel, dtype=th.float32, device=device)
-        self.exp_avg_sq = th.zeros(numel, dtype=th.float32, device=device)
-        self.step_count = 0
-        self.param_groups = [{"lr": lr, "betas": (0.9, 0.999), "eps": 1e-8}]
-
-
-class AgentSAC(AgentBase):
+class AgentSAC(_OffPolicyFlatAgent):
     _actor_class = ActorSAC
     _actor_variant = _hip.SAC_ACTOR_SAC
     _default_ensembles = 4
+    _ring_loop_path = "one C call (erl_sac_update_ring_loop_f32: the sample inside every step's first launch)"
+    _per_why = "prioritised replay (per_path names its route)"
 
     def __init__(self, net_dims: List[int], state_dim: int, action_dim: int, gpu_id: int = 0, args: Config = None):
         args = Config() if args is None else args
         super().__init__(net_dims, state_dim, action_dim, gpu_id, args)
-        self.if_off_policy = True
         if self.if_discrete:
             raise NotImplementedError("SAC is a continuous-action agent")
         # (without a GPU the agent can still be constructed, to read `kernel_path`; it runs on the HIP kernels only and there is no CPU
@@ -170,9 +152,6 @@ class AgentSAC(AgentBase):
         # only; opt-in -- args.per_draw_in_step = True or ERL_SAC_PER_DRAW_IN_STEP=1 -- until profiles/sac_per_loop_ab.txt shows the win
         # DESIGN.md section 9 asks of a default
         self.per_draw_in_step = bool(getattr(args, "per_draw_in_step", os.environ.get("ERL_SAC_PER_DRAW_IN_STEP", "0") != "0"))
-        self.per_path = None                       # which route the last prioritised update_net took (None: none yet / not prioritised)
-        self.update_path = None                    # which route the last update_net took: "one C call ..." / "per step: <reason>"
-        self.rollout_path = None                   # which route the last _explore_vec_env took: "one launch ..." / "per-step loop ...: <reason>"
         self.fused_mod_rollout = False             # AgentModSAC's switch for the ActorFixSAC forms of the rollout launches (_variant_kernel_path)
         self._spec = ops.SacSpec(state_dim, action_dim, net_dims, self.num_ensembles, actor_variant=self._actor_variant)
         dev, f32 = self.device, th.float32
@@ -182,19 +161,14 @@ class AgentSAC(AgentBase):
         act = self._actor_class(net_dims, state_dim, action_dim).to(dev)
         cri = CriticEnsemble(net_dims, state_dim, action_dim, num_ensembles=self.num_ensembles).to(dev)
         cri_target = deepcopy(cri)
-        self._bind_a = FlatNet(act, _Slices(self._spec.actor_slices()), self._actor_flat)
-        self._bind_c = FlatNet(cri, _Slices(self._spec.critic_slices()), self._critic_flat)
-        self._bind_t = FlatNet(cri_target, _Slices(self._spec.critic_slices()), self._target_flat)
-        self._act, self.cri, self.cri_target = act, cri, cri_target
+        self._bind("_act", act, self._spec.actor_slices(), self._actor_flat)
+        self._bind("cri", cri, self._spec.critic_slices(), self._critic_flat)
+        self._bind("cri_target", cri_target, self._spec.critic_slices(), self._target_flat)
         self.act_optimizer = _FlatAdamState(self._spec.actor_count, self.learning_rate, dev)
         self.cri_optimizer = _FlatAdamState(self._spec.critic_count, self.learning_rate, dev)
         self.alpha_optim = _FlatAdamState(1, self.learning_rate, dev)
         self.alpha_log = th.full((1,), -1.0, dtype=f32, device=dev)
         self.target_entropy = math.log(action_dim)               # np.log(action_dim), as the reference (:31)
-        self._step = 0
-        self._objs = th.zeros(2, dtype=f32, device=dev)
-        self.objs_all = None                       # (update_times, 2) device tensor: the last update_net's (obj_critic, obj_actor) per step
-        self._td_error = None                      # per-sample td errors of a prioritised step (csrc/sac.hip critic_loss_kernel)
         self.save_attr_names = self.save_attr_names | {"alpha_log", "alpha_optim"}
         import ctypes as _ct
         hid = (_ct.c_int * len(net_dims))(*[int(h) for h in net_dims])
@@ -210,37 +184,14 @@ class AgentSAC(AgentBase):
         if not getattr(args, "quiet", False) and os.environ.get("ERL_QUIET", "0") == "0":
             print(f"| {type(self).__name__}: {self.kernel_path}", flush=True)
 
-    def _on_act_replaced(self):
-        if getattr(self, "_bind_a", None) is not None and self._act is not None and not self._bind_a.is_bound(self._act):
-            self._act = self._act.to(self.device)
-            self._bind_a.bind(self._act)
+    def _optimizers(self) -> tuple:
+        return self.act_optimizer, self.cri_optimizer, self.alpha_optim
 
-    def _sync_modules(self):
-        for bind, mod in ((self._bind_a, self._act), (self._bind_c, self.cri), (self._bind_t, self.cri_target)):
-            if not bind.is_bound(mod):
-                bind.bind(mod)
-
-    def save_or_load_agent(self, cwd: str, if_save: bool):
-        """AgentBase.save_or_load_agent plus what a resumed SAC run needs beyond the reference's file set: the temperature
-        and its optimiser state (`alpha_log`, `alpha_optim`), the Adam step (bias correction) and the Philox counters."""
-        if if_save:
-            for opt in (self.act_optimizer, self.cri_optimizer, self.alpha_optim):
-                opt.step_count = self._step
-                opt.rng_counter = self.rng_counter
-        super().save_or_load_agent(cwd, if_save)
+    def _checkpoint_extras(self, if_save: bool):
+        """beyond the reference's file set a resumed SAC run needs the temperature and its optimiser state (`alpha_log`, `alpha_optim`:
+        save_attr_names)"""
         if not if_save:
             self.alpha_log = self.alpha_log.to(self.device, th.float32).contiguous()
-            for opt in (self.act_optimizer, self.cri_optimizer, self.alpha_optim):
-                opt.exp_avg = opt.exp_avg.to(self.device, th.float32).contiguous()
-                opt.exp_avg_sq = opt.exp_avg_sq.to(self.device, th.float32).contiguous()
-            self._step = int(self.act_optimizer.step_count)
-            self.rng_counter = int(getattr(self.act_optimizer, "rng_counter", self.rng_counter))
-            if self.cri is not None:
-                self.cri = self.cri.to(self.device)
-            if self.cri_target is not None:
-                self.cri_target = self.cri_target.to(self.device)
-            self._on_act_replaced()
-            self._sync_modules()
 
     @_hip.on_device
     def _explore_vec_env(self, env, horizon_len: int, noise: Optional[TEN] = None) -> Tuple[TEN, ...]:
@@ -363,13 +314,25 @@ class AgentSAC(AgentBase):
         """why this agent class keeps a prioritised update_net on _per_step whatever the buffer offers (None: it does not)"""
         return None
 
-    def _ring_step_reason(self) -> Optional[str]:
-        """None when this agent's step takes the replay sample inside its first launch (the ring forms), else why not"""
+    def _variant_ring_step_reason(self) -> Optional[str]:
+        """None when this agent class's step takes the replay sample inside its first launch (the ring forms), else why not"""
         return "ActorFixSAC / two-time-scale options take the layered step, which reads a finished batch" if self._actor_variant else None
 
-    def _update_ring_loop(self, buffer, ring, id_all: TEN, objs: TEN) -> str:
+    def _ring_step_reason(self) -> Optional[str]:
+        # the sample rides in the step's first launch (erl_sac_update_ring_f32) where nothing needs ids0 / ids1 before the step
+        return ("args.sample_ids_ahead is off" if not self.sample_ids_ahead else
+                "args.sample_in_step is off" if not self.sample_in_step else
+                "lambda_fit_cum_r needs ids0 / ids1 on the host side of every step" if self.lambda_fit_cum_r else
+                self._variant_ring_step_reason())
+
+    def _ring_loop_reason(self, buffer, ring) -> Optional[str]:
+        if not ring:
+            return f"{type(buffer).__name__} offers no continuous-action ring of >= 2 rows for the sample inside the step"
+        return None if self.update_loop_in_c else "args.update_loop_in_c is off"
+
+    def _update_ring_loop(self, buffer, ring, id_all: TEN, objs: TEN):
         """update_net's whole loop from ONE C call (erl_sac_update_ring_loop_f32, round 6): step t = what _update_from_ring(id_all[t])
-        enqueues; returns the route's name"""
+        enqueues"""
         from .. import ops
         arrays, sample_len, stage = ring
         update_times = id_all.shape[0]
@@ -378,29 +341,35 @@ class AgentSAC(AgentBase):
         self._step += update_times
         buffer.ids0, buffer.ids1 = stage.ids
         self._set_step_counts()
-        return "one C call (erl_sac_update_ring_loop_f32: the sample inside every step's first launch)"
 
-    def _update_per_loop(self, buffer, per, objs: TEN, per_uniform: Optional[TEN]) -> str:
+    def _per_draw_why(self) -> Optional[str]:
+        """None when the prioritised loop's draw + gather ride in every step's first launch, else why they are a launch of their own"""
+        return self._per_draw_reason() if self.per_draw_in_step else "args.per_draw_in_step is off"
+
+    def _per_loop_path(self) -> str:
+        """`per_path` of the prioritised loop as one C call"""
+        draw_why = self._per_draw_why()
+        if draw_why is None:
+            return ("prioritised update loop in one C call (erl_sac_update_per_draw_loop_f32: draw + gather inside the step's first launch, "
+                    "tree update behind every step)")
+        return ("prioritised update loop in one C call (erl_sac_update_per_loop_f32: draw + gather, step, tree update per step)" +
+                (f"; args.per_draw_in_step ignored: {draw_why}" if self.per_draw_in_step else ""))
+
+    def _update_per_loop(self, buffer, per, objs: TEN, per_uniform: Optional[TEN]):
         """the prioritised loop from ONE C call (erl_sac_update_per_loop_f32): step t = what _per_step enqueues on uniforms[t].  The
         uniforms of ALL the steps in one th.rand (sample_for_per draws (num_seqs, batch_size // num_seqs) per step: same distribution,
-        same generator; the trees change inside the loop, the uniforms do not depend on them); returns the route's name"""
+        same generator; the trees change inside the loop, the uniforms do not depend on them)"""
         from .. import ops
         p_ring, trees, cur_size, cursor, per_alpha, per_beta, stage, per_stage = per
         update_times = objs.shape[0]
         per_uniform = self._per_uniforms(buffer, update_times, per_uniform)
-        draw_why = self._per_draw_reason() if self.per_draw_in_step else "args.per_draw_in_step is off"
-        loop = ops.sac_update_per_loop if draw_why else ops.sac_update_per_draw_loop
+        loop = ops.sac_update_per_loop if self._per_draw_why() else ops.sac_update_per_draw_loop
         loop(*self._nets(), p_ring, trees, per_uniform, cur_size, cursor, per_alpha, per_beta, stage, per_stage, self._step + 1, **self._hyper(),
              objs_all=objs, seed=self.rng_seed + 1, counter0=self._step + 1)
         self._step += update_times
         buffer.ids0, buffer.ids1 = stage.ids
         self._td_error = per_stage.td_error
         self._set_step_counts()
-        if draw_why is None:
-            return ("prioritised update loop in one C call (erl_sac_update_per_draw_loop_f32: draw + gather inside the step's first launch, "
-                    "tree update behind every step)")
-        return ("prioritised update loop in one C call (erl_sac_update_per_loop_f32: draw + gather, step, tree update per step)" +
-                (f"; args.per_draw_in_step ignored: {draw_why}" if self.per_draw_in_step else ""))
 
     def _per_uniforms(self, buffer, update_times: int, per_uniform: Optional[TEN]) -> TEN:
         """the prioritised sampler's uniforms of a whole loop, (update_times, num_seqs, batch_size // num_seqs), drawn here unless injected"""
@@ -431,30 +400,10 @@ class AgentSAC(AgentBase):
                        lambda_fit_cum_r=float(self.lambda_fit_cum_r or 0.0), **self._step_options(update_t))
         self._set_step_counts()
 
-    @_hip.on_device
-    def update_objectives(self, buffer, update_t: int, ids: Optional[TEN] = None,
-                          noises: Optional[Tuple[TEN, TEN]] = None) -> Tuple[float, float]:
-        """one SAC step (AgentSAC.py:42-86).  `ids` / `noises` = (eps for next_state, eps for state) inject the random draws."""
-        assert isinstance(update_t, int)
-        self._sync_modules()
-        if self.if_use_per:                                                               # AgentSAC.py:45-47, :60-62
-            self._per_step(buffer, self._objs, noises, update_t=update_t)
-        else:
-            batch = buffer.sample(self.batch_size, ids=ids)                               # HIP K9
-            self._update_on_batch(batch, self._objs, noises, buffer=buffer, update_t=update_t)
-        oc, oa = self._objs.cpu().tolist()
-        _hip.check_async_faults()          # the stream is drained: a skipped optimiser step (grid-wait timeout) raises here
-        return oc, oa
+    def _step_kwargs(self, buffer, update_t: int, noise=None) -> dict:
+        """`noise` = (eps for next_state, eps for state) injects the step's draws (AgentSAC.py:42-86)"""
+        return dict(noises=noise, update_t=update_t)
 
-    def _per_step(self, buffer, objs_out: TEN, noises=None, update_t: int = 0, uniform: Optional[TEN] = None):
-        """one step on a prioritised sample: importance weights into the critic objective, td errors back into the trees"""
-        *batch, is_weight, is_index = buffer.sample_for_per(self.batch_size) if uniform is None else buffer.sample_for_per(self.batch_size, uniform)
-        if self._td_error is None or self._td_error.numel() != is_weight.numel():
-            self._td_error = th.empty_like(is_weight)
-        self._update_on_batch(batch, objs_out, noises, is_weight=is_weight, td_error_out=self._td_error, buffer=buffer, update_t=update_t)
-        buffer.td_error_update_for_per(is_index, self._td_error)
-
-    @_hip.on_device
     def _per_loop_reason(self, buffer) -> Optional[str]:
         """None when a prioritised update_net runs as one C call, else why it takes one _per_step per step"""
         if not self.per_loop_in_c:
@@ -470,63 +419,17 @@ class AgentSAC(AgentBase):
             return f"{type(buffer).__name__} has no per_for_fused_loop"
         return None
 
-    @_hip.on_device
-    def update_net(self, buffer, per_uniform: Optional[TEN] = None) -> Tuple[float, float]:
-        """AgentBase.update_net (:172-189) with ONE host sync: the per-step objectives stay on the device until the end.
-        `per_uniform` (update_times, num_seqs, batch_size // num_seqs) in [0, 1) injects the prioritised sampler's random numbers (tests)."""
+    def _per_route(self, buffer) -> tuple:
+        why = self._per_loop_reason(buffer)
+        per = None if why else buffer.per_for_fused_loop(self.batch_size)
+        if per:
+            return self._per_loop_path(), per
+        return "prioritised update loop per step (_per_step: six host-driven calls): " + (
+            why or "the buffer is not an interleaved continuous-action ring of >= 2 rows, or batch_size is no multiple of num_seqs"), None
+
+    def _before_update_net(self, buffer):
         if self.lambda_fit_cum_r:                     # AgentBase.py:176-177 (bootstraps with the current actor: see get_cumulative_rewards)
             buffer.update_cum_rewards(get_cumulative_rewards=self.get_cumulative_rewards)
-        self._sync_modules()
-        update_times = int(buffer.cur_size * self.repeat_times / self.batch_size)
-        if update_times < 1:
-            return 0.0, 0.0
-        objs = self.objs_all = th.zeros((update_times, 2), dtype=th.float32, device=self.device)
-        id_rows = None
-        if not self.if_use_per and self.sample_ids_ahead:
-            # the sample ids of ALL the steps in one th.randint (the reference draws batch_size of them per step, replay_buffer.py:121-122:
-            # same distribution, same generator, one launch instead of `update_times`; nothing is written to the buffer inside this loop)
-            id_all = th.randint((buffer.cur_size - 1) * buffer.num_seqs, size=(update_times, self.batch_size), requires_grad=False,
-                                device=self.device)
-            id_rows = id_all.unbind(0)
-        # the sample rides in the step's first launch (erl_sac_update_ring_f32) where the buffer is the library's continuous-action ring and
-        # nothing needs ids0 / ids1 before the step
-        why = ("prioritised replay (per_path names its route)" if self.if_use_per else
-               "args.sample_ids_ahead is off" if id_rows is None else
-               "args.sample_in_step is off" if not self.sample_in_step else
-               "lambda_fit_cum_r needs ids0 / ids1 on the host side of every step" if self.lambda_fit_cum_r else self._ring_step_reason())
-        ring = None
-        if why is None:
-            ring = getattr(buffer, "ring_for_fused_sample", None) and buffer.ring_for_fused_sample(self.batch_size)
-            if not ring:
-                why = f"{type(buffer).__name__} offers no continuous-action ring of >= 2 rows for the sample inside the step"
-            elif not self.update_loop_in_c:
-                why = "args.update_loop_in_c is off"
-        if ring and self.update_loop_in_c:
-            self.update_path = self._update_ring_loop(buffer, ring, id_all, objs)
-            update_times = 0                              # (nothing left for the Python loop)
-        else:
-            self.update_path = "per step: " + why
-        if self.if_use_per:
-            why = self._per_loop_reason(buffer)
-            per = None if why else buffer.per_for_fused_loop(self.batch_size)
-            if per:
-                self.per_path = self._update_per_loop(buffer, per, objs, per_uniform)
-                update_times = 0
-            else:
-                self.per_path = "prioritised update loop per step (_per_step: six host-driven calls): " + (
-                    why or "the buffer is not an interleaved continuous-action ring of >= 2 rows, or batch_size is no multiple of num_seqs")
-        for t in range(update_times):
-            if self.if_use_per:
-                self._per_step(buffer, objs[t], update_t=t, uniform=None if per_uniform is None else per_uniform[t])
-            elif ring:
-                self._update_from_ring(buffer, ring, id_rows[t], objs[t], update_t=t)
-            else:       # (the batch is consumed before the next draw)
-                self._update_on_batch(buffer.sample(self.batch_size, ids=None if id_rows is None else id_rows[t], reuse=True), objs[t], buffer=buffer,
-                                      update_t=t)
-        o = objs.cpu().numpy()
-        _hip.check_async_faults()          # the stream is drained: a skipped optimiser step (grid-wait timeout) raises here
-        oa = o[:, 1][~np.isnan(o[:, 1])]   # (AgentModSAC: steps whose actor update was skipped log nan, AgentBase.py:186-188)
-        return float(np.nanmean(o[:, 0])), float(oa.mean()) if oa.size else 0.0
 
 
 class AgentModSAC(AgentSAC):
@@ -545,6 +448,7 @@ class AgentModSAC(AgentSAC):
     _actor_class = ActorFixSAC
     _actor_variant = _hip.SAC_ACTOR_FIX
     _default_ensembles = 8
+    _ring_loop_path = "one C call (erl_sac_update_mod_ring_loop_f32: the sample inside every step's first launch, the two-time-scale rule in C)"
     # the fused step against the layered one has no A/B record yet (tools/modsac_update_ab.py writes profiles/modsac_update_ab.txt): until
     # it has, the route is opt-in -- args.fused_step = True or ERL_FUSED_MODSAC_STEP=1
     _fused_step_default = "0"
@@ -562,18 +466,12 @@ class AgentModSAC(AgentSAC):
         self.update_a = 0                                        # actor updates of the current update_net loop (:111)
         self._actor_step = 0                                     # the actor optimiser's own Adam step (it steps only when updated)
         self._actor_target_flat = self._actor_flat.clone()
-        self.act_target = deepcopy(self._act)
-        self._bind_at = FlatNet(self.act_target, _Slices(self._spec.actor_slices()), self._actor_target_flat)
+        self._bind("act_target", deepcopy(self._act), self._spec.actor_slices(), self._actor_target_flat)
         self._last_actor_updated = True
         # a prioritised update_net as ONE C call (erl_sac_update_mod_per_loop_f32: the prioritised loop and the two-time-scale rule together,
         # bit-identical to _per_step on the fused step): opt-in -- args.mod_per_loop_in_c = True or ERL_SAC_MOD_PER_LOOP_IN_C=1 -- until
         # profiles/sac_per_loop_ab.txt shows the win DESIGN.md section 9 asks of a default; it needs the fused step (there is no layered form)
         self.mod_per_loop_in_c = bool(getattr(args, "mod_per_loop_in_c", os.environ.get("ERL_SAC_MOD_PER_LOOP_IN_C", "0") != "0"))
-
-    def _sync_modules(self):
-        super()._sync_modules()
-        if not self._bind_at.is_bound(self.act_target):
-            self._bind_at.bind(self.act_target)
 
     def _fused_step_reason(self, batch_size: Optional[int] = None) -> Optional[str]:
         """None when a step on `batch_size` rows runs the fused ModSAC step (erl_sac_update_mod_*), else why it is layered.  Asked per call:
@@ -609,7 +507,7 @@ class AgentModSAC(AgentSAC):
                            "per-step action on the tile kernel (erl_sac_explore_action_tile_f32)")
         return step + "; rollout: per-step loop: " + why
 
-    def _ring_step_reason(self) -> Optional[str]:
+    def _variant_ring_step_reason(self) -> Optional[str]:
         why = self._fused_step_reason()
         return None if why is None else "layered ModSAC step, which reads a finished batch: " + why
 
@@ -617,7 +515,7 @@ class AgentModSAC(AgentSAC):
         self.cri_optimizer.step_count = self.alpha_optim.step_count = self._step
         self.act_optimizer.step_count = self._actor_step         # (th.optim.Adam's own count: the actor steps only when it is updated)
 
-    def _update_ring_loop(self, buffer, ring, id_all: TEN, objs: TEN) -> str:
+    def _update_ring_loop(self, buffer, ring, id_all: TEN, objs: TEN):
         """update_net's whole loop from ONE C call (erl_sac_update_mod_ring_loop_f32): the two-time-scale rule is evaluated in C, exactly as
         _step_options does per step; afterwards the counters are what the per-step route would have left"""
         from .. import ops
@@ -629,7 +527,6 @@ class AgentModSAC(AgentSAC):
         self._count_loop(T, n_upd)
         buffer.ids0, buffer.ids1 = stage.ids
         self._set_step_counts()
-        return "one C call (erl_sac_update_mod_ring_loop_f32: the sample inside every step's first launch, the two-time-scale rule in C)"
 
     def _count_loop(self, T: int, n_upd: int):
         """the counters after a T-step loop in C that updated the actor n_upd times: the rule re-derived here as _step_options applies it
@@ -650,25 +547,27 @@ class AgentModSAC(AgentSAC):
         why = self._fused_step_reason()
         return None if why is None else "AgentModSAC's prioritised loop (erl_sac_update_mod_per_loop_f32) has no layered form: " + why
 
-    def _update_per_loop(self, buffer, per, objs: TEN, per_uniform: Optional[TEN]) -> str:
+    def _per_loop_path(self) -> str:
+        # (the step here is the fused one, _variant_per_loop_reason: per_draw_in_step is never ignored)
+        return ("prioritised update loop in one C call (erl_sac_update_mod_per_loop_f32: " +
+                ("draw + gather inside the step's first launch" if self.per_draw_in_step else "draw + gather, step") +
+                ", tree update behind every step, the two-time-scale rule in C)")
+
+    def _update_per_loop(self, buffer, per, objs: TEN, per_uniform: Optional[TEN]):
         """the prioritised loop from ONE C call (erl_sac_update_mod_per_loop_f32): step t = what _per_step enqueues on uniforms[t] with
         _step_options(t), the trees updated behind skipped actor steps too; afterwards the counters are what the per-step route leaves"""
         from .. import ops
         p_ring, trees, cur_size, cursor, per_alpha, per_beta, stage, per_stage = per
         T = objs.shape[0]
         per_uniform = self._per_uniforms(buffer, T, per_uniform)
-        draw = self.per_draw_in_step                            # (the step here is the fused one: _variant_per_loop_reason)
         n_upd = ops.sac_update_mod_per_loop(*self._nets(), p_ring, trees, per_uniform, cur_size, cursor, per_alpha, per_beta, stage, per_stage,
                                             self._step + 1, self._actor_step, float(self.critic_value), **self._hyper(), objs_all=objs,
-                                            actor_target=self._actor_target_flat, draw_in_step=draw, seed=self.rng_seed + 1,
+                                            actor_target=self._actor_target_flat, draw_in_step=self.per_draw_in_step, seed=self.rng_seed + 1,
                                             counter0=self._step + 1)
         self._count_loop(T, n_upd)
         buffer.ids0, buffer.ids1 = stage.ids
         self._td_error = per_stage.td_error
         self._set_step_counts()
-        return ("prioritised update loop in one C call (erl_sac_update_mod_per_loop_f32: " +
-                ("draw + gather inside the step's first launch" if draw else "draw + gather, step") +
-                ", tree update behind every step, the two-time-scale rule in C)")
 
     def _update_from_ring(self, buffer, ring, ids: TEN, objs_out: TEN, noises=None, update_t: int = 0):
         from .. import ops
@@ -699,12 +598,9 @@ class AgentModSAC(AgentSAC):
         else:
             super()._update_on_batch(batch, objs_out, noises, is_weight=is_weight, td_error_out=td_error_out, buffer=buffer, update_t=update_t)
 
-    def save_or_load_agent(self, cwd: str, if_save: bool):
-        if if_save:
-            self.act_optimizer.actor_step = self._actor_step
-        super().save_or_load_agent(cwd, if_save)
-        if not if_save:
+    def _checkpoint_extras(self, if_save: bool):
+        super()._checkpoint_extras(if_save)
+        if if_save:      # the file keeps its layout: the actor optimiser's own count beside the update step
+            self.act_optimizer.actor_step, self.act_optimizer.step_count = self._actor_step, self._step
+        else:
             self._actor_step = int(getattr(self.act_optimizer, "actor_step", self._step))
-            if getattr(self, "act_target", None) is not None:
-                self.act_target = self.act_target.to(self.device)
-            self._sync_modules()

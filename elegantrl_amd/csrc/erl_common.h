@@ -168,6 +168,38 @@ static inline int erl_hip_status(hipError_t e, const char *what)
 
 #define ERL_LAUNCH_CHECK(what) return erl_hip_status(hipGetLastError(), what)
 
+// ---- the replay ring of an update entry that samples (ErlRingSample; sac.hip and td3.hip: one rule, so their validators cannot drift) ----
+// what such an entry refuses about its ring before its first launch, under the entry's own name; need_ids: the entry reads ring->ids
+// itself (a loop patches them in per step)
+static inline int erl_ring_refusals(const char *what, const ErlRingSample *ring, bool need_ids, int S, int A)
+{
+    ERL_REQUIRE(ring && ring->buf_states && (!need_ids || ring->ids) &&
+                    (ring->row_floats || (ring->buf_actions && ring->buf_rewards && ring->buf_undones && ring->buf_unmasks)),
+                "%s: NULL ring tensor", what);
+    ERL_REQUIRE(ring->row_floats == 0 || (ring->row_floats == erl_replay_row_floats(S, A) && ring->sample_len < ring->max_size &&
+                                          (reinterpret_cast<uintptr_t>(ring->buf_states) & 15) == 0),
+                "%s: interleaved ring with row_floats=%lld (expected %lld), sample_len=%lld", what, (long long)ring->row_floats,
+                (long long)erl_replay_row_floats(S, A), (long long)ring->sample_len);
+    ERL_REQUIRE(ring->num_seqs >= 1 && ring->sample_len >= 1 && ring->sample_len <= ring->max_size,
+                "%s: bad ring shape max_size=%lld num_seqs=%lld sample_len=%lld", what, (long long)ring->max_size, (long long)ring->num_seqs,
+                (long long)ring->sample_len);
+    return ERL_OK;
+}
+
+// ReplayBuffer.sample(ring->ids) as a launch of its own, into the batch pointers of a step that reads a finished batch: the interleaved
+// block or the five planar arrays
+static inline int erl_ring_sample_enqueue(const ErlRingSample *r, int S, int A, int64_t B, const float *state, const float *action,
+                                          const float *reward, const float *undone, const float *unmask, const float *next_state, void *stream)
+{
+    float *const o[6] = {const_cast<float *>(state), const_cast<float *>(action), const_cast<float *>(reward),
+                         const_cast<float *>(undone), const_cast<float *>(unmask), const_cast<float *>(next_state)};
+    return r->row_floats ? erl_replay_sample_rows_f32(r->buf_states, r->max_size, r->num_seqs, S, A, r->ids, B, r->sample_len, o[0], o[1], o[2],
+                                                      o[3], o[4], o[5], r->out_ids0, r->out_ids1, stream)
+                         : erl_replay_sample_f32(r->buf_states, r->buf_actions, r->buf_rewards, r->buf_undones, r->buf_unmasks, r->max_size,
+                                                 r->num_seqs, S, A, r->ids, B, r->sample_len, o[0], o[1], o[2], o[3], o[4], o[5], r->out_ids0,
+                                                 r->out_ids1, stream);
+}
+
 // ---------------------------------------------------------------------------------------------
 // measurement hook (api.cpp; include/erl_hip.h erl_kernel_span_*): a kernel's own duration on the device's constant-rate clock, first
 // workgroup in to last workgroup out -- what rocprofv3's kernel duration measures, available to bench.py in the loop without a

@@ -411,4 +411,20 @@ int backward(hipStream_t s, const NetDims &nd, const float *P, int64_t rows, flo
     return 0;
 }
 
+// ---- the tail of an off-policy step on flat blocks (sac.hip, td3.hip) ----
+// AgentBase.soft_update over a whole block
+__global__ __launch_bounds__(256) void soft_update_kernel(float *__restrict__ tar, const float *__restrict__ cur, float tau, int64_t n)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        tar[i] = erl_soft_update(cur[i], tar[i], tau);
+}
+
+// clip + Adam (erl_clip_adam_f32, optim.hip) on one whole block as one group
+inline int clip_adam_block(float *params, const float *grads, float *m, float *v, int64_t count, int32_t step, float lr, float beta1, float beta2,
+                           float eps, float max_norm, void *stream)
+{
+    const int64_t off = 0;
+    return erl_clip_adam_f32(params, grads, m, v, &off, &count, 1, nullptr, step, lr, beta1, beta2, eps, max_norm, 1.0f, stream);
+}
+
 }  // namespace

@@ -19,10 +19,6 @@
 #include "eval_ws.h"
 #include "per_draw.h"        // per_newest: the fill state a draw inside the step needs, as erl_per_sample_rows_f32 derives it
 
-extern "C" int erl_clip_adam_f32(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, const int64_t *group_off,
-                                 const int64_t *group_len, int n_groups, const int32_t *step_base, int32_t step_offset, float lr,
-                                 float beta1, float beta2, float eps, float max_norm, float grad_scale, void *stream);
-
 namespace {
 
 constexpr int MAXE = 16;
@@ -250,12 +246,6 @@ __global__ __launch_bounds__(256) void actor_obj_kernel(const float *__restrict_
     if (threadIdx.x == 0) out[0] = tq / ((float)E * (float)B) - expf(alpha_log[0]) * (tl / (float)B);
 }
 
-__global__ __launch_bounds__(256) void soft_update_kernel(float *__restrict__ tar, const float *__restrict__ cur, float tau, int64_t n)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        tar[i] = erl_soft_update(cur[i], tar[i], tau);
-}
-
 __global__ void clamp_alpha_kernel(float *alpha_log)
 {
     if (threadIdx.x == 0 && blockIdx.x == 0) alpha_log[0] = fminf(fmaxf(alpha_log[0], -16.f), 2.f);
@@ -433,18 +423,8 @@ int sac_step_layered(const SacCall &c, const SacDims &d, const SacStep &st)
     const int64_t B = c.B;
     hipStream_t s = (hipStream_t)c.stream;
     int rc;
-    if (const ErlRingSample *r = st.ring) {        // the layered step reads a finished batch: the sample as a launch of its own
-        rc = r->row_floats
-                 ? erl_replay_sample_rows_f32(r->buf_states, r->max_size, r->num_seqs, S, A, r->ids, B, r->sample_len,
-                                              const_cast<float *>(c.state), const_cast<float *>(c.action), const_cast<float *>(c.reward),
-                                              const_cast<float *>(c.undone), const_cast<float *>(c.unmask), const_cast<float *>(c.next_state),
-                                              r->out_ids0, r->out_ids1, c.stream)
-                 : erl_replay_sample_f32(r->buf_states, r->buf_actions, r->buf_rewards, r->buf_undones, r->buf_unmasks, r->max_size, r->num_seqs, S,
-                                   A, r->ids, B, r->sample_len, const_cast<float *>(c.state), const_cast<float *>(c.action),
-                                   const_cast<float *>(c.reward), const_cast<float *>(c.undone), const_cast<float *>(c.unmask),
-                                   const_cast<float *>(c.next_state), r->out_ids0, r->out_ids1, c.stream);
-        if (rc) return rc;
-    }
+    // the layered step reads a finished batch: the sample as a launch of its own
+    if (st.ring && (rc = erl_ring_sample_enqueue(st.ring, S, A, B, c.state, c.action, c.reward, c.undone, c.unmask, c.next_state, c.stream))) return rc;
 
     Ws ws{(char *)c.workspace, 0, c.workspace_bytes};
     int maxd = S + A;
@@ -506,12 +486,8 @@ int sac_step_layered(const SacCall &c, const SacDims &d, const SacStep &st)
         float *ea[2] = {xa, cw.enc};
         if ((rc = backward(s, d.enc, c.critic, B, ea, nullptr, dEnc, g_critic, cs_scr, nullptr, false, tmpA, tmpB))) return rc;
     }
-    {
-        const int64_t off = 0, len = d.Pc;
-        if ((rc = erl_clip_adam_f32(c.critic, g_critic, c.critic_m, c.critic_v, &off, &len, 1, nullptr, st.step, c.lr, c.beta1, c.beta2, c.eps_adam,
-                                    c.max_norm, 1.0f, c.stream)))
-            return rc;
-    }
+    if ((rc = clip_adam_block(c.critic, g_critic, c.critic_m, c.critic_v, d.Pc, st.step, c.lr, c.beta1, c.beta2, c.eps_adam, c.max_norm, c.stream)))
+        return rc;
     hipLaunchKernelGGL(soft_update_kernel, dim3(grid1d(d.Pc)), blk, 0, s, c.target, c.critic, c.tau, d.Pc);
 
     // ---- (3) policy-gradient sample, temperature step                                              (:72-81)
@@ -551,12 +527,8 @@ int sac_step_layered(const SacCall &c, const SacDims &d, const SacStep &st)
     hipLaunchKernelGGL(head_backward_kernel, rows_grid, blk, 0, s, aact[d.actor.n], act_t, eps_used, dxa + S, S + A, c.alpha_log, A, B, dHead, c.variant);
     hipLaunchKernelGGL(clamp_alpha_kernel, dim3(1), dim3(64), 0, s, c.alpha_log);                  // after alpha was read (:80-81)
     if ((rc = backward(s, d.actor, c.actor, B, aact, agd, dHead, g_actor, cs_scr, nullptr, false, tmpA, tmpB))) return rc;
-    {
-        const int64_t off = 0, len = d.Pa;
-        if ((rc = erl_clip_adam_f32(c.actor, g_actor, c.actor_m, c.actor_v, &off, &len, 1, nullptr, st.actor_step, c.lr, c.beta1, c.beta2, c.eps_adam,
-                                    c.max_norm, 1.0f, c.stream)))
-            return rc;
-    }
+    if ((rc = clip_adam_block(c.actor, g_actor, c.actor_m, c.actor_v, d.Pa, st.actor_step, c.lr, c.beta1, c.beta2, c.eps_adam, c.max_norm, c.stream)))
+        return rc;
     if (c.actor_target)      // AgentModSAC: soft_update(act_target, act, tau) after the actor's step (AgentSAC.py:156)
         hipLaunchKernelGGL(soft_update_kernel, dim3(grid1d(d.Pa)), blk, 0, s, c.actor_target, c.actor, c.tau, d.Pa);
     ERL_LAUNCH_CHECK("erl_sac_update_f32");
@@ -582,17 +554,7 @@ int sac_validate(const char *what, const SacCall &c, const SacStep &st, bool sam
     const int64_t need = erl_sac_workspace_bytes(c.S, c.A, c.hidden, c.n_hidden, c.E, c.B);
     ERL_REQUIRE(c.workspace_bytes >= need, "%s: workspace too small (%lld bytes, erl_sac_workspace_bytes = %lld)", what, (long long)c.workspace_bytes,
                 (long long)need);
-    if (!sample) return ERL_OK;
-    const ErlRingSample *ring = st.ring;
-    ERL_REQUIRE(ring && ring->buf_states && (!need_ids || ring->ids) && (ring->row_floats || (ring->buf_actions && ring->buf_rewards && ring->buf_undones && ring->buf_unmasks)),
-                "%s: NULL ring tensor", what);
-    ERL_REQUIRE(ring->row_floats == 0 || (ring->row_floats == erl_replay_row_floats(c.S, c.A) && ring->sample_len < ring->max_size &&
-                                       (reinterpret_cast<uintptr_t>(ring->buf_states) & 15) == 0),
-                "%s: interleaved ring with row_floats=%lld (expected %lld), sample_len=%lld", what, (long long)ring->row_floats,
-                (long long)erl_replay_row_floats(c.S, c.A), (long long)ring->sample_len);
-    ERL_REQUIRE(ring->num_seqs >= 1 && ring->sample_len >= 1 && ring->sample_len <= ring->max_size, "%s: bad ring shape max_size=%lld num_seqs=%lld sample_len=%lld",
-                what, (long long)ring->max_size, (long long)ring->num_seqs, (long long)ring->sample_len);
-    return ERL_OK;
+    return sample ? erl_ring_refusals(what, st.ring, need_ids, c.S, c.A) : ERL_OK;
 }
 
 // One validated step.  Off-policy batch sizes with two hidden layers up to 256 wide (config 3): the fused step, 12 launches

@@ -26,10 +26,6 @@
 
 #include "mlpn_common.h"
 
-extern "C" int erl_clip_adam_f32(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, const int64_t *group_off,
-                                 const int64_t *group_len, int n_groups, const int32_t *step_base, int32_t step_offset, float lr,
-                                 float beta1, float beta2, float eps, float max_norm, float grad_scale, void *stream);
-
 namespace {
 
 constexpr int TD3_MAXE = 8;
@@ -179,12 +175,6 @@ __global__ __launch_bounds__(256) void td3_tanh_backward_kernel(const float *__r
     }
 }
 
-__global__ __launch_bounds__(256) void td3_soft_update_kernel(float *__restrict__ tar, const float *__restrict__ cur, float tau, int64_t n)
-{
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        tar[i] = erl_soft_update(cur[i], tar[i], tau);
-}
-
 __global__ void td3_set_kernel(float *p, float v)
 {
     if (threadIdx.x == 0 && blockIdx.x == 0) p[0] = v;
@@ -248,19 +238,7 @@ int td3_validate(const char *what, const Td3Call &c, const Td3Step &st, bool sam
     const int64_t need = td3_ws_floats(*d, c.B) * 4 + 8192;
     ERL_REQUIRE(c.workspace_bytes >= need, "%s: workspace too small (%lld bytes, erl_td3_workspace_bytes = %lld)", what,
                 (long long)c.workspace_bytes, (long long)need);
-    if (!sample) return ERL_OK;
-    const ErlRingSample *ring = st.ring;
-    ERL_REQUIRE(ring && ring->buf_states && (!need_ids || ring->ids) &&
-                    (ring->row_floats || (ring->buf_actions && ring->buf_rewards && ring->buf_undones && ring->buf_unmasks)),
-                "%s: NULL ring tensor", what);
-    ERL_REQUIRE(ring->row_floats == 0 || (ring->row_floats == erl_replay_row_floats(c.S, c.A) && ring->sample_len < ring->max_size &&
-                                          (reinterpret_cast<uintptr_t>(ring->buf_states) & 15) == 0),
-                "%s: interleaved ring with row_floats=%lld (expected %lld), sample_len=%lld", what, (long long)ring->row_floats,
-                (long long)erl_replay_row_floats(c.S, c.A), (long long)ring->sample_len);
-    ERL_REQUIRE(ring->num_seqs >= 1 && ring->sample_len >= 1 && ring->sample_len <= ring->max_size,
-                "%s: bad ring shape max_size=%lld num_seqs=%lld sample_len=%lld", what, (long long)ring->max_size, (long long)ring->num_seqs,
-                (long long)ring->sample_len);
-    return ERL_OK;
+    return sample ? erl_ring_refusals(what, st.ring, need_ids, c.S, c.A) : ERL_OK;
 }
 
 // One validated step: 10 L + 20 launches when the actor is updated, 5 L + 11 when it is skipped (L hidden layers; + 1 with a ring; each
@@ -271,18 +249,7 @@ int td3_step(const char *what, const Td3Call &c, const Td3Dims &d, const Td3Step
     const int64_t B = c.B;
     hipStream_t s = (hipStream_t)c.stream;
     int rc;
-    if (const ErlRingSample *r = st.ring) {
-        rc = r->row_floats
-                 ? erl_replay_sample_rows_f32(r->buf_states, r->max_size, r->num_seqs, S, A, r->ids, B, r->sample_len,
-                                              const_cast<float *>(c.state), const_cast<float *>(c.action), const_cast<float *>(c.reward),
-                                              const_cast<float *>(c.undone), const_cast<float *>(c.unmask), const_cast<float *>(c.next_state),
-                                              r->out_ids0, r->out_ids1, c.stream)
-                 : erl_replay_sample_f32(r->buf_states, r->buf_actions, r->buf_rewards, r->buf_undones, r->buf_unmasks, r->max_size,
-                                         r->num_seqs, S, A, r->ids, B, r->sample_len, const_cast<float *>(c.state),
-                                         const_cast<float *>(c.action), const_cast<float *>(c.reward), const_cast<float *>(c.undone),
-                                         const_cast<float *>(c.unmask), const_cast<float *>(c.next_state), r->out_ids0, r->out_ids1, c.stream);
-        if (rc) return rc;
-    }
+    if (st.ring && (rc = erl_ring_sample_enqueue(st.ring, S, A, B, c.state, c.action, c.reward, c.undone, c.unmask, c.next_state, c.stream))) return rc;
 
     Ws ws{(char *)c.workspace, 0, c.workspace_bytes};
     const int maxd = td3_maxd(d);
@@ -322,13 +289,10 @@ int td3_step(const char *what, const Td3Call &c, const Td3Dims &d, const Td3Step
                        c.crit_kind, c.crit_beta);
     hipLaunchKernelGGL(td3_fold_kernel, dim3(1), blk, 0, s, part, (int64_t)nparts, 1.0f / (float)B, st.objs_out);
     if ((rc = backward(s, d.critic, c.critic, B, cact, cgd, dq, g_critic, cs_scr, nullptr, false, tmpA, tmpB))) return rc;
-    {
-        const int64_t off = 0, len = d.critic.count;
-        if ((rc = erl_clip_adam_f32(c.critic, g_critic, c.critic_m, c.critic_v, &off, &len, 1, nullptr, st.step, c.lr, c.beta1, c.beta2,
-                                    c.eps_adam, c.max_norm, 1.0f, c.stream)))
-            return rc;
-    }
-    hipLaunchKernelGGL(td3_soft_update_kernel, dim3(grid1d(d.critic.count)), blk, 0, s, c.critic_target, c.critic, c.tau, d.critic.count);
+    if ((rc = clip_adam_block(c.critic, g_critic, c.critic_m, c.critic_v, d.critic.count, st.step, c.lr, c.beta1, c.beta2, c.eps_adam, c.max_norm,
+                              c.stream)))
+        return rc;
+    hipLaunchKernelGGL(soft_update_kernel, dim3(grid1d(d.critic.count)), blk, 0, s, c.critic_target, c.critic, c.tau, d.critic.count);
 
     if (!st.update_actor) {                                          // (:68-69) obj_actor = nan; actor, target and moments untouched
         hipLaunchKernelGGL(td3_set_kernel, dim3(1), dim3(64), 0, s, st.objs_out + 1, __builtin_nanf(""));
@@ -345,13 +309,10 @@ int td3_step(const char *what, const Td3Call &c, const Td3Dims &d, const Td3Step
     if ((rc = backward(s, d.critic, c.critic, B, cact, cgd, dq, nullptr, cs_scr, dxa, false, tmpA, tmpB))) return rc;   // dL/d[state | action]
     hipLaunchKernelGGL(td3_tanh_backward_kernel, dim3(grid1d(B * A)), blk, 0, s, dxa, xa, S, A, B, dY);
     if ((rc = backward(s, d.actor, c.actor, B, aact, agd, dY, g_actor, cs_scr, nullptr, false, tmpA, tmpB))) return rc;
-    {
-        const int64_t off = 0, len = d.actor.count;
-        if ((rc = erl_clip_adam_f32(c.actor, g_actor, c.actor_m, c.actor_v, &off, &len, 1, nullptr, st.actor_step, c.lr, c.beta1, c.beta2,
-                                    c.eps_adam, c.max_norm, 1.0f, c.stream)))
-            return rc;
-    }
-    hipLaunchKernelGGL(td3_soft_update_kernel, dim3(grid1d(d.actor.count)), blk, 0, s, c.actor_target, c.actor, c.tau, d.actor.count);
+    if ((rc = clip_adam_block(c.actor, g_actor, c.actor_m, c.actor_v, d.actor.count, st.actor_step, c.lr, c.beta1, c.beta2, c.eps_adam,
+                              c.max_norm, c.stream)))
+        return rc;
+    hipLaunchKernelGGL(soft_update_kernel, dim3(grid1d(d.actor.count)), blk, 0, s, c.actor_target, c.actor, c.tau, d.actor.count);
     ERL_LAUNCH_CHECK(what);
 }
 

@@ -682,19 +682,32 @@ def ppo_update_discrete(flat_params: TEN, exp_avg: TEN, exp_avg_sq: TEN, act_avg
 # ------------------------------------------------------------------------------------------------
 # SAC (erl_sac_*)
 # ------------------------------------------------------------------------------------------------
-class SacSpec:
+class _OffPolicySpec:
+    """shapes of an off-policy agent's actor and critic as flat fp32 blocks (include/erl_hip.h): the two block sizes and the step's
+    workspace, asked of the library through the subclass's two symbols; the slice tables stay with each subclass"""
+    _param_counts = _workspace_bytes = ""
+
+    def __init__(self, S: int, A: int, hidden: Sequence[int], num_ensembles: int):
+        self.S, self.A, self.hidden, self.E = int(S), int(A), [int(h) for h in hidden], int(num_ensembles)
+        self._c = (ctypes.c_int * len(self.hidden))(*self.hidden)
+        pa, pc = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(getattr(lib(), self._param_counts)(self.S, self.A, self._c, len(self.hidden), self.E, ctypes.byref(pa), ctypes.byref(pc)),
+              self._param_counts)
+        self.actor_count, self.critic_count = pa.value, pc.value
+
+    def workspace_bytes(self, B: int) -> int:
+        return getattr(lib(), self._workspace_bytes)(self.S, self.A, self._c, len(self.hidden), self.E, B)
+
+
+class SacSpec(_OffPolicySpec):
     """shapes of ActorSAC / CriticEnsemble as flat fp32 blocks (include/erl_hip.h)."""
+    _param_counts, _workspace_bytes = "erl_sac_param_counts", "erl_sac_workspace_bytes"
 
     def __init__(self, S: int, A: int, hidden: Sequence[int], num_ensembles: int, actor_variant: int = 0):
         """actor_variant: _hip.SAC_ACTOR_SAC (ActorSAC) or _hip.SAC_ACTOR_FIX (AgentModSAC's ActorFixSAC: same block sizes, a raw last
         encoder layer and the two one-layer decoders as the two row halves of the head)"""
-        self.S, self.A, self.hidden, self.E = int(S), int(A), [int(h) for h in hidden], int(num_ensembles)
+        super().__init__(S, A, hidden, num_ensembles)
         self.actor_variant = int(actor_variant)
-        self._c = (ctypes.c_int * len(self.hidden))(*self.hidden)
-        pa, pc = ctypes.c_int64(0), ctypes.c_int64(0)
-        check(lib().erl_sac_param_counts(self.S, self.A, self._c, len(self.hidden), self.E, ctypes.byref(pa), ctypes.byref(pc)),
-              "erl_sac_param_counts")
-        self.actor_count, self.critic_count = pa.value, pc.value
 
     def actor_slices(self):
         """(parameter name in ActorSAC, offset, shape) in flat order."""
@@ -724,9 +737,6 @@ class SacSpec:
                 o += b * a + b
         return out
 
-    def workspace_bytes(self, B: int) -> int:
-        return lib().erl_sac_workspace_bytes(self.S, self.A, self._c, len(self.hidden), self.E, B)
-
 
 class _SacOptions(ctypes.Structure):        # include/erl_hip.h ErlSacOptions
     _fields_ = [("actor_variant", ctypes.c_int32), ("update_actor", ctypes.c_int32), ("actor_step", ctypes.c_int32),
@@ -747,7 +757,7 @@ class _PerSample(ctypes.Structure):         # include/erl_hip.h ErlPerSample
 
 
 # The erl_sac_update_* entries name the same arguments in the same order (_hip._SAC_HEAD / _SAC_BATCH / _SAC_KEY / _SAC_HYPER / _SAC_TAIL);
-# the wrappers below put them together from these pieces.
+# the wrappers below put them together from these pieces.  The erl_td3_update_* entries share the batch, the stage, the ring and the tail.
 _U64 = 2 ** 64 - 1
 
 
@@ -758,11 +768,11 @@ def _sac_head(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TE
             spec.S, spec.A, spec._c, len(spec.hidden), spec.E)
 
 
-def _sac_batch(batch: Sequence[TEN]) -> tuple:
+def _batch_ptrs(batch: Sequence[TEN]) -> tuple:
     return tuple(ptr(t, th.float32) for t in batch)
 
 
-def _sac_stage(stage: ReplayStage) -> tuple:
+def _stage_ptrs(stage: ReplayStage) -> tuple:
     """the staging block a ring entry's sample fills, as the batch pointers"""
     return stage.p_state, stage.p_action, stage.p_reward, stage.p_undone, stage.p_unmask, stage.p_next
 
@@ -772,12 +782,13 @@ def _sac_hyper(seed: int, counter: int, gamma, target_entropy, tau, lr, betas, e
     return seed & _U64, counter & _U64, gamma, target_entropy, tau, lr, betas[0], betas[1], eps, max_norm
 
 
-def _sac_tail(spec: SacSpec, device: th.device, B: int) -> tuple:
+def _call_tail(spec: _OffPolicySpec, device: th.device, B: int) -> tuple:
+    """workspace, its size, the stream"""
     ws = _workspace(device, spec.workspace_bytes(B))
     return ptr(ws), ws.numel(), stream_ptr()
 
 
-def _ring_sample(spec: SacSpec, ring, ids: Optional[TEN], sample_len: int, stage: ReplayStage, B: int):
+def _ring_sample(spec: _OffPolicySpec, ring, ids: Optional[TEN], sample_len: int, stage: ReplayStage, B: int):
     """(ErlRingSample, device) of a ReplayRing (interleaved block) or of the five planar tensors"""
     f32 = th.float32
     if isinstance(ring, ReplayRing):
@@ -801,10 +812,10 @@ def sac_update(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: T
     `cum_reward` (B,) + `lambda_fit_cum_r`: the critic's fit-the-batch's-mean-return term (AgentSAC.py:66-68)."""
     B = batch[0].shape[0]
     n_next, n_cur = (None, None) if noises is None else noises
-    args = (*_sac_head(spec, actor, critic, target, alpha_log, moments), *_sac_batch(batch), ptr(is_weight), ptr(td_error_out), ptr(cum_reward),
+    args = (*_sac_head(spec, actor, critic, target, alpha_log, moments), *_batch_ptrs(batch), ptr(is_weight), ptr(td_error_out), ptr(cum_reward),
             float(lambda_fit_cum_r), B, ptr(n_next), ptr(n_cur), *_sac_hyper(seed, counter, gamma, target_entropy, tau, lr, betas, eps, max_norm),
             step, ptr(objs_out, th.float32))
-    ws, ws_bytes, stream = _sac_tail(spec, batch[0].device, B)
+    ws, ws_bytes, stream = _call_tail(spec, batch[0].device, B)
     if spec.actor_variant or not update_actor or actor_step or actor_target is not None:
         # AgentModSAC's step (include/erl_hip.h, ErlSacOptions): ActorFixSAC's head, the actor skipped by the two-time-scale rule, the
         # actor optimiser's own step count, the actor target's soft update
@@ -823,9 +834,9 @@ def sac_update_from_ring(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, al
     B = ids.numel()
     rs, dev = _ring_sample(spec, ring, ids, sample_len, stage, B)
     n_next, n_cur = (None, None) if noises is None else noises
-    _update_call("erl_sac_update_ring_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs), *_sac_stage(stage), B,
+    _update_call("erl_sac_update_ring_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs), *_stage_ptrs(stage), B,
                                         ptr(n_next), ptr(n_cur), *_sac_hyper(seed, counter, gamma, target_entropy, tau, lr, betas, eps, max_norm),
-                                        step, ptr(objs_out, th.float32), *_sac_tail(spec, dev, B))
+                                        step, ptr(objs_out, th.float32), *_call_tail(spec, dev, B))
 
 
 def sac_update_ring_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring, ids_all: TEN,
@@ -837,9 +848,9 @@ def sac_update_ring_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, al
     assert ids_all.is_contiguous() and objs_all.shape == (T, 2) and objs_all.is_contiguous()
     rs, dev = _ring_sample(spec, ring, None, sample_len, stage, B)
     _update_call("erl_sac_update_ring_loop_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs),
-                                             ptr(ids_all, th.int64), T, *_sac_stage(stage), B,
+                                             ptr(ids_all, th.int64), T, *_stage_ptrs(stage), B,
                                              *_sac_hyper(seed, counter0, gamma, target_entropy, tau, lr, betas, eps, max_norm), int(step0),
-                                             ptr(objs_all, th.float32), *_sac_tail(spec, dev, B))
+                                             ptr(objs_all, th.float32), *_call_tail(spec, dev, B))
 
 
 def sac_mod_fused_supported(spec: SacSpec, B: int) -> bool:
@@ -861,11 +872,11 @@ def sac_update_mod(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_lo
     the cum_reward term; `update_actor` False leaves the actor, its moments and `actor_target` untouched and writes nan to objs_out[1]"""
     B = batch[0].shape[0]
     n_next, n_cur = (None, None) if noises is None else noises
-    _update_call("erl_sac_update_mod_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), *_sac_batch(batch), ptr(is_weight),
+    _update_call("erl_sac_update_mod_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), *_batch_ptrs(batch), ptr(is_weight),
                                        ptr(td_error_out), B, ptr(n_next), ptr(n_cur),
                                        *_sac_hyper(seed, counter, gamma, target_entropy, tau, lr, betas, eps, max_norm), step,
                                        int(bool(update_actor)), int(actor_step), ptr(actor_target, th.float32), ptr(objs_out, th.float32),
-                                       *_sac_tail(spec, batch[0].device, B))
+                                       *_call_tail(spec, batch[0].device, B))
 
 
 def sac_update_mod_from_ring(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring, ids: TEN,
@@ -877,11 +888,11 @@ def sac_update_mod_from_ring(spec: SacSpec, actor: TEN, critic: TEN, target: TEN
     B = ids.numel()
     rs, dev = _ring_sample(spec, ring, ids, sample_len, stage, B)
     n_next, n_cur = (None, None) if noises is None else noises
-    _update_call("erl_sac_update_mod_ring_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs), *_sac_stage(stage),
+    _update_call("erl_sac_update_mod_ring_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs), *_stage_ptrs(stage),
                                             B, ptr(n_next), ptr(n_cur),
                                             *_sac_hyper(seed, counter, gamma, target_entropy, tau, lr, betas, eps, max_norm), step,
                                             int(bool(update_actor)), int(actor_step), ptr(actor_target, th.float32), ptr(objs_out, th.float32),
-                                            *_sac_tail(spec, dev, B))
+                                            *_call_tail(spec, dev, B))
 
 
 def sac_update_mod_ring_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alpha_log: TEN, moments: Sequence[TEN], ring, ids_all: TEN,
@@ -896,10 +907,10 @@ def sac_update_mod_ring_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN
     rs, dev = _ring_sample(spec, ring, None, sample_len, stage, B)
     updates = ctypes.c_int32(0)
     _update_call("erl_sac_update_mod_ring_loop_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs),
-                                                 ptr(ids_all, th.int64), T, *_sac_stage(stage), B,
+                                                 ptr(ids_all, th.int64), T, *_stage_ptrs(stage), B,
                                                  *_sac_hyper(seed, counter0, gamma, target_entropy, tau, lr, betas, eps, max_norm), int(step0),
                                                  int(actor_step0), float(critic_value), ptr(actor_target, th.float32), ptr(objs_all, th.float32),
-                                                 ctypes.byref(updates), *_sac_tail(spec, dev, B))
+                                                 ctypes.byref(updates), *_call_tail(spec, dev, B))
     return int(updates.value)
 
 
@@ -920,8 +931,8 @@ def sac_update_per_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN, alp
                     float(per_beta), ptr(uniform_all, f32), ptr(per_stage.is_index, th.int64), ptr(per_stage.is_weight, f32),
                     ptr(per_stage.td_error, f32))
     _update_call("erl_sac_update_per_loop_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs), ctypes.addressof(pr),
-                                            T, *_sac_stage(stage), B, *_sac_hyper(seed, counter0, gamma, target_entropy, tau, lr, betas, eps, max_norm),
-                                            int(step0), ptr(objs_all, f32), *_sac_tail(spec, dev, B))
+                                            T, *_stage_ptrs(stage), B, *_sac_hyper(seed, counter0, gamma, target_entropy, tau, lr, betas, eps, max_norm),
+                                            int(step0), ptr(objs_all, f32), *_call_tail(spec, dev, B))
 
 
 def _per_loop_structs(spec: SacSpec, ring: ReplayRing, trees: PerTrees, uniform_all: TEN, cur_size: int, cursor: int, per_alpha: float,
@@ -951,10 +962,10 @@ def sac_update_mod_per_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN,
     T, B, rs, pr, dev = _per_loop_structs(spec, ring, trees, uniform_all, cur_size, cursor, per_alpha, per_beta, stage, per_stage, objs_all)
     updates = ctypes.c_int32(0)
     _update_call("erl_sac_update_mod_per_loop_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs),
-                                                ctypes.addressof(pr), T, *_sac_stage(stage), B,
+                                                ctypes.addressof(pr), T, *_stage_ptrs(stage), B,
                                                 *_sac_hyper(seed, counter0, gamma, target_entropy, tau, lr, betas, eps, max_norm), int(step0),
                                                 int(actor_step0), float(critic_value), ptr(actor_target, th.float32), ptr(objs_all, th.float32),
-                                                ctypes.byref(updates), int(bool(draw_in_step)), *_sac_tail(spec, dev, B))
+                                                ctypes.byref(updates), int(bool(draw_in_step)), *_call_tail(spec, dev, B))
     return int(updates.value)
 
 
@@ -966,9 +977,9 @@ def sac_update_per_draw_loop(spec: SacSpec, actor: TEN, critic: TEN, target: TEN
     the same arguments, the same bits in everything it leaves"""
     T, B, rs, pr, dev = _per_loop_structs(spec, ring, trees, uniform_all, cur_size, cursor, per_alpha, per_beta, stage, per_stage, objs_all)
     _update_call("erl_sac_update_per_draw_loop_f32", criterion, *_sac_head(spec, actor, critic, target, alpha_log, moments), ctypes.addressof(rs),
-                                                 ctypes.addressof(pr), T, *_sac_stage(stage), B,
+                                                 ctypes.addressof(pr), T, *_stage_ptrs(stage), B,
                                                  *_sac_hyper(seed, counter0, gamma, target_entropy, tau, lr, betas, eps, max_norm), int(step0),
-                                                 ptr(objs_all, th.float32), *_sac_tail(spec, dev, B))
+                                                 ptr(objs_all, th.float32), *_call_tail(spec, dev, B))
 
 
 def sac_explore_action(spec: SacSpec, actor: TEN, state: TEN, *, noise: Optional[TEN] = None, seed: int = 0, counter: int = 0,
@@ -1003,16 +1014,9 @@ def sac_explore_action(spec: SacSpec, actor: TEN, state: TEN, *, noise: Optional
 # ------------------------------------------------------------------------------------------------
 # TD3 / DDPG (csrc/td3.hip)
 # ------------------------------------------------------------------------------------------------
-class Td3Spec:
+class Td3Spec(_OffPolicySpec):
     """shapes of Actor / CriticTwin (Critic: E = 1) of elegantrl/agents/AgentTD3.py as flat fp32 blocks (include/erl_hip.h)."""
-
-    def __init__(self, S: int, A: int, hidden: Sequence[int], num_ensembles: int):
-        self.S, self.A, self.hidden, self.E = int(S), int(A), [int(h) for h in hidden], int(num_ensembles)
-        self._c = (ctypes.c_int * len(self.hidden))(*self.hidden)
-        pa, pc = ctypes.c_int64(0), ctypes.c_int64(0)
-        check(lib().erl_td3_param_counts(self.S, self.A, self._c, len(self.hidden), self.E, ctypes.byref(pa), ctypes.byref(pc)),
-              "erl_td3_param_counts")
-        self.actor_count, self.critic_count = pa.value, pc.value
+    _param_counts, _workspace_bytes = "erl_td3_param_counts", "erl_td3_workspace_bytes"
 
     @staticmethod
     def _slices(dims):
@@ -1028,9 +1032,6 @@ class Td3Spec:
 
     def critic_slices(self):
         return self._slices([self.S + self.A, *self.hidden, self.E])
-
-    def workspace_bytes(self, B: int) -> int:
-        return lib().erl_td3_workspace_bytes(self.S, self.A, self._c, len(self.hidden), self.E, B)
 
 
 def _td3_head(spec: Td3Spec, nets: Sequence[TEN], moments: Sequence[TEN]) -> tuple:
@@ -1053,10 +1054,9 @@ def td3_update(spec: Td3Spec, nets: Sequence[TEN], moments: Sequence[TEN], batch
     critic target), `moments` = (actor_m, actor_v, critic_m, critic_v), `batch` = (state, action, reward, undone, unmask, next_state);
     objs_out: float32[2] on the device; `noise` (B, A) injects the target-policy draw"""
     B = batch[0].shape[0]
-    ws = _workspace(batch[0].device, spec.workspace_bytes(B))
-    _update_call("erl_td3_update_f32", criterion, *_td3_head(spec, nets, moments), *_sac_batch(batch), ptr(is_weight), ptr(td_error_out), B,
+    _update_call("erl_td3_update_f32", criterion, *_td3_head(spec, nets, moments), *_batch_ptrs(batch), ptr(is_weight), ptr(td_error_out), B,
                  ptr(noise), *_td3_hyper(seed, counter, policy_noise_std, gamma, tau, lr, betas, eps, max_norm), int(step),
-                 int(bool(update_actor)), int(actor_step), ptr(objs_out, th.float32), ptr(ws), ws.numel(), stream_ptr())
+                 int(bool(update_actor)), int(actor_step), ptr(objs_out, th.float32), *_call_tail(spec, batch[0].device, B))
 
 
 def td3_update_from_ring(spec: Td3Spec, nets: Sequence[TEN], moments: Sequence[TEN], ring, ids: TEN, sample_len: int, stage: ReplayStage,
@@ -1066,10 +1066,9 @@ def td3_update_from_ring(spec: Td3Spec, nets: Sequence[TEN], moments: Sequence[T
     """ReplayBuffer.sample(ids) + one step from ONE call (erl_td3_update_ring_f32); `ring` / `stage` as in sac_update_from_ring"""
     B = ids.numel()
     rs, dev = _ring_sample(spec, ring, ids, sample_len, stage, B)
-    ws = _workspace(dev, spec.workspace_bytes(B))
-    _update_call("erl_td3_update_ring_f32", criterion, *_td3_head(spec, nets, moments), ctypes.addressof(rs), *_sac_stage(stage), B, ptr(noise),
+    _update_call("erl_td3_update_ring_f32", criterion, *_td3_head(spec, nets, moments), ctypes.addressof(rs), *_stage_ptrs(stage), B, ptr(noise),
                  *_td3_hyper(seed, counter, policy_noise_std, gamma, tau, lr, betas, eps, max_norm), int(step), int(bool(update_actor)),
-                 int(actor_step), ptr(objs_out, th.float32), ptr(ws), ws.numel(), stream_ptr())
+                 int(actor_step), ptr(objs_out, th.float32), *_call_tail(spec, dev, B))
 
 
 def td3_update_ring_loop(spec: Td3Spec, nets: Sequence[TEN], moments: Sequence[TEN], ring, ids_all: TEN, sample_len: int, stage: ReplayStage,
@@ -1082,12 +1081,11 @@ def td3_update_ring_loop(spec: Td3Spec, nets: Sequence[TEN], moments: Sequence[T
     T, B = ids_all.shape
     assert ids_all.is_contiguous() and objs_all.shape == (T, 2) and objs_all.is_contiguous()
     rs, dev = _ring_sample(spec, ring, None, sample_len, stage, B)
-    ws = _workspace(dev, spec.workspace_bytes(B))
     n_upd = ctypes.c_int32(-1)
     _update_call("erl_td3_update_ring_loop_f32", criterion, *_td3_head(spec, nets, moments), ctypes.addressof(rs), ptr(ids_all, th.int64), T,
-                 *_sac_stage(stage), B, *_td3_hyper(seed, counter0, policy_noise_std, gamma, tau, lr, betas, eps, max_norm), int(step0),
-                 int(actor_step0), int(update_freq), int(bool(actor_gate)), ptr(objs_all, th.float32), ctypes.byref(n_upd), ptr(ws),
-                 ws.numel(), stream_ptr())
+                 *_stage_ptrs(stage), B, *_td3_hyper(seed, counter0, policy_noise_std, gamma, tau, lr, betas, eps, max_norm), int(step0),
+                 int(actor_step0), int(update_freq), int(bool(actor_gate)), ptr(objs_all, th.float32), ctypes.byref(n_upd),
+                 *_call_tail(spec, dev, B))
     return int(n_upd.value)
 
 
