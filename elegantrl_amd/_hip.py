@@ -143,6 +143,11 @@ _SIGNATURES = {
                                           _P, c_int64, _P]),
     "erl_mlpn_ppo_step_f32": (c_int, [_P, _P, _P, _P, _P, _P, POINTER(c_int), c_int, _P, _P, _P, _P, _P, _P, c_int64, c_int64, _P,
                                       c_int64, c_float, c_float, c_float, c_int, _P, _P, c_int64, _P]),
+    # one dense layer's three contractions, called directly (for the operator-level tests)
+    "erl_dense_forward_f32": (c_int, [_P] * 5 + [c_int64, c_int, c_int, c_int, POINTER(c_int), _P]),
+    "erl_dense_backward_input_f32": (c_int, [_P] * 4 + [c_int, c_int64, c_int, c_int, POINTER(c_int), _P]),
+    "erl_dense_weight_grad_workspace_bytes": (c_int64, [c_int64, c_int, c_int]),
+    "erl_dense_weight_grad_f32": (c_int, [_P] * 4 + [c_int64, c_int, c_int, _P, c_int64, POINTER(c_int), _P]),
     "erl_mlpn_rollout_step_discrete_f32": (c_int, [_P, _P, _P, POINTER(c_int), c_int, _P, c_int64, _P, c_uint64, c_uint64, _P, _P,
                                                    _P, _P, _P, c_int64, _P]),
     "erl_mlpn_ppo_step_discrete_f32": (c_int, [_P, _P, _P, _P, _P, _P, POINTER(c_int), c_int, _P, _P, _P, _P, _P, _P, c_int64,

@@ -336,8 +336,10 @@ void gemm_go(dim3 grid, size_t lds, hipStream_t s, const GemmArgs &g)
     hipLaunchKernelGGL((gemm_kernel<AOP, BOP, EPI, VA, VB, RM, RN>), grid, dim3(256), lds, s, g);
 }
 
+// `form` (host only, may be NULL) receives which kernel the rule below chose: 0 = gemm_small_kernel, 1 + 2 VA + VB = gemm_kernel with
+// those load forms (the operator-level tests assert on it: a case meant for one kernel cannot quietly run on the other)
 template <int AOP, int BOP, int EPI>
-int gemm_launch(hipStream_t s, const GemmArgs &g_in, int splits, const char *what)
+int gemm_launch(hipStream_t s, const GemmArgs &g_in, int splits, const char *what, int *form = nullptr)
 {
     GemmArgs g = g_in;
     if (g.nbatch < 1) g.nbatch = 1;
@@ -346,12 +348,14 @@ int gemm_launch(hipStream_t s, const GemmArgs &g_in, int splits, const char *wha
     if (tiles64 < 128 || g.nbatch > 1) {   // fewer 64 x 64 tiles than half the CUs (or a batch of small problems): 32 x 32 tiles with the
                                            // reduction split over the waves
         const dim3 grid((unsigned)erl_cdiv(g.N, ST), (unsigned)erl_cdiv(g.M, ST), (unsigned)(splits * g.nbatch));
+        if (form) *form = 0;
         hipLaunchKernelGGL((gemm_small_kernel<AOP, BOP, EPI>), grid, dim3(256), 0, s, g);
     } else {
         auto vec_ok = [](int op, const float *P, int ld, int outs, int red) {
             return (reinterpret_cast<uintptr_t>(P) & 15) == 0 && ld % 4 == 0 && (op == OP_RC ? red : outs) % 4 == 0;
         };
         const bool va = vec_ok(AOP, g.A, g.lda, g.M, g.K), vb = vec_ok(BOP, g.B, g.ldb, g.N, g.K);
+        if (form) *form = 1 + 2 * (int)va + (int)vb;
         // tile shape: 64 x 64.  The 128-wide shapes exist (ERL_GEMM_TILE=12|21|22 forces one) and were MEASURED SLOWER at the PPO
         // minibatch (B = 16384; profiles/r03_gemm_tile_ab.txt: whole layered step 180 / 227 / 266 us with 64 x 64 tiles against
         // 222 / 266 / 307 with 64 x 128, 227 / 264 / 308 with 128 x 64 and 329 / 361 / 418 with 128 x 128 at [128,128] / (256,128) /
@@ -381,22 +385,24 @@ int gemm_launch(hipStream_t s, const GemmArgs &g_in, int splits, const char *wha
 }
 
 // Y[rows][Nw] = act(X[rows][K] . W[Nw][K]^T + b);  gelu: hidden layer (G receives GELU' when not NULL)
-int dense_forward(hipStream_t s, const float *X, const float *W, const float *b, float *Y, float *G, int rows, int Nw, int K, bool gelu)
+int dense_forward(hipStream_t s, const float *X, const float *W, const float *b, float *Y, float *G, int rows, int Nw, int K, bool gelu,
+                  int *form = nullptr)
 {
     GemmArgs g{};
     g.A = X; g.lda = K; g.B = W; g.ldb = K; g.M = rows; g.N = Nw; g.K = K; g.C = Y; g.ldc = Nw; g.bias = b; g.G = G;
-    return gelu ? gemm_launch<OP_RC, OP_RC, EPI_BIAS_GELU>(s, g, 1, "dense_forward") : gemm_launch<OP_RC, OP_RC, EPI_BIAS>(s, g, 1, "dense_forward");
+    return gelu ? gemm_launch<OP_RC, OP_RC, EPI_BIAS_GELU>(s, g, 1, "dense_forward", form)
+                : gemm_launch<OP_RC, OP_RC, EPI_BIAS>(s, g, 1, "dense_forward", form);
 }
 
 // dX[rows][K] (=, +=, or = gate *) dZ[rows][Nw] . W[Nw][K]
 int dense_backward_input(hipStream_t s, const float *dZ, const float *W, float *dX, const float *gate, bool accumulate, int rows, int Nw,
-                         int K)
+                         int K, int *form = nullptr)
 {
     GemmArgs g{};
     g.A = dZ; g.lda = Nw; g.B = W; g.ldb = K; g.M = rows; g.N = K; g.K = Nw; g.C = dX; g.ldc = K; g.G = const_cast<float *>(gate);
-    if (gate) return gemm_launch<OP_RC, OP_OC, EPI_MUL>(s, g, 1, "dense_backward_input");
-    return accumulate ? gemm_launch<OP_RC, OP_OC, EPI_ACC>(s, g, 1, "dense_backward_input")
-                      : gemm_launch<OP_RC, OP_OC, EPI_STORE>(s, g, 1, "dense_backward_input");
+    if (gate) return gemm_launch<OP_RC, OP_OC, EPI_MUL>(s, g, 1, "dense_backward_input", form);
+    return accumulate ? gemm_launch<OP_RC, OP_OC, EPI_ACC>(s, g, 1, "dense_backward_input", form)
+                      : gemm_launch<OP_RC, OP_OC, EPI_STORE>(s, g, 1, "dense_backward_input", form);
 }
 
 }  // namespace

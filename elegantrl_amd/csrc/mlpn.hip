@@ -310,3 +310,64 @@ extern "C" int erl_mlpn_ppo_step_discrete_f32(const float *actor_params, const f
                          actor_dims, n_dims, states, actions, unmasks, logprobs, advantages, reward_sums, H, N, ids, B, ratio_clip,
                          lambda_entropy, inv_batch, ERL_PPO_OBJ_REFERENCE, flat_grad, workspace, workspace_bytes, stream);
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// The three contractions of one dense layer, called directly (for the operator-level tests: tests/test_gemm_forms_gpu.py).  Each
+// entry validates and calls the host helper the layers call -- the same gemm_launch rule, the same kernels -- with the pointers as
+// given (a caller may pass an unaligned base on purpose); *out_form (may be NULL) receives what gemm_launch chose.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+
+int dense_shape_refusals(const char *what, int64_t rows, int Nw, int K)
+{
+    ERL_REQUIRE(rows >= 1 && Nw >= 1 && K >= 1, "%s: bad shape (rows=%lld, Nw=%d, K=%d: each must be >= 1)", what, (long long)rows, Nw, K);
+    ERL_REQUIRE(Nw <= ERL_MAXN_WIDTH && K <= ERL_MAXN_WIDTH, "%s: bad shape (Nw=%d, K=%d: widths are at most %d)", what, Nw, K, ERL_MAXN_WIDTH);
+    ERL_REQUIRE(rows < (1LL << 31), "%s: bad shape (rows=%lld: must be below 2^31)", what, (long long)rows);
+    return ERL_OK;
+}
+
+inline int64_t round256(int64_t bytes) { return (bytes + 255) / 256 * 256; }
+// split scratch of dense_weight_grad: the dW (+ joint db) partials, then the db partials of a separate db
+inline int64_t dense_dw_bytes(int64_t rows, int Nw, int K) { return round256(dw_scratch_floats(rows, (int64_t)Nw * K) * 4); }
+inline int64_t dense_cs_bytes(int64_t rows, int Nw) { return rows >= 4 * DW_CHUNK ? round256(erl_cdiv(rows, DW_CHUNK) * Nw * 4) : 0; }
+
+}  // namespace
+
+extern "C" int erl_dense_forward_f32(const float *X, const float *W, const float *b, float *Y, float *G, int64_t rows, int Nw, int K,
+                                     int gelu, int *out_form, void *stream)
+{
+    ERL_REQUIRE(X && W && b && Y, "erl_dense_forward_f32: NULL tensor");
+    if (int rc = dense_shape_refusals("erl_dense_forward_f32", rows, Nw, K)) return rc;
+    return dense_forward((hipStream_t)stream, X, W, b, Y, G, (int)rows, Nw, K, gelu != 0, out_form);
+}
+
+extern "C" int erl_dense_backward_input_f32(const float *dZ, const float *W, float *dX, const float *gate, int accumulate, int64_t rows,
+                                            int Nw, int K, int *out_form, void *stream)
+{
+    ERL_REQUIRE(dZ && W && dX, "erl_dense_backward_input_f32: NULL tensor");
+    ERL_REQUIRE(!(gate && accumulate), "erl_dense_backward_input_f32: a gate and accumulate exclude each other");
+    if (int rc = dense_shape_refusals("erl_dense_backward_input_f32", rows, Nw, K)) return rc;
+    return dense_backward_input((hipStream_t)stream, dZ, W, dX, gate, accumulate != 0, (int)rows, Nw, K, out_form);
+}
+
+extern "C" int64_t erl_dense_weight_grad_workspace_bytes(int64_t rows, int Nw, int K)
+{
+    if (dense_shape_refusals("erl_dense_weight_grad_workspace_bytes", rows, Nw, K)) return -1;
+    return dense_dw_bytes(rows, Nw, K) + dense_cs_bytes(rows, Nw);
+}
+
+extern "C" int erl_dense_weight_grad_f32(const float *dZ, const float *X, float *dW, float *db, int64_t rows, int Nw, int K, void *workspace,
+                                         int64_t workspace_bytes, int *out_form, void *stream)
+{
+    ERL_REQUIRE(dZ && X && dW && db, "erl_dense_weight_grad_f32: NULL tensor");
+    if (int rc = dense_shape_refusals("erl_dense_weight_grad_f32", rows, Nw, K)) return rc;
+    float *dw_scr = nullptr, *cs_scr = nullptr;
+    if (workspace) {     // (NULL: no split scratch, the contraction runs unsplit whatever the row count)
+        const int64_t need = dense_dw_bytes(rows, Nw, K) + dense_cs_bytes(rows, Nw);
+        ERL_REQUIRE(workspace_bytes >= need, "erl_dense_weight_grad_f32: workspace too small (%lld bytes, need erl_dense_weight_grad_workspace_bytes = %lld)",
+                    (long long)workspace_bytes, (long long)need);
+        dw_scr = (float *)workspace;
+        cs_scr = (float *)((char *)workspace + dense_dw_bytes(rows, Nw, K));
+    }
+    return dense_weight_grad((hipStream_t)stream, dZ, X, dW, db, (int)rows, Nw, K, dw_scr, cs_scr, out_form);
+}

@@ -366,7 +366,7 @@ int forward(hipStream_t s, const NetDims &nd, const float *P, int64_t rows, floa
 // chunks of DW_CHUNK rows over blockIdx.z when scratch is available; each split writes its own partial (dW partials to
 // dw_scratch, db partials to cs_scratch) and the partials are summed in a fixed order (deterministic).
 int dense_weight_grad(hipStream_t s, const float *dZ, const float *X, float *dW, float *db, int rows, int Nw, int K, float *dw_scratch,
-                      float *cs_scratch)
+                      float *cs_scratch, int *form = nullptr)
 {
     GemmArgs g{};
     g.A = dZ; g.lda = Nw; g.B = X; g.ldb = K; g.M = Nw; g.N = K; g.K = rows; g.ldc = K;
@@ -380,7 +380,7 @@ int dense_weight_grad(hipStream_t s, const float *dZ, const float *X, float *dW,
     g.c_split = (int64_t)Nw * K + (joint ? Nw : 0);
     g.rowsum = joint ? dw_scratch + (size_t)Nw * K : (split ? cs_scratch : db);
     g.rs_split = joint ? g.c_split : Nw;
-    int rc = gemm_launch<OP_OC, OP_OC, EPI_PARTIAL>(s, g, nsplit, "dense_weight_grad");
+    int rc = gemm_launch<OP_OC, OP_OC, EPI_PARTIAL>(s, g, nsplit, "dense_weight_grad", form);
     if (rc || !split) return rc;
     if (joint) return erl_grad_reduce_f32(dw_scratch, nsplit, g.c_split, dW, (void *)s);
     if ((rc = erl_grad_reduce_f32(dw_scratch, nsplit, (int64_t)Nw * K, dW, (void *)s))) return rc;

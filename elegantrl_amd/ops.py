@@ -600,6 +600,45 @@ def mlpn_ppo_step(actor_params: TEN, critic_params: TEN, act_avg: TEN, act_std: 
                                       inv_batch, int(objective), ptr(flat_grad, th.float32), ptr(ws), ws.numel(), stream_ptr())
 
 
+def dense_forward(X: TEN, W: TEN, b: TEN, Y: TEN, G: Optional[TEN] = None, *, gelu: bool = False) -> int:
+    """Y (rows, Nw) = act(X (rows, K) . W (Nw, K)^T + b) by the layered path's own dense-layer helper (for tests: include/erl_hip.h,
+    erl_dense_forward_f32); gelu: exact-erf GELU, G receives GELU'.  Returns out_form: 0 = the 32 x 32-tile kernel, 1 + 2 VA + VB = the
+    64 x 64-tile kernel and its load forms.  The tensors' addresses go to the kernel as they are (views at odd offsets included)."""
+    (rows, K), Nw, form = X.shape, W.shape[0], ctypes.c_int(-1)
+    assert W.shape == (Nw, K) and b.numel() == Nw and Y.shape == (rows, Nw) and (G is None or G.shape == Y.shape)
+    check(lib().erl_dense_forward_f32(ptr(X, th.float32), ptr(W, th.float32), ptr(b, th.float32), ptr(Y, th.float32), ptr(G, th.float32),
+                                      rows, Nw, K, int(bool(gelu)), ctypes.byref(form), stream_ptr()), "erl_dense_forward_f32")
+    return form.value
+
+
+def dense_backward_input(dZ: TEN, W: TEN, dX: TEN, gate: Optional[TEN] = None, *, accumulate: bool = False) -> int:
+    """dX (rows, K) =, += or = gate * (dZ (rows, Nw) . W (Nw, K)) (erl_dense_backward_input_f32); returns out_form as dense_forward."""
+    (rows, Nw), K, form = dZ.shape, W.shape[1], ctypes.c_int(-1)
+    assert W.shape == (Nw, K) and dX.shape == (rows, K) and (gate is None or gate.shape == dX.shape)
+    check(lib().erl_dense_backward_input_f32(ptr(dZ, th.float32), ptr(W, th.float32), ptr(dX, th.float32), ptr(gate, th.float32),
+                                             int(bool(accumulate)), rows, Nw, K, ctypes.byref(form), stream_ptr()),
+          "erl_dense_backward_input_f32")
+    return form.value
+
+
+def dense_weight_grad_workspace_bytes(rows: int, Nw: int, K: int) -> int:
+    need = lib().erl_dense_weight_grad_workspace_bytes(rows, Nw, K)
+    check(0 if need >= 0 else -1, "erl_dense_weight_grad_workspace_bytes")
+    return need
+
+
+def dense_weight_grad(dZ: TEN, X: TEN, dW: TEN, db: TEN, *, split: bool = True) -> int:
+    """dW (Nw, K) = dZ (rows, Nw)^T . X (rows, K) and db (Nw) = column sums of dZ (erl_dense_weight_grad_f32); split: hand the entry the
+    scratch with which it splits 1024 rows or more into chunks of 256 (False: no scratch, one pass over all rows).  db placed right behind dW
+    (one buffer of Nw * K + Nw floats) takes the joint fixed-order sum.  Returns out_form as dense_forward."""
+    (rows, Nw), K, form = dZ.shape, X.shape[1], ctypes.c_int(-1)
+    assert X.shape == (rows, K) and dW.shape == (Nw, K) and db.numel() == Nw
+    ws = _workspace(dZ.device, dense_weight_grad_workspace_bytes(rows, Nw, K)) if split else None
+    check(lib().erl_dense_weight_grad_f32(ptr(dZ, th.float32), ptr(X, th.float32), ptr(dW, th.float32), ptr(db, th.float32), rows, Nw, K,
+                                          ptr(ws), ws.numel() if split else 0, ctypes.byref(form), stream_ptr()), "erl_dense_weight_grad_f32")
+    return form.value
+
+
 def mlpn_rollout_step_discrete(params: TEN, spec: MlpSpecN, state_avg: TEN, state_std: TEN, state: TEN, *,
                                uniform: Optional[TEN] = None, seed: int = 0, counter: int = 0, out_state: Optional[TEN] = None,
                                out_action: Optional[TEN] = None, out_logprob: Optional[TEN] = None,

@@ -739,6 +739,25 @@ ERL_API int erl_mlpn_ppo_step_f32(const float *actor_params, const float *critic
                           float inv_batch, int objective, float *flat_grad, void *workspace, int64_t workspace_bytes,
                           void *stream);
 
+/* The three contractions of ONE dense layer of the layered path, called directly (csrc/gemm_tiles.h; additive, ABI 23).  They exist for
+ * the operator-level tests (tests/test_gemm_forms_gpu.py): each validates its arguments and calls the host helper the layers of
+ * erl_mlpn_*, erl_sac_* and erl_td3_* call, so the kernel and its load forms are chosen by the production rule.  Row-major fp32:
+ *   forward         Y[rows][Nw] = act(X[rows][K] . W[Nw][K]^T + b[Nw]);  gelu != 0: exact-erf GELU, G (may be NULL) receives GELU'(z)
+ *   backward input  dX[rows][K] = dZ[rows][Nw] . W[Nw][K];  `gate` != NULL: times gate[rows][K];  accumulate != 0: added to dX
+ *   weight grad     dW[Nw][K] = dZ^T . X,  db[Nw] = column sums of dZ.  `workspace` (erl_dense_weight_grad_workspace_bytes; 0 bytes below
+ *                   1024 rows) holds the per-256-row partials that a fixed-order sum folds; NULL: no split, whatever the row count.
+ *                   db == dW + Nw * K: one sum folds both (the parameter block's layout), otherwise one each.
+ * The pointers are used as given (nothing is re-aligned: an unaligned base selects the scalar load form).  *out_form (may be NULL)
+ * receives the kernel chosen: 0 = the 32 x 32-tile kernel, 1 + 2 VA + VB = the 64 x 64-tile kernel with 16-byte loads of operand A / B.
+ * Refused before any launch: a NULL tensor; rows, Nw or K < 1; Nw or K > ERL_MAXN_WIDTH; rows >= 2^31; a workspace that is too small. */
+ERL_API int erl_dense_forward_f32(const float *X, const float *W, const float *b, float *Y, float *G, int64_t rows, int Nw, int K,
+                                  int gelu, int *out_form, void *stream);
+ERL_API int erl_dense_backward_input_f32(const float *dZ, const float *W, float *dX, const float *gate, int accumulate, int64_t rows,
+                                         int Nw, int K, int *out_form, void *stream);
+ERL_API int64_t erl_dense_weight_grad_workspace_bytes(int64_t rows, int Nw, int K);
+ERL_API int erl_dense_weight_grad_f32(const float *dZ, const float *X, float *dW, float *db, int64_t rows, int Nw, int K, void *workspace,
+                                      int64_t workspace_bytes, int *out_form, void *stream);
+
 /* Discrete-action sibling (AgentDiscretePPO / ActorDiscretePPO, elegantrl/agents/AgentPPO.py:305-320, :393-422): the actor
  * block has no action_std_log (erl_mlpn_param_count(dims, n_dims, 0)), dims[n_dims-1] = number of actions (<= 64).
  * Rollout: a ~ Categorical(softmax(logits)) by inverse CDF with one U[0,1) per env (`uniform` (N) injected, or

@@ -1,6 +1,10 @@
 """Generic-shape MLP path (erl_mlpn_*: any depth / width; own MFMA GEMMs with fused epilogues) against the
 depth-generic numpy oracle, and AgentPPO end to end on the reference's larger demo shapes (256, 128) / (256, 128, 64)
-(examples/demo_A2C_PPO.py:117,171).  Same bars as the fused kernels: rtol 1e-4 vs the fp32 oracle."""
+(examples/demo_A2C_PPO.py:117,171).  Same bars as the fused kernels: rtol 1e-4 vs the fp32 oracle.
+
+These are whole steps: at these shapes every weight gradient and most layers take the small GEMM kernel.  Coverage per kernel form (both
+kernels, every epilogue, the four load forms, the split weight gradient, ragged tiles and reduction tails), one dense layer at a time
+against exact references, lives in tests/test_gemm_forms_gpu.py."""
 import numpy as np
 import pytest
 import torch as th
