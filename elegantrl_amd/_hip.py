@@ -108,6 +108,11 @@ _SIGNATURES = {
     "erl_grad_reduce_f32": (c_int, [_P, c_int, c_int64, _P, _P]),
     "erl_clip_adam_f32": (c_int, [_P, _P, _P, _P, POINTER(c_int64), POINTER(c_int64), c_int, _P, c_int32, c_float,
                                   c_float, c_float, c_float, c_float, c_float, _P]),
+    "erl_clip_adam_form": (c_int, [c_int64, c_int, c_int]),
+    "erl_clip_adam_soft_f32": (c_int, [_P, _P, _P, _P, POINTER(c_int64), POINTER(c_int64), c_int, c_int32, c_float, c_float, c_float,
+                                       c_float, c_float, c_float, _P, c_float, _P]),
+    "erl_clip_adam_parts_soft_f32": (c_int, [_P, _P, _P, _P, c_int64, _P, c_int, c_int32, c_float, c_float, c_float, c_float, c_float,
+                                             _P, c_float, _P]),
     "erl_tail_fused_ok": (c_int, [c_int64]),
     "erl_reduce_clip_adam_fused_f32": (c_int, [_P, c_int, c_int64, _P, _P, _P, _P, POINTER(c_int64), POINTER(c_int64), c_int, c_int32, c_float,
                                                c_float, c_float, c_float, c_float, c_float, _P]),

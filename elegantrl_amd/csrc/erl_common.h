@@ -63,10 +63,8 @@ int erl_launch_reduce_exchange_f32(const float *slabs, int n_slabs, int64_t stri
                                    int n_groups, float grad_scale, bool want_partials, const ErlExchange *ex, hipStream_t stream);
 int erl_launch_exchange_f64(double *buf, int64_t count, const ErlExchange *ex, hipStream_t stream);
 
-// optim.hip: clip + Adam with the soft target update folded in; sac_fused.hip: the fused SAC step and its shape class
-int erl_clip_adam_soft_f32(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, const int64_t *group_off,
-                           const int64_t *group_len, int n_groups, int32_t step, float lr, float beta1, float beta2, float eps, float max_norm,
-                           float grad_scale, float *soft, float tau, hipStream_t stream);
+// optim.hip: clip + Adam with the soft target update folded in (erl_clip_adam_soft_f32, erl_clip_adam_parts_soft_f32: exported,
+// include/erl_hip.h); sac_fused.hip: the fused SAC step and its shape class
 // rollout_wide.hip: the one-launch rollout step of net_dims = (256, h2) behind erl_mlpn_rollout_step_f32
 int erl_rollout_wide_supported(const int *dims, int n_dims, int64_t N);
 int erl_rollout_wide_step(const float *actor_params, const float *state_avg, const float *state_std, const int *dims, int n_dims, const float *state, int64_t N,
@@ -75,9 +73,6 @@ int erl_rollout_wide_step(const float *actor_params, const float *state_avg, con
 int erl_value_wide_supported(const int *dims, int n_dims);
 int erl_value_wide_forward(const float *params, const float *state_avg, const float *state_std, const int *dims, int n_dims, const float *states,
                            int64_t rows, float *values, hipStream_t stream);
-int erl_clip_adam_parts_soft_f32(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t len, const double *parts,
-                                 int nparts, int32_t step, float lr, float beta1, float beta2, float eps, float max_norm, float *soft, float tau,
-                                 hipStream_t stream);
 bool erl_sac_fused_supported(int S, int A, const int *hidden, int n_hidden, int E, int64_t B);
 int erl_sac_rollout_fused(const float *actor_params, int S, int A, int h0, int h1, const int64_t *aoff, float *env_state, const float *Ws,
                           const float *Wa, float *phys, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,

@@ -215,6 +215,29 @@ static int device_capacity(const void *kernel, int threads)
     return per_cu * cus > 0 ? per_cu * cus : -1;
 }
 
+// the kernel form of a launch (erl_clip_adam_form, include/erl_hip.h): 0 per-thread, 1 grid-wait, 2 loop.  The one place that decides it:
+// clip_adam_impl branches on it, the exported query reports it.
+static int clip_adam_form(int64_t longest, int n_groups, bool device_step)
+{
+    const int64_t bx = erl_cdiv(longest, 1024);
+    if (bx <= 64) return 0;                  // per <= 1024 in clip_adam_kernel: one element per thread
+    if (!device_step) {                      // the grid-wait kernel takes a host step, and the whole launch resident at once
+        int dev = -1;
+        static int capacity[32] = {0};
+        if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 32) {
+            if (!capacity[dev]) capacity[dev] = device_capacity((const void *)clip_adam_grid_kernel, 1024);
+            if (bx * n_groups <= capacity[dev] && bx * n_groups <= kRaMaxBlocks * 4) return 1;
+        }
+    }
+    return 2;                                // 64 workgroups per group, each loops over its slice
+}
+
+extern "C" int erl_clip_adam_form(int64_t longest, int n_groups, int device_step)
+{
+    ERL_REQUIRE(longest >= 0 && n_groups >= 1 && n_groups <= 4, "erl_clip_adam_form: longest=%lld n_groups=%d", (long long)longest, n_groups);
+    return clip_adam_form(longest, n_groups, device_step != 0);
+}
+
 static int clip_adam_impl(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, const int64_t *group_off,
                           const int64_t *group_len, int n_groups, const int32_t *step_base, int32_t step_offset, float lr, float beta1,
                           float beta2, float eps, float max_norm, float grad_scale, float *soft, float tau, void *stream)
@@ -232,24 +255,17 @@ static int clip_adam_impl(float *params, const float *grads, float *exp_avg, flo
     }
     int bx = (int)erl_cdiv(longest, 1024);   // one element per thread in the Adam phase (latency bound: no serial loop)
     if (bx < 1) bx = 1;
-    if (bx > 64 && !step_base) {             // long groups: partial norms + a grid-wide wait, if the whole launch is resident at once
-        int dev = -1;
-        static int capacity[32] = {0};
-        if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 32) {
-            if (!capacity[dev]) capacity[dev] = device_capacity((const void *)clip_adam_grid_kernel, 1024);
-            if ((int64_t)bx * n_groups <= capacity[dev] && (int64_t)bx * n_groups <= kRaMaxBlocks * 4) {
-                RaScratch *sc = nullptr;
-                unsigned target = 0;
-                int rc = ra_arrivals("erl_clip_adam_f32", (int64_t)bx * n_groups, (hipStream_t)stream, &sc, &target);
-                if (rc) return rc;
-                const double bc1 = 1.0 - pow((double)beta1, (double)step_offset), bc2 = 1.0 - pow((double)beta2, (double)step_offset);
-                hipLaunchKernelGGL(clip_adam_grid_kernel, dim3(bx, n_groups), dim3(1024), 0, (hipStream_t)stream, params, grads, exp_avg,
-                                   exp_avg_sq, gr, beta1, beta2, eps, max_norm, grad_scale, (float)((double)lr / bc1), (float)sqrt(bc2),
-                                   reinterpret_cast<double *>(sc->ptr + 256), reinterpret_cast<unsigned *>(sc->ptr), target, erl_fault_word(ERL_FAULT_ADAM_GRID_WAIT),
-                                   soft, tau);
-                ERL_LAUNCH_CHECK("erl_clip_adam_f32");
-            }
-        }
+    if (clip_adam_form(longest, n_groups, step_base != nullptr) == 1) {   // long groups: partial norms + a grid-wide wait
+        RaScratch *sc = nullptr;
+        unsigned target = 0;
+        int rc = ra_arrivals("erl_clip_adam_f32", (int64_t)bx * n_groups, (hipStream_t)stream, &sc, &target);
+        if (rc) return rc;
+        const double bc1 = 1.0 - pow((double)beta1, (double)step_offset), bc2 = 1.0 - pow((double)beta2, (double)step_offset);
+        hipLaunchKernelGGL(clip_adam_grid_kernel, dim3(bx, n_groups), dim3(1024), 0, (hipStream_t)stream, params, grads, exp_avg,
+                           exp_avg_sq, gr, beta1, beta2, eps, max_norm, grad_scale, (float)((double)lr / bc1), (float)sqrt(bc2),
+                           reinterpret_cast<double *>(sc->ptr + 256), reinterpret_cast<unsigned *>(sc->ptr), target, erl_fault_word(ERL_FAULT_ADAM_GRID_WAIT),
+                           soft, tau);
+        ERL_LAUNCH_CHECK("erl_clip_adam_f32");
     }
     if (bx > 64) bx = 64;
     float step_size = 0.f, bc2_sqrt = 1.f;
@@ -273,26 +289,26 @@ extern "C" int erl_clip_adam_f32(float *params, const float *grads, float *exp_a
 
 // the same with the soft target update  soft <- params_new * tau + soft * (1 - tau)  of every updated element folded into the
 // launch (AgentBase.soft_update, elegantrl/agents/AgentBase.py:270-278; the arithmetic of soft_update_kernel, sac.hip);
-// `soft` has the layout of `params` and may be NULL.  Internal (sac_fused.hip).
-int erl_clip_adam_soft_f32(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, const int64_t *group_off,
+// `soft` has the layout of `params` and may be NULL.
+extern "C" int erl_clip_adam_soft_f32(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, const int64_t *group_off,
                            const int64_t *group_len, int n_groups, int32_t step, float lr, float beta1, float beta2, float eps, float max_norm,
-                           float grad_scale, float *soft, float tau, hipStream_t stream)
+                           float grad_scale, float *soft, float tau, void *stream)
 {
     return clip_adam_impl(params, grads, exp_avg, exp_avg_sq, group_off, group_len, n_groups, nullptr, step, lr, beta1, beta2, eps, max_norm,
-                          grad_scale, soft, tau, (void *)stream);
+                          grad_scale, soft, tau, stream);
 }
 
 
 // clip_grad_norm_ + Adam (+ soft target update) of ONE group whose squared gradient norm arrives as `nparts` fp64 pieces (see
-// clip_adam_parts_kernel).  Internal (sac_fused.hip).
-int erl_clip_adam_parts_soft_f32(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t len, const double *parts,
+// clip_adam_parts_kernel): the fused SAC step's optimiser launch (sac_fused.hip).
+extern "C" int erl_clip_adam_parts_soft_f32(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t len, const double *parts,
                                  int nparts, int32_t step, float lr, float beta1, float beta2, float eps, float max_norm, float *soft, float tau,
-                                 hipStream_t stream)
+                                 void *stream)
 {
     ERL_REQUIRE(params && grads && exp_avg && exp_avg_sq && parts, "erl_clip_adam_parts_soft_f32: NULL tensor");
     ERL_REQUIRE(len >= 1 && nparts >= 1 && step >= 1, "erl_clip_adam_parts_soft_f32: bad shape len=%lld nparts=%d step=%d", (long long)len, nparts, (int)step);
     const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-    hipLaunchKernelGGL(clip_adam_parts_kernel, dim3((unsigned)erl_cdiv(len, 1024)), dim3(1024), 0, stream, params, grads, exp_avg, exp_avg_sq, len,
+    hipLaunchKernelGGL(clip_adam_parts_kernel, dim3((unsigned)erl_cdiv(len, 1024)), dim3(1024), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, len,
                        parts, nparts, beta1, beta2, eps, max_norm, (float)((double)lr / bc1), (float)sqrt(bc2), soft, tau);
     ERL_LAUNCH_CHECK("erl_clip_adam_parts_soft_f32");
 }

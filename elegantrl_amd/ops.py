@@ -433,9 +433,41 @@ def clip_adam(params: TEN, grads: TEN, exp_avg: TEN, exp_avg_sq: TEN, groups: Se
           "erl_clip_adam_f32")
 
 
+CLIP_ADAM_PER_THREAD, CLIP_ADAM_GRID_WAIT, CLIP_ADAM_LOOP = 0, 1, 2
+
+
+def clip_adam_form(longest: int, n_groups: int, device_step: bool = False) -> int:
+    """the kernel form `clip_adam` takes for a launch whose longest group has `longest` elements (erl_clip_adam_form: the launcher's own
+    branch): CLIP_ADAM_PER_THREAD, CLIP_ADAM_GRID_WAIT or CLIP_ADAM_LOOP; `device_step`: the call passes `step_base`."""
+    form = lib().erl_clip_adam_form(longest, n_groups, int(bool(device_step)))
+    if form < 0:
+        check(form, "erl_clip_adam_form")
+    return form
+
+
 def _groups_c(groups):
     n = len(groups)
     return n, (ctypes.c_int64 * n)(*[g[0] for g in groups]), (ctypes.c_int64 * n)(*[g[1] for g in groups])
+
+
+def clip_adam_soft(params: TEN, grads: TEN, exp_avg: TEN, exp_avg_sq: TEN, groups: Sequence[Tuple[int, int]], step: int, lr: float,
+                   max_norm: float, soft: Optional[TEN], tau: float, grad_scale: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+    """`clip_adam` with a host step and soft <- params_new * tau + soft * (1 - tau) in the same launch (`soft` None: no target)"""
+    n, off, ln = _groups_c(groups)
+    check(lib().erl_clip_adam_soft_f32(ptr(params, th.float32), ptr(grads, th.float32), ptr(exp_avg, th.float32), ptr(exp_avg_sq, th.float32),
+                                       off, ln, n, step, lr, betas[0], betas[1], eps, max_norm, grad_scale, ptr(soft, th.float32), tau,
+                                       stream_ptr()), "erl_clip_adam_soft_f32")
+
+
+def clip_adam_parts_soft(params: TEN, grads: TEN, exp_avg: TEN, exp_avg_sq: TEN, length: int, parts: TEN, nparts: int, step: int, lr: float,
+                         max_norm: float, soft: Optional[TEN], tau: float, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+    """clip + Adam (+ soft target update) of the one group [0, length) whose squared gradient norm is the sum of the `nparts` float64
+    pieces in `parts` (the fused SAC step's optimiser launch)"""
+    if parts.numel() < nparts:
+        raise ValueError(f"parts holds {parts.numel()} pieces, nparts = {nparts}")
+    check(lib().erl_clip_adam_parts_soft_f32(ptr(params, th.float32), ptr(grads, th.float32), ptr(exp_avg, th.float32),
+                                             ptr(exp_avg_sq, th.float32), length, ptr(parts, th.float64), nparts, step, lr, betas[0], betas[1],
+                                             eps, max_norm, ptr(soft, th.float32), tau, stream_ptr()), "erl_clip_adam_parts_soft_f32")
 
 
 def grad_reduce_partials(slabs: TEN, n_slabs: int, stride: int, flat_grad: TEN, groups: Sequence[Tuple[int, int]],

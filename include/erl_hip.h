@@ -572,6 +572,24 @@ ERL_API int erl_clip_adam_f32(float *params, const float *grads, float *exp_avg,
                       const int64_t *group_off, const int64_t *group_len, int n_groups, const int32_t *step_base,
                       int32_t step_offset, float lr, float beta1, float beta2, float eps, float max_norm,
                       float grad_scale, void *stream);
+/* Which kernel form erl_clip_adam_f32 takes for a launch whose longest group has `longest` elements (added within ABI 23; the
+ * launcher branches on this same function): 0 per-thread (longest <= 65 536: one element per thread, every workgroup re-derives the
+ * norm), 1 grid-wait (longer, host step, and the whole launch of ceil(longest / 1024) x n_groups workgroups resident at once on the
+ * current device: partial norms + a grid-wide wait), 2 loop (longer otherwise: 64 workgroups per group, each loops over its slice).
+ * device_step != 0: the step comes from `step_base`.  ERL_EINVAL for longest < 0 or n_groups outside 1..4.  Answers 0 need no device. */
+ERL_API int erl_clip_adam_form(int64_t longest, int n_groups, int device_step);
+/* erl_clip_adam_f32 with a host step and the soft target update  soft <- params_new * tau + soft * (1 - tau)  of every updated
+ * element in the same launch (AgentBase.soft_update, AgentBase.py:270-278); `soft` has the layout of `params`, NULL: no target.
+ * erl_clip_adam_parts_soft_f32: the same for ONE group at offset 0 whose squared gradient norm arrives as `nparts` fp64 pieces
+ * on the device (the fused SAC step's weight-gradient workgroups leave them): every workgroup adds the pieces in one fixed order
+ * (thread T takes T + 1024 j, a butterfly per wave, the 16 waves in order) -- no pass over the gradient, no wait; grad_scale 1.
+ * (Added within ABI 23: the fused SAC and ModSAC steps' optimiser launches, exported so that they can be tested on their own.) */
+ERL_API int erl_clip_adam_soft_f32(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, const int64_t *group_off,
+                           const int64_t *group_len, int n_groups, int32_t step, float lr, float beta1, float beta2, float eps,
+                           float max_norm, float grad_scale, float *soft, float tau, void *stream);
+ERL_API int erl_clip_adam_parts_soft_f32(float *params, const float *grads, float *exp_avg, float *exp_avg_sq, int64_t len,
+                                 const double *parts, int nparts, int32_t step, float lr, float beta1, float beta2, float eps,
+                                 float max_norm, float *soft, float tau, void *stream);
 
 /* The optimiser tail of a PPO minibatch as TWO launches (csrc/grad_tail.hip; the default of erl_ppo_update_f32 /
  * erl_ppo_update_dp_f32 since round 3).  optimizer_backward = zero_grad / backward / clip_grad_norm_ / Adam.step

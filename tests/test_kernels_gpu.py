@@ -1073,8 +1073,14 @@ def test_ppo_step_objective_forms(ops, dev, S, h1, h2, A, objective):
 
 @pytest.mark.parametrize("n_a,n_c", [(25872, 24961), (279556, 70662), (70000, 5)])
 def test_clip_adam_matches_oracle(ops, dev, n_a, n_c):
-    """(25872, 24961): one element per thread; groups beyond 64 Ki elements take the partial-norm + grid-wait kernel (SAC's
-    critic ensemble and actor sizes), also next to a short group in the same launch."""
+    """What erl_clip_adam_form reports on the MI355X (asserted, so that a case cannot change kernels unnoticed):
+    (25872, 24961): 0, per-thread -- one element per thread, every workgroup re-derives the norm;
+    (279556, 70662), SAC's critic ensemble and actor sizes: 2, the LOOP form -- 274 x 2 = 548 workgroups of 1024 threads, and the device
+    holds 512 of clip_adam_grid_kernel at once (two per CU: four groups of 128 workgroups still wait on the grid, four of 129 do not), so
+    the grid-wait kernel is not taken;
+    (70000, 5): 1, grid-wait -- 69 x 2 = 138 workgroups, partial norms + a grid-wide wait, next to a short group in the same launch.
+    Every form bit for bit, with its moments: tests/test_clip_adam_forms_gpu.py."""
+    assert ops.clip_adam_form(max(n_a, n_c), 2) == {25872: ops.CLIP_ADAM_PER_THREAD, 279556: ops.CLIP_ADAM_LOOP, 70000: ops.CLIP_ADAM_GRID_WAIT}[n_a]
     rng = np.random.default_rng(9)
     p = rng.standard_normal(n_a + n_c).astype(np.float32)
     P, M1, M2 = cu(p, dev), th.zeros(n_a + n_c, device=dev), th.zeros(n_a + n_c, device=dev)
