@@ -200,6 +200,16 @@ _SIGNATURES = {
     "erl_td3_update_ring_f32": (c_int, _TD3_HEAD + [_P] + _SAC_BATCH + [c_int64, _P] + _SAC_KEY + _TD3_HYPER + [c_int32] * 3 + [_P] + _SAC_TAIL),
     "erl_td3_update_ring_loop_f32": (c_int, _TD3_HEAD + [_P, _P, c_int64] + _SAC_BATCH + [c_int64] + _SAC_KEY + _TD3_HYPER + [c_int32] * 4 +
                                             [_P, POINTER(c_int32)] + _SAC_TAIL),
+    # AgentTD3's / AgentDDPG's one-launch rollout / evaluation and their per-step twin (csrc/sac_fused.hip, the DET forms): the argument
+    # lists of the erl_sac_* twins, the rollouts with action_std in front of the stream
+    "erl_td3_rollout_supported": (c_int, [c_int, c_int, POINTER(c_int), c_int, c_int64]),
+    "erl_td3_explore_action_tile_f32": (c_int, [_P, c_int, c_int, POINTER(c_int), c_int, _P, c_int64, _P] + _SAC_KEY + [c_float, _P, _P] + _SAC_TAIL),
+    "erl_td3_rollout_synenv_f32": (c_int, _SAC_SYN + _SAC_ROLL_TAIL[:-1] + [c_float, _P]),
+    "erl_td3_rollout_pendulum_f32": (c_int, _SAC_PEN + _SAC_ROLL_TAIL[:-1] + [c_float, _P]),
+    "erl_td3_rollout_pointchasing_f32": (c_int, _SAC_PNT + _SAC_ROLL_TAIL[:-1] + [c_float, _P]),
+    "erl_td3_eval_synenv_f32": (c_int, _SAC_SYN + _EVAL_TAIL),
+    "erl_td3_eval_pendulum_f32": (c_int, _SAC_PEN + _EVAL_TAIL),
+    "erl_td3_eval_pointchasing_f32": (c_int, _SAC_PNT + _EVAL_TAIL),
     "erl_eval_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "erl_eval_synenv_f32": (c_int, [_P] * 3 + _PPO_SYN + _EVAL_TAIL),
     "erl_eval_pendulum_f32": (c_int, [_P] * 3 + _PPO_PEN + _EVAL_TAIL),

@@ -7,6 +7,9 @@ min over the target critic's heads, critic objective, clip + Adam, soft updates,
 and `update_net`'s loop can be ONE `erl_td3_update_ring_loop_f32` call.  The `nn.Module`s below describe the parameter layout (their
 tensors are views into the flat blocks the kernels read and write, in the order of the reference's `state_dict`) and serve the
 Evaluator's `actor(state)` and the checkpoints.  No torch fallback for the update math: its restatement lives in tests/td3_ref.py.
+Opt-in (`args.fused_td3_rollout`): the exploration action as one launch of a tile kernel (`erl_td3_explore_action_tile_f32`) and, on the
+device-resident continuous envs, the whole rollout and the whole evaluation as one launch each (`erl_td3_rollout_*_f32`,
+`erl_td3_eval_*_f32`: csrc/sac_fused.hip, the deterministic-actor forms of AgentSAC's persistent rollout kernel).
 
 The module is called AgentDDPG, not AgentTD3: `from elegantrl.agents import AgentTD3, AgentDDPG` is the path the reference's scripts use and
 the one supported; `import elegantrl.agents.AgentTD3` stays a ModuleNotFoundError.
@@ -76,13 +79,21 @@ class Critic(CriticTwin):
 class AgentTD3(_OffPolicyFlatAgent):
     """Twin Delayed DDPG (AgentTD3.py:15-70): `num_ensembles` (8) heads on one critic trunk, target-policy smoothing with
     `policy_noise_std` (0.10), the actor and its target updated every `update_freq`-th (2) step, exploration noise `explore_noise_std`
-    (0.05).  `update_path` / `rollout_path` name the route the last `update_net` / rollout took and, for a fallback, why."""
+    (0.05).  `update_path` / `rollout_path` name the route the last `update_net` / rollout took and, for a fallback, why.
+    With `fused_td3_rollout` on and inside erl_td3_rollout_supported's shapes, `explore_action` is the tile kernel
+    (erl_td3_explore_action_tile_f32) and, on SynVecEnv / PendulumVecEnv / PointChasingVecEnv with `fused_rollout`, `explore_env` and
+    `evaluate_env` are one launch each (erl_td3_rollout_*, erl_td3_eval_*: csrc/sac_fused.hip sac_rollout_synenv_kernel<.., DET>)."""
     # update_net's loop as ONE C call (erl_td3_update_ring_loop_f32), bit-identical to one erl_td3_update_ring_f32 call per step: the
     # default follows the A/B record (tools/td3_update_ab.py -> profiles/td3_update_ab.txt, DESIGN.md section 9);
     # args.td3_loop_in_c / ERL_TD3_LOOP_IN_C override it
     _loop_in_c_default = "0"
     _ring_loop_path = "one C call (erl_td3_update_ring_loop_f32: sample, step and the actor's delay rule per step inside the call)"
     _per_why = "prioritised replay (a prioritised one-call loop is out of scope): sample_for_per, erl_td3_update_f32, tree update per step"
+    # the one-launch rollout / evaluation and the tile action (erl_td3_rollout_*, erl_td3_eval_*, erl_td3_explore_action_tile_f32): opt-in
+    # -- args.fused_td3_rollout = True or ERL_FUSED_TD3_ROLLOUT=1 (tools/td3_rollout_ab.py writes profiles/td3_rollout_ab.txt); off, the
+    # rollout and the evaluation are the per-step loops on erl_td3_explore_action_f32.  The tile kernel sums a layer in another order
+    # than the layered path, so the switch changes a run's bits within the tolerance either has against fp64.
+    _fused_td3_rollout_default = "0"
 
     def __init__(self, net_dims: List[int], state_dim: int, action_dim: int, gpu_id: int = 0, args: Config = None):
         args = Config() if args is None else args
@@ -95,6 +106,10 @@ class AgentTD3(_OffPolicyFlatAgent):
         from .. import ops
         self._read_args(args)
         self.td3_loop_in_c = bool(getattr(args, "td3_loop_in_c", os.environ.get("ERL_TD3_LOOP_IN_C", self._loop_in_c_default) != "0"))
+        self.fused_td3_rollout = bool(getattr(args, "fused_td3_rollout",
+                                              os.environ.get("ERL_FUSED_TD3_ROLLOUT", self._fused_td3_rollout_default) != "0"))
+        # with the switch on, device-resident envs that offer it: the whole off-policy rollout as one launch (False: the per-step loop)
+        self.fused_rollout = bool(getattr(args, "fused_rollout", True))
         self._spec = ops.Td3Spec(state_dim, action_dim, net_dims, self.num_ensembles)
         dev, f32 = self.device, th.float32
         sp = self._spec
@@ -114,6 +129,11 @@ class AgentTD3(_OffPolicyFlatAgent):
         L = len(net_dims)
         self.kernel_path = (f"layered TD3 step (csrc/td3.hip: one MFMA GEMM launch per dense layer, {10 * L + 20} launches with the actor's "
                             f"update, {5 * L + 11} without)")
+        if self.fused_td3_rollout:
+            why = self._one_launch_agent_reason()
+            self.kernel_path += ("; rollout: one launch on device-resident envs, and so the evaluation (erl_td3_rollout_*, erl_td3_eval_*), "
+                                 "per-step action on the tile kernel (erl_td3_explore_action_tile_f32)" if why is None else
+                                 "; rollout: per-step loop: " + why)
         if not getattr(args, "quiet", False) and os.environ.get("ERL_QUIET", "0") == "0":
             print(f"| {type(self).__name__}: {self.kernel_path}", flush=True)
 
@@ -149,30 +169,93 @@ class AgentTD3(_OffPolicyFlatAgent):
     # ---- rollout ------------------------------------------------------------------------------------------
     @_hip.on_device
     def explore_action(self, state: TEN, noise: Optional[TEN] = None, out: Optional[TEN] = None, out_state: Optional[TEN] = None) -> TEN:
-        """Actor.get_action(state, explore_noise_std) in one launch (erl_td3_explore_action_f32); `noise` (n, action_dim) injects the
-        draw, else Philox keyed by (rng_seed, rng_counter, row, component).  `out` (n, action_dim) / `out_state` (n, state_dim),
-        contiguous: the kernel writes the action / a copy of `state` there (the rollout passes its buffer rows: no copies)"""
+        """Actor.get_action(state, explore_noise_std) (erl_td3_explore_action_f32: the layered path; with `fused_td3_rollout` and inside
+        its shapes erl_td3_explore_action_tile_f32: one launch); `noise` (n, action_dim) injects the draw, else Philox keyed by (rng_seed,
+        rng_counter, row, component).  `out` (n, action_dim) / `out_state` (n, state_dim), contiguous: the kernel writes the action / a
+        copy of `state` there (the rollout passes its buffer rows: no copies)"""
         from .. import ops
         self._sync_modules()
         action = ops.td3_explore_action(self._spec, self._actor_flat, state.contiguous(), self.explore_noise_std,
                                         noise=None if noise is None else noise.contiguous(), seed=self.rng_seed, counter=self.rng_counter,
-                                        out=out, out_state=out_state)
+                                        out=out, out_state=out_state, tile=self._tile_action_reason(state.shape[0]) is None)
         self.rng_counter += 1
         return action
 
-    _ROLLOUT_WHY = "one-launch rollouts are out of scope for AgentTD3 / AgentDDPG (DESIGN.md section 8)"
+    _SWITCH_OFF = "args.fused_td3_rollout is off (ERL_FUSED_TD3_ROLLOUT; profiles/td3_rollout_ab.txt)"
+
+    def _shape_reason(self, n_rows: int, what: str) -> Optional[str]:
+        """None when the deterministic-actor tile kernels cover this actor on `n_rows` rows, else why not"""
+        sp = self._spec
+        if _hip.lib().erl_td3_rollout_supported(sp.S, sp.A, sp._c, len(sp.hidden), int(n_rows)):
+            return None
+        return f"S={sp.S} A={sp.A} net_dims={list(self.net_dims)} rows={n_rows} outside {what}'s shapes"
+
+    def _one_launch_agent_reason(self) -> Optional[str]:
+        if not self.fused_td3_rollout:
+            return self._SWITCH_OFF
+        if not self.fused_rollout:
+            return "args.fused_rollout is off (the persistent rollout and its evaluation form go together)"
+        return self._shape_reason(self.num_envs, "the persistent off-policy rollout")
+
+    def _tile_action_reason(self, n_rows: int) -> Optional[str]:
+        """None when `explore_action` on `n_rows` states is erl_td3_explore_action_tile_f32 (the per-step twin of the one-launch rollouts),
+        else why it is the layered erl_td3_explore_action_f32"""
+        if not self.fused_td3_rollout:
+            return self._SWITCH_OFF
+        return self._shape_reason(n_rows, "the tile kernel")
+
+    def _loop_path(self, n_rows: int, env_call: str, why: str) -> str:
+        tile_why = self._tile_action_reason(n_rows)
+        if tile_why is None:
+            return f"per-step loop (tile action erl_td3_explore_action_tile_f32 + {env_call} per step): {why}"
+        return f"per-step loop (erl_td3_explore_action_f32 + {env_call} per step): {why if why == tile_why else why + '; ' + tile_why}"
 
     @_hip.on_device
     def _explore_vec_env(self, env, horizon_len: int, noise: Optional[TEN] = None) -> Tuple[TEN, ...]:
-        """AgentBase._explore_vec_env (AgentBase.py:130-170) as a per-step loop on any env of the vector protocol (`step_into` where the
-        env has it): one erl_td3_explore_action_f32 launch writes the action and the state row, then the env steps"""
-        self.rollout_path = f"per-step loop (erl_td3_explore_action_f32 + env.{'step_into' if hasattr(env, 'step_into') else 'step'} per step): {self._ROLLOUT_WHY}"
-        return super()._explore_vec_env(env, horizon_len, noise)
+        """AgentBase._explore_vec_env (AgentBase.py:130-170).  With `fused_td3_rollout`, on a device-resident env that offers
+        `fused_rollout_offpolicy`, the whole loop is ONE launch (erl_td3_rollout_*_f32: the five tensors, the final state and the env's
+        counters of the per-step loop on the tile action, bit for bit; `args.fused_rollout = False` keeps the loop).  Else a per-step loop
+        on any env of the vector protocol (`step_into` where the env has it): one explore_action launch writes the action and the state
+        row, then the env steps.  `rollout_path` says which route ran and, for the loop, why."""
+        H, N, S, A, dev = horizon_len, self.num_envs, self.state_dim, self.action_dim, self.device
+        why = self._one_launch_reason(env, "fused_rollout_offpolicy")
+        if why is not None:
+            self._last_state_token = None
+            self.rollout_path = self._loop_path(N, f"env.{'step_into' if hasattr(env, 'step_into') else 'step'}", why)
+            return super()._explore_vec_env(env, horizon_len, noise)
+        self.rollout_path = f"one launch (erl_td3_rollout_*_f32 through {type(env).__name__}.fused_rollout_offpolicy)"
+        self._sync_modules()
+        state = self.last_state.to(dev, th.float32)
+        assert state.shape == (N, S)
+        self._hand_state_to_env(env, state)
+        states = th.empty((H, N, S), dtype=th.float32, device=dev)
+        actions = th.empty((H, N, A), dtype=th.float32, device=dev)
+        rewards = th.empty((H, N), dtype=th.float32, device=dev)
+        undones = th.empty((H, N), dtype=th.bool, device=dev)
+        unmasks = th.empty((H, N), dtype=th.bool, device=dev)
+        last_out = th.empty((N, S), dtype=th.float32, device=dev)
+        env.fused_rollout_offpolicy(self, H, None if noise is None else noise.contiguous(), (states, actions, rewards, undones, unmasks), last_out)
+        self.rng_counter += H
+        self._record_last_state(env, last_out)
+        return states, actions, rewards, undones, unmasks
 
     @_hip.on_device
     def _explore_one_env(self, env, horizon_len: int) -> Tuple[TEN, ...]:
-        self.rollout_path = f"per-step loop (erl_td3_explore_action_f32 + env.step per step, one numpy env): {self._ROLLOUT_WHY}"
+        self.rollout_path = self._loop_path(1, "env.step", "one numpy env")
         return super()._explore_one_env(env, horizon_len)
+
+    def _fused_eval_reason(self, env) -> Optional[str]:
+        """None when `evaluate_env(env)` runs the fused evaluation, else why not"""
+        return self._one_launch_reason(env, "fused_evaluate_offpolicy")
+
+    @_hip.on_device
+    def evaluate_env(self, env) -> Optional[TEN]:
+        """AgentBase.evaluate_env on the persistent rollout's evaluation form (erl_td3_eval_*_f32): env.reset(), env.max_step steps of
+        Actor.forward in one launch, the episode table from a second; None outside its shapes or with `fused_td3_rollout` off."""
+        if self._fused_eval_reason(env) is not None:
+            return None
+        self._sync_modules()
+        return self._evaluate_env_fused(env, lambda ws: env.fused_evaluate_offpolicy(self, int(env.max_step), ws))
 
     # ---- update -------------------------------------------------------------------------------------------
     def _nets(self) -> tuple:

@@ -80,7 +80,15 @@ int erl_sac_rollout_fused(const float *actor_params, int S, int A, int h0, int h
                           float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, hipStream_t stream,
                           float2 *ev_rec = nullptr, int32_t *ev_cnt = nullptr,        // ev_*: the evaluation form (eval_ws.h)
                           int variant = 0,                                            // ERL_SAC_ACTOR_FIX: ActorFixSAC (AgentModSAC)
-                          int env_kind = 0);                                          // ContEnv::kind (cont_env_args.h): whose `phys` this is
+                          int env_kind = 0,                                           // ContEnv::kind (cont_env_args.h): whose `phys` this is
+                          float action_std = 0.f,                                     // ERL_ROLLOUT_ACTOR_DET: Actor.get_action's std
+                          const char *what = nullptr);                                // the entry a failed launch is reported under (NULL: erl_sac_rollout_synenv_f32)
+// `variant` beside ERL_SAC_ACTOR_SAC / ERL_SAC_ACTOR_FIX, inside the library only: the deterministic Actor of AgentTD3 / AgentDDPG
+// (build_mlp([S, h0, h1, A]) with tanh on top), behind erl_td3_rollout_*_f32 / erl_td3_eval_*_f32
+#define ERL_ROLLOUT_ACTOR_DET 2
+int erl_td3_explore_tile_fused(const float *actor_params, int S, int A, int h0, int h1, const int64_t *aoff, const float *state, int64_t N,
+                               const float *noise, uint64_t seed, uint64_t counter, float action_std, float *action_out, float *state_out,
+                               hipStream_t stream);
 int64_t erl_sac_fused_ws_floats(int S, int A, int h0, int h1, int E, int64_t B, int64_t Pa, int64_t Pc);
 int erl_sac_explore_fused(const float *actor_params, int S, int A, int h0, int h1, const int64_t *aoff, const float *state, int64_t N,
                           const float *noise, uint64_t seed, uint64_t counter, float *action_out, float *state_out, float *lp_scratch,

@@ -862,6 +862,12 @@ static int sac_rollout_layout(const char *what, int variant, bool terse, int S, 
                            "ERL_SAC_FUSED=0 turns it off)", what, S, A, (long long)N);
         return ERL_EINVAL;
     }
+    if (variant == ERL_ROLLOUT_ACTOR_DET) {              // Actor = build_mlp([S, h0, h1, A]) (AgentTD3.py:126-136): W b W b W b, the head A wide
+        const int dims[4] = {S, hidden[0], hidden[1], A};
+        int64_t o = 0;
+        for (int l = 0; l < 3; ++l) { aoff[2 * l] = o; o += (int64_t)dims[l + 1] * dims[l]; aoff[2 * l + 1] = o; o += dims[l + 1]; }
+        return ERL_OK;
+    }
     SacDims d;
     ERL_REQUIRE(make_sac_dims(S, A, hidden, n_hidden, 1, &d, variant), "%s: unsupported dims", what);
     for (int l = 0; l < 3; ++l) { aoff[2 * l] = d.actor.oW[l]; aoff[2 * l + 1] = d.actor.ob[l]; }
@@ -875,64 +881,81 @@ static int sac_rollout_layout(const char *what, int variant, bool terse, int S, 
 static int sac_rollout_impl(const char *what, int variant, const float *actor_params, int S, int A, const int *hidden, int n_hidden,
                             const ContEnv &e, int64_t N, int64_t H, const float *noise, uint64_t seed, uint64_t counter0, float reward_scale,
                             float *out_states, float *out_actions, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks,
-                            float *out_last_state, void *stream)
+                            float *out_last_state, void *stream, float action_std = 0.f)
 {
     ERL_REQUIRE(actor_params && out_states && out_actions && out_rewards && out_undones && out_unmasks, "%s: NULL tensor", what);
     if (int rc = cont_env_check(what, e, false)) return rc;
     int64_t aoff[6];
     if (int rc = sac_rollout_layout(what, variant, e.kind == ENV_PENDULUM, S, A, hidden, n_hidden, N, aoff)) return rc;
     ERL_REQUIRE(H >= 1 && H < (1LL << 30) && e.max_step >= 1, "%s: bad H=%lld max_step=%d", what, (long long)H, e.max_step);
+    ERL_REQUIRE(action_std >= 0.f && action_std < INFINITY, "%s: action_std=%g", what, (double)action_std);
     return erl_sac_rollout_fused(actor_params, S, A, hidden[0], hidden[1], aoff, e.env_state, e.Ws, e.Wa, e.phys, e.step_count, e.episode,
                                  e.max_step, e.env_seed, N, H, noise, seed, counter0, reward_scale, out_states, out_actions, out_rewards,
-                                 out_undones, out_unmasks, out_last_state, (hipStream_t)stream, nullptr, nullptr, variant, e.kind);
+                                 out_undones, out_unmasks, out_last_state, (hipStream_t)stream, nullptr, nullptr, variant, e.kind, action_std,
+                                 variant == ERL_ROLLOUT_ACTOR_DET ? what : nullptr);
 }
 
 #define SAC_SYNENV {ENV_SYN, env_state, nullptr, Ws, Wa, step_count, episode, max_step, env_seed}
 #define SAC_PENDULUM {ENV_PENDULUM, obs, phys, nullptr, nullptr, step_count, episode, max_step, env_seed}
 #define SAC_POINT {ENV_POINT, state, distance, nullptr, nullptr, step_count, episode, max_step, env_seed}
-#define SAC_ROLLOUT_SYNENV(NAME, VARIANT)                                                                                                    \
+// STD_DECL / STD: the erl_td3_rollout_* entries name `float action_std` in front of the stream (SAC_TD3_STD), the others nothing (SAC_NO_STD)
+#define SAC_NO_STD
+#define SAC_TD3_STD float action_std,
+#define SAC_ROLLOUT_SYNENV(NAME, VARIANT, STD_DECL, STD)                                                                                     \
     extern "C" int NAME(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state, const float *Ws,         \
                         const float *Wa, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,       \
                         const float *noise, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states, float *out_actions,     \
-                        float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, void *stream)                 \
+                        float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, STD_DECL void *stream)        \
     {                                                                                                                                        \
         return sac_rollout_impl(#NAME, VARIANT, actor_params, S, A, hidden, n_hidden, SAC_SYNENV, N, H, noise, seed, counter0, reward_scale, \
-                                out_states, out_actions, out_rewards, out_undones, out_unmasks, out_last_state, stream);                     \
+                                out_states, out_actions, out_rewards, out_undones, out_unmasks, out_last_state, stream, STD);                \
     }
 // the same loop on the device-resident PendulumVecEnv (S = 3, A = 1; phys: (N, 2) theta, theta_dot; obs: (N, 3) the live observation)
-#define SAC_ROLLOUT_PENDULUM(NAME, VARIANT)                                                                                                  \
+#define SAC_ROLLOUT_PENDULUM(NAME, VARIANT, STD_DECL, STD)                                                                                   \
     extern "C" int NAME(const float *actor_params, const int *hidden, int n_hidden, float *phys, float *obs, int32_t *step_count,            \
                         int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H, const float *noise, uint64_t seed,          \
                         uint64_t counter0, float reward_scale, float *out_states, float *out_actions, float *out_rewards,                    \
-                        uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, void *stream)                                     \
+                        uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, STD_DECL void *stream)                            \
     {                                                                                                                                        \
         return sac_rollout_impl(#NAME, VARIANT, actor_params, 3, 1, hidden, n_hidden, SAC_PENDULUM, N, H, noise, seed, counter0,             \
-                                reward_scale, out_states, out_actions, out_rewards, out_undones, out_unmasks, out_last_state, stream);       \
+                                reward_scale, out_states, out_actions, out_rewards, out_undones, out_unmasks, out_last_state, stream, STD);  \
     }
 // ... on the device-resident PointChasingVecEnv (S = 4 A, A = dim in 1..4; state: (N, S) the live observation; distance: (N,) the carried |p0 - p1|)
-#define SAC_ROLLOUT_POINT(NAME, VARIANT)                                                                                                     \
+#define SAC_ROLLOUT_POINT(NAME, VARIANT, STD_DECL, STD)                                                                                      \
     extern "C" int NAME(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *state, float *distance,             \
                         int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H, const float *noise,    \
                         uint64_t seed, uint64_t counter0, float reward_scale, float *out_states, float *out_actions, float *out_rewards,     \
-                        uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, void *stream)                                     \
+                        uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, STD_DECL void *stream)                            \
     {                                                                                                                                        \
         if (int rc = cont_env_point_dims(#NAME, S, A)) return rc;                                                                            \
         return sac_rollout_impl(#NAME, VARIANT, actor_params, S, A, hidden, n_hidden, SAC_POINT, N, H, noise, seed, counter0, reward_scale,  \
-                                out_states, out_actions, out_rewards, out_undones, out_unmasks, out_last_state, stream);                     \
+                                out_states, out_actions, out_rewards, out_undones, out_unmasks, out_last_state, stream, STD);                \
     }
-SAC_ROLLOUT_SYNENV(erl_sac_rollout_synenv_f32, ERL_SAC_ACTOR_SAC)
-SAC_ROLLOUT_PENDULUM(erl_sac_rollout_pendulum_f32, ERL_SAC_ACTOR_SAC)
+SAC_ROLLOUT_SYNENV(erl_sac_rollout_synenv_f32, ERL_SAC_ACTOR_SAC, SAC_NO_STD, 0.f)
+SAC_ROLLOUT_PENDULUM(erl_sac_rollout_pendulum_f32, ERL_SAC_ACTOR_SAC, SAC_NO_STD, 0.f)
 // ActorFixSAC.get_action (AgentSAC.py:217-224) in the same launches: AgentModSAC's rollout
-SAC_ROLLOUT_SYNENV(erl_sac_rollout_mod_synenv_f32, ERL_SAC_ACTOR_FIX)
-SAC_ROLLOUT_PENDULUM(erl_sac_rollout_mod_pendulum_f32, ERL_SAC_ACTOR_FIX)
-SAC_ROLLOUT_POINT(erl_sac_rollout_pointchasing_f32, ERL_SAC_ACTOR_SAC)
-SAC_ROLLOUT_POINT(erl_sac_rollout_mod_pointchasing_f32, ERL_SAC_ACTOR_FIX)
+SAC_ROLLOUT_SYNENV(erl_sac_rollout_mod_synenv_f32, ERL_SAC_ACTOR_FIX, SAC_NO_STD, 0.f)
+SAC_ROLLOUT_PENDULUM(erl_sac_rollout_mod_pendulum_f32, ERL_SAC_ACTOR_FIX, SAC_NO_STD, 0.f)
+SAC_ROLLOUT_POINT(erl_sac_rollout_pointchasing_f32, ERL_SAC_ACTOR_SAC, SAC_NO_STD, 0.f)
+SAC_ROLLOUT_POINT(erl_sac_rollout_mod_pointchasing_f32, ERL_SAC_ACTOR_FIX, SAC_NO_STD, 0.f)
+// Actor.get_action(state, action_std) of AgentTD3 / AgentDDPG (AgentTD3.py:132-136) in the same launches (sac_rollout_synenv_kernel<.., DET>)
+SAC_ROLLOUT_SYNENV(erl_td3_rollout_synenv_f32, ERL_ROLLOUT_ACTOR_DET, SAC_TD3_STD, action_std)
+SAC_ROLLOUT_PENDULUM(erl_td3_rollout_pendulum_f32, ERL_ROLLOUT_ACTOR_DET, SAC_TD3_STD, action_std)
+SAC_ROLLOUT_POINT(erl_td3_rollout_pointchasing_f32, ERL_ROLLOUT_ACTOR_DET, SAC_TD3_STD, action_std)
 #undef SAC_ROLLOUT_SYNENV
 #undef SAC_ROLLOUT_PENDULUM
 #undef SAC_ROLLOUT_POINT
+#undef SAC_NO_STD
+#undef SAC_TD3_STD
 
 // the ActorFixSAC launches cover the shapes of their AgentSAC twins
 extern "C" int erl_sac_rollout_mod_supported(int S, int A, const int *hidden, int n_hidden, int64_t N)
+{
+    return erl_sac_rollout_synenv_supported(S, A, hidden, n_hidden, N);
+}
+
+// ... and so do the deterministic actor's (erl_td3_rollout_*_f32, erl_td3_eval_*_f32, erl_td3_explore_action_tile_f32)
+extern "C" int erl_td3_rollout_supported(int S, int A, const int *hidden, int n_hidden, int64_t N)
 {
     return erl_sac_rollout_synenv_supported(S, A, hidden, n_hidden, N);
 }
@@ -955,7 +978,7 @@ static int sac_eval_impl(const char *what, int variant, const float *actor_param
     const ErlEvalWs w = erl_eval_ws_layout(workspace, N, H);
     return erl_sac_rollout_fused(actor_params, S, A, hidden[0], hidden[1], aoff, e.env_state, e.Ws, e.Wa, e.phys, e.step_count, e.episode,
                                  e.max_step, e.env_seed, N, H, nullptr, 0, 0, 1.0f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                 (hipStream_t)stream, w.rec, w.cnt, variant, e.kind);
+                                 (hipStream_t)stream, w.rec, w.cnt, variant, e.kind, 0.f, variant == ERL_ROLLOUT_ACTOR_DET ? what : nullptr);
 }
 
 #define SAC_EVAL_SYNENV(NAME, VARIANT)                                                                                                       \
@@ -986,6 +1009,10 @@ SAC_EVAL_SYNENV(erl_sac_eval_mod_synenv_f32, ERL_SAC_ACTOR_FIX)
 SAC_EVAL_PENDULUM(erl_sac_eval_mod_pendulum_f32, ERL_SAC_ACTOR_FIX)
 SAC_EVAL_POINT(erl_sac_eval_pointchasing_f32, ERL_SAC_ACTOR_SAC)
 SAC_EVAL_POINT(erl_sac_eval_mod_pointchasing_f32, ERL_SAC_ACTOR_FIX)
+// Actor.forward of AgentTD3 / AgentDDPG: tanh of the A head outputs
+SAC_EVAL_SYNENV(erl_td3_eval_synenv_f32, ERL_ROLLOUT_ACTOR_DET)
+SAC_EVAL_PENDULUM(erl_td3_eval_pendulum_f32, ERL_ROLLOUT_ACTOR_DET)
+SAC_EVAL_POINT(erl_td3_eval_pointchasing_f32, ERL_ROLLOUT_ACTOR_DET)
 #undef SAC_EVAL_SYNENV
 #undef SAC_EVAL_PENDULUM
 #undef SAC_EVAL_POINT
@@ -1060,4 +1087,22 @@ extern "C" int erl_sac_explore_action_tile_f32(const float *actor_params, int S,
     const int64_t aoff[6] = {d.actor.oW[0], d.actor.ob[0], d.actor.oW[1], d.actor.ob[1], d.actor.oW[2], d.actor.ob[2]};
     return erl_sac_explore_fused(actor_params, S, A, hidden[0], hidden[1], aoff, state, N, noise, seed, counter, action_out, state_out, lp_s,
                                  (hipStream_t)stream, variant);
+}
+
+// Actor.get_action(state, action_std) of AgentTD3 / AgentDDPG on the tile kernel (sac_fused.hip det_actor_tile_kernel: one launch, 16 rows per
+// workgroup) -- the per-step twin of erl_td3_rollout_*_f32, bit for bit.  Arguments of erl_td3_explore_action_f32 (td3.hip), which keeps
+// its layered route and its bits; `workspace` is not read here (the kernel keeps nothing) and may be NULL.  Outside
+// erl_td3_rollout_supported the call is refused: there is no layered form here.
+extern "C" int erl_td3_explore_action_tile_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, const float *state,
+                                               int64_t N, const float *noise, uint64_t seed, uint64_t counter, float action_std,
+                                               float *action_out, float *state_out, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    const char *const what = "erl_td3_explore_action_tile_f32";
+    (void)workspace; (void)workspace_bytes;
+    ERL_REQUIRE(actor_params && state && action_out && hidden, "%s: NULL tensor", what);
+    int64_t aoff[6];
+    if (int rc = sac_rollout_layout(what, ERL_ROLLOUT_ACTOR_DET, false, S, A, hidden, n_hidden, N, aoff)) return rc;
+    ERL_REQUIRE(action_std >= 0.f && action_std < INFINITY, "%s: action_std=%g", what, (double)action_std);
+    return erl_td3_explore_tile_fused(actor_params, S, A, hidden[0], hidden[1], aoff, state, N, noise, seed, counter, action_std, action_out,
+                                      state_out, (hipStream_t)stream);
 }

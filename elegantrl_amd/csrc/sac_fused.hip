@@ -40,6 +40,8 @@
 // and its options (SacCall / SacStep): the actor's own Adam count, its target's soft update behind that step, and -- on the steps its two-time-scale
 // rule skips -- one small launch (sac_skip_finish_kernel) in place of launches (7)-(10).  Its rollout and evaluation are the FIX forms of the
 // persistent rollout (a template parameter there: sac_rollout_synenv_kernel).
+// AgentTD3 / AgentDDPG (elegantrl/agents/AgentTD3.py) update on the layered path (td3.hip); their rollout and evaluation are the DET forms
+// of the persistent rollout, and det_actor_tile_kernel is one step of those as a launch of its own.
 #include "cont_env_args.h"
 #include "mlpn_common.h"
 #include "per_draw.h"
@@ -1391,12 +1393,18 @@ struct SacRolloutArgs {
     // of episodes each env finished (eval_ws.h)
     float2 *ev_rec;
     int32_t *ev_cnt;
+    float action_std;                              // DET forms: Actor.get_action's std (the last member: nothing the other forms read moved)
 };
 
 constexpr int SR_XLD = 68, SR_WLD = 68;
 // dynamic LDS (floats): [XS 16 x 68][WST 64 x 68][WAT 64 x 16][ACT 16 x 16][RED 8 x 16 x 2][W1L 256 x 68: the actor's first layer][BIA 3 x 256: b1 | b2 | head bias]
 constexpr int SR_O_XS = 0, SR_O_WST = SR_O_XS + 16 * SR_XLD, SR_O_WAT = SR_O_WST + 64 * SR_WLD, SR_O_ACT = SR_O_WAT + 64 * 16;
 constexpr int SR_O_RED = SR_O_ACT + 16 * 16, SR_O_W1L = SR_O_RED + 8 * 16 * 2, SR_O_BIA = SR_O_W1L + FMAXW * SR_WLD, SR_FLOATS = SR_O_BIA + 3 * FMAXW;
+// the DET forms add [WHL 2 x 512 x 4: every thread's eight head weights] behind it: held in registers across the loop, as the other forms
+// hold them, they put the [256,256] SynVecEnv training form into scratch (profiles/td3_rollout_kernel_resources.txt)
+constexpr int SR_O_WHL = SR_FLOATS, SR_FLOATS_DET = SR_FLOATS + 2 * FT * 4;
+static_assert(SR_O_WHL % 4 == 0, "WHL is read and written as float4");
+static_assert(sizeof(float) * SR_FLOATS_DET + sizeof(float) * (2 * TS * LDT + FWV * TS * 16 + TS * 16 + FWV) <= 160 * 1024, "a CU's LDS");
 
 enum { SR_ENV_SYN = 0, SR_ENV_PENDULUM = 1, SR_ENV_POINT = 2 };
 static_assert(SR_ENV_SYN == ENV_SYN && SR_ENV_PENDULUM == ENV_PENDULUM && SR_ENV_POINT == ENV_POINT, "the launcher is handed ContEnv::kind");
@@ -1413,9 +1421,26 @@ static_assert(SR_ENV_SYN == ENV_SYN && SR_ENV_PENDULUM == ENV_PENDULUM && SR_ENV
 // is ActorFixSAC.forward.  A template parameter, not the run-time value ActorFwdArgs::variant is: as a run-time value it cost every
 // training form two registers and put the [256,256] SynVecEnv one, which sits at 255, into scratch
 // (profiles/modsac_rollout_kernel_resources.txt); this way the ActorSAC instantiations are the code they were.
-template <int C0, int C1, int ENV, bool EV = false, bool FIX = false>
+//
+// DET (behind erl_td3_rollout_*_f32 / erl_td3_eval_*_f32): the deterministic actor of AgentTD3 / AgentDDPG, Actor = build_mlp([S, h0, h1, A])
+// with tanh on top (AgentTD3.py:126-136) -- ActorSAC's layers with a head A wide instead of 2 A, both hidden layers activated; the training
+// action is det_action below (td3.hip td3_action_kernel's statements: clip(tanh(y) + action_std * eps, -1, 1), plain tanh(y) at
+// action_std == 0), the EV action tanh(y).  A template parameter for FIX's reason (profiles/td3_rollout_kernel_resources.txt): the
+// other instantiations are the code they were.
+// one component of Actor.get_action on the head's output y; `eps` is read only where std != 0
+template <typename Y, typename Eps>
+__device__ __forceinline__ float det_action(Y y, float std, Eps eps)
+{
+    float t = tanhf(y());
+    if (std != 0.f) t = fminf(fmaxf(t + std * eps(), -1.f), 1.f);
+    return t;
+}
+
+template <int C0, int C1, int ENV, bool EV = false, bool FIX = false, bool DET = false>
 __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g)
 {
+    static_assert(!(FIX && DET), "one actor form per instantiation");
+    constexpr int HW = DET ? 1 : 2;                        // the head's width in units of A
     __shared__ TileLds lds;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *XS = smem + SR_O_XS, *WST = smem + SR_O_WST, *WAT = smem + SR_O_WAT, *ACT = smem + SR_O_ACT, *RED = smem + SR_O_RED, *W1L = smem + SR_O_W1L, *BIA = smem + SR_O_BIA;
@@ -1430,7 +1455,11 @@ __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g
     FwdW<WClass<C0>::KT, WClass<C1>::NU> w2;
     SmallW wh;
     layer_fwd_load<WClass<C0>::KT, WClass<C1>::NU, true>(g.P + d.aW2, d.h0, d.h1, L, w2);
-    layer_small_load<false, true>(g.P + d.aWh, d.h1, 2 * d.A, 0, 0, L, wh);
+    layer_small_load<false, true>(g.P + d.aWh, d.h1, HW * d.A, 0, 0, L, wh);
+    if constexpr (DET) {                                   // ... and the head's wait in LDS too, each thread's own eight (SR_O_WHL)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) *reinterpret_cast<float4 *>(smem + SR_O_WHL + (u * FT + L.tid) * 4) = make_float4(wh.v[u][0], wh.v[u][1], wh.v[u][2], wh.v[u][3]);
+    }
     clear_images(lds.T0, lds.T1, L);
     for (int e = L.tid; e < 16 * 64; e += FT) {            // state tile (rows past N: env N - 1), zero beyond S
         const int i = e >> 6, k = e & 63;
@@ -1454,7 +1483,7 @@ __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g
     }
     for (int e = L.tid; e < 3 * FMAXW; e += FT) {          // the biases too (read per step: hoisted out of the loop they would be 24 more registers)
         const int which = e / FMAXW, k = e - which * FMAXW;
-        const int n = which == 0 ? d.h0 : (which == 1 ? d.h1 : 2 * A);
+        const int n = which == 0 ? d.h0 : (which == 1 ? d.h1 : HW * A);
         BIA[e] = k < n ? g.P[(which == 0 ? d.ab1 : (which == 1 ? d.ab2 : d.abh)) + min(k, n - 1)] : 0.f;
     }
     const float *wst_row = WST + ((16 * L.wave + L.l15) & 63) * SR_WLD + 4 * L.q, *wat_row = WAT + ((16 * L.wave + L.l15) & 63) * 16 + 4 * L.q;
@@ -1500,14 +1529,34 @@ __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g
         layer_fwd_mma<WClass<C0>::KT, WClass<C1>::NU, true>(w2, BIA + FMAXW, d.h0, d.h1, lds.T1, L, z);
         emit_hidden(z, d.h1, !FIX, lds.T0, gk, nullptr, nullptr, row, valid, L);
         lds_barrier();
-        layer_small_mma<false, true>(wh, BIA + 2 * FMAXW, d.h1, 2 * d.A, lds.T0, lds.part, lds.Yl, L);
+        if constexpr (DET) {                               // (the values layer_small_load left: the same operands, read back per step)
+            SmallW whs;
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const float4 v = *reinterpret_cast<const float4 *>(smem + SR_O_WHL + (u * FT + L.tid) * 4);
+                whs.v[u][0] = v.x; whs.v[u][1] = v.y; whs.v[u][2] = v.z; whs.v[u][3] = v.w;
+            }
+            layer_small_mma<false, true>(whs, BIA + 2 * FMAXW, d.h1, HW * d.A, lds.T0, lds.part, lds.Yl, L);
+        } else {
+            layer_small_mma<false, true>(wh, BIA + 2 * FMAXW, d.h1, HW * d.A, lds.T0, lds.part, lds.Yl, L);
+        }
         if (L.tid < TS) {                                  // actor_fwd_kernel's tail: action = tanh(mean + std * eps)
             const int64_t b = row0 + L.tid, bc = min(b, N - 1);
             if constexpr (EV) {                            // ActorSAC.forward (AgentSAC.py:47-48): tanh of the first A head outputs (ActorFixSAC.forward: decoder_a_avg is that row half)
 #pragma unroll 1
                 for (int a = 0; a < A; ++a) ACT[L.tid * 16 + a] = tanhf(lds.Yl[L.tid * 16 + a]);
             }
-            for (int a = 0; !EV && a < A; ++a) {
+            if constexpr (DET && !EV) {                    // Actor.get_action (td3.hip td3_action_kernel; the tile twin: det_actor_tile_kernel)
+#pragma unroll 1
+                for (int a = 0; a < A; ++a) {
+                    const float tv = det_action([&] { return lds.Yl[L.tid * 16 + a]; }, g.action_std, [&] {
+                        return g.noise ? g.noise[((size_t)t * N + bc) * A + a] : philox_normal(g.seed, g.counter0 + (uint64_t)t, (uint32_t)bc, (uint32_t)a);
+                    });
+                    ACT[L.tid * 16 + a] = tv;
+                    if (b < N) g.o_actions[((size_t)t * N + b) * A + a] = tv;
+                }
+            }
+            for (int a = 0; !EV && !DET && a < A; ++a) {
                 const float mean = lds.Yl[L.tid * 16 + a], ls = lds.Yl[L.tid * 16 + A + a];
                 const float lsc = fminf(fmaxf(ls, FIX ? -20.f : -16.f), 2.f);
                 const float sd = expf(lsc);
@@ -1681,6 +1730,62 @@ __global__ __launch_bounds__(FT) void sac_rollout_synenv_kernel(SacRolloutArgs g
             g.phys[2 * prow] = th;
             g.phys[2 * prow + 1] = thdot;
         } else g.phys[prow] = pdist;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Actor.get_action of AgentTD3 / AgentDDPG on 16 state rows per workgroup: ONE step of the DET rollout above as a launch of its own
+// (erl_td3_explore_action_tile_f32) -- the layer calls of actor_fwd_body in their order with a head A wide and det_action as the tail,
+// so a per-step loop on it and the one-launch rollout agree bit for bit under the same Philox keys / injected noise.  A kernel of its
+// own, not a form of actor_fwd_body: that one is the first launch of the SAC step and stays the code it was.
+// ---------------------------------------------------------------------------------------------------------
+struct DetTileArgs {
+    const float *P;
+    FusedDims d;                   // B = number of rows; aWh / abh: the A-wide head
+    const float *X;                // (B, S)
+    float *Xcopy;                  // (B, S) or NULL: the rollout's states[t] = state
+    const float *noise;            // (B, A) or NULL: Philox keyed by (seed, counter, row, a)
+    uint64_t seed, counter;
+    float action_std;
+    float *act;                    // (B, A)
+};
+
+template <int C0, int C1>
+__global__ __launch_bounds__(FT) void det_actor_tile_kernel(DetTileArgs g)
+{
+    __shared__ TileLds lds;
+    const LaneId L = lane_id();
+    const FusedDims &d = g.d;
+    const int64_t row0 = (int64_t)blockIdx.x * TS, row = row0 + L.l15;
+    const bool valid = row < d.B;
+    FwdW<4, WClass<C0>::NU> w1;
+    FwdW<WClass<C0>::KT, WClass<C1>::NU> w2;
+    SmallW wh;
+    layer_fwd_load<4, WClass<C0>::NU, false>(g.P + d.aW1, d.S, d.h0, L, w1);
+    layer_fwd_load<WClass<C0>::KT, WClass<C1>::NU, true>(g.P + d.aW2, d.h0, d.h1, L, w2);
+    layer_small_load<false, true>(g.P + d.aWh, d.h1, d.A, 0, 0, L, wh);
+    clear_images(lds.T0, lds.T1, L);
+    lds_barrier();
+    load_rows(g.X, d.S, nullptr, 0, row0, d.B, lds.T0, g.Xcopy, L);
+    lds_barrier();
+    f32x4 z[2], gk[2];
+    layer_fwd_mma<4, WClass<C0>::NU, false>(w1, g.P + d.ab1, d.S, d.h0, lds.T0, L, z);
+    emit_hidden(z, d.h0, true, lds.T1, gk, nullptr, nullptr, row, valid, L);
+    lds_barrier();
+    layer_fwd_mma<WClass<C0>::KT, WClass<C1>::NU, true>(w2, g.P + d.ab2, d.h0, d.h1, lds.T1, L, z);
+    emit_hidden(z, d.h1, true, lds.T0, gk, nullptr, nullptr, row, valid, L);
+    lds_barrier();
+    layer_small_mma<false, true>(wh, g.P + d.abh, d.h1, d.A, lds.T0, lds.part, lds.Yl, L);
+    if (L.tid < TS) {
+        const int64_t b = row0 + L.tid;
+        if (b < d.B) {
+            const int A = d.A;
+#pragma unroll 1
+            for (int a = 0; a < A; ++a)
+                g.act[b * A + a] = det_action([&] { return lds.Yl[L.tid * 16 + a]; }, g.action_std, [&] {
+                    return g.noise ? g.noise[b * A + a] : philox_normal(g.seed, g.counter, (uint32_t)b, (uint32_t)a);
+                });
+        }
     }
 }
 
@@ -1956,7 +2061,7 @@ int erl_sac_rollout_fused(const float *actor_params, int S, int A, int h0, int h
                           const float *Wa, float *phys, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
                           const float *noise, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states, float *out_actions,
                           float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, hipStream_t stream,
-                          float2 *ev_rec, int32_t *ev_cnt, int variant, int env_kind)
+                          float2 *ev_rec, int32_t *ev_cnt, int variant, int env_kind, float action_std, const char *what)
 {
     FusedDims d{};
     d.S = S; d.A = A; d.E = 1; d.h0 = h0; d.h1 = h1; d.B = N;
@@ -1966,21 +2071,29 @@ int erl_sac_rollout_fused(const float *actor_params, int S, int A, int h0, int h
     g.o_states = out_states; g.o_actions = out_actions; g.o_rewards = out_rewards; g.o_undones = out_undones; g.o_unmasks = out_unmasks;
     g.o_last_state = out_last_state; g.env_state = env_state; g.Ws = Ws; g.Wa = Wa; g.phys = phys; g.step_count = step_count; g.episode = episode;
     g.max_step = max_step; g.env_seed = env_seed;
-    g.ev_rec = ev_rec; g.ev_cnt = ev_cnt;
+    g.ev_rec = ev_rec; g.ev_cnt = ev_cnt; g.action_std = action_std;
     const dim3 grid((unsigned)((N + TS - 1) / TS)), blk(FT);
-    const size_t lds_bytes = (size_t)SR_FLOATS * sizeof(float);
-    static bool attr[2][2][3][9] = {};                   // (the dynamic part alone is beyond 64 KB)
-#define LAUNCH_SAC_ROLLOUT_E(K0, K1, ENV_, EVAL_, FIX_)                                                                         \
+    const size_t lds_bytes = (size_t)(variant == ERL_ROLLOUT_ACTOR_DET ? SR_FLOATS_DET : SR_FLOATS) * sizeof(float);
+    static bool attr[3][2][3][9] = {};                   // (the dynamic part alone is beyond 64 KB)
+#define LAUNCH_SAC_ROLLOUT_E(K0, K1, ENV_, EVAL_, FIX_) LAUNCH_SAC_ROLLOUT_F(K0, K1, ENV_, EVAL_, FIX_, false)
+#define LAUNCH_SAC_ROLLOUT_F(K0, K1, ENV_, EVAL_, FIX_, DET_)                                                                   \
     do {                                                                                                                        \
-        if (!attr[FIX_][EVAL_][ENV_][K0 * 3 + K1]) {                                                                            \
-            int rc = erl_hip_status(hipFuncSetAttribute((const void *)sac_rollout_synenv_kernel<K0, K1, ENV_, EVAL_, FIX_>,     \
+        if (!attr[DET_ ? 2 : FIX_][EVAL_][ENV_][K0 * 3 + K1]) {                                                                 \
+            int rc = erl_hip_status(hipFuncSetAttribute((const void *)sac_rollout_synenv_kernel<K0, K1, ENV_, EVAL_, FIX_, DET_>, \
                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes),            \
                                     "hipFuncSetAttribute(sac_rollout_synenv_kernel)");                                          \
             if (rc) return rc;                                                                                                  \
-            attr[FIX_][EVAL_][ENV_][K0 * 3 + K1] = true;                                                                        \
+            attr[DET_ ? 2 : FIX_][EVAL_][ENV_][K0 * 3 + K1] = true;                                                             \
         }                                                                                                                       \
-        hipLaunchKernelGGL((sac_rollout_synenv_kernel<K0, K1, ENV_, EVAL_, FIX_>), grid, blk, lds_bytes, stream, g);            \
+        hipLaunchKernelGGL((sac_rollout_synenv_kernel<K0, K1, ENV_, EVAL_, FIX_, DET_>), grid, blk, lds_bytes, stream, g);      \
     } while (0)
+// the deterministic actor's forms (erl_td3_rollout_*_f32, erl_td3_eval_*_f32)
+#define LAUNCH_DET_ROLLOUT_SYN(K0, K1) LAUNCH_SAC_ROLLOUT_F(K0, K1, SR_ENV_SYN, false, false, true)
+#define LAUNCH_DET_ROLLOUT_PEN(K0, K1) LAUNCH_SAC_ROLLOUT_F(K0, K1, SR_ENV_PENDULUM, false, false, true)
+#define LAUNCH_DET_ROLLOUT_PNT(K0, K1) LAUNCH_SAC_ROLLOUT_F(K0, K1, SR_ENV_POINT, false, false, true)
+#define LAUNCH_DET_EVAL_SYN(K0, K1) LAUNCH_SAC_ROLLOUT_F(K0, K1, SR_ENV_SYN, true, false, true)
+#define LAUNCH_DET_EVAL_PEN(K0, K1) LAUNCH_SAC_ROLLOUT_F(K0, K1, SR_ENV_PENDULUM, true, false, true)
+#define LAUNCH_DET_EVAL_PNT(K0, K1) LAUNCH_SAC_ROLLOUT_F(K0, K1, SR_ENV_POINT, true, false, true)
 #define LAUNCH_SAC_ROLLOUT_SYN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_SYN, false, false)
 #define LAUNCH_SAC_ROLLOUT_PEN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_PENDULUM, false, false)
 #define LAUNCH_SAC_EVAL_SYN(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_SYN, true, false)
@@ -1995,7 +2108,12 @@ int erl_sac_rollout_fused(const float *actor_params, int S, int A, int h0, int h
 #define LAUNCH_MOD_EVAL_PNT(K0, K1) LAUNCH_SAC_ROLLOUT_E(K0, K1, SR_ENV_POINT, true, true)
     const bool fix = variant == ERL_SAC_ACTOR_FIX;
     const bool pen = env_kind == SR_ENV_PENDULUM;
-    if (env_kind == SR_ENV_POINT) {
+    if (variant == ERL_ROLLOUT_ACTOR_DET) {
+        if (env_kind == SR_ENV_POINT) { if (ev_rec) { FUSED_KT_DISPATCH(LAUNCH_DET_EVAL_PNT) } else { FUSED_KT_DISPATCH(LAUNCH_DET_ROLLOUT_PNT) } }
+        else if (pen) { if (ev_rec) { FUSED_KT_DISPATCH(LAUNCH_DET_EVAL_PEN) } else { FUSED_KT_DISPATCH(LAUNCH_DET_ROLLOUT_PEN) } }
+        else { if (ev_rec) { FUSED_KT_DISPATCH(LAUNCH_DET_EVAL_SYN) } else { FUSED_KT_DISPATCH(LAUNCH_DET_ROLLOUT_SYN) } }
+    }
+    else if (env_kind == SR_ENV_POINT) {
         if (ev_rec) { if (fix) { FUSED_KT_DISPATCH(LAUNCH_MOD_EVAL_PNT) } else { FUSED_KT_DISPATCH(LAUNCH_SAC_EVAL_PNT) } }
         else { if (fix) { FUSED_KT_DISPATCH(LAUNCH_MOD_ROLLOUT_PNT) } else { FUSED_KT_DISPATCH(LAUNCH_SAC_ROLLOUT_PNT) } }
     }
@@ -2005,6 +2123,12 @@ int erl_sac_rollout_fused(const float *actor_params, int S, int A, int h0, int h
     }
     else if (pen) { if (fix) { FUSED_KT_DISPATCH(LAUNCH_MOD_ROLLOUT_PEN) } else { FUSED_KT_DISPATCH(LAUNCH_SAC_ROLLOUT_PEN) } }
     else { if (fix) { FUSED_KT_DISPATCH(LAUNCH_MOD_ROLLOUT_SYN) } else { FUSED_KT_DISPATCH(LAUNCH_SAC_ROLLOUT_SYN) } }
+#undef LAUNCH_DET_EVAL_PNT
+#undef LAUNCH_DET_EVAL_PEN
+#undef LAUNCH_DET_EVAL_SYN
+#undef LAUNCH_DET_ROLLOUT_PNT
+#undef LAUNCH_DET_ROLLOUT_PEN
+#undef LAUNCH_DET_ROLLOUT_SYN
 #undef LAUNCH_MOD_EVAL_PNT
 #undef LAUNCH_MOD_ROLLOUT_PNT
 #undef LAUNCH_SAC_EVAL_PNT
@@ -2018,5 +2142,25 @@ int erl_sac_rollout_fused(const float *actor_params, int S, int A, int h0, int h
 #undef LAUNCH_SAC_ROLLOUT_SYN
 #undef LAUNCH_SAC_ROLLOUT_PEN
 #undef LAUNCH_SAC_ROLLOUT_E
-    return erl_hip_status(hipGetLastError(), "erl_sac_rollout_synenv_f32");
+#undef LAUNCH_SAC_ROLLOUT_F
+    return erl_hip_status(hipGetLastError(), what ? what : "erl_sac_rollout_synenv_f32");
+}
+
+// Actor.get_action of AgentTD3 / AgentDDPG as ONE launch (det_actor_tile_kernel: 16 rows per workgroup): the per-step twin of the DET
+// rollout forms.  aoff: the offsets of W b W b W b in the actor's block, the head A wide.
+int erl_td3_explore_tile_fused(const float *actor_params, int S, int A, int h0, int h1, const int64_t *aoff, const float *state, int64_t N,
+                               const float *noise, uint64_t seed, uint64_t counter, float action_std, float *action_out, float *state_out,
+                               hipStream_t stream)
+{
+    FusedDims d{};
+    d.S = S; d.A = A; d.E = 1; d.h0 = h0; d.h1 = h1; d.B = N;
+    d.aW1 = aoff[0]; d.ab1 = aoff[1]; d.aW2 = aoff[2]; d.ab2 = aoff[3]; d.aWh = aoff[4]; d.abh = aoff[5];
+    DetTileArgs g{};
+    g.P = actor_params; g.d = d; g.X = state; g.Xcopy = state_out; g.noise = noise; g.seed = seed; g.counter = counter;
+    g.action_std = action_std; g.act = action_out;
+    const dim3 tgrid((unsigned)((N + TS - 1) / TS)), blk(FT);
+#define LAUNCH_DET_TILE(K0, K1) hipLaunchKernelGGL((det_actor_tile_kernel<K0, K1>), tgrid, blk, 0, stream, g)
+    FUSED_KT_DISPATCH(LAUNCH_DET_TILE)
+#undef LAUNCH_DET_TILE
+    return erl_hip_status(hipGetLastError(), "erl_td3_explore_action_tile_f32");
 }

@@ -87,8 +87,9 @@ def compact_episodes(workspace: TEN, num_envs: int, horizon_len: int, rows: TEN,
 
 class _ContinuousGpuVecEnv(_GpuVecEnv):
     """what the device-resident continuous envs share: the per-step launch (erl_<stem>_step_f32, csrc/envs.hip) and the one-launch rollout /
-    evaluation of a PPO agent (erl_rollout_<stem>_f32, erl_eval_<stem>_f32) and of a SAC agent (erl_sac_rollout_[mod_]<stem>_f32,
-    erl_sac_eval_[mod_]<stem>_f32).  An env adds its constructor, `reset`, the three attributes below and `_live`."""
+    evaluation of a PPO agent (erl_rollout_<stem>_f32, erl_eval_<stem>_f32), of a SAC agent (erl_sac_rollout_[mod_]<stem>_f32,
+    erl_sac_eval_[mod_]<stem>_f32) and of a TD3 / DDPG agent (erl_td3_rollout_<stem>_f32, erl_td3_eval_<stem>_f32).  An env adds its
+    constructor, `reset`, the three attributes below and `_live`."""
     _stem = ""                              # "synenv" | "pendulum" | "pointchasing"
     _action_at = 0                          # how many of the live buffers the per-step entry takes in front of the action
     _takes_dims = False                     # the entries take state_dim and action_dim (else they fix them)
@@ -139,12 +140,20 @@ class _ContinuousGpuVecEnv(_GpuVecEnv):
 
     def _sac_call(self, form: str, agent, *rest) -> None:
         """erl_sac_<form>_<stem>_f32 -- for an agent whose actor is ActorFixSAC (AgentModSAC, `agent._spec.actor_variant`) the launch's
-        ActorFixSAC form, erl_sac_<form>_mod_<stem>_f32 -- on the agent's actor, the env block and `rest`"""
+        ActorFixSAC form, erl_sac_<form>_mod_<stem>_f32; for one whose spec names the entry family "td3" (AgentTD3 / AgentDDPG:
+        `spec.rollout_family`) erl_td3_<form>_<stem>_f32, whose rollout takes the agent's `explore_noise_std` in front of the stream --
+        on the agent's actor, the env block and `rest`"""
         self.state_epoch += 1
         spec = agent._spec
-        entry = f"erl_sac_{form}_{'mod_' if spec.actor_variant else ''}{self._stem}_f32"
+        extra = ()
+        if getattr(spec, "rollout_family", "sac") == "td3":
+            entry = f"erl_td3_{form}_{self._stem}_f32"
+            if form == "rollout":
+                extra = (float(agent.explore_noise_std),)
+        else:
+            entry = f"erl_sac_{form}_{'mod_' if spec.actor_variant else ''}{self._stem}_f32"
         _hip.check(getattr(_hip.lib(), entry)(
-            _hip.ptr(agent._actor_flat, th.float32), *self._dims(spec.S, spec.A), spec._c, len(spec.hidden), *self._env_args(), *rest,
+            _hip.ptr(agent._actor_flat, th.float32), *self._dims(spec.S, spec.A), spec._c, len(spec.hidden), *self._env_args(), *rest, *extra,
             _hip.stream_ptr()), entry)
 
     def fused_rollout(self, agent, horizon_len: int, noise, bufs, values, next_value, epilogue=None) -> None:
@@ -163,7 +172,7 @@ class _ContinuousGpuVecEnv(_GpuVecEnv):
 
     def fused_rollout_offpolicy(self, agent, horizon_len: int, noise, bufs, last_state_out) -> None:
         """all `horizon_len` steps of the off-policy AgentBase._explore_vec_env in ONE launch (erl_sac_rollout_<stem>_f32; AgentModSAC:
-        erl_sac_rollout_mod_<stem>_f32): `bufs` = (states, actions, rewards, undones, unmasks) time-major, written in place (rewards scaled,
+        erl_sac_rollout_mod_<stem>_f32; AgentTD3 / AgentDDPG: erl_td3_rollout_<stem>_f32 with the agent's explore_noise_std): `bufs` = (states, actions, rewards, undones, unmasks) time-major, written in place (rewards scaled,
         flags inverted); `last_state_out` (N, S) or None: the agent's own copy of the final state; the env's state / counters advance."""
         p, f32 = _hip.ptr, th.float32
         states, actions, rewards, undones, unmasks = bufs
@@ -181,7 +190,8 @@ class _ContinuousGpuVecEnv(_GpuVecEnv):
 
     def fused_evaluate_offpolicy(self, agent, horizon_len: int, workspace) -> None:
         """... of the deterministic policy of a fused-path AgentSAC (erl_sac_eval_<stem>_f32: the evaluation form of
-        `fused_rollout_offpolicy`; AgentModSAC: erl_sac_eval_mod_<stem>_f32, ActorFixSAC.forward)"""
+        `fused_rollout_offpolicy`; AgentModSAC: erl_sac_eval_mod_<stem>_f32, ActorFixSAC.forward; AgentTD3 / AgentDDPG:
+        erl_td3_eval_<stem>_f32, Actor.forward)"""
         self._sac_call("eval", agent, horizon_len, _hip.ptr(workspace, th.uint8), workspace.numel())
 
 

@@ -1088,6 +1088,8 @@ def sac_explore_action(spec: SacSpec, actor: TEN, state: TEN, *, noise: Optional
 class Td3Spec(_OffPolicySpec):
     """shapes of Actor / CriticTwin (Critic: E = 1) of elegantrl/agents/AgentTD3.py as flat fp32 blocks (include/erl_hip.h)."""
     _param_counts, _workspace_bytes = "erl_td3_param_counts", "erl_td3_workspace_bytes"
+    # what _ContinuousGpuVecEnv._sac_call reads off a spec: the entry family of the one-launch rollout / evaluation (erl_td3_<form>_<stem>_f32)
+    rollout_family = "td3"
 
     @staticmethod
     def _slices(dims):
@@ -1161,17 +1163,29 @@ def td3_update_ring_loop(spec: Td3Spec, nets: Sequence[TEN], moments: Sequence[T
 
 
 def td3_explore_action(spec: Td3Spec, actor: TEN, state: TEN, action_std: float, *, noise: Optional[TEN] = None, seed: int = 0,
-                       counter: int = 0, out: Optional[TEN] = None, out_state: Optional[TEN] = None) -> TEN:
+                       counter: int = 0, out: Optional[TEN] = None, out_state: Optional[TEN] = None, tile: bool = False) -> TEN:
     """Actor.get_action(state, action_std) (erl_td3_explore_action_f32); `out` (N, A): the action's destination (e.g. the rollout's row);
-    `out_state` (N, S): a copy of `state` from the same launch"""
+    `out_state` (N, S): a copy of `state` from the same launch.  `tile`: the one-launch tile kernel (erl_td3_explore_action_tile_f32: the
+    per-step twin of the one-launch rollouts; refused outside `td3_rollout_supported`)."""
     N = state.shape[0]
     out = th.empty((N, spec.A), dtype=th.float32, device=state.device) if out is None else out
+    if tile:
+        check(lib().erl_td3_explore_action_tile_f32(ptr(actor, th.float32), spec.S, spec.A, spec._c, len(spec.hidden), ptr(state, th.float32), N,
+                                                    ptr(noise), seed & _U64, counter & _U64, float(action_std), ptr(out, th.float32),
+                                                    ptr(out_state, th.float32) if out_state is not None else None, None, 0, stream_ptr()),
+              "erl_td3_explore_action_tile_f32")
+        return out
     ws = _workspace(state.device, lib().erl_td3_workspace_bytes(spec.S, spec.A, spec._c, len(spec.hidden), 1, N))
     check(lib().erl_td3_explore_action_f32(ptr(actor, th.float32), spec.S, spec.A, spec._c, len(spec.hidden), ptr(state, th.float32), N,
                                            ptr(noise), seed & _U64, counter & _U64, float(action_std), ptr(out, th.float32),
                                            ptr(out_state, th.float32) if out_state is not None else None, ptr(ws), ws.numel(), stream_ptr()),
           "erl_td3_explore_action_f32")
     return out
+
+
+def td3_rollout_supported(spec: Td3Spec, n_rows: int) -> bool:
+    """the shapes of erl_td3_rollout_*_f32, erl_td3_eval_*_f32 and erl_td3_explore_action_tile_f32 (erl_td3_rollout_supported)"""
+    return bool(lib().erl_td3_rollout_supported(spec.S, spec.A, spec._c, len(spec.hidden), int(n_rows)))
 
 
 # ------------------------------------------------------------------------------------------------

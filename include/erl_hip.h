@@ -1187,6 +1187,49 @@ ERL_API int erl_td3_update_ring_loop_f32(float *actor_params, float *critic_para
                                  int32_t actor_gate, float *objs_all, int32_t *actor_updates_out, void *workspace,
                                  int64_t workspace_bytes, void *stream);
 
+/* AgentTD3's / AgentDDPG's rollout and evaluation in one launch (added within ABI 23: symbols added, none changed).  The
+ * erl_sac_rollout_<env>_f32 / erl_sac_eval_<env>_f32 launches with the deterministic Actor = build_mlp([S, h0, h1, A]) (tanh on top,
+ * AgentTD3.py:126-136) as a compile-time form of sac_rollout_synenv_kernel: ActorSAC's layers with a head A wide, both hidden layers
+ * activated; the training action is clip(tanh(y) + action_std * eps, -1, 1) -- plain tanh(y) at action_std == 0, no draw read -- with
+ * eps = noise (H, N, A) or, NULL, Philox keyed by (seed, counter0 + t, env, component): the keys of H consecutive
+ * erl_td3_explore_action_f32 calls from counter0; the evaluation's action is tanh(y), Actor.forward.  Arguments, validation (their own
+ * names in the messages) and outputs as the erl_sac_* twins, with `float action_std` in front of the stream in the rollout entries
+ * (< 0 or not finite: ERL_EINVAL).  erl_td3_rollout_supported answers as erl_sac_rollout_synenv_supported: two hidden layers of 16..256
+ * in steps of 16, S <= 64, A <= 8, S + A <= 64, 1 <= N <= 4096, off under ERL_SAC_FUSED=0.
+ * erl_td3_explore_action_tile_f32 is their per-step twin: one launch, 16 rows per workgroup, the arithmetic of one step of the
+ * rollouts (bit-identical under the same keys / noise); arguments of erl_td3_explore_action_f32 (which keeps its layered route and
+ * its bits), `workspace` is not read and may be NULL.  It has no layered form: outside erl_td3_rollout_supported it is ERL_EINVAL
+ * before any launch. */
+ERL_API int erl_td3_rollout_supported(int S, int A, const int *hidden, int n_hidden, int64_t N);
+ERL_API int erl_td3_explore_action_tile_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, const float *state,
+                                    int64_t N, const float *noise, uint64_t seed, uint64_t counter, float action_std,
+                                    float *action_out, float *state_out, void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_td3_rollout_synenv_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state,
+                               const float *Ws, const float *Wa, int32_t *step_count, int32_t *episode, int max_step,
+                               uint64_t env_seed, int64_t N, int64_t H, const float *noise, uint64_t seed, uint64_t counter0,
+                               float reward_scale, float *out_states, float *out_actions, float *out_rewards,
+                               uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, float action_std, void *stream);
+ERL_API int erl_td3_rollout_pendulum_f32(const float *actor_params, const int *hidden, int n_hidden, float *phys, float *obs,
+                                 int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
+                                 const float *noise, uint64_t seed, uint64_t counter0, float reward_scale, float *out_states,
+                                 float *out_actions, float *out_rewards, uint8_t *out_undones, uint8_t *out_unmasks,
+                                 float *out_last_state, float action_std, void *stream);
+ERL_API int erl_td3_rollout_pointchasing_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *state,
+                                     float *distance, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
+                                     int64_t N, int64_t H, const float *noise, uint64_t seed, uint64_t counter0,
+                                     float reward_scale, float *out_states, float *out_actions, float *out_rewards,
+                                     uint8_t *out_undones, uint8_t *out_unmasks, float *out_last_state, float action_std,
+                                     void *stream);
+ERL_API int erl_td3_eval_synenv_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *env_state,
+                            const float *Ws, const float *Wa, int32_t *step_count, int32_t *episode, int max_step,
+                            uint64_t env_seed, int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_td3_eval_pendulum_f32(const float *actor_params, const int *hidden, int n_hidden, float *phys, float *obs,
+                              int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed, int64_t N, int64_t H,
+                              void *workspace, int64_t workspace_bytes, void *stream);
+ERL_API int erl_td3_eval_pointchasing_f32(const float *actor_params, int S, int A, const int *hidden, int n_hidden, float *state,
+                                  float *distance, int32_t *step_count, int32_t *episode, int max_step, uint64_t env_seed,
+                                  int64_t N, int64_t H, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * GPU-resident synthetic environments for measurement; they implement the
  * env protocol of elegantrl (step -> state, reward, terminal, truncate; auto-reset).
